@@ -10,6 +10,7 @@ import os
 import struct
 
 F32, BF16, F16 = 0, 1, 2
+F32_MATH_DIRECT, F32_MATH_MFMA = 0, 1      # gct2_ctx_set_f32_math
 DTYPE_NAMES = {F32: "f32", BF16: "bf16", F16: "f16"}
 ABI_VERSION = 17
 # gct2_diffusion_update modes (include/gct2.h; the sampler's objective switches, train.py:29-32)
@@ -53,6 +54,7 @@ SIGNATURES = {
     "gct2_bias_queue_flush": [_vp, _vp],
     "gct2_ctx_set_tuning": [_vp, _i],
     "gct2_ctx_force_direct": [_vp, _i],
+    "gct2_ctx_set_f32_math": [_vp, _i],
     "gct2_ctx_set_stamp_buffer": [_vp, _vp, _sz],
     "gct2_ctx_set_relu_bits": [_vp, _vp, _i],
     "gct2_ctx_log_launches": [_vp, _i],
@@ -308,6 +310,7 @@ class Context:
         self.version = 0
         self.tuning = 0
         self.direct = False
+        self.f32_math = F32_MATH_DIRECT
         self.logging = False
 
     def set_relu_bits(self, ptr, ld_bytes: int) -> None:
@@ -339,12 +342,14 @@ class Context:
         return [t for t in buf.value.decode().split(";") if t]
 
     def mirror(self, other: "Context") -> None:
-        """take over the steering / observing state of another context (not its scratch): tile knobs, the direct-kernel switch, whether
+        """take over the steering / observing state of another context (not its scratch): tile knobs, the direct-kernel switch, the fp32 math mode, whether
         launches are logged, the diagnostic stamp buffer"""
         if self.tuning != other.tuning:
             self.set_tuning(other.tuning)
         if self.direct != other.direct:
             self.force_direct(other.direct)
+        if self.f32_math != other.f32_math:
+            self.set_f32_math(other.f32_math)
         if self.logging != other.logging:
             self.log_launches(other.logging)
         if self._keep[2] is not other._keep[2]:
@@ -378,6 +383,12 @@ class Context:
         self.version += 1
         self.direct = bool(on)
         call("gct2_ctx_force_direct", self.handle, int(bool(on)))
+
+    def set_f32_math(self, mode: int) -> None:
+        """fp32 4x4 / stride-2 convolutions of this context: F32_MATH_DIRECT (default) or F32_MATH_MFMA (fp32 matrix cores)"""
+        call("gct2_ctx_set_f32_math", self.handle, int(mode))
+        self.version += 1
+        self.f32_math = int(mode)
 
     def __del__(self):
         try:

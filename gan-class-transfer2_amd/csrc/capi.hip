@@ -11,6 +11,8 @@ int tapgemm_direct(int dtype, int form, int epi, const TapGemmParams& p, hipStre
 bool wgrad_mfma_supported(int dtype, const WgradParams& p);
 int wgrad_mfma(gct2_ctx& c, int dtype, WgradParams p, hipStream_t s, WgradSlabs* defer);
 int wgrad_direct(int dtype, const WgradParams& p, hipStream_t s);
+int f32_tapgemm(gct2_ctx& c, int form, int epi, TapGemmParams p, hipStream_t s);
+int f32_wgrad(gct2_ctx& c, WgradParams p, hipStream_t s, WgradSlabs* defer);
 bool halo_head_supported(const gct2_ctx& c, int dtype, const TapGemmParams& p);
 int halo_head(gct2_ctx& c, int dtype, TapGemmParams p, float* dw, float* db, float* loss, float* db_up, int accumulate, hipStream_t s);
 bool rgb_fwd_supported(int dtype, const TapGemmParams& p);
@@ -122,20 +124,24 @@ int finish_relu_bits(gct2_ctx& c, int dtype, const TapGemmParams& p, size_t pixe
   gct2_log(c, "relu_bits:derived");
   return pw_relu_bits(dtype, p.y, p.ldy, pixels, p.N, p.bits, p.ldbits, S(stream));
 }
+// fp32 on the matrix cores (gct2_ctx_set_f32_math); force_direct wins, so the direct kernels stay the independent reference
+inline bool f32_on_mfma(const gct2_ctx& c, int dtype) { return dtype == GCT2_F32 && c.f32_math == GCT2_F32_MATH_MFMA && !c.force_direct; }
 int run_tapgemm(gct2_ctx& c, int dtype, int form, int epi, const TapGemmParams& p, void* stream) {
+  if (f32_on_mfma(c, dtype)) return f32_tapgemm(c, form, epi, p, S(stream));
   if (!c.force_direct && tapgemm_mfma_supported(dtype, p)) return tapgemm_mfma(c, dtype, form, epi, p, S(stream));
   gct2_log(c, "direct:tap");
   return tapgemm_direct(dtype, form, epi, p, S(stream));
 }
 // input-gradient launch with optional fused bias gradient: db (+)= column sums of the masked gradient THIS call produces
 // (channels [0, split) -> db, the rest -> db2).  MFMA path: fused into the epilogue / split-K finalize.  Direct path:
-// column sums of the output view after the launch, minus those before it when the launch accumulates.
+// column sums of the output view after the launch, minus those before it when the launch accumulates (the fp32 matrix-core path too).
 int run_dgrad(gct2_ctx& c, int dtype, int form, TapGemmParams p, size_t out_pixels, float* db, int split, float* db2, int db_acc,
               void* stream) {
   if (split < 0 || split > p.N) return gct2_fail(GCT2_EINVAL, "dgrad: db_split out of range");
   p.db = db; p.db_split = split; p.db2 = db2; p.db_acc = db_acc;
   if (!c.force_direct && tapgemm_mfma_supported(dtype, p)) return tapgemm_mfma(c, dtype, form, EPI_MASK, p, S(stream));
-  gct2_log(c, "direct:tap");
+  const bool f32m = f32_on_mfma(c, dtype);
+  if (!f32m) gct2_log(c, "direct:tap");
   // the column-sum kernels below add with atomics, at once: row sets queued for the same targets are reduced first (a queued
   // overwrite would otherwise run behind this call's add and erase it)
   if (int e = tapgemm_dbq_flush_for(c, db, split, db2, p.N - split, S(stream))) return e;
@@ -148,10 +154,11 @@ int run_dgrad(gct2_ctx& c, int dtype, int form, TapGemmParams p, size_t out_pixe
     return GCT2_OK;
   };
   if ((db || db2) && p.accumulate) if (int e = sums(-1.f)) return e;
-  if (int e = tapgemm_direct(dtype, form, EPI_MASK, p, S(stream))) return e;
+  if (int e = f32m ? f32_tapgemm(c, form, EPI_MASK, p, S(stream)) : tapgemm_direct(dtype, form, EPI_MASK, p, S(stream))) return e;
   return (db || db2) ? sums(1.f) : GCT2_OK;
 }
 int run_wgrad(gct2_ctx& c, int dtype, const WgradParams& p, void* stream, WgradSlabs* defer = nullptr) {
+  if (f32_on_mfma(c, dtype)) return f32_wgrad(c, p, S(stream), defer);
   if (!c.force_direct && wgrad_mfma_supported(dtype, p)) return wgrad_mfma(c, dtype, p, S(stream), defer);
   if (defer) *defer = WgradSlabs{nullptr, 0, 0};
   gct2_log(c, "direct:wgrad");
@@ -285,6 +292,12 @@ int gct2_ctx_read_launch_log(gct2_ctx* ctx, char* buf, size_t bytes, size_t* nee
 int gct2_ctx_force_direct(gct2_ctx* ctx, int on) {
   if (!ctx) return gct2_fail(GCT2_EINVAL, "ctx_force_direct: null ctx");
   ctx->force_direct = on ? 1 : 0;
+  return GCT2_OK;
+}
+int gct2_ctx_set_f32_math(gct2_ctx* ctx, int mode) {
+  if (!ctx) return gct2_fail(GCT2_EINVAL, "ctx_set_f32_math: null ctx");
+  if (mode != GCT2_F32_MATH_DIRECT && mode != GCT2_F32_MATH_MFMA) return gct2_fail(GCT2_EINVAL, "ctx_set_f32_math: unknown mode %d", mode);
+  ctx->f32_math = mode;
   return GCT2_OK;
 }
 

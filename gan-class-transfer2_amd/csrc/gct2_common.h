@@ -31,6 +31,7 @@ struct gct2_ctx {
   int wgrad_split = 0;                             // forced pixel split of the 128 x 128 weight-gradient tile: 0 = automatic, v: 2^(v-1)
   int no_splitk = 0;                               // 1: forward / input-gradient GEMMs never split their reduction (tuning bit 8)
   int force_direct = 0;
+  int f32_math = GCT2_F32_MATH_DIRECT;              // gct2_ctx_set_f32_math: fp32 4x4 / stride-2 convolutions on the matrix cores (f32_mfma.hip)
   unsigned long long* stamps = nullptr; size_t stamps_bytes = 0;   // diagnostic builds only (gct2_ctx_set_stamp_buffer)
   // ReLU bit plane for the NEXT layer call (gct2_ctx_set_relu_bits): every layer entry point takes it out of the ctx first thing
   // (consumed by the forward / input-gradient calls, an error on the others); relu_bits_done: the launch that just ran wrote the

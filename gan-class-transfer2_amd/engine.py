@@ -290,7 +290,7 @@ class UNetEngine:
                  base_lr: float = 2e-5, warm_up: int = 2000, beta_1: float = 0.9, beta_2: float = 0.999,
                  epsilon: float = 1e-7, loss_scaling: bool = False, seed: int = 1234, rng_seed: int = 0,
                  workspace_mb: int = 64, predict_x: bool = True, predict_scaled_epsilon: bool = False,
-                 prediction_weighting: bool = False, ordinary_differential_equation: bool = False):
+                 prediction_weighting: bool = False, ordinary_differential_equation: bool = False, f32_matrix: bool = False):
         self.lib = _lib.load()
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         if self.device.type != "cuda":
@@ -299,6 +299,11 @@ class UNetEngine:
             self.device = torch.device("cuda", torch.cuda.current_device())
         call("gct2_device_check")
         self.topo, self.dtype, self.steps = topo, dtype, steps
+        if f32_matrix and dtype != F32:
+            raise ValueError("UNetEngine: f32_matrix selects the fp32 matrix-core kernels and needs dtype F32")
+        # fp32 convolutions on the matrix cores (gct2_ctx_set_f32_math) in every call context this engine creates (_new_ctx); fixed at
+        # construction, so neither the step-plan key nor the sampler's graph cache needs it beyond the contexts' versions
+        self._f32_matrix = bool(f32_matrix)
         self.base_lr, self.warm_up = base_lr, warm_up
         self.beta_1, self.beta_2, self.epsilon = beta_1, beta_2, epsilon
         self.loss_scaling = loss_scaling
@@ -322,7 +327,7 @@ class UNetEngine:
         self._bufs: "OrderedDict[Tuple[int, int, int], _Buffers]" = OrderedDict()
         self.max_buffer_sets = 4
         # the call context (include/gct2.h gct2_ctx): this engine's scratch tensors and tile knobs; nothing is process-wide
-        self.ctx = _lib.Context()
+        self.ctx = self._new_ctx()
         # split-K scratch for the bottleneck layers, partial rows of the fused bias gradients / the head; caller-owned = this tensor
         self.workspace = torch.empty(workspace_mb << 18, dtype=torch.float32, device=self.device) if workspace_mb else None
         # second stream + its own scratch: the weight-gradient kernels (and, single-GPU, the per-layer Adam launches) run
@@ -347,7 +352,7 @@ class UNetEngine:
         # do by then, so that it runs BESIDE DownShuffle_1's MFMA-bound weight gradient instead of behind it at the very end of the
         # step; its slabs go to the chain's own scratch (free once the last input gradient is done): a second context
         self.tail_on_chain = True
-        self.ctx_tail = _lib.Context()
+        self.ctx_tail = self._new_ctx()
         self.ctx_tail.set_workspace(self.workspace)
         # deferred optimizer steps (r04): in the fused single-replica step the Adam launches of the layers the forward pass needs LAST
         # (the head and the outer UpShuffle levels: 5.5 M of the 41.7 M parameters, but three of the six 64-MiB slab sets) are not run
@@ -458,6 +463,18 @@ class UNetEngine:
         else:
             stream.wait_event(token)
 
+    @property
+    def f32_matrix(self) -> bool:
+        """fp32 convolutions run on the matrix cores (constructor argument; read-only)"""
+        return self._f32_matrix
+
+    def _new_ctx(self) -> "_lib.Context":
+        """every call context of this engine comes from here: the engine-wide settings of a context (the fp32 math mode) are applied once"""
+        c = _lib.Context()
+        if self._f32_matrix:
+            c.set_f32_math(_lib.F32_MATH_MFMA)
+        return c
+
     def _wait_stream(self, waiter: "torch.cuda.Stream", other: "torch.cuda.Stream", system_scope: bool = False) -> None:
         self._wait(waiter, self._mark(other, system_scope))
 
@@ -468,7 +485,7 @@ class UNetEngine:
         step through self.ctx steers and observes these launches too"""
         c = self._defer_ctxs.get(layer)
         if c is None:
-            c = self._defer_ctxs[layer] = _lib.Context()
+            c = self._defer_ctxs[layer] = self._new_ctx()
             self._defer_ws[layer] = torch.empty_like(self.wgrad_workspace)
             c.set_wgrad_workspace(self._defer_ws[layer])
         c.mirror(self.ctx)
@@ -663,7 +680,7 @@ class UNetEngine:
             # so both chains may share the context; one context per tuning word because setters are not part of a step plan
             c = self._split_ctxs.get(tuning)
             if c is None:
-                c = self._split_ctxs[tuning] = _lib.Context()
+                c = self._split_ctxs[tuning] = self._new_ctx()
                 c.set_tuning(tuning)
             return c
 

@@ -44,6 +44,10 @@ warm_up = 2_000
 # MI355X knob: None -> float32, or float16 when mixed_precision (train.py:38); "bfloat16" selects the
 # bf16-operand / fp32-accumulate MFMA path that BASELINE.json's metric is quoted on.
 compute_dtype: Optional[str] = None
+# MI355X knob: in fp32 mode (the default above), run the planned train step's and the sampler's 4x4 / stride-2 convolutions on the
+# exact fp32 matrix cores (UNetEngine(f32_matrix=True)) instead of the one-thread-per-output kernels.  The eager per-layer calls
+# (DownShuffle.call and the others) pass no call context and stay on the direct kernels.
+f32_matrix_cores: bool = False
 
 _DTYPES = {"float32": F32, "bfloat16": BF16, "float16": F16}
 
@@ -394,6 +398,8 @@ class Denoiser(Layer):
             # no optimizer known yet (train.py:505-509 calls the model before compile): the module-level mixed_precision
             # decides about loss scaling, as it decides about the LossScaleOptimizer wrapper in train.py:82-83
             kw = dict(steps=steps, warm_up=warm_up, seed=self._seed, loss_scaling=bool(mixed_precision), **objective_switches())
+            if self.dtype_code == F32:
+                kw["f32_matrix"] = bool(f32_matrix_cores)
             kw.update(engine_kw)
             self.engine = UNetEngine(self.topology, self.dtype_code, self._device, **kw)
             A = self.engine.arena

@@ -96,6 +96,13 @@ int gct2_bias_queue_flush(gct2_ctx* ctx, void* stream);
 int gct2_ctx_set_tuning(gct2_ctx* ctx, int v);
 /* test hook: non-zero routes every convolution of this ctx through the direct (non-MFMA) kernels */
 int gct2_ctx_force_direct(gct2_ctx* ctx, int on);
+/* fp32 arithmetic of the 4x4 / stride-2 convolutions (dtype GCT2_F32: forward, input and weight gradients) for the calls of this ctx:
+ * GCT2_F32_MATH_DIRECT (the default) = one thread per output; GCT2_F32_MATH_MFMA = LDS tiles on the exact fp32-input matrix cores
+ * (v_mfma_f32_16x16x4_f32).  An unsplit forward / input-gradient launch of the MFMA mode sums every output in the direct kernel's
+ * order (taps, then ascending channels: the same fmaf chain); split reductions (split-K, weight-gradient pixel splits) add ordered
+ * fp32 partial sums.  force_direct wins over this setting.  Any other mode, or a NULL ctx: GCT2_EINVAL. */
+enum { GCT2_F32_MATH_DIRECT = 0, GCT2_F32_MATH_MFMA = 1 };
+int gct2_ctx_set_f32_math(gct2_ctx* ctx, int mode);
 /* ReLU bit plane for the NEXT layer call of this ctx (r03, ABI v13; one-shot: the call consumes and clears it).
  * bits: device bytes [pixels][ld_bytes], bit k of byte c <-> channel 8c + k of the call's output view.
  *  - before gct2_conv4s2_fwd / gct2_convT4s2_fwd: the call ALSO writes bits = (y > 0) for its Cout channels (in the epilogue of the
