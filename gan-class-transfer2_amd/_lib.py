@@ -385,7 +385,7 @@ class Context:
         call("gct2_ctx_force_direct", self.handle, int(bool(on)))
 
     def set_f32_math(self, mode: int) -> None:
-        """fp32 4x4 / stride-2 convolutions of this context: F32_MATH_DIRECT (default) or F32_MATH_MFMA (fp32 matrix cores)"""
+        """fp32 convolutions of this context (4x4 / stride-2 and stride-1): F32_MATH_DIRECT (default) or F32_MATH_MFMA (fp32 matrix cores)"""
         call("gct2_ctx_set_f32_math", self.handle, int(mode))
         self.version += 1
         self.f32_math = int(mode)

@@ -446,9 +446,11 @@ int gct2_conv2d_s1_fwd(gct2_ctx* ctx, int dtype, const void* x, int ldx, const v
   if (int e = PlaneTaken(c).none("conv2d_s1_fwd")) return e;
   if (int e = check_s1("conv2d_s1_fwd", dtype, x, w, y, B, H, W, Cin, Cout, KS)) return e;
   if (ldx < Cin || ldy < Cout) return gct2_fail(GCT2_EINVAL, "conv2d_s1_fwd: ld smaller than channel count");
-  {   // matrix-core form (third tap-GEMM form: ks x ks taps on one grid) where the 16-bit layouts allow it, else one thread per output
+  {   // matrix-core form (third tap-GEMM form: ks x ks taps on one grid): fp32 on the fp32 matrix cores when the ctx asks for them, 16-bit
+      // where its layouts allow it; else one thread per output
     TapGemmParams p{x, ldx, w, bias, nullptr, 0, y, ldy, B, H, W, Cin, Cout, relu, 0};
     p.ks = KS;
+    if (f32_on_mfma(c, dtype)) return f32_tapgemm(c, FORM_S1, EPI_BIAS_ACT, p, S(stream));
     if (!c.force_direct && KS <= 5 && tapgemm_mfma_supported(dtype, p)) return tapgemm_mfma(c, dtype, FORM_S1, EPI_BIAS_ACT, p, S(stream));
   }
   return conv_s1_direct(dtype, false, x, ldx, w, bias, nullptr, 0, y, ldy, B, H, W, Cin, Cout, KS, relu, 0, S(stream));
@@ -462,6 +464,7 @@ int gct2_conv2d_s1_dgrad(gct2_ctx* ctx, int dtype, const void* dz, int lddz, con
   {
     TapGemmParams p{dz, lddz, w, nullptr, act, ldact, dx, lddx, B, H, W, Cout, Cin, 0, accumulate};
     p.ks = KS;
+    if (f32_on_mfma(c, dtype)) return f32_tapgemm(c, FORM_S1T, EPI_MASK, p, S(stream));
     if (!c.force_direct && KS <= 5 && tapgemm_mfma_supported(dtype, p)) return tapgemm_mfma(c, dtype, FORM_S1T, EPI_MASK, p, S(stream));
   }
   return conv_s1_direct(dtype, true, dz, lddz, w, nullptr, act, ldact, dx, lddx, B, H, W, Cout, Cin, KS, 0, accumulate, S(stream));
@@ -475,7 +478,9 @@ int gct2_conv2d_s1_wgrad(gct2_ctx* ctx, int dtype, const void* x, int ldx, const
   WgradParams p{x, ldx, dz, lddz, dw, B, H, W, Cin, Cout, 1};
   p.accumulate = accumulate ? 1 : 0;
   p.ks = KS;
-  if (!c.force_direct && wgrad_mfma_supported(dtype, p)) {
+  if (f32_on_mfma(c, dtype)) {
+    if (int e = f32_wgrad(c, p, S(stream), nullptr)) return e;
+  } else if (!c.force_direct && wgrad_mfma_supported(dtype, p)) {
     if (int e = wgrad_mfma(c, dtype, p, S(stream), nullptr)) return e;
   } else if (int e = conv_s1_wgrad_direct(dtype, x, ldx, dz, lddz, dw, B, H, W, Cin, Cout, KS, accumulate, S(stream))) return e;
   if (db) return wgrad_db(c, dtype, dz, lddz, db, (size_t)B * H * W, Cout, accumulate, stream);

@@ -1,16 +1,18 @@
-// fp32 tap GEMMs and weight gradients of the 4x4 / stride-2 layers on the fp32-input matrix cores (v_mfma_f32_16x16x4_f32):
-// the reference's default arithmetic (train.py:34,38: mixed_precision = False) at the MFMA rate instead of one thread per output
-// (direct_kernels.hip).  Selected per call context (gct2_ctx_set_f32_math); the direct kernels stay the default and the reference.
+// fp32 tap GEMMs and weight gradients of the 4x4 / stride-2 layers and of the 'same' stride-1 convolutions (ks x ks, ks odd <= 7:
+// Block's 3x3, the 1x1 projection) on the fp32-input matrix cores (v_mfma_f32_16x16x4_f32): the reference's default arithmetic
+// (train.py:34,38: mixed_precision = False) at the MFMA rate instead of one thread per output (direct_kernels.hip).  Selected per call
+// context (gct2_ctx_set_f32_math); the direct kernels stay the default and the reference.
 //
 // One work-group = 4 waves = a 128 x BN output tile (BN = 128, or 64 for narrow outputs), each wave 64 x BN/2 = 4 x BN/32 MFMA tiles
 // of 16 x 16.  A reduction stage = 16 reduction elements, staged through LDS k-major ([k][m] and [k][n], rows padded to 144 floats:
 // the 16 lanes of a k-row read 16 consecutive floats, the four k-rows of one MFMA land on four distinct 16-bank groups).
 // Global -> registers for stage s + 1 is issued before the MFMAs of stage s.
 //
-// Reduction order (the contract of the forward / input-gradient GEMMs): stages walk the taps in the direct kernel's order and, inside
-// a tap, the channels in 16-channel chunks; an MFMA k-group is 4 consecutive channels of one tap with lane k-index 0 the lowest, and
-// v_mfma_f32_16x16x4_f32 is exactly the k-ordered fmaf chain.  An unsplit launch therefore computes every output as the same fmaf
-// chain as direct_tapgemm_kernel; taps outside the source grid and channels beyond K are staged as zeros and add exact zeros.
+// Reduction order (the contract of the forward / input-gradient GEMMs): stages walk the taps in the direct kernel's order (FORM_S1 /
+// FORM_S1T: kh, then kw ascending, as direct_conv_s1_kernel) and, inside a tap, the channels in 16-channel chunks; an MFMA k-group is
+// 4 consecutive channels of one tap with lane k-index 0 the lowest, and v_mfma_f32_16x16x4_f32 is exactly the k-ordered fmaf chain.
+// An unsplit launch therefore computes every output as the same fmaf chain as direct_tapgemm_kernel / direct_conv_s1_kernel; taps
+// outside the source grid and channels beyond K are staged as zeros and add exact zeros.
 #include "gct2_common.h"
 #include <algorithm>
 
@@ -72,7 +74,9 @@ enum { F_AVEC = 1, F_BVEC = 2 };
 template <int FORM, int EPI, int BN>
 __global__ __launch_bounds__(256) void f32_tapgemm_kernel(TapGemmParams p, int flags) {
   constexpr int WN = BN / 32;                        // MFMA tiles per wave along n
-  constexpr int NT = FORM == FORM_CONV ? 4 : 2;      // taps per direction
+  constexpr bool FLIP = FORM == FORM_CONVT || FORM == FORM_S1T;   // the taps walk the source backwards, weights [tap][N][K]
+  const int NT = FORM == FORM_CONV ? 4 : (FORM == FORM_CONVT ? 2 : p.ks);     // taps per direction
+  const int pad = (p.ks - 1) / 2;                    // FORM_S1 / FORM_S1T
   constexpr int NBG = BN * FBK / 4 / 256;            // 4-float groups of the B stage per thread (2 or 1)
   __shared__ float As[FBK * FLD], Bs[FBK * FLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave & 1, wn = wave >> 1;
@@ -93,7 +97,9 @@ __global__ __launch_bounds__(256) void f32_tapgemm_kernel(TapGemmParams p, int f
     int sw, sh, b;
     decode_pixel(m < M ? m : 0, Hs, Ws, -1, -1, sw, sh, b);
     if (FORM == FORM_CONV) { hb[g] = 2 * sh - 1; wb[g] = 2 * sw - 1; }
-    else { hb[g] = sh + ph; wb[g] = sw + pw; }
+    else if (FORM == FORM_CONVT) { hb[g] = sh + ph; wb[g] = sw + pw; }
+    else if (FORM == FORM_S1) { hb[g] = sh - pad; wb[g] = sw - pad; }
+    else { hb[g] = sh + pad; wb[g] = sw + pad; }
     rowb[g] = b * Hsrc;
     if (m >= M) hb[g] = -4 * Hsrc - 8;               // never inside the source grid
   }
@@ -104,12 +110,12 @@ __global__ __launch_bounds__(256) void f32_tapgemm_kernel(TapGemmParams p, int f
   f32x4_t ra[2], rb[NBG];
   auto load_stage = [&](int st) {
     const int t = st / nchunks, k0 = (st - t * nchunks) * FBK;
-    const int ta = t / NT, tc = t % NT;
-    const int tap16 = FORM == FORM_CONV ? ta * 4 + tc : (1 - ph + 2 * ta) * 4 + (1 - pw + 2 * tc);
+    const int ta = t / NT, tc = t - ta * NT;         // (kh, kw) of the stride-1 forms
+    const int tap = FORM == FORM_CONV ? ta * 4 + tc : (FORM == FORM_CONVT ? (1 - ph + 2 * ta) * 4 + (1 - pw + 2 * tc) : t);
 #pragma unroll
     for (int g = 0; g < 2; g++) {
       const int kq = (tid + 256 * g) & 3;
-      const int h = FORM == FORM_CONV ? hb[g] + ta : hb[g] - ta, ww = FORM == FORM_CONV ? wb[g] + tc : wb[g] - tc;
+      const int h = FLIP ? hb[g] - ta : hb[g] + ta, ww = FLIP ? wb[g] - tc : wb[g] + tc;
       const int k = k0 + 4 * kq;
       const bool ok = (unsigned)h < (unsigned)Hsrc && (unsigned)ww < (unsigned)Wsrc;
       ra[g] = load4(ok ? x + ((size_t)(rowb[g] + h) * Wsrc + ww) * p.ldx + k : x, ok ? min(4, K - k) : 0, avec);
@@ -117,14 +123,14 @@ __global__ __launch_bounds__(256) void f32_tapgemm_kernel(TapGemmParams p, int f
 #pragma unroll
     for (int g = 0; g < NBG; g++) {
       const int e = tid + 256 * g;
-      if (FORM == FORM_CONV) {        // [tap][K][N]: 4 consecutive n of row k
+      if (!FLIP) {                    // [tap][K][N]: 4 consecutive n of row k
         const int k = k0 + e / (BN / 4), n = n0 + 4 * (e % (BN / 4));
         const bool ok = k < K;
-        rb[g] = load4(w + ((size_t)tap16 * K + (ok ? k : 0)) * N + n, ok ? min(4, N - n) : 0, bvec);
+        rb[g] = load4(w + ((size_t)tap * K + (ok ? k : 0)) * N + n, ok ? min(4, N - n) : 0, bvec);
       } else {                        // [tap][N][K]: 4 consecutive k of row n
         const int n = n0 + (e >> 2), k = k0 + 4 * (e & 3);
         const bool ok = n < N;
-        rb[g] = load4(w + ((size_t)tap16 * N + (ok ? n : 0)) * K + k, ok ? min(4, K - k) : 0, bvec);
+        rb[g] = load4(w + ((size_t)tap * N + (ok ? n : 0)) * K + k, ok ? min(4, K - k) : 0, bvec);
       }
     }
   };
@@ -138,7 +144,7 @@ __global__ __launch_bounds__(256) void f32_tapgemm_kernel(TapGemmParams p, int f
 #pragma unroll
     for (int g = 0; g < NBG; g++) {
       const int e = tid + 256 * g;
-      if (FORM == FORM_CONV) *reinterpret_cast<f32x4_t*>(&Bs[(e / (BN / 4)) * FLD + 4 * (e % (BN / 4))]) = rb[g];
+      if (!FLIP) *reinterpret_cast<f32x4_t*>(&Bs[(e / (BN / 4)) * FLD + 4 * (e % (BN / 4))]) = rb[g];
       else {
 #pragma unroll
         for (int j = 0; j < 4; j++) Bs[(4 * (e & 3) + j) * FLD + (e >> 2)] = rb[g][j];
@@ -196,15 +202,18 @@ __global__ __launch_bounds__(256) void f32_tapgemm_finalize_kernel(TapGemmParams
 }
 
 // dw[tap][cb][cs] (+)= sum_r big[pix_big(r, tap)][cb] * small[r][cs]: a GEMM with rows m = tap * Cb + cb, columns cs, reduction over the
-// pixels r of the SMALL grid in stages of 16; launch-y = pixel split.  out: slab rsplit index (mode 0), owner (1), atomics (2)
+// pixels r of the SMALL grid in stages of 16; launch-y = pixel split.  4x4 / stride-2 (p.ks = 0): 16 taps, tap = 4 kh + kw reads the
+// big pixel (2 sh + kh - 1, 2 sw + kw - 1); stride-1 (p.ks odd): both tensors on one grid, ks * ks taps, tap = ks kh + kw reads
+// (sh + kh - pad, sw + kw - pad).  out: slab rsplit index (mode 0), owner (1), atomics (2)
 enum { WG_SLABS = 0, WG_OWNER = 1, WG_ATOMICS = 2 };
 template <int BN>
 __global__ __launch_bounds__(256) void f32_wgrad_kernel(WgradParams p, int flags, int m_tiles, int per, int mode) {
   constexpr int WN = BN / 32, NBG = BN * FBK / 4 / 256;
   __shared__ float As[FBK * FLD], Bs[FBK * FLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave & 1, wn = wave >> 1;
-  const int Hs = p.Hs, Ws = p.Ws, Hb = 2 * Hs, Wb = 2 * Ws, Cb = p.Cb, Cs = p.Cs;
-  const int R = p.B * Hs * Ws, M = 16 * Cb;
+  const int ks = p.ks ? p.ks : 4, pad = p.ks ? (p.ks - 1) / 2 : 1, str = p.ks ? 1 : 2;    // taps per direction, tap offset, stride
+  const int Hs = p.Hs, Ws = p.Ws, Hb = str * Hs, Wb = str * Ws, Cb = p.Cb, Cs = p.Cs;
+  const int R = p.B * Hs * Ws, M = ks * ks * Cb;
   const int mt = blockIdx.x % m_tiles, nt = blockIdx.x / m_tiles;
   const int m0 = mt * FBM, n0 = nt * BN;
   const bool avec = flags & F_AVEC, bvec = flags & F_BVEC;
@@ -215,10 +224,10 @@ __global__ __launch_bounds__(256) void f32_wgrad_kernel(WgradParams p, int flags
 #pragma unroll
   for (int j = 0; j < 4; j++) {
     const int m = m0 + 4 * (tid & 31) + j;
-    const int tap = m / Cb;
+    const int tap = m / Cb, kh = tap / ks;
     cbj[j] = m - tap * Cb;
-    dh[j] = m < M ? (tap >> 2) - 1 : -4 * Hb - 8;    // an invalid row never lands inside the big grid
-    dw[j] = (tap & 3) - 1;
+    dh[j] = m < M ? kh - pad : -4 * Hb - 8;          // an invalid row never lands inside the big grid
+    dw[j] = tap - kh * ks - pad;
   }
   const int stages = (R + FBK - 1) / FBK;
   const int s_lo = blockIdx.y * per, s_hi = min(stages, s_lo + per);
@@ -232,13 +241,13 @@ __global__ __launch_bounds__(256) void f32_wgrad_kernel(WgradParams p, int flags
       if (r < r_end) decode_pixel(r, Hs, Ws, -1, -1, sw, sh, b);
       const bool rok = r < r_end;
       if (avec) {                     // Cb % 4 == 0: the four rows share one tap, 16-byte aligned
-        const int h = 2 * sh + dh[0], ww = 2 * sw + dw[0];
+        const int h = str * sh + dh[0], ww = str * sw + dw[0];
         const bool ok = rok && (unsigned)h < (unsigned)Hb && (unsigned)ww < (unsigned)Wb;
         ra[g] = load4(ok ? big + ((size_t)(b * Hb + h) * Wb + ww) * p.ldbig + cbj[0] : big, ok ? 4 : 0, true);
       } else {
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-          const int h = 2 * sh + dh[j], ww = 2 * sw + dw[j];
+          const int h = str * sh + dh[j], ww = str * sw + dw[j];
           const bool ok = rok && (unsigned)h < (unsigned)Hb && (unsigned)ww < (unsigned)Wb;
           ra[g][j] = ok ? big[((size_t)(b * Hb + h) * Wb + ww) * p.ldbig + cbj[j]] : 0.f;
         }
@@ -303,17 +312,18 @@ void launch_tap(int bn, dim3 grid, hipStream_t s, const TapGemmParams& p, int fl
 
 }  // namespace
 
-// fp32 forward / input-gradient tap GEMM (FORM_CONV / FORM_CONVT, both epilogues) on the matrix cores.  The fused bias gradient of the
+// fp32 forward / input-gradient tap GEMM (all four forms, both epilogues) on the matrix cores.  The fused bias gradient of the
 // input-gradient calls is not this function's: run_dgrad (capi.hip) takes the column sums of the output view around it.
 int f32_tapgemm(gct2_ctx& c, int form, int epi, TapGemmParams p, hipStream_t s) {
-  if (form != FORM_CONV && form != FORM_CONVT) return gct2_fail(GCT2_EINVAL, "f32_tapgemm: form %d", form);
+  if (form < FORM_CONV || form > FORM_S1T) return gct2_fail(GCT2_EINVAL, "f32_tapgemm: form %d", form);
   const int M = p.B * p.Hs * p.Ws;
   const int PH = form == FORM_CONVT ? 4 : 1;
   const int bn = p.N <= 64 ? 64 : 128;
   p.m_tiles = (M + FBM - 1) / FBM;
   p.n_tiles = (p.N + bn - 1) / bn;
   const int tiles = p.m_tiles * p.n_tiles * PH;
-  const int niter = (form == FORM_CONV ? 16 : 4) * ((p.K + FBK - 1) / FBK);
+  const int taps = form == FORM_CONV ? 16 : (form == FORM_CONVT ? 4 : p.ks * p.ks);      // per launch phase
+  const int niter = taps * ((p.K + FBK - 1) / FBK);
   const size_t npix = (size_t)M * PH;
   // the small-M deep levels cannot fill 256 CUs with output tiles: split the reduction into ordered slabs, >= 8 stages each
   p.ksplit = 1;
@@ -328,17 +338,30 @@ int f32_tapgemm(gct2_ctx& c, int form, int epi, TapGemmParams p, hipStream_t s) 
       p.ws = c.ws;
     }
   }
+  const bool flip = form == FORM_CONVT || form == FORM_S1T;     // weights [tap][N][K], else [tap][K][N]
   int flags = 0;
   if (p.K % 4 == 0 && p.ldx % 4 == 0 && (uintptr_t)p.x % 16 == 0) flags |= F_AVEC;
-  if ((uintptr_t)p.w % 16 == 0 && (form == FORM_CONV ? p.N % 4 == 0 : p.K % 4 == 0)) flags |= F_BVEC;
-  gct2_log(c, "f32mfma:%s:ksplit=%d", form == FORM_CONV ? "conv" : "convT", p.ksplit);
+  if ((uintptr_t)p.w % 16 == 0 && (flip ? p.K % 4 == 0 : p.N % 4 == 0)) flags |= F_BVEC;
+  static const char* const names[] = {"conv", "convT", "s1", "s1t"};
+  gct2_log(c, "f32mfma:%s:ksplit=%d", names[form], p.ksplit);
   const dim3 grid((unsigned)(p.m_tiles * p.n_tiles), (unsigned)p.ksplit, (unsigned)PH);
-  if (form == FORM_CONV) {
-    if (epi == EPI_BIAS_ACT) launch_tap<FORM_CONV, EPI_BIAS_ACT>(bn, grid, s, p, flags);
-    else launch_tap<FORM_CONV, EPI_MASK>(bn, grid, s, p, flags);
-  } else {
-    if (epi == EPI_BIAS_ACT) launch_tap<FORM_CONVT, EPI_BIAS_ACT>(bn, grid, s, p, flags);
-    else launch_tap<FORM_CONVT, EPI_MASK>(bn, grid, s, p, flags);
+  const bool bias_act = epi == EPI_BIAS_ACT;
+  switch (form) {
+    case FORM_CONV:
+      if (bias_act) launch_tap<FORM_CONV, EPI_BIAS_ACT>(bn, grid, s, p, flags);
+      else launch_tap<FORM_CONV, EPI_MASK>(bn, grid, s, p, flags);
+      break;
+    case FORM_CONVT:
+      if (bias_act) launch_tap<FORM_CONVT, EPI_BIAS_ACT>(bn, grid, s, p, flags);
+      else launch_tap<FORM_CONVT, EPI_MASK>(bn, grid, s, p, flags);
+      break;
+    case FORM_S1:
+      if (bias_act) launch_tap<FORM_S1, EPI_BIAS_ACT>(bn, grid, s, p, flags);
+      else launch_tap<FORM_S1, EPI_MASK>(bn, grid, s, p, flags);
+      break;
+    default:
+      if (bias_act) launch_tap<FORM_S1T, EPI_BIAS_ACT>(bn, grid, s, p, flags);
+      else launch_tap<FORM_S1T, EPI_MASK>(bn, grid, s, p, flags);
   }
   if (p.ksplit > 1) {
     const dim3 fgrid((unsigned)((npix * p.N + 255) / 256));
@@ -348,13 +371,13 @@ int f32_tapgemm(gct2_ctx& c, int form, int epi, TapGemmParams p, hipStream_t s) 
   return gct2_check_launch("f32_tapgemm");
 }
 
-// fp32 weight gradient of the 4x4 / stride-2 layers on the matrix cores.  Pixel splits leave ordered slabs in the weight-gradient
-// scratch (reduced by wgrad_reduce in slab order, or handed to the caller's optimizer through `defer` - the wgrad_mfma contract);
-// without scratch: one owner per tile, or fp32 atomics when the tiles need a split to fill the chip.
+// fp32 weight gradient of the 4x4 / stride-2 layers (p.ks = 0) and of the stride-1 convolutions (p.ks odd) on the matrix cores.  Pixel
+// splits leave ordered slabs in the weight-gradient scratch (reduced by wgrad_reduce in slab order, or handed to the caller's optimizer
+// through `defer` - the wgrad_mfma contract); without scratch: one owner per tile, or fp32 atomics when the tiles need a split to fill
+// the chip.
 int f32_wgrad(gct2_ctx& c, WgradParams p, hipStream_t s, WgradSlabs* defer) {
   if (defer) *defer = WgradSlabs{nullptr, 0, 0};
-  if (p.ks) return gct2_fail(GCT2_EINVAL, "f32_wgrad: stride-1 form");
-  const int R = p.B * p.Hs * p.Ws, M = 16 * p.Cb;
+  const int R = p.B * p.Hs * p.Ws, M = (p.ks ? p.ks * p.ks : 16) * p.Cb;
   const int bn = p.Cs <= 64 ? 64 : 128;
   const int m_tiles = (M + FBM - 1) / FBM, tiles = m_tiles * ((p.Cs + bn - 1) / bn);
   const int stages = (R + FBK - 1) / FBK;
@@ -378,7 +401,8 @@ int f32_wgrad(gct2_ctx& c, WgradParams p, hipStream_t s, WgradSlabs* defer) {
   if (p.Cb % 4 == 0 && p.ldbig % 4 == 0 && (uintptr_t)p.big % 16 == 0) flags |= F_AVEC;
   if (p.Cs % 4 == 0 && p.ldsmall % 4 == 0 && (uintptr_t)p.small % 16 == 0) flags |= F_BVEC;
   if (mode == WG_ATOMICS && !p.accumulate) (void)hipMemsetAsync(p.dw, 0, n * sizeof(float), s);     // atomics add into the target
-  gct2_log(c, "f32mfma:wgrad:rsplit=%d:%s", rsplit, mode == WG_SLABS ? "slabs" : (mode == WG_OWNER ? "owner" : "atomics"));
+  gct2_log(c, "f32mfma:%s:rsplit=%d:%s", p.ks ? "wgrad_s1" : "wgrad", rsplit,
+           mode == WG_SLABS ? "slabs" : (mode == WG_OWNER ? "owner" : "atomics"));
   const dim3 grid((unsigned)tiles, (unsigned)rsplit);
   if (bn == 64) hipLaunchKernelGGL((f32_wgrad_kernel<64>), grid, dim3(256), 0, s, p, flags, m_tiles, per, mode);
   else hipLaunchKernelGGL((f32_wgrad_kernel<128>), grid, dim3(256), 0, s, p, flags, m_tiles, per, mode);

@@ -31,7 +31,7 @@ struct gct2_ctx {
   int wgrad_split = 0;                             // forced pixel split of the 128 x 128 weight-gradient tile: 0 = automatic, v: 2^(v-1)
   int no_splitk = 0;                               // 1: forward / input-gradient GEMMs never split their reduction (tuning bit 8)
   int force_direct = 0;
-  int f32_math = GCT2_F32_MATH_DIRECT;              // gct2_ctx_set_f32_math: fp32 4x4 / stride-2 convolutions on the matrix cores (f32_mfma.hip)
+  int f32_math = GCT2_F32_MATH_DIRECT;              // gct2_ctx_set_f32_math: fp32 convolutions on the matrix cores (f32_mfma.hip)
   unsigned long long* stamps = nullptr; size_t stamps_bytes = 0;   // diagnostic builds only (gct2_ctx_set_stamp_buffer)
   // ReLU bit plane for the NEXT layer call (gct2_ctx_set_relu_bits): every layer entry point takes it out of the ctx first thing
   // (consumed by the forward / input-gradient calls, an error on the others); relu_bits_done: the launch that just ran wrote the
@@ -294,7 +294,7 @@ struct TapGemmParams {
   int db_acc;                            // bit 0: db is added to (else overwritten); bit 1: the same for db2
   float* dbws;                           // partial bias-gradient rows [m_tiles*phases | finalize rows][N] in the workspace, or null (atomics)
   HeadFuse head;                         // EPI_HEAD only
-  int ks = 0;                            // FORM_S1 / FORM_S1T: kernel size (odd, <= 5)
+  int ks = 0;                            // FORM_S1 / FORM_S1T: kernel size (odd; <= 5 on the 16-bit matrix cores, <= 7 on the fp32 ones)
   int bits_words = 0;                    // 1: plane and strides are 4-byte aligned and N % 32 == 0 -> the four lane rows of a pixel merge their bytes into ONE 32-bit store
   unsigned char* bits = nullptr; int ldbits = 0;   // ReLU bit plane [pixel][ldbits bytes], bit k of byte c = (channel 8c + k of the view > 0):
                                          // EPI_BIAS_ACT writes it beside y, EPI_MASK reads it instead of act (16-byte epilogues only)

@@ -44,9 +44,11 @@ warm_up = 2_000
 # MI355X knob: None -> float32, or float16 when mixed_precision (train.py:38); "bfloat16" selects the
 # bf16-operand / fp32-accumulate MFMA path that BASELINE.json's metric is quoted on.
 compute_dtype: Optional[str] = None
-# MI355X knob: in fp32 mode (the default above), run the planned train step's and the sampler's 4x4 / stride-2 convolutions on the
-# exact fp32 matrix cores (UNetEngine(f32_matrix=True)) instead of the one-thread-per-output kernels.  The eager per-layer calls
-# (DownShuffle.call and the others) pass no call context and stay on the direct kernels.
+# MI355X knob: in fp32 mode (the default above), run the engine's and the sampler's convolutions on the exact fp32 matrix cores
+# instead of the one-thread-per-output kernels: the planned train step of the default network (UNetEngine(f32_matrix=True)) and,
+# once block_depth, residual or concat leave that topology, the variant engine and its sampler (VariantEngine(f32_matrix=True):
+# Block's 3x3 and the 1x1 projection too).  The eager per-layer calls (DownShuffle.call and the others) pass no call context and
+# stay on the direct kernels.
 f32_matrix_cores: bool = False
 
 _DTYPES = {"float32": F32, "bfloat16": BF16, "float16": F16}
@@ -391,6 +393,8 @@ class Denoiser(Layer):
         if self.engine is None and self.variant():
             from .variants import VariantEngine
             kw = dict(steps=steps, warm_up=warm_up, seed=self._seed, loss_scaling=bool(mixed_precision), **objective_switches())
+            if self.dtype_code == F32:
+                kw["f32_matrix"] = bool(f32_matrix_cores)
             kw.update(engine_kw)
             self.engine = VariantEngine(pixel_size, max_size, octaves, block_depth, residual, concat, self.dtype_code, self._device, **kw)
             self._bind_variant_parameters()

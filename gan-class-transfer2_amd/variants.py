@@ -261,13 +261,15 @@ def build_structure(net: _Net, pixel_size: int, max_size: int, octaves: int, blo
 
 class VariantEngine:
     """train step of a Denoiser built with block_depth > 0 / residual / concat=False (same surface as UNetEngine where it matters:
-    train_step, predict, get/set_params, get_grads, iterations, loss_scale, the objective switches)."""
+    train_step, predict, get/set_params, get_grads, iterations, loss_scale, the objective switches, f32_matrix)."""
 
     def __init__(self, pixel_size: int, max_size: int, octaves: int, block_depth: int, residual: bool, concat: bool, dtype: int = F32,
                  device: Optional[torch.device] = None, steps: int = 200, base_lr: float = 2e-5, warm_up: int = 2000, beta_1: float = 0.9,
                  beta_2: float = 0.999, epsilon: float = 1e-7, loss_scaling: bool = False, seed: int = 1234, rng_seed: int = 0,
                  predict_x: bool = True, predict_scaled_epsilon: bool = False, prediction_weighting: bool = False,
-                 ordinary_differential_equation: bool = False):
+                 ordinary_differential_equation: bool = False, f32_matrix: bool = False):
+        if f32_matrix and dtype != F32:
+            raise ValueError("VariantEngine: f32_matrix selects the fp32 matrix-core kernels and needs dtype F32")
         _lib.load()
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         if self.device.type != "cuda":
@@ -278,6 +280,11 @@ class VariantEngine:
         self.predict_x, self.predict_scaled_epsilon = predict_x, predict_scaled_epsilon
         self.prediction_weighting, self.ordinary_differential_equation = prediction_weighting, ordinary_differential_equation
         self.net = _Net(dtype, self.device)
+        # every fp32 convolution of the train step and of predict (the sampler) on the matrix cores (gct2_ctx_set_f32_math); the
+        # workspace below doubles as their split-K and weight-gradient scratch
+        self._f32_matrix = bool(f32_matrix)
+        if self._f32_matrix:
+            self.net.ctx.set_f32_math(_lib.F32_MATH_MFMA)
         self.workspace = torch.empty(16 << 18, dtype=torch.float32, device=self.device)
         self.net.ctx.set_workspace(self.workspace)
         self.top, self.head_cin = build_structure(self.net, pixel_size, max_size, octaves, block_depth, residual, concat)
@@ -323,6 +330,11 @@ class VariantEngine:
 
     def get_grads(self):
         return {k: self.net.view(self.net.g, k).cpu().numpy().copy() for k in self.net.shapes}
+
+    @property
+    def f32_matrix(self) -> bool:
+        """fp32 convolutions run on the matrix cores (constructor argument; read-only)"""
+        return self._f32_matrix
 
     @property
     def iterations(self) -> int:

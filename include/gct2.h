@@ -96,7 +96,8 @@ int gct2_bias_queue_flush(gct2_ctx* ctx, void* stream);
 int gct2_ctx_set_tuning(gct2_ctx* ctx, int v);
 /* test hook: non-zero routes every convolution of this ctx through the direct (non-MFMA) kernels */
 int gct2_ctx_force_direct(gct2_ctx* ctx, int on);
-/* fp32 arithmetic of the 4x4 / stride-2 convolutions (dtype GCT2_F32: forward, input and weight gradients) for the calls of this ctx:
+/* fp32 arithmetic of every convolution entry point (dtype GCT2_F32: forward, input and weight gradients of the 4x4 / stride-2 layers
+ * and of the stride-1 'same' convolutions gct2_conv2d_s1_*, every KS they accept: 1, 3, 5, 7) for the calls of this ctx:
  * GCT2_F32_MATH_DIRECT (the default) = one thread per output; GCT2_F32_MATH_MFMA = LDS tiles on the exact fp32-input matrix cores
  * (v_mfma_f32_16x16x4_f32).  An unsplit forward / input-gradient launch of the MFMA mode sums every output in the direct kernel's
  * order (taps, then ascending channels: the same fmaf chain); split reductions (split-K, weight-gradient pixel splits) add ordered
@@ -211,7 +212,8 @@ int gct2_convT4s2_wgrad(gct2_ctx* ctx, int dtype, const void* x, int ldx, const 
  * dgrad: dx[b,h,w,i] (+)= mask * sum dz[b,h-kh+p,w-kw+p,o] w[kh,kw,i,o] (mask / accumulate as for conv4s2_dgrad);
  * wgrad: dw (+)= sum x dz (fp32), db (+)= column sums of dz.  16-bit dtypes with whole 8-channel chunks (Cin, Cout and the lds
  * multiples of 8, 16-byte aligned views, KS <= 5) run on the matrix cores as a third tap-GEMM form (KS x KS taps on one grid;
- * split-K / slabs through the ctx scratch like the 4x4 layers); fp32 and the remaining shapes (the 3-channel input of a Block in
+ * split-K / slabs through the ctx scratch like the 4x4 layers); fp32 on the fp32 matrix cores, every shape, when the ctx is in
+ * GCT2_F32_MATH_MFMA mode (gct2_ctx_set_f32_math); fp32 otherwise and the remaining 16-bit shapes (the 3-channel input of a Block in
  * front of level 0) on direct kernels, one thread per output. */
 int gct2_conv2d_s1_fwd(gct2_ctx* ctx, int dtype, const void* x, int ldx, const void* w, const float* bias, void* y, int ldy,
                        int B, int H, int W, int Cin, int Cout, int KS, int relu, void* stream);
