@@ -13,7 +13,6 @@ HBM layout (all NHWC, `ld` = pixel stride in elements):
 from __future__ import annotations
 
 import ctypes
-import math
 import os
 import threading
 from collections import OrderedDict
@@ -25,6 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import BF16, F16, F32, Slot, call
+from .trainer_math import TrainerState, glorot_limit
 
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 
@@ -188,13 +188,7 @@ class ParamArena:
             if name.endswith(".b"):
                 self.param(name).zero_()
                 continue
-            if len(shp) == 2:
-                fan_in, fan_out = shp
-            else:
-                rf = shp[0] * shp[1]
-                fan_in, fan_out = rf * shp[2], rf * shp[3]
-            lim = math.sqrt(6.0 / (fan_in + fan_out))
-            w = (torch.rand(shp, generator=gen, dtype=torch.float32) * 2 - 1) * lim
+            w = (torch.rand(shp, generator=gen, dtype=torch.float32) * 2 - 1) * glorot_limit(shp)
             self.param(name).copy_(w.to(self.device))
 
 
@@ -283,7 +277,7 @@ def _pick_stream(key: tuple, device: torch.device, role: str, caller: "torch.cud
 _ADAM_INPUT_FIELDS = ("p", "m", "v", "shadow", "shadow_dtype", "n", "beta1", "beta2", "eps", "grad_mul", "defer")
 
 
-class UNetEngine:
+class UNetEngine(TrainerState):
     """the planned (zero-copy concat) forward / backward / optimizer step of the Denoiser U-Net."""
 
     def __init__(self, topo: Topology, dtype: int = BF16, device: Optional[torch.device] = None, steps: int = 200,
@@ -291,25 +285,9 @@ class UNetEngine:
                  epsilon: float = 1e-7, loss_scaling: bool = False, seed: int = 1234, rng_seed: int = 0,
                  workspace_mb: int = 64, predict_x: bool = True, predict_scaled_epsilon: bool = False,
                  prediction_weighting: bool = False, ordinary_differential_equation: bool = False, f32_matrix: bool = False):
-        self.lib = _lib.load()
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise _lib.Gct2Error("UNetEngine needs a HIP device (torch device 'cuda'); there is no CPU path")
-        if self.device.index is None:                       # ("cuda" without an index: the current device - the stream registry keys on it)
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        call("gct2_device_check")
-        self.topo, self.dtype, self.steps = topo, dtype, steps
-        if f32_matrix and dtype != F32:
-            raise ValueError("UNetEngine: f32_matrix selects the fp32 matrix-core kernels and needs dtype F32")
-        # fp32 convolutions on the matrix cores (gct2_ctx_set_f32_math) in every call context this engine creates (_new_ctx); fixed at
-        # construction, so neither the step-plan key nor the sampler's graph cache needs it beyond the contexts' versions
-        self._f32_matrix = bool(f32_matrix)
-        self.base_lr, self.warm_up = base_lr, warm_up
-        self.beta_1, self.beta_2, self.epsilon = beta_1, beta_2, epsilon
-        self.loss_scaling = loss_scaling
-        # the objective switches of train.py:29-32 (defaults = the reference's: the network predicts the clean image)
-        self.predict_x, self.predict_scaled_epsilon = predict_x, predict_scaled_epsilon
-        self.prediction_weighting, self.ordinary_differential_equation = prediction_weighting, ordinary_differential_equation
+        super().__init__(dtype, device, steps, base_lr, warm_up, beta_1, beta_2, epsilon, loss_scaling, rng_seed, predict_x,
+                         predict_scaled_epsilon, prediction_weighting, ordinary_differential_equation, f32_matrix)
+        self.topo = topo
         self.use_fused_head = True     # False: dense_fwd + mse_fwd_bwd + dense_bwd as three kernels
         self.fuse_u0_head = True       # train step: the head runs in UpShuffle_0's forward epilogue (R_0 is never written)
         self.keep_pred = False         # train step: also store the prediction (buffers().pred); the loss does not need it
@@ -320,8 +298,6 @@ class UNetEngine:
         self.arena = ParamArena(topo, dtype, self.device)
         self.arena.glorot_init(seed)
         self.arena.refresh_shadow(self._stream())
-        self._iterations = 0           # optimizer.iterations [TF] (with loss scaling the counter lives on the device)
-        self.rng_seed, self.rng_offset_t, self.rng_offset_eps = rng_seed, 0, 0
         # activation / gradient buffer sets by (B, H, W), least recently used first; at most `max_buffer_sets` stay allocated (the
         # train step, the sampler's batch 1 and batch 6 sets and one spare: a set at config 3 is ~0.8 GB, r02 kept every shape ever seen)
         self._bufs: "OrderedDict[Tuple[int, int, int], _Buffers]" = OrderedDict()
@@ -367,11 +343,6 @@ class UNetEngine:
         # r05: the eleven small launches that sum the partial rows of the fused bias gradients leave the input-gradient chain - the calls
         # queue their rows (gct2_ctx_set_bias_queue) and ONE flush (two launches) behind the last input gradient sums them: same bits
         self.defer_rowsums = True
-        # EXPERIMENT (r06; off): the outer `split_forward_levels` levels of the forward pass of a train step run as
-        # TWO half-batch chains on two streams (convolutions are image-local, train.py:148-166), so that the tail of one chain's launch
-        # overlaps the head of the other's - prices the launch ramp / drain of those levels with the kernels that exist
-        self.split_forward_levels = 0
-        self._split_ctxs: Dict[int, "_lib.Context"] = {}
         self._bias_queue = None
         self._bias_queue_on = False
         self._pending: list = []
@@ -391,9 +362,6 @@ class UNetEngine:
         self._plans: Dict[tuple, "_StepPlan"] = {}
         self._plan_seen: Dict[tuple, int] = {}
         self.plan_after = 2              # a step shape is recorded once it has been seen this many times (buffers and deferrals warmed)
-        self.ls_state = None
-        if loss_scaling:
-            self.enable_loss_scaling()
         # called with the layer name as soon as that layer's gradient kernels are enqueued (DP all-reduce)
         self.grad_ready_hook: Optional[Callable[[str], None]] = None
         # plan-aware hooks (the data-parallel wrappers): the hook does its stream plumbing through _wait_stream / apply_adam(stream=...)
@@ -410,36 +378,6 @@ class UNetEngine:
         self._grads_in_arena = True    # False after a step whose fused optimizer consumed weight-gradient slabs in place
 
     # ------------------------------------------------------------------------------------------
-    def enable_loss_scaling(self, initial_scale: float = 2.0 ** 15) -> None:
-        """tf.keras.mixed_precision.LossScaleOptimizer (train.py:82-83): allocate the device-side state (32-byte
-        gct2_loss_scale_state).  Allowed until the first optimizer step, so `trainer(example)` may come before `compile`
-        exactly as in train.py:505-514."""
-        if self.ls_state is not None:
-            return
-        if self._iterations != 0:
-            raise _lib.Gct2Error("loss scaling cannot be switched on after optimizer steps have been applied")
-        self.loss_scaling = True
-        self.ls_state = torch.zeros(8, dtype=torch.int32, device=self.device)
-        call("gct2_loss_scale_init", self.ls_state.data_ptr(), float(initial_scale), self._stream())
-
-    @property
-    def iterations(self) -> int:
-        """optimizer.iterations [TF].  Under LossScaleOptimizer a skipped step does not advance it, and whether a step was
-        skipped is only known on the device: the counter lives there (gct2_loss_scale_state.applied_steps) and reading it
-        synchronises."""
-        if self.ls_state is not None:
-            return int(self.ls_state[4].item())
-        return self._iterations
-
-    @iterations.setter
-    def iterations(self, k: int) -> None:
-        self._iterations = int(k)
-        if self.ls_state is not None:
-            self.ls_state[4] = int(k)
-
-    def _stream(self) -> int:
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def stream_for(self, role: str) -> "torch.cuda.Stream":
         """the registered stream of `role` beside this engine's caller stream (the data-parallel wrappers ask for "comm")"""
         return distinct_stream(self.device, role, self._caller0)
@@ -462,18 +400,6 @@ class UNetEngine:
             P.wait(stream.cuda_stream, token)
         else:
             stream.wait_event(token)
-
-    @property
-    def f32_matrix(self) -> bool:
-        """fp32 convolutions run on the matrix cores (constructor argument; read-only)"""
-        return self._f32_matrix
-
-    def _new_ctx(self) -> "_lib.Context":
-        """every call context of this engine comes from here: the engine-wide settings of a context (the fp32 math mode) are applied once"""
-        c = _lib.Context()
-        if self._f32_matrix:
-            c.set_f32_math(_lib.F32_MATH_MFMA)
-        return c
 
     def _wait_stream(self, waiter: "torch.cuda.Stream", other: "torch.cuda.Stream", system_scope: bool = False) -> None:
         self._wait(waiter, self._mark(other, system_scope))
@@ -670,24 +596,6 @@ class UNetEngine:
         def plane(level: int, ch: int) -> None:                 # one-shot: applies to the layer call that follows
             if planes and b.bits[level] is not None:
                 self.ctx.set_relu_bits(b.bits[level].data_ptr() + ch // 8, b.ld[level] // 8)
-        # two half-batch chains for the outer levels (experiment, see __init__): chain 0 on the current stream, chain 1 on the side stream
-        L = min(int(self.split_forward_levels), n - 1) if (in_step and self.overlap and b.B % 2 == 0 and dt != F32) else 0
-        es, Bh = self._esize(), b.B // 2
-        side = self._side
-
-        def split_ctx(tuning: int) -> "_lib.Context":
-            # the tile the FULL batch would take, forced (a half batch falls below the automatic thresholds), never split-K: no scratch,
-            # so both chains may share the context; one context per tuning word because setters are not part of a step plan
-            c = self._split_ctxs.get(tuning)
-            if c is None:
-                c = self._split_ctxs[tuning] = self._new_ctx()
-                c.set_tuning(tuning)
-            return c
-
-        def halves():
-            return ((0, cur), (1, side))
-        if L:
-            self._wait_stream(side, cur)                       # the noised image is there
         for i in range(n):                                      # DownShuffle_i  (train.py:184)
             H, W = b.hw[i]
             if i < n - 1:
@@ -695,17 +603,6 @@ class UNetEngine:
             else:
                 y, ldy = b.Dlast.data_ptr(), t.fd(i)
             x, ldx = (b.img.data_ptr(), 4) if i == 0 else (self._slice_ptr(b.R[i], t.fu(i)), b.ld[i])
-            if i < L:
-                tiles256 = ((b.B * (H // 2) * (W // 2) + 255) // 256) * ((t.fd(i) + 127) // 128)
-                c = split_ctx((5 if tiles256 >= 512 else 2) | (1 << 8))
-                for h, st in halves():
-                    if planes and b.bits[i + 1] is not None:
-                        c.set_relu_bits(b.bits[i + 1].data_ptr() + t.fu(i + 1) // 8 + h * Bh * (H // 2) * (W // 2) * (b.ld[i + 1] // 8), b.ld[i + 1] // 8)
-                    call("gct2_conv4s2_fwd", c.handle, dt, x + h * Bh * H * W * ldx * es, ldx, A.wptr(f"D{i}.w"), A.pptr(f"D{i}.b"),
-                         y + h * Bh * (H // 2) * (W // 2) * ldy * es, ldy, Bh, H, W, t.cx(i), t.fd(i), 1, st.cuda_stream)
-                if i == L - 1:
-                    self._wait_stream(cur, side)
-                continue
             if i < n - 1:
                 plane(i + 1, t.fu(i + 1))
             call("gct2_conv4s2_fwd", cx, dt, x, ldx, A.wptr(f"D{i}.w"), A.pptr(f"D{i}.b"), y, ldy, b.B, H, W, t.cx(i), t.fd(i), 1, s)
@@ -721,20 +618,8 @@ class UNetEngine:
                 x, ldx = b.Dlast.data_ptr(), t.fd(i)
             if f"U{i}" in self._pending_names or i == 0:
                 join_pending()
-            if i == 0 and L > 1:
-                self._wait_stream(cur, side)                   # both chains of the levels above are done
             if i == 0 and stop_before_u0:
                 return b.pred
-            if 1 <= i < L:
-                if i == L - 1:
-                    self._wait_stream(side, cur)               # UpShuffle_L's output (and the deferred updates joined above)
-                c = split_ctx(2 << 24)                         # the halo kernel wherever it is allowed, as at the full batch
-                for h, st in halves():
-                    if planes and b.bits[i] is not None:
-                        c.set_relu_bits(b.bits[i].data_ptr() + h * Bh * 4 * Hi * Wi * (b.ld[i] // 8), b.ld[i] // 8)
-                    call("gct2_convT4s2_fwd", c.handle, dt, x + h * Bh * Hi * Wi * ldx * es, ldx, A.wptr(f"U{i}.w"), A.pptr(f"U{i}.b"),
-                         b.R[i].data_ptr() + h * Bh * 4 * Hi * Wi * b.ld[i] * es, b.ld[i], Bh, Hi, Wi, t.up_in(i), t.fu(i), 1, st.cuda_stream)
-                continue
             if i >= 1:
                 plane(i, 0)
             call("gct2_convT4s2_fwd", cx, dt, x, ldx, A.wptr(f"U{i}.w"), A.pptr(f"U{i}.b"), b.R[i].data_ptr(), b.ld[i],
@@ -749,40 +634,17 @@ class UNetEngine:
 
     def loss_and_dpred(self, b: _Buffers, target: torch.Tensor, target_is_x: bool = False) -> torch.Tensor:
         """fp32 MSE against the clean image (predict_x, train.py:243-244,262-272) and its gradient."""
-        ls_ptr = self.ls_state.data_ptr() if self.ls_state is not None else None
+        ls_ptr = self._ls_ptr()
         call("gct2_mse_fwd_bwd", b.pred.data_ptr(), Slot("x", target.data_ptr()) if target_is_x else target.data_ptr(), b.dpred.data_ptr(), b.loss.data_ptr(),
              b.partials.data_ptr(), b.pred.numel(), ls_ptr, self._stream())
         return b.loss
 
     # ---- objectives other than the default (train.py:238-252) ----------------------------------------------------------
-    def default_objective(self) -> bool:
-        return self.predict_x and not self.ordinary_differential_equation
-
-    def objective_weighted(self) -> bool:
-        """train.py:250-252: prediction and target both scaled by sqrt(1 - alpha_dash(t)) (epsilon branch only)."""
-        return (not self.default_objective()) and (not self.ordinary_differential_equation) and self.prediction_weighting
-
-    def objective_coefficients(self, b: _Buffers) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """per-image (a, c, w): target = a x + c eps, prediction weight w - B-element vectors from t_int."""
-        t = b.t_int.to(torch.float32)
-        ad = lambda u: 0.25 * (1.0 - u / (self.steps + 1)) ** 2          # alpha_dash, train.py:85-93
-        one, zero = torch.ones_like(t), torch.zeros_like(t)
-        if self.ordinary_differential_equation:                           # train.py:238-242
-            a1 = ad(t - 1)
-            return a1.sqrt().contiguous(), (1 - a1).sqrt().contiguous(), one
-        if self.predict_x:                                                # train.py:243-244
-            return one, zero, one
-        s = (1 - ad(t)).sqrt()
-        c = s if self.predict_scaled_epsilon else one                     # train.py:245-248
-        if self.prediction_weighting:                                     # train.py:250-252
-            return zero, (c * s).contiguous(), s.contiguous()
-        return zero, c.contiguous(), one
-
     def make_target(self, b: _Buffers, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """the regression target of train.py:238-252 as an fp32 [B,H,W,3] tensor (needs b.eps) and the prediction weights."""
         if b.target is None:
             b.target = torch.zeros_like(b.eps)
-        a, c, w = self.objective_coefficients(b)
+        a, c, w = self.objective_coefficients(b.t_int)
         b._coef = (a, c, w)                                               # keep the vectors alive until the kernels ran
         call("gct2_mix_per_image", x.data_ptr(), b.eps.data_ptr(), a.data_ptr(), c.data_ptr(), b.target.data_ptr(), b.B,
              b.H * b.W * 3, self._stream())
@@ -805,7 +667,7 @@ class UNetEngine:
     def head_train(self, b: _Buffers, target: torch.Tensor, target_is_x: bool = False) -> torch.Tensor:
         """Dense(3) + fp32 MSE + both of their gradients in one pass over R_0 (gct2_dense_head_train)."""
         t, A = self.topo, self.arena
-        ls_ptr = self.ls_state.data_ptr() if self.ls_state is not None else None
+        ls_ptr = self._ls_ptr()
         call("gct2_dense_head_train", self.ctx.handle, self.dtype, b.R[0].data_ptr(), b.ld[0], A.pptr("dense.w"), A.pptr("dense.b"),
              Slot("x", target.data_ptr()) if target_is_x else target.data_ptr(), b.pred.data_ptr() if self.keep_pred else None, b.dR[0].data_ptr(), b.ldd[0], A.gptr("dense.w"), A.gptr("dense.b"),
              b.loss.data_ptr(), b.partials.data_ptr(), b.B * b.H * b.W, t.fu(0) + 3, 3, t.fu(0), ls_ptr, A.gptr("U0.b"),
@@ -826,7 +688,7 @@ class UNetEngine:
         t, A, n = self.topo, self.arena, self.topo.octaves
         Hi, Wi = b.hw[1]
         x, ldx = (b.R[1].data_ptr(), b.ld[1]) if n > 1 else (b.Dlast.data_ptr(), t.fd(0))
-        ls_ptr = self.ls_state.data_ptr() if self.ls_state is not None else None
+        ls_ptr = self._ls_ptr()
         call("gct2_convT4s2_fwd_head_train", self.ctx.handle, self.dtype, x, ldx, A.wptr("U0.w"), A.pptr("U0.b"),
              A.pptr("dense.w"), A.pptr("dense.b"), Slot("x", target.data_ptr()) if target_is_x else target.data_ptr(),
              b.pred.data_ptr() if self.keep_pred else None, b.dR[0].data_ptr(), b.ldd[0],
@@ -1006,21 +868,6 @@ class UNetEngine:
             self._wait_stream(caller, main)
 
     # ---- optimizer (train.py:50-65,75) -----------------------------------------------------------
-    def learning_rate(self, k: Optional[int] = None) -> float:
-        """WarmUp.__call__ (train.py:57-65), float32 arithmetic like the reference."""
-        k = self.iterations if k is None else k
-        if k < self.warm_up:
-            return float(np.float32(self.base_lr) * np.float32(k + 1) / np.float32(self.warm_up + 1))
-        return float(np.float32(self.base_lr))
-
-    def adam_alpha(self, k: Optional[int] = None) -> float:
-        """lr_k * sqrt(1 - b2^t) / (1 - b1^t), t = k + 1, with the betas as the float32 hyper-parameters Keras holds them as
-        [TF]; gct2_loss_scale_begin computes the same on the device when the step counter lives there."""
-        k = self.iterations if k is None else k
-        tt = k + 1
-        b1, b2 = float(np.float32(self.beta_1)), float(np.float32(self.beta_2))
-        return self.learning_rate(k) * math.sqrt(1.0 - b2 ** tt) / (1.0 - b1 ** tt)
-
     def apply_adam(self, lo: int = 0, hi: Optional[int] = None, grad_div: float = 1.0, stream: Optional[int] = None) -> None:
         """Keras Adam on arena range [lo, hi); does not advance `iterations` (see finish_step).
         grad_div > 1 folds the data-parallel mean (sum over ranks / world size) into the gradient read."""
@@ -1032,29 +879,16 @@ class UNetEngine:
         hi = A.total if hi is None else hi
         # with loss scaling the kernel takes inv_scale / found_inf / alpha from the device-resident state (the step counter that
         # alpha depends on only advances on applied steps); otherwise alpha comes from the host's counter
-        ls_ptr = self.ls_state.data_ptr() if self.ls_state is not None else None
+        ls_ptr = self._ls_ptr()
         alpha = 0.0 if self.ls_state is not None else self.adam_alpha()
         shadow = None if A._shadow is None else A._shadow.data_ptr() + 2 * lo
         call("gct2_adam_keras_multi", A._p.data_ptr() + 4 * lo, A._m.data_ptr() + 4 * lo, A._v.data_ptr() + 4 * lo,
              A.g.data_ptr() + 4 * lo, shadow, self.dtype, hi - lo, Slot("alpha", alpha), self.beta_1, self.beta_2,
              self.epsilon, 1.0 / grad_div, ls_ptr, 0, s)
 
-    def finish_step(self) -> None:
-        if self.ls_state is not None:      # applied_steps (= optimizer.iterations) advances on the device, only if finite
-            call("gct2_loss_scale_update", self.ls_state.data_ptr(), 2000, self._stream())
-        else:
-            self._iterations += 1
-
-    def begin_step(self) -> None:
-        if self.ls_state is not None:
-            call("gct2_loss_scale_begin", self.ls_state.data_ptr(), float(self.base_lr), int(self.warm_up), float(self.beta_1),
-                 float(self.beta_2), self._stream())
-
     def check_finite(self, lo: int = 0, hi: Optional[int] = None, stream: Optional[int] = None) -> None:
-        if self.ls_state is not None:
-            hi = self.arena.total if hi is None else hi
-            call("gct2_scale_check_finite", self.arena.g.data_ptr() + 4 * lo, hi - lo, self.ls_state.data_ptr(),
-                 self._stream() if stream is None else stream)
+        hi = self.arena.total if hi is None else hi
+        self._check_finite(self.arena.g.data_ptr() + 4 * lo, hi - lo, stream)
 
     # ---- the whole step ---------------------------------------------------------------------------
     def train_step(self, x: torch.Tensor, t_int: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
@@ -1136,7 +970,7 @@ class UNetEngine:
                 # baked into recorded arguments (gct2_adam_keras_multi, gct2_loss_scale_begin) or restored into the per-layer
                 # gct2_adam_args by every replay: Trainer.compile() may legally rewrite them between steps
                 self.dtype, float(self.beta_1), float(self.beta_2), float(self.epsilon), float(self.base_lr), int(self.warm_up),
-                id(self.post_replay), int(self.split_forward_levels), self._side.cuda_stream,
+                id(self.post_replay), self._side.cuda_stream,
                 self._chain_stream.cuda_stream if self._chain_stream is not None else 0)
 
     def _planned_step(self, b: _Buffers, x: torch.Tensor, apply: bool, inline: bool, cur: "torch.cuda.Stream") -> torch.Tensor:
@@ -1324,9 +1158,3 @@ class UNetEngine:
     def load_checkpoint(self, path: str) -> None:
         from safetensors.torch import load_file        # safetensors: loading executes nothing from the file
         self.load_state_dict(load_file(path))
-
-    def loss_scale(self) -> Tuple[float, int]:
-        if self.ls_state is None:
-            return 1.0, 0
-        raw = self.ls_state.cpu()
-        return float(raw[:1].view(torch.float32)[0]), int(raw[2])

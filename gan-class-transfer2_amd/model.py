@@ -16,6 +16,7 @@ from typing import Callable, Dict, Iterable, List, Optional, Sequence as Seq
 import torch
 
 from . import _lib
+from . import trainer_math
 from ._lib import BF16, F16, F32, call
 from .engine import TORCH_DTYPE, Topology, UNetEngine
 
@@ -86,10 +87,7 @@ class WarmUp:
         self.warmup_steps = warmup_steps
 
     def __call__(self, step):
-        import numpy as np
-        if step < self.warmup_steps:
-            return float(np.float32(self.base) * np.float32(step + 1) / np.float32(self.warmup_steps + 1))
-        return float(np.float32(self.base))
+        return trainer_math.warmup_lr(step, self.base, self.warmup_steps)
 
 
 class Adam:
@@ -127,10 +125,22 @@ def default_optimizer():
     return LossScaleOptimizer(opt) if mixed_precision else opt
 
 
+def engine_hyper_parameters(optimizer) -> Dict[str, object]:
+    """an optimizer (train.py:75, 82-83) as the engines' hyper-parameter attributes / constructor arguments; a learning rate
+    that is neither a WarmUp nor a constant leaves base_lr and warm_up out"""
+    inner = getattr(optimizer, "inner", optimizer)
+    kw = dict(beta_1=inner.beta_1, beta_2=inner.beta_2, epsilon=inner.epsilon)
+    lr = inner.learning_rate
+    if isinstance(lr, WarmUp):
+        kw.update(base_lr=lr.base, warm_up=lr.warmup_steps)
+    elif not callable(lr):
+        kw.update(base_lr=float(lr), warm_up=0)
+    return kw
+
+
 def alpha_dash(t):
-    """train.py:85-93"""
-    t = t / (steps + 1)
-    return (1 - t) ** 2 * 0.25
+    """train.py:85-93 (reads the module-level `steps` when called, like the reference)"""
+    return trainer_math.alpha_dash(t, steps)
 
 
 test_step = 25  # train.py:95
@@ -236,12 +246,9 @@ class _ConvLayer(Layer):
     def build(self, input_shape):
         if self.kernel is not None:
             return
-        import math
-        cin = input_shape[-1]
-        shp = self._kernel_shape(cin)
-        lim = math.sqrt(6.0 / (16 * shp[2] + 16 * shp[3]))
+        shp = self._kernel_shape(input_shape[-1])
         dev = torch.device("cuda", torch.cuda.current_device())
-        self.kernel = ((torch.rand(shp) * 2 - 1) * lim).to(dev)
+        self.kernel = ((torch.rand(shp) * 2 - 1) * trainer_math.glorot_limit(shp)).to(dev)
         self.bias = torch.zeros(self.filters, device=dev)
 
     def _operand_tensor(self) -> torch.Tensor:
@@ -253,16 +260,6 @@ class Conv3x3(_ConvLayer):
 
     def _kernel_shape(self, cin):
         return (3, 3, cin, self.filters)
-
-    def build(self, input_shape):
-        if self.kernel is not None:
-            return
-        import math
-        cin = input_shape[-1]
-        lim = math.sqrt(6.0 / (9 * cin + 9 * self.filters))
-        dev = torch.device("cuda", torch.cuda.current_device())
-        self.kernel = ((torch.rand(3, 3, cin, self.filters) * 2 - 1) * lim).to(dev)
-        self.bias = torch.zeros(self.filters, device=dev)
 
     def call(self, input):
         x = _as_compute(input, self.dtype_code)
@@ -322,11 +319,9 @@ class Dense(Layer):
     def build(self, input_shape):
         if self.kernel is not None:
             return
-        import math
-        cin = input_shape[-1]
-        lim = math.sqrt(6.0 / (cin + self.units))
+        shp = (input_shape[-1], self.units)
         dev = torch.device("cuda", torch.cuda.current_device())
-        self.kernel = ((torch.rand(cin, self.units) * 2 - 1) * lim).to(dev)
+        self.kernel = ((torch.rand(shp) * 2 - 1) * trainer_math.glorot_limit(shp)).to(dev)
         self.bias = torch.zeros(self.units, device=dev) if self.use_bias else None
 
     def call(self, input):
@@ -390,21 +385,19 @@ class Denoiser(Layer):
         on_epoch_begin, or `trainer(...)` - the engine gets the objective switches of train.py:29-32 from the module-level
         globals (train.py reads them as module constants at call time; r02 took them from Trainer's constructor only, so an
         engine built by anything else silently trained the default objective)."""
-        if self.engine is None and self.variant():
+        if self.engine is not None:
+            return self.engine
+        # no optimizer known yet (train.py:505-509 calls the model before compile): the module-level mixed_precision
+        # decides about loss scaling, as it decides about the LossScaleOptimizer wrapper in train.py:82-83
+        kw = dict(steps=steps, warm_up=warm_up, seed=self._seed, loss_scaling=bool(mixed_precision), **objective_switches())
+        if self.dtype_code == F32:
+            kw["f32_matrix"] = bool(f32_matrix_cores)
+        kw.update(engine_kw)
+        if self.variant():
             from .variants import VariantEngine
-            kw = dict(steps=steps, warm_up=warm_up, seed=self._seed, loss_scaling=bool(mixed_precision), **objective_switches())
-            if self.dtype_code == F32:
-                kw["f32_matrix"] = bool(f32_matrix_cores)
-            kw.update(engine_kw)
             self.engine = VariantEngine(pixel_size, max_size, octaves, block_depth, residual, concat, self.dtype_code, self._device, **kw)
             self._bind_variant_parameters()
-        if self.engine is None:
-            # no optimizer known yet (train.py:505-509 calls the model before compile): the module-level mixed_precision
-            # decides about loss scaling, as it decides about the LossScaleOptimizer wrapper in train.py:82-83
-            kw = dict(steps=steps, warm_up=warm_up, seed=self._seed, loss_scaling=bool(mixed_precision), **objective_switches())
-            if self.dtype_code == F32:
-                kw["f32_matrix"] = bool(f32_matrix_cores)
-            kw.update(engine_kw)
+        else:
             self.engine = UNetEngine(self.topology, self.dtype_code, self._device, **kw)
             A = self.engine.arena
             for i in range(octaves):
@@ -490,16 +483,10 @@ class Trainer(Layer):
         opt = self.optimizer
         kw = {}
         if opt is not None and self.denoiser.engine is None:
-            inner = getattr(opt, "inner", opt)
-            kw.update(beta_1=inner.beta_1, beta_2=inner.beta_2, epsilon=inner.epsilon,
-                      loss_scaling=bool(inner.loss_scaling))
-            lr = inner.learning_rate
-            if isinstance(lr, WarmUp):
-                kw.update(base_lr=lr.base, warm_up=lr.warmup_steps)
-            elif not callable(lr):
-                kw.update(base_lr=float(lr), warm_up=0)
-            else:
+            kw = engine_hyper_parameters(opt)
+            if "base_lr" not in kw:
                 raise NotImplementedError("only WarmUp or constant learning rates are supported")
+            kw["loss_scaling"] = bool(getattr(opt, "inner", opt).loss_scaling)
         eng = self.denoiser.ensure_engine(**kw)
         # train.py:238-252 reads the objective globals every time Trainer.call runs: an engine built earlier (by denoiser(...),
         # trainable_variables, the log_sample callback) follows the switches as they stand now
@@ -528,12 +515,8 @@ class Trainer(Layer):
         """train.py:511-514"""
         if self.denoiser.engine is not None and optimizer is not None:
             eng, inner = self.denoiser.engine, getattr(optimizer, "inner", optimizer)
-            eng.beta_1, eng.beta_2, eng.epsilon = inner.beta_1, inner.beta_2, inner.epsilon
-            lr = inner.learning_rate
-            if isinstance(lr, WarmUp):
-                eng.base_lr, eng.warm_up = lr.base, lr.warmup_steps
-            elif not callable(lr):
-                eng.base_lr, eng.warm_up = float(lr), 0
+            for k, v in engine_hyper_parameters(optimizer).items():
+                setattr(eng, k, v)
             if inner.loss_scaling and eng.ls_state is None:
                 eng.enable_loss_scaling()                 # train.py:505-514: the model is called before compile
             elif not inner.loss_scaling and eng.ls_state is not None:

@@ -19,11 +19,7 @@ from . import _lib
 from . import model as M
 from ._lib import SAMPLE_EPS, SAMPLE_ODE, SAMPLE_SCALED_EPS, SAMPLE_X, call
 from .engine import TORCH_DTYPE, UNetEngine
-
-
-def _alpha(t: float, steps: int) -> float:
-    tt = t / (steps + 1)                        # train.py:85-93, python floats as in the reference
-    return (1 - tt) ** 2 * 0.25
+from .trainer_math import alpha_dash            # train.py:85-93 on python floats, as in the reference
 
 
 def sample_mode(predict_x: bool, predict_scaled_epsilon: bool, ordinary_differential_equation: bool) -> int:
@@ -120,12 +116,12 @@ class _Sampler:
              e.data_ptr() if e is not None else None, pred.numel(), self._stream())
 
     def step(self, B: int, x, e, fake, t: int) -> None:
-        a = _alpha(t, self.steps)
+        a = alpha_dash(t, self.steps)
         self.mix(B, x, e, a, fake)
         pred = self.evaluate(B)
         # ODE mode leaves epsilon_theta alone (train.py:382-392: only x_theta is assigned; `fake = ...` there is dead, the next
         # iteration recomputes it)
-        self.update(pred, fake, a, _alpha(t - 1, self.steps), x, None if self.mode == SAMPLE_ODE else e)
+        self.update(pred, fake, a, alpha_dash(t - 1, self.steps), x, None if self.mode == SAMPLE_ODE else e)
 
 
 def _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_differential_equation) -> int:
@@ -169,10 +165,10 @@ def log_sample(denoiser: "M.Denoiser", example_image: torch.Tensor, example: tor
 
     # ---- single-shot denoising (train.py:325-361): at test_step; ODE mode mixes with alpha_dash(steps / 2) ** 0.5
     if mode == SAMPLE_ODE:
-        factor = _alpha(steps / 2, steps) ** 0.5                  # train.py:326-328
-        a_t, a_prev = _alpha(steps / 2, steps), _alpha(steps / 2 - 1, steps)
+        factor = alpha_dash(steps / 2, steps) ** 0.5                  # train.py:326-328
+        a_t, a_prev = alpha_dash(steps / 2, steps), alpha_dash(steps / 2 - 1, steps)
     else:
-        factor = _alpha(test_step, steps)
+        factor = alpha_dash(test_step, steps)
         a_t, a_prev = factor, 0.0
     fake = torch.empty_like(image)
     S.mix(1, image, example[0, :1].contiguous(), factor, fake)

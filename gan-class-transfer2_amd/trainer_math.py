@@ -1,0 +1,198 @@
+"""The host-side arithmetic of the reference's `Trainer` (train.py:50-93, 223-272), once, for every engine.
+
+Pure functions (no GPU needed): the noise schedule, the WarmUp learning rate, the Adam step size, the Glorot limit and the
+per-image coefficients of the objective.  `TrainerState` is what `UNetEngine` and `VariantEngine` inherit: the hyper-parameters,
+the objective switches, the RNG stream positions, the step counter and the dynamic loss-scale state with its three calls.
+The order of the float32 operations in every formula is the reference's; the golden fixture of tests/test_trainer_math_cpu.py
+holds the values bit for bit.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import F32, call
+
+LOSS_SCALE_GROWTH_INTERVAL = 2000   # tf.keras.mixed_precision.LossScaleOptimizer's dynamic_growth_steps default [TF]
+
+
+def alpha_dash(t, steps: int):
+    """train.py:85-93; `t` a python float (the sampler) or a tensor (float32: the train step's t_int)."""
+    return (1 - t / (steps + 1)) ** 2 * 0.25
+
+
+def warmup_lr(k: int, base_lr: float, warm_up: int) -> float:
+    """WarmUp.__call__ (train.py:57-65) at optimizer.iterations = k, float32 arithmetic like the reference."""
+    if k < warm_up:
+        return float(np.float32(base_lr) * np.float32(k + 1) / np.float32(warm_up + 1))
+    return float(np.float32(base_lr))
+
+
+def adam_step_size(lr: float, k: int, beta_1: float, beta_2: float) -> float:
+    """lr * sqrt(1 - b2^t) / (1 - b1^t), t = k + 1, with the betas as the float32 hyper-parameters Keras holds them as [TF];
+    gct2_loss_scale_begin computes the same on the device when the step counter lives there."""
+    tt = k + 1
+    b1, b2 = float(np.float32(beta_1)), float(np.float32(beta_2))
+    return lr * math.sqrt(1.0 - b2 ** tt) / (1.0 - b1 ** tt)
+
+
+def glorot_limit(shape: Sequence[int]) -> float:
+    """limit of Keras glorot_uniform for a kernel [..., fan-in channels, fan-out channels] (train.py:134,149,162)."""
+    rf = int(np.prod(shape[:-2]))
+    return math.sqrt(6.0 / (rf * shape[-2] + rf * shape[-1]))
+
+
+def default_objective(predict_x: bool, ordinary_differential_equation: bool) -> bool:
+    """the network predicts the clean image and the target is the batch itself (train.py:243-244)"""
+    return bool(predict_x and not ordinary_differential_equation)
+
+
+def objective_weighted(predict_x: bool, prediction_weighting: bool, ordinary_differential_equation: bool) -> bool:
+    """train.py:250-252: prediction and target both scaled by sqrt(1 - alpha_dash(t)) (epsilon branch only)."""
+    return bool(not predict_x and not ordinary_differential_equation and prediction_weighting)
+
+
+def objective_coefficients(t_int: torch.Tensor, steps: int, predict_x: bool = True, predict_scaled_epsilon: bool = False,
+                           prediction_weighting: bool = False, ordinary_differential_equation: bool = False,
+                           ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """per-image (a, c, w) of train.py:238-252: target = a x + c eps, prediction weight w (ones unless objective_weighted) -
+    contiguous float32 vectors on t_int's device."""
+    t = t_int.to(torch.float32)
+    one, zero = torch.ones_like(t), torch.zeros_like(t)
+    if ordinary_differential_equation:                                # train.py:238-242
+        a1 = alpha_dash(t - 1, steps)
+        return a1.sqrt().contiguous(), (1 - a1).sqrt().contiguous(), one
+    if predict_x:                                                     # train.py:243-244
+        return one, zero, one
+    s = (1 - alpha_dash(t, steps)).sqrt()
+    c = s if predict_scaled_epsilon else one                          # train.py:245-248
+    if prediction_weighting:                                          # train.py:250-252
+        return zero, (c * s).contiguous(), s.contiguous()
+    return zero, c.contiguous(), one
+
+
+OBJECTIVE_SWITCHES = ("predict_x", "predict_scaled_epsilon", "prediction_weighting", "ordinary_differential_equation")
+
+
+class TrainerState:
+    """what a train-step engine holds besides its network: constructor arguments checked, then plain attributes that
+    `Trainer.compile()` may rewrite between steps (base_lr, warm_up, beta_1, beta_2, epsilon) and `Trainer` sets before every
+    step (the four objective switches of train.py:29-32; defaults = the reference's: the network predicts the clean image)."""
+
+    def __init__(self, dtype: int, device: Optional[torch.device], steps: int, base_lr: float, warm_up: int, beta_1: float,
+                 beta_2: float, epsilon: float, loss_scaling: bool, rng_seed: int, predict_x: bool, predict_scaled_epsilon: bool,
+                 prediction_weighting: bool, ordinary_differential_equation: bool, f32_matrix: bool):
+        who = type(self).__name__
+        if f32_matrix and dtype != F32:
+            raise ValueError(f"{who}: f32_matrix selects the fp32 matrix-core kernels and needs dtype F32")
+        self.lib = _lib.load()
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        if self.device.type != "cuda":
+            raise _lib.Gct2Error(f"{who} needs a HIP device (torch device 'cuda'); there is no CPU path")
+        if self.device.index is None:                       # ("cuda" without an index: the current device - the stream registry keys on it)
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        call("gct2_device_check")
+        self.dtype, self.steps = dtype, steps
+        # fp32 convolutions on the matrix cores (gct2_ctx_set_f32_math) in every call context the engine creates (_new_ctx); fixed at
+        # construction, so neither the step-plan key nor the sampler's graph cache needs it beyond the contexts' versions
+        self._f32_matrix = bool(f32_matrix)
+        self.base_lr, self.warm_up = base_lr, warm_up
+        self.beta_1, self.beta_2, self.epsilon = beta_1, beta_2, epsilon
+        self.predict_x, self.predict_scaled_epsilon = predict_x, predict_scaled_epsilon
+        self.prediction_weighting, self.ordinary_differential_equation = prediction_weighting, ordinary_differential_equation
+        self.rng_seed, self.rng_offset_t, self.rng_offset_eps = rng_seed, 0, 0
+        self._iterations = 0           # optimizer.iterations [TF] (with loss scaling the counter lives on the device)
+        self.loss_scaling = loss_scaling
+        self.ls_state = None
+        if loss_scaling:
+            self.enable_loss_scaling()
+
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    @property
+    def f32_matrix(self) -> bool:
+        """fp32 convolutions run on the matrix cores (constructor argument; read-only)"""
+        return self._f32_matrix
+
+    def _new_ctx(self) -> "_lib.Context":
+        """every call context of an engine comes from here: the engine-wide settings of a context (the fp32 math mode) are applied once"""
+        c = _lib.Context()
+        if self._f32_matrix:
+            c.set_f32_math(_lib.F32_MATH_MFMA)
+        return c
+
+    # ---- the objective (train.py:238-252) ------------------------------------------------------------------------------------
+    def default_objective(self) -> bool:
+        return default_objective(self.predict_x, self.ordinary_differential_equation)
+
+    def objective_weighted(self) -> bool:
+        return objective_weighted(self.predict_x, self.prediction_weighting, self.ordinary_differential_equation)
+
+    def objective_coefficients(self, t_int: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        return objective_coefficients(t_int, self.steps, *(getattr(self, k) for k in OBJECTIVE_SWITCHES))
+
+    # ---- optimizer (train.py:50-65,75) ---------------------------------------------------------------------------------------
+    def learning_rate(self, k: Optional[int] = None) -> float:
+        return warmup_lr(self.iterations if k is None else k, self.base_lr, self.warm_up)
+
+    def adam_alpha(self, k: Optional[int] = None) -> float:
+        k = self.iterations if k is None else k
+        return adam_step_size(self.learning_rate(k), k, self.beta_1, self.beta_2)
+
+    # ---- dynamic loss scaling (train.py:82-83) -------------------------------------------------------------------------------
+    def enable_loss_scaling(self, initial_scale: float = 2.0 ** 15) -> None:
+        """tf.keras.mixed_precision.LossScaleOptimizer (train.py:82-83): allocate the device-side state (32-byte
+        gct2_loss_scale_state).  Allowed until the first optimizer step, so `trainer(example)` may come before `compile`
+        exactly as in train.py:505-514."""
+        if self.ls_state is not None:
+            return
+        if self._iterations != 0:
+            raise _lib.Gct2Error("loss scaling cannot be switched on after optimizer steps have been applied")
+        self.loss_scaling = True
+        self.ls_state = torch.zeros(8, dtype=torch.int32, device=self.device)
+        call("gct2_loss_scale_init", self.ls_state.data_ptr(), float(initial_scale), self._stream())
+
+    @property
+    def iterations(self) -> int:
+        """optimizer.iterations [TF].  Under LossScaleOptimizer a skipped step does not advance it, and whether a step was
+        skipped is only known on the device: the counter lives there (gct2_loss_scale_state.applied_steps) and reading it
+        synchronises."""
+        if self.ls_state is not None:
+            return int(self.ls_state[4].item())
+        return self._iterations
+
+    @iterations.setter
+    def iterations(self, k: int) -> None:
+        self._iterations = int(k)
+        if self.ls_state is not None:
+            self.ls_state[4] = int(k)
+
+    def loss_scale(self) -> Tuple[float, int]:
+        """(current scale, finite steps since it last changed)"""
+        if self.ls_state is None:
+            return 1.0, 0
+        raw = self.ls_state.cpu()
+        return float(raw[:1].view(torch.float32)[0]), int(raw[2])
+
+    def _ls_ptr(self) -> Optional[int]:
+        return self.ls_state.data_ptr() if self.ls_state is not None else None
+
+    def begin_step(self) -> None:
+        if self.ls_state is not None:
+            call("gct2_loss_scale_begin", self.ls_state.data_ptr(), float(self.base_lr), int(self.warm_up), float(self.beta_1),
+                 float(self.beta_2), self._stream())
+
+    def _check_finite(self, grads_ptr: int, n: int, stream: Optional[int] = None) -> None:
+        if self.ls_state is not None:
+            call("gct2_scale_check_finite", grads_ptr, n, self.ls_state.data_ptr(), self._stream() if stream is None else stream)
+
+    def finish_step(self) -> None:
+        if self.ls_state is not None:      # applied_steps (= optimizer.iterations) advances on the device, only if finite
+            call("gct2_loss_scale_update", self.ls_state.data_ptr(), LOSS_SCALE_GROWTH_INTERVAL, self._stream())
+        else:
+            self._iterations += 1

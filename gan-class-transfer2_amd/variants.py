@@ -14,7 +14,6 @@ roofline: these branches are unreachable at the reference's defaults.
 """
 from __future__ import annotations
 
-import math
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -22,6 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import BF16, F16, F32, call
+from .trainer_math import TrainerState, glorot_limit
 
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 
@@ -29,12 +29,12 @@ TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 class _Net:
     """parameter bookkeeping shared by the nodes: one flat fp32 arena each for p, m, v, g and a compute-dtype operand copy."""
 
-    def __init__(self, dtype: int, device: torch.device):
+    def __init__(self, dtype: int, device: torch.device, ctx: "_lib.Context"):
         self.dtype, self.device = dtype, device
         self.specs: List[Tuple[str, Tuple[int, ...]]] = []
         self.offsets: Dict[str, int] = {}
         self.total = 0
-        self.ctx = _lib.Context()
+        self.ctx = ctx
 
     def declare(self, name: str, shape: Tuple[int, ...]) -> str:
         self.specs.append((name, shape))
@@ -259,7 +259,7 @@ def build_structure(net: _Net, pixel_size: int, max_size: int, octaves: int, blo
     return _Seq([b0, mid, b1, head]), c
 
 
-class VariantEngine:
+class VariantEngine(TrainerState):
     """train step of a Denoiser built with block_depth > 0 / residual / concat=False (same surface as UNetEngine where it matters:
     train_step, predict, get/set_params, get_grads, iterations, loss_scale, the objective switches, f32_matrix)."""
 
@@ -268,34 +268,17 @@ class VariantEngine:
                  beta_2: float = 0.999, epsilon: float = 1e-7, loss_scaling: bool = False, seed: int = 1234, rng_seed: int = 0,
                  predict_x: bool = True, predict_scaled_epsilon: bool = False, prediction_weighting: bool = False,
                  ordinary_differential_equation: bool = False, f32_matrix: bool = False):
-        if f32_matrix and dtype != F32:
-            raise ValueError("VariantEngine: f32_matrix selects the fp32 matrix-core kernels and needs dtype F32")
-        _lib.load()
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise _lib.Gct2Error("VariantEngine needs a HIP device (torch device 'cuda'); there is no CPU path")
-        call("gct2_device_check")
-        self.dtype, self.steps, self.octaves = dtype, steps, octaves
-        self.base_lr, self.warm_up, self.beta_1, self.beta_2, self.epsilon = base_lr, warm_up, beta_1, beta_2, epsilon
-        self.predict_x, self.predict_scaled_epsilon = predict_x, predict_scaled_epsilon
-        self.prediction_weighting, self.ordinary_differential_equation = prediction_weighting, ordinary_differential_equation
-        self.net = _Net(dtype, self.device)
-        # every fp32 convolution of the train step and of predict (the sampler) on the matrix cores (gct2_ctx_set_f32_math); the
-        # workspace below doubles as their split-K and weight-gradient scratch
-        self._f32_matrix = bool(f32_matrix)
-        if self._f32_matrix:
-            self.net.ctx.set_f32_math(_lib.F32_MATH_MFMA)
+        super().__init__(dtype, device, steps, base_lr, warm_up, beta_1, beta_2, epsilon, loss_scaling, rng_seed, predict_x,
+                         predict_scaled_epsilon, prediction_weighting, ordinary_differential_equation, f32_matrix)
+        self.octaves = octaves
+        # one call context for the train step and for predict (the sampler): with f32_matrix every fp32 convolution runs on the
+        # matrix cores, and the workspace below doubles as their split-K and weight-gradient scratch
+        self.net = _Net(dtype, self.device, self._new_ctx())
         self.workspace = torch.empty(16 << 18, dtype=torch.float32, device=self.device)
         self.net.ctx.set_workspace(self.workspace)
         self.top, self.head_cin = build_structure(self.net, pixel_size, max_size, octaves, block_depth, residual, concat)
         self.net.allocate()
         self.glorot_init(seed)
-        self._iterations = 0
-        self.ls_state = None
-        if loss_scaling:
-            self.ls_state = torch.zeros(8, dtype=torch.int32, device=self.device)
-            call("gct2_loss_scale_init", self.ls_state.data_ptr(), float(2 ** 15), self.net.stream())
-        self.rng_seed, self.rng_offset_t, self.rng_offset_eps = rng_seed, 0, 0
         self.partials = torch.zeros(1024, dtype=torch.float32, device=self.device)
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.last = {}
@@ -311,9 +294,7 @@ class VariantEngine:
         for name, shp in self.net.specs:
             if name.endswith(".b"):
                 continue
-            rf = int(np.prod(shp[:-2])) if len(shp) > 2 else 1
-            lim = math.sqrt(6.0 / (rf * shp[-2] + rf * shp[-1]))
-            self.net.view(self.net.p, name).copy_(((torch.rand(shp, generator=gen) * 2 - 1) * lim).to(self.device))
+            self.net.view(self.net.p, name).copy_(((torch.rand(shp, generator=gen) * 2 - 1) * glorot_limit(shp)).to(self.device))
         self.refresh_operands()
 
     def refresh_operands(self) -> None:
@@ -331,28 +312,7 @@ class VariantEngine:
     def get_grads(self):
         return {k: self.net.view(self.net.g, k).cpu().numpy().copy() for k in self.net.shapes}
 
-    @property
-    def f32_matrix(self) -> bool:
-        """fp32 convolutions run on the matrix cores (constructor argument; read-only)"""
-        return self._f32_matrix
-
-    @property
-    def iterations(self) -> int:
-        return int(self.ls_state[4].item()) if self.ls_state is not None else self._iterations
-
-    def loss_scale(self):
-        if self.ls_state is None:
-            return 1.0, 0
-        raw = self.ls_state.cpu()
-        return float(raw[:1].view(torch.float32)[0]), int(raw[2])
-
     # ---- the step -----------------------------------------------------------------------------------------------------------
-    def _alpha(self) -> float:
-        k = self._iterations
-        lr = float(np.float32(self.base_lr) * np.float32(k + 1) / np.float32(self.warm_up + 1)) if k < self.warm_up else float(np.float32(self.base_lr))
-        b1, b2 = float(np.float32(self.beta_1)), float(np.float32(self.beta_2))
-        return lr * math.sqrt(1.0 - b2 ** (k + 1)) / (1.0 - b1 ** (k + 1))
-
     def _noised(self, x, t_int, eps):
         B, H, W, _ = x.shape
         s = self.net.stream()
@@ -375,34 +335,16 @@ class VariantEngine:
 
     def _objective(self, x, t_int, eps):
         """(target fp32, prediction weights or None) of train.py:238-252."""
-        ode, px = self.ordinary_differential_equation, self.predict_x
-        if px and not ode:
+        if self.default_objective():
             return x, None
-        t = t_int.to(torch.float32)
-        ad = lambda u: 0.25 * (1.0 - u / (self.steps + 1)) ** 2
-        one, zero = torch.ones_like(t), torch.zeros_like(t)
-        w = None
-        if ode:
-            a1 = ad(t - 1)
-            a, c = a1.sqrt(), (1 - a1).sqrt()
-        else:
-            s = (1 - ad(t)).sqrt()
-            a, c = zero, (s if self.predict_scaled_epsilon else one)
-            if self.prediction_weighting:
-                c, w = c * s, s.contiguous()
-        a, c = a.contiguous(), c.contiguous()
+        a, c, w = self.objective_coefficients(t_int)
+        if not self.objective_weighted():
+            w = None
         target = torch.empty_like(x)
         call("gct2_mix_per_image", x.data_ptr(), eps.data_ptr(), a.data_ptr(), c.data_ptr(), target.data_ptr(), x.shape[0],
              x.numel() // x.shape[0], self.net.stream())
         self.last["coef"] = (a, c, w)
         return target, w
-
-    def enable_loss_scaling(self, initial_scale: float = 2.0 ** 15) -> None:
-        if self.ls_state is None:
-            if self._iterations:
-                raise _lib.Gct2Error("loss scaling cannot be switched on after optimizer steps have been applied")
-            self.ls_state = torch.zeros(8, dtype=torch.int32, device=self.device)
-            call("gct2_loss_scale_init", self.ls_state.data_ptr(), float(initial_scale), self.net.stream())
 
     def train_step(self, x, t_int=None, eps=None, apply: bool = True, backward: bool = True):
         """backward=False: Trainer.call (train.py:223-272), the loss of a freshly noised batch without gradients."""
@@ -414,16 +356,14 @@ class VariantEngine:
             raise ValueError(f"spatial size {H}x{W} is not divisible by 2**octaves (train.py:114-119)")
         s = self.net.stream()
         n = B * H * W * 3
-        if self.ls_state is not None:
-            call("gct2_loss_scale_begin", self.ls_state.data_ptr(), float(self.base_lr), int(self.warm_up), float(self.beta_1), float(self.beta_2), s)
+        self.begin_step()
         noised, t_int, eps = self._noised(x, t_int, eps)
         pred = self.top.fwd(noised)
         target, w = self._objective(x, t_int, eps)
         if w is not None:
             call("gct2_mix_per_image", pred.data_ptr(), None, w.data_ptr(), None, pred.data_ptr(), B, H * W * 3, s)
         dpred = torch.empty_like(pred)
-        ls_ptr = self.ls_state.data_ptr() if self.ls_state is not None else None
-        call("gct2_mse_fwd_bwd", pred.data_ptr(), target.data_ptr(), dpred.data_ptr(), self.loss.data_ptr(), self.partials.data_ptr(), n, ls_ptr, s)
+        call("gct2_mse_fwd_bwd", pred.data_ptr(), target.data_ptr(), dpred.data_ptr(), self.loss.data_ptr(), self.partials.data_ptr(), n, self._ls_ptr(), s)
         if w is not None:
             call("gct2_mix_per_image", dpred.data_ptr(), None, w.data_ptr(), None, dpred.data_ptr(), B, H * W * 3, s)
         self.last.update(pred=pred, noised=noised)
@@ -436,16 +376,11 @@ class VariantEngine:
 
     def apply_adam(self) -> None:
         N, s = self.net, self.net.stream()
-        if self.ls_state is not None:
-            call("gct2_scale_check_finite", N.g.data_ptr(), N.g.numel(), self.ls_state.data_ptr(), s)
+        self._check_finite(N.g.data_ptr(), N.g.numel(), s)
         shadow = N.op.data_ptr() if self.dtype != F32 else None
         call("gct2_adam_keras_multi", N.p.data_ptr(), N.m.data_ptr(), N.v.data_ptr(), N.g.data_ptr(), shadow, self.dtype, N.p.numel(),
-             0.0 if self.ls_state is not None else self._alpha(), self.beta_1, self.beta_2, self.epsilon, 1.0,
-             self.ls_state.data_ptr() if self.ls_state is not None else None, 0, s)
-        if self.ls_state is not None:
-            call("gct2_loss_scale_update", self.ls_state.data_ptr(), 2000, s)
-        else:
-            self._iterations += 1
+             0.0 if self.ls_state is not None else self.adam_alpha(), self.beta_1, self.beta_2, self.epsilon, 1.0, self._ls_ptr(), 0, s)
+        self.finish_step()
 
     def predict(self, noised: torch.Tensor) -> torch.Tensor:
         return self.top.fwd(noised.to(self.device, TORCH_DTYPE[self.dtype]).contiguous())
