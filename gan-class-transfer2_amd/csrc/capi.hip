@@ -4,52 +4,6 @@
 #include <cstdio>
 #include <cstring>
 
-// implemented in the kernel translation units
-bool tapgemm_mfma_supported(int dtype, const TapGemmParams& p);
-int tapgemm_mfma(gct2_ctx& c, int dtype, int form, int epi, const TapGemmParams& p, hipStream_t s);
-int tapgemm_direct(int dtype, int form, int epi, const TapGemmParams& p, hipStream_t s);
-bool wgrad_mfma_supported(int dtype, const WgradParams& p);
-int wgrad_mfma(gct2_ctx& c, int dtype, WgradParams p, hipStream_t s, WgradSlabs* defer);
-int wgrad_direct(int dtype, const WgradParams& p, hipStream_t s);
-int f32_tapgemm(gct2_ctx& c, int form, int epi, TapGemmParams p, hipStream_t s);
-int f32_wgrad(gct2_ctx& c, WgradParams p, hipStream_t s, WgradSlabs* defer);
-bool halo_head_supported(const gct2_ctx& c, int dtype, const TapGemmParams& p);
-int halo_head(gct2_ctx& c, int dtype, TapGemmParams p, float* dw, float* db, float* loss, float* db_up, int accumulate, hipStream_t s);
-bool rgb_fwd_supported(int dtype, const TapGemmParams& p);
-int rgb_fwd(int dtype, const TapGemmParams& p, hipStream_t s);
-bool rgb_fwd_writes_bits(const TapGemmParams& p);
-int pw_relu_bits(int dtype, const void* y, int ldy, size_t pixels, int channels, unsigned char* bits, int ldbits, hipStream_t s);   // pointwise.hip
-bool rgb_wgrad_supported(int dtype, const WgradParams& p);
-int rgb_wgrad(const gct2_ctx& c, int dtype, WgradParams p, hipStream_t s, WgradSlabs* defer);
-int pw_rng_uniform_int(uint64_t, uint64_t, uint64_t, int32_t*, size_t, int, int, hipStream_t);
-int pw_rng_normal(uint64_t, uint64_t, uint64_t, float*, size_t, hipStream_t);
-int pw_noise(int, const float*, const int32_t*, const float*, void*, int, void*, int, int, int, int, int, hipStream_t);
-int pw_noise_rng(int, const float*, const int32_t*, uint64_t, uint64_t, uint64_t, float*, void*, int, void*, int, int, int, int, int, hipStream_t);
-int pw_dense_fwd(int, const void*, int, const float*, const float*, float*, int, int, int, hipStream_t);
-int pw_dense_bwd(int, const void*, int, const float*, const float*, void*, int, float*, float*, int, int, int, int, int, hipStream_t);
-int pw_mse(const float*, const float*, float*, float*, float*, size_t, const float*, hipStream_t);
-int pw_dense_head_train(const gct2_ctx&, int, const void*, int, const float*, const float*, const float*, float*, void*, int, float*, float*,
-                        float*, float*, int, int, int, int, const float*, float*, const void*, int, int, hipStream_t);
-int pw_colsum(int, const void*, int, float*, size_t, int, float, hipStream_t);
-int pw_relu_mask(int, const void*, int, void*, int, size_t, int, hipStream_t);
-int pw_add(int, void*, int, const void*, int, size_t, int, hipStream_t);
-int pw_mix_per_image(const float*, const float*, const float*, const float*, float*, int, size_t, hipStream_t);
-int conv_s1_direct(int dtype, bool dgrad, const void* x, int ldx, const void* w, const float* bias, const void* act, int ldact, void* y, int ldy,
-                   int B, int H, int W, int K, int N, int KS, int relu, int accumulate, hipStream_t s);
-int conv_s1_wgrad_direct(int dtype, const void* x, int ldx, const void* dz, int lddz, float* dw, int B, int H, int W, int Cin, int Cout, int KS,
-                         int accumulate, hipStream_t s);
-int pw_diffusion_mix(int, const float*, const float*, float, float*, void*, int, void*, int, size_t, int, hipStream_t);
-int pw_diffusion_update(int, const float*, const float*, double, double, float*, float*, size_t, hipStream_t);
-int pw_noise_edits(const float*, const float*, int, float*, int, int, int, hipStream_t);
-int pw_image_prepare(const uint8_t*, const int64_t*, const int32_t*, float*, int, int, hipStream_t);
-int pw_adam(float*, float*, float*, float*, void*, int, size_t, float, float, float, float, float, const gct2_loss_scale_state*, int, hipStream_t,
-            const float* slabs = nullptr, int nslab = 0, size_t slab_stride = 0, size_t n_slab = 0);
-int pw_cast(int, const float*, void*, size_t, hipStream_t);
-int pw_ls_init(gct2_loss_scale_state*, float, hipStream_t);
-int pw_ls_begin(gct2_loss_scale_state*, float, int, float, float, hipStream_t);
-int pw_ls_check(const float*, size_t, gct2_loss_scale_state*, hipStream_t);
-int pw_ls_update(gct2_loss_scale_state*, int, hipStream_t);
-
 // the only static storage of the library, all of it per host thread: the text of the last error, and the context that stands in
 // for ctx = NULL (no scratch, automatic tiles; reset at every use)
 static thread_local char g_err[512] = "";
@@ -126,9 +80,15 @@ int finish_relu_bits(gct2_ctx& c, int dtype, const TapGemmParams& p, size_t pixe
 }
 // fp32 on the matrix cores (gct2_ctx_set_f32_math); force_direct wins, so the direct kernels stay the independent reference
 inline bool f32_on_mfma(const gct2_ctx& c, int dtype) { return dtype == GCT2_F32 && c.f32_math == GCT2_F32_MATH_MFMA && !c.force_direct; }
+// forward / input-gradient launch of every form: fp32 on the fp32 matrix cores when the ctx asks for them, 16-bit on the matrix cores
+// where their layouts allow it (stride-1 forms: kernel sizes <= 5), else one thread per output (the stride-1 fall-back logs nothing)
 int run_tapgemm(gct2_ctx& c, int dtype, int form, int epi, const TapGemmParams& p, void* stream) {
+  const bool s1 = form == FORM_S1 || form == FORM_S1T;
   if (f32_on_mfma(c, dtype)) return f32_tapgemm(c, form, epi, p, S(stream));
-  if (!c.force_direct && tapgemm_mfma_supported(dtype, p)) return tapgemm_mfma(c, dtype, form, epi, p, S(stream));
+  if (!c.force_direct && (!s1 || p.ks <= 5) && tapgemm_mfma_supported(dtype, p)) return tapgemm_mfma(c, dtype, form, epi, p, S(stream));
+  if (s1)
+    return conv_s1_direct(dtype, form == FORM_S1T, p.x, p.ldx, p.w, p.bias, p.act, p.ldact, p.y, p.ldy, p.B, p.Hs, p.Ws, p.K, p.N, p.ks, p.relu,
+                          p.accumulate, S(stream));
   gct2_log(c, "direct:tap");
   return tapgemm_direct(dtype, form, epi, p, S(stream));
 }
@@ -157,10 +117,13 @@ int run_dgrad(gct2_ctx& c, int dtype, int form, TapGemmParams p, size_t out_pixe
   if (int e = f32m ? f32_tapgemm(c, form, EPI_MASK, p, S(stream)) : tapgemm_direct(dtype, form, EPI_MASK, p, S(stream))) return e;
   return (db || db2) ? sums(1.f) : GCT2_OK;
 }
-int run_wgrad(gct2_ctx& c, int dtype, const WgradParams& p, void* stream, WgradSlabs* defer = nullptr) {
+// weight-gradient launch, 4x4 / stride-2 (p.ks == 0) or stride-1 (the stride-1 fall-back logs nothing)
+int run_wgrad(gct2_ctx& c, int dtype, const WgradParams& p, void* stream, WgradSlabs* defer) {
   if (f32_on_mfma(c, dtype)) return f32_wgrad(c, p, S(stream), defer);
   if (!c.force_direct && wgrad_mfma_supported(dtype, p)) return wgrad_mfma(c, dtype, p, S(stream), defer);
   if (defer) *defer = WgradSlabs{nullptr, 0, 0};
+  if (p.ks)
+    return conv_s1_wgrad_direct(dtype, p.big, p.ldbig, p.small, p.ldsmall, p.dw, p.B, p.Hs, p.Ws, p.Cb, p.Cs, p.ks, p.accumulate, S(stream));
   gct2_log(c, "direct:wgrad");
   return wgrad_direct(dtype, p, S(stream));
 }
@@ -180,13 +143,58 @@ int check_adam_args(const gct2_adam_args* a, const float* dw, size_t nw) {
     return gct2_fail(GCT2_EINVAL, "wgrad + adam: range shorter than the weight tensor or misaligned");
   return GCT2_OK;
 }
+// the optimizer launch of a gct2_adam_args: the kernel gradient (nw elements) is in dw or in the slabs `sl`
+int run_adam(const gct2_adam_args* a, float* dw, size_t nw, const WgradSlabs& sl, void* stream) {
+  return pw_adam(a->p, a->m, a->v, dw, a->shadow, a->shadow_dtype, a->n, a->alpha, a->beta1, a->beta2, a->eps, a->grad_mul, nullptr, 0,
+                 S(stream), sl.base, sl.nslab, sl.stride, sl.nslab ? nw : 0);
+}
 int adam_after_wgrad(gct2_adam_args* a, float* dw, size_t nw, const WgradSlabs& sl, void* stream) {
   if (a->defer) {      // the caller runs the step later (gct2_adam_apply): tell it where the kernel gradient is
     a->slab_base = sl.base; a->nslab = sl.nslab; a->slab_stride = sl.stride;
     return GCT2_OK;
   }
-  return pw_adam(a->p, a->m, a->v, dw, a->shadow, a->shadow_dtype, a->n, a->alpha, a->beta1, a->beta2, a->eps, a->grad_mul, nullptr, 0,
-                 S(stream), sl.base, sl.nslab, sl.stride, sl.nslab ? nw : 0);
+  return run_adam(a, dw, nw, sl, stream);
+}
+int check_s1(const char* fn, int KS) {
+  if (KS < 1 || KS > 7 || !(KS & 1)) return gct2_fail(GCT2_EINVAL, "%s: kernel size %d (odd, 1..7: 'same' padding is symmetric then)", fn, KS);
+  return GCT2_OK;
+}
+// The three weight-gradient entry points.  x: [B, H, W, Cin]; dz: [B, H/2, W/2, Cout] (WG_CONV), [B, 2H, 2W, Cout] (WG_CONVT) or
+// [B, H, W, Cout] (WG_S1, KS x KS taps); dw fp32 in the Keras layout of the layer, db fp32[Cout] or null.  The order of the checks
+// is part of the interface: it decides the message of a call with more than one mistake.
+enum WgradKind { WG_CONV, WG_CONVT, WG_S1 };
+int wgrad_entry(gct2_ctx* ctx, const char* fn, WgradKind kind, int dtype, const void* x, int ldx, const void* dz, int lddz, float* dw, float* db,
+                int B, int H, int W, int Cin, int Cout, int KS, int accumulate, gct2_adam_args* adam, void* stream) {
+  gct2_ctx& c = C(ctx);
+  if (int e = PlaneTaken(c).none(fn)) return e;
+  const int up = kind == WG_CONVT ? 2 : 1;           // (the argument checks see the larger of the two grids)
+  if (int e = check_conv_args(fn, dtype, x, dz, dw, B, up * H, up * W, Cin, Cout)) return e;
+  if (kind == WG_S1) if (int e = check_s1(fn, KS)) return e;
+  if (kind == WG_CONV && ((H & 1) || (W & 1))) return gct2_fail(GCT2_EINVAL, "%s: H=%d W=%d must be even", fn, H, W);
+  if (ldx < Cin || lddz < Cout) return gct2_fail(GCT2_EINVAL, "%s: ld smaller than channel count", fn);
+  if (adam && accumulate) return gct2_fail(GCT2_EINVAL, "%s: the fused optimizer step needs accumulate = 0", fn);
+  // WgradParams: the tensor on the BIG grid first (the transposed layer's is dz)
+  WgradParams p = kind == WG_CONV    ? WgradParams{x, ldx, dz, lddz, dw, B, H / 2, W / 2, Cin, Cout, 1}
+                  : kind == WG_CONVT ? WgradParams{dz, lddz, x, ldx, dw, B, H, W, Cout, Cin, 1}
+                                     : WgradParams{x, ldx, dz, lddz, dw, B, H, W, Cin, Cout, 1};
+  p.accumulate = accumulate ? 1 : 0;
+  p.ks = kind == WG_S1 ? KS : 0;
+  const size_t nw = (size_t)16 * Cin * Cout, dz_pixels = (size_t)B * p.Hs * p.Ws * (kind == WG_CONVT ? 4 : 1);
+  WgradSlabs sl{nullptr, 0, 0};
+  WgradSlabs* defer = adam ? &sl : nullptr;
+  if (adam) if (int e = check_adam_args(adam, dw, nw)) return e;
+  if (kind == WG_CONV && !c.force_direct && rgb_wgrad_supported(dtype, p)) {                  // image layer (Cin <= 4)
+    gct2_log(c, "rgb:wgrad");
+    if (int e = rgb_wgrad(c, dtype, p, S(stream), defer)) return e;
+  } else if (int e = run_wgrad(c, dtype, p, stream, defer)) return e;
+  if (db) if (int e = wgrad_db(c, dtype, dz, lddz, db, dz_pixels, Cout, accumulate, stream)) return e;
+  return adam ? adam_after_wgrad(adam, dw, nw, sl, stream) : GCT2_OK;
+}
+// the scratch setters: a ctx, and a null or 16-byte aligned buffer
+int check_scratch(const char* fn, const gct2_ctx* ctx, const void* buf) {
+  if (!ctx) return gct2_fail(GCT2_EINVAL, "%s: null ctx", fn);
+  if (buf && ((uintptr_t)buf % 16)) return gct2_fail(GCT2_EINVAL, "%s: pointer must be 16-byte aligned", fn);
+  return GCT2_OK;
 }
 }  // namespace
 
@@ -212,22 +220,19 @@ int gct2_ctx_destroy(gct2_ctx* ctx) {
   return GCT2_OK;
 }
 int gct2_ctx_set_workspace(gct2_ctx* ctx, void* ws, size_t bytes) {
-  if (!ctx) return gct2_fail(GCT2_EINVAL, "ctx_set_workspace: null ctx");
-  if (ws && ((uintptr_t)ws % 16)) return gct2_fail(GCT2_EINVAL, "ctx_set_workspace: pointer must be 16-byte aligned");
+  if (int e = check_scratch("ctx_set_workspace", ctx, ws)) return e;
   ctx->ws = ws ? reinterpret_cast<float*>(ws) : nullptr;
   ctx->ws_bytes = ws ? bytes : 0;
   return GCT2_OK;
 }
 int gct2_ctx_set_wgrad_workspace(gct2_ctx* ctx, void* ws, size_t bytes) {
-  if (!ctx) return gct2_fail(GCT2_EINVAL, "ctx_set_wgrad_workspace: null ctx");
-  if (ws && ((uintptr_t)ws % 16)) return gct2_fail(GCT2_EINVAL, "ctx_set_wgrad_workspace: pointer must be 16-byte aligned");
+  if (int e = check_scratch("ctx_set_wgrad_workspace", ctx, ws)) return e;
   ctx->wws = ws ? reinterpret_cast<float*>(ws) : nullptr;
   ctx->wws_bytes = ws ? bytes : 0;
   return GCT2_OK;
 }
 int gct2_ctx_set_bias_queue(gct2_ctx* ctx, void* buf, size_t bytes) {
-  if (!ctx) return gct2_fail(GCT2_EINVAL, "ctx_set_bias_queue: null ctx");
-  if (buf && ((uintptr_t)buf % 16)) return gct2_fail(GCT2_EINVAL, "ctx_set_bias_queue: pointer must be 16-byte aligned");
+  if (int e = check_scratch("ctx_set_bias_queue", ctx, buf)) return e;
   ctx->dbq_jobs.clear();                     // (row sets recorded and not flushed are dropped: flush before changing the buffer)
   ctx->dbq_used = 0;
   ctx->dbq = buf ? reinterpret_cast<float*>(buf) : nullptr;
@@ -351,24 +356,7 @@ int gct2_conv4s2_dgrad(gct2_ctx* ctx, int dtype, const void* dz, int lddz, const
 
 int gct2_conv4s2_wgrad(gct2_ctx* ctx, int dtype, const void* x, int ldx, const void* dz, int lddz, float* dw, float* db, int B, int H, int W,
                        int Cin, int Cout, int accumulate, gct2_adam_args* adam, void* stream) {
-  gct2_ctx& c = C(ctx);
-  if (int e = PlaneTaken(c).none("conv4s2_wgrad")) return e;
-  if (int e = check_conv_args("conv4s2_wgrad", dtype, x, dz, dw, B, H, W, Cin, Cout)) return e;
-  if ((H & 1) || (W & 1)) return gct2_fail(GCT2_EINVAL, "conv4s2_wgrad: H=%d W=%d must be even", H, W);
-  if (ldx < Cin || lddz < Cout) return gct2_fail(GCT2_EINVAL, "conv4s2_wgrad: ld smaller than channel count");
-  if (adam && accumulate) return gct2_fail(GCT2_EINVAL, "conv4s2_wgrad: the fused optimizer step needs accumulate = 0");
-  WgradParams p{x, ldx, dz, lddz, dw, B, H / 2, W / 2, Cin, Cout, 1};
-  p.accumulate = accumulate ? 1 : 0;
-  WgradSlabs sl{nullptr, 0, 0};
-  if (adam) if (int e = check_adam_args(adam, dw, (size_t)16 * Cin * Cout)) return e;
-  if (!c.force_direct && rgb_wgrad_supported(dtype, p)) {
-    gct2_log(c, "rgb:wgrad");
-    if (int e = rgb_wgrad(c, dtype, p, S(stream), adam ? &sl : nullptr)) return e;
-  } else if (int e = run_wgrad(c, dtype, p, stream, adam ? &sl : nullptr)) return e;
-  if (db)
-    if (int e = wgrad_db(c, dtype, dz, lddz, db, (size_t)B * (H / 2) * (W / 2), Cout, accumulate, stream)) return e;
-  if (adam) return adam_after_wgrad(adam, dw, (size_t)16 * Cin * Cout, sl, stream);
-  return GCT2_OK;
+  return wgrad_entry(ctx, "conv4s2_wgrad", WG_CONV, dtype, x, ldx, dz, lddz, dw, db, B, H, W, Cin, Cout, 0, accumulate, adam, stream);
 }
 
 int gct2_convT4s2_fwd(gct2_ctx* ctx, int dtype, const void* x, int ldx, const void* w, const float* bias, void* y, int ldy, int B, int H, int W,
@@ -418,73 +406,35 @@ int gct2_convT4s2_dgrad(gct2_ctx* ctx, int dtype, const void* dz, int lddz, cons
 
 int gct2_convT4s2_wgrad(gct2_ctx* ctx, int dtype, const void* x, int ldx, const void* dz, int lddz, float* dw, float* db, int B, int H, int W,
                         int Cin, int Cout, int accumulate, gct2_adam_args* adam, void* stream) {
-  gct2_ctx& c = C(ctx);
-  if (int e = PlaneTaken(c).none("convT4s2_wgrad")) return e;
-  if (int e = check_conv_args("convT4s2_wgrad", dtype, x, dz, dw, B, 2 * H, 2 * W, Cin, Cout)) return e;
-  if (ldx < Cin || lddz < Cout) return gct2_fail(GCT2_EINVAL, "convT4s2_wgrad: ld smaller than channel count");
-  if (adam && accumulate) return gct2_fail(GCT2_EINVAL, "convT4s2_wgrad: the fused optimizer step needs accumulate = 0");
-  WgradParams p{dz, lddz, x, ldx, dw, B, H, W, Cout, Cin, 1};
-  p.accumulate = accumulate ? 1 : 0;
-  WgradSlabs sl{nullptr, 0, 0};
-  if (adam) if (int e = check_adam_args(adam, dw, (size_t)16 * Cin * Cout)) return e;
-  if (int e = run_wgrad(c, dtype, p, stream, adam ? &sl : nullptr)) return e;
-  if (db)
-    if (int e = wgrad_db(c, dtype, dz, lddz, db, (size_t)B * (2 * H) * (2 * W), Cout, accumulate, stream)) return e;
-  if (adam) return adam_after_wgrad(adam, dw, (size_t)16 * Cin * Cout, sl, stream);
-  return GCT2_OK;
+  return wgrad_entry(ctx, "convT4s2_wgrad", WG_CONVT, dtype, x, ldx, dz, lddz, dw, db, B, H, W, Cin, Cout, 0, accumulate, adam, stream);
 }
 
 // ---- off-by-default model variants (train.py:20 block_depth, train.py:26 residual, train.py:29-32 targets) ----------------------
-static int check_s1(const char* fn, int dtype, const void* a, const void* b, const void* c, int B, int H, int W, int Cin, int Cout, int KS) {
-  if (int e = check_conv_args(fn, dtype, a, b, c, B, H, W, Cin, Cout)) return e;
-  if (KS < 1 || KS > 7 || !(KS & 1)) return gct2_fail(GCT2_EINVAL, "%s: kernel size %d (odd, 1..7: 'same' padding is symmetric then)", fn, KS);
-  return GCT2_OK;
-}
 int gct2_conv2d_s1_fwd(gct2_ctx* ctx, int dtype, const void* x, int ldx, const void* w, const float* bias, void* y, int ldy, int B, int H, int W,
                        int Cin, int Cout, int KS, int relu, void* stream) {
   gct2_ctx& c = C(ctx);
   if (int e = PlaneTaken(c).none("conv2d_s1_fwd")) return e;
-  if (int e = check_s1("conv2d_s1_fwd", dtype, x, w, y, B, H, W, Cin, Cout, KS)) return e;
+  if (int e = check_conv_args("conv2d_s1_fwd", dtype, x, w, y, B, H, W, Cin, Cout)) return e;
+  if (int e = check_s1("conv2d_s1_fwd", KS)) return e;
   if (ldx < Cin || ldy < Cout) return gct2_fail(GCT2_EINVAL, "conv2d_s1_fwd: ld smaller than channel count");
-  {   // matrix-core form (third tap-GEMM form: ks x ks taps on one grid): fp32 on the fp32 matrix cores when the ctx asks for them, 16-bit
-      // where its layouts allow it; else one thread per output
-    TapGemmParams p{x, ldx, w, bias, nullptr, 0, y, ldy, B, H, W, Cin, Cout, relu, 0};
-    p.ks = KS;
-    if (f32_on_mfma(c, dtype)) return f32_tapgemm(c, FORM_S1, EPI_BIAS_ACT, p, S(stream));
-    if (!c.force_direct && KS <= 5 && tapgemm_mfma_supported(dtype, p)) return tapgemm_mfma(c, dtype, FORM_S1, EPI_BIAS_ACT, p, S(stream));
-  }
-  return conv_s1_direct(dtype, false, x, ldx, w, bias, nullptr, 0, y, ldy, B, H, W, Cin, Cout, KS, relu, 0, S(stream));
+  TapGemmParams p{x, ldx, w, bias, nullptr, 0, y, ldy, B, H, W, Cin, Cout, relu, 0};     // third tap-GEMM form: ks x ks taps on one grid
+  p.ks = KS;
+  return run_tapgemm(c, dtype, FORM_S1, EPI_BIAS_ACT, p, stream);
 }
 int gct2_conv2d_s1_dgrad(gct2_ctx* ctx, int dtype, const void* dz, int lddz, const void* w, const void* act, int ldact, void* dx, int lddx, int B,
                          int H, int W, int Cin, int Cout, int KS, int accumulate, void* stream) {
   gct2_ctx& c = C(ctx);
   if (int e = PlaneTaken(c).none("conv2d_s1_dgrad")) return e;
-  if (int e = check_s1("conv2d_s1_dgrad", dtype, dz, w, dx, B, H, W, Cin, Cout, KS)) return e;
+  if (int e = check_conv_args("conv2d_s1_dgrad", dtype, dz, w, dx, B, H, W, Cin, Cout)) return e;
+  if (int e = check_s1("conv2d_s1_dgrad", KS)) return e;
   if (lddz < Cout || lddx < Cin || (act && ldact < Cin)) return gct2_fail(GCT2_EINVAL, "conv2d_s1_dgrad: ld smaller than channel count");
-  {
-    TapGemmParams p{dz, lddz, w, nullptr, act, ldact, dx, lddx, B, H, W, Cout, Cin, 0, accumulate};
-    p.ks = KS;
-    if (f32_on_mfma(c, dtype)) return f32_tapgemm(c, FORM_S1T, EPI_MASK, p, S(stream));
-    if (!c.force_direct && KS <= 5 && tapgemm_mfma_supported(dtype, p)) return tapgemm_mfma(c, dtype, FORM_S1T, EPI_MASK, p, S(stream));
-  }
-  return conv_s1_direct(dtype, true, dz, lddz, w, nullptr, act, ldact, dx, lddx, B, H, W, Cout, Cin, KS, 0, accumulate, S(stream));
+  TapGemmParams p{dz, lddz, w, nullptr, act, ldact, dx, lddx, B, H, W, Cout, Cin, 0, accumulate};
+  p.ks = KS;
+  return run_tapgemm(c, dtype, FORM_S1T, EPI_MASK, p, stream);
 }
 int gct2_conv2d_s1_wgrad(gct2_ctx* ctx, int dtype, const void* x, int ldx, const void* dz, int lddz, float* dw, float* db, int B, int H, int W,
                          int Cin, int Cout, int KS, int accumulate, void* stream) {
-  gct2_ctx& c = C(ctx);
-  if (int e = PlaneTaken(c).none("conv2d_s1_wgrad")) return e;
-  if (int e = check_s1("conv2d_s1_wgrad", dtype, x, dz, dw, B, H, W, Cin, Cout, KS)) return e;
-  if (ldx < Cin || lddz < Cout) return gct2_fail(GCT2_EINVAL, "conv2d_s1_wgrad: ld smaller than channel count");
-  WgradParams p{x, ldx, dz, lddz, dw, B, H, W, Cin, Cout, 1};
-  p.accumulate = accumulate ? 1 : 0;
-  p.ks = KS;
-  if (f32_on_mfma(c, dtype)) {
-    if (int e = f32_wgrad(c, p, S(stream), nullptr)) return e;
-  } else if (!c.force_direct && wgrad_mfma_supported(dtype, p)) {
-    if (int e = wgrad_mfma(c, dtype, p, S(stream), nullptr)) return e;
-  } else if (int e = conv_s1_wgrad_direct(dtype, x, ldx, dz, lddz, dw, B, H, W, Cin, Cout, KS, accumulate, S(stream))) return e;
-  if (db) return wgrad_db(c, dtype, dz, lddz, db, (size_t)B * H * W, Cout, accumulate, stream);
-  return GCT2_OK;
+  return wgrad_entry(ctx, "conv2d_s1_wgrad", WG_S1, dtype, x, ldx, dz, lddz, dw, db, B, H, W, Cin, Cout, KS, accumulate, nullptr, stream);
 }
 int gct2_relu_mask(int dtype, const void* act, int ldact, void* d, int ldd, size_t npix, int C, void* stream) {
   if (!dtype_ok(dtype) || !act || !d || C <= 0 || ldact < C || ldd < C) return gct2_fail(GCT2_EINVAL, "relu_mask: bad dtype, null pointer or ld < C");
@@ -615,8 +565,7 @@ int gct2_adam_apply(const gct2_adam_args* a, float* dw, size_t nw, void* stream)
   if (!a || !dw) return gct2_fail(GCT2_EINVAL, "adam_apply: null pointer");
   if (int e = check_adam_args(a, dw, nw)) return e;
   if (a->nslab < 0 || (a->nslab > 0 && (!a->slab_base || a->slab_stride < nw))) return gct2_fail(GCT2_EINVAL, "adam_apply: bad slab description");
-  return pw_adam(a->p, a->m, a->v, dw, a->shadow, a->shadow_dtype, a->n, a->alpha, a->beta1, a->beta2, a->eps, a->grad_mul, nullptr, 0,
-                 S(stream), a->slab_base, a->nslab, a->slab_stride, a->nslab ? nw : 0);
+  return run_adam(a, dw, nw, WgradSlabs{a->slab_base, a->nslab, a->slab_stride}, stream);
 }
 
 int gct2_cast_from_f32(int dtype, const float* src, void* dst, size_t n, void* stream) {

@@ -81,22 +81,25 @@ __global__ __launch_bounds__(256) void direct_wgrad_kernel(WgradParams p) {
   if (r_lo < r_hi) atomicAdd(p.dw + idx, acc);
 }
 
-template <typename T>
-int launch_tapgemm(int form, int epi, const TapGemmParams& p, hipStream_t s) {
+}  // namespace
+
+int tapgemm_direct(int dtype, int form, int epi, const TapGemmParams& p, hipStream_t s) {
   const size_t total = (size_t)p.B * p.Hs * p.Ws * p.N;
   dim3 grid((unsigned)((total + 255) / 256), 1, form == FORM_CONVT ? 4 : 1);
-  if (form == FORM_CONV) {
-    if (epi == EPI_BIAS_ACT) hipLaunchKernelGGL((direct_tapgemm_kernel<T, FORM_CONV, EPI_BIAS_ACT>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((direct_tapgemm_kernel<T, FORM_CONV, EPI_MASK>), grid, dim3(256), 0, s, p);
-  } else {
-    if (epi == EPI_BIAS_ACT) hipLaunchKernelGGL((direct_tapgemm_kernel<T, FORM_CONVT, EPI_BIAS_ACT>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((direct_tapgemm_kernel<T, FORM_CONVT, EPI_MASK>), grid, dim3(256), 0, s, p);
-  }
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (form == FORM_CONV) {
+      if (epi == EPI_BIAS_ACT) hipLaunchKernelGGL((direct_tapgemm_kernel<T, FORM_CONV, EPI_BIAS_ACT>), grid, dim3(256), 0, s, p);
+      else hipLaunchKernelGGL((direct_tapgemm_kernel<T, FORM_CONV, EPI_MASK>), grid, dim3(256), 0, s, p);
+    } else {
+      if (epi == EPI_BIAS_ACT) hipLaunchKernelGGL((direct_tapgemm_kernel<T, FORM_CONVT, EPI_BIAS_ACT>), grid, dim3(256), 0, s, p);
+      else hipLaunchKernelGGL((direct_tapgemm_kernel<T, FORM_CONVT, EPI_MASK>), grid, dim3(256), 0, s, p);
+    }
+  });
   return gct2_check_launch("direct_tapgemm");
 }
 
-template <typename T>
-int launch_wgrad(WgradParams p, hipStream_t s) {
+int wgrad_direct(int dtype, WgradParams p, hipStream_t s) {
   const size_t total = (size_t)16 * p.Cb * p.Cs;
   const int R = p.B * p.Hs * p.Ws;
   // enough threads to fill the chip: ~256k threads, each summing >= 64 rows
@@ -105,26 +108,11 @@ int launch_wgrad(WgradParams p, hipStream_t s) {
   p.rsplit = rsplit;
   dim3 grid((unsigned)((total + 255) / 256), 1, rsplit);
   if (!p.accumulate) (void)hipMemsetAsync(p.dw, 0, total * sizeof(float), s);      // the kernel adds with atomics
-  hipLaunchKernelGGL(direct_wgrad_kernel<T>, grid, dim3(256), 0, s, p);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(direct_wgrad_kernel<T>, grid, dim3(256), 0, s, p);
+  });
   return gct2_check_launch("direct_wgrad");
-}
-
-}  // namespace
-
-int tapgemm_direct(int dtype, int form, int epi, const TapGemmParams& p, hipStream_t s) {
-  switch (dtype) {
-    case GCT2_F32: return launch_tapgemm<float>(form, epi, p, s);
-    case GCT2_BF16: return launch_tapgemm<__bf16>(form, epi, p, s);
-    default: return launch_tapgemm<_Float16>(form, epi, p, s);
-  }
-}
-
-int wgrad_direct(int dtype, const WgradParams& p, hipStream_t s) {
-  switch (dtype) {
-    case GCT2_F32: return launch_wgrad<float>(p, s);
-    case GCT2_BF16: return launch_wgrad<__bf16>(p, s);
-    default: return launch_wgrad<_Float16>(p, s);
-  }
 }
 
 // ---- stride-1 'same' convolutions with a KS x KS kernel (KS odd): Block's Conv2D(filters, 3, 1, 'same', relu) (train.py:131-139)
@@ -207,43 +195,31 @@ __global__ __launch_bounds__(256) void direct_conv_s1_wgrad_kernel(const T* __re
   if (r_lo < r_hi) atomicAdd(dw + idx, acc);
 }
 
-template <typename T>
-int conv_s1_t(bool dgrad, const ConvS1Params& p, hipStream_t s) {
-  const size_t total = (size_t)p.B * p.H * p.W * p.N;
-  dim3 grid((unsigned)((total + 255) / 256));
-  if (dgrad) hipLaunchKernelGGL((direct_conv_s1_kernel<T, true>), grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((direct_conv_s1_kernel<T, false>), grid, dim3(256), 0, s, p);
-  return gct2_check_launch("conv2d_s1");
-}
-template <typename T>
-int conv_s1_wgrad_t(const void* x, int ldx, const void* dz, int lddz, float* dw, int B, int H, int W, int Cin, int Cout, int KS, int accumulate,
-                    hipStream_t s) {
-  const size_t total = (size_t)KS * KS * Cin * Cout;
-  const int R = B * H * W;
-  int rsplit = (int)((262144 + total - 1) / total);
-  rsplit = max(1, min(rsplit, (R + 63) / 64));
-  if (!accumulate) (void)hipMemsetAsync(dw, 0, total * sizeof(float), s);
-  hipLaunchKernelGGL(direct_conv_s1_wgrad_kernel<T>, dim3((unsigned)((total + 255) / 256), 1, rsplit), dim3(256), 0, s,
-                     reinterpret_cast<const T*>(x), ldx, reinterpret_cast<const T*>(dz), lddz, dw, B, H, W, Cin, Cout, KS, rsplit);
-  return gct2_check_launch("conv2d_s1_wgrad");
-}
-
 }  // namespace
 
 int conv_s1_direct(int dtype, bool dgrad, const void* x, int ldx, const void* w, const float* bias, const void* act, int ldact, void* y, int ldy,
                    int B, int H, int W, int K, int N, int KS, int relu, int accumulate, hipStream_t s) {
   ConvS1Params p{x, ldx, w, bias, act, ldact, y, ldy, B, H, W, K, N, KS, relu, accumulate, dgrad ? N : K, dgrad ? K : N};
-  switch (dtype) {
-    case GCT2_F32: return conv_s1_t<float>(dgrad, p, s);
-    case GCT2_BF16: return conv_s1_t<__bf16>(dgrad, p, s);
-    default: return conv_s1_t<_Float16>(dgrad, p, s);
-  }
+  const size_t total = (size_t)p.B * p.H * p.W * p.N;
+  dim3 grid((unsigned)((total + 255) / 256));
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (dgrad) hipLaunchKernelGGL((direct_conv_s1_kernel<T, true>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((direct_conv_s1_kernel<T, false>), grid, dim3(256), 0, s, p);
+  });
+  return gct2_check_launch("conv2d_s1");
 }
 int conv_s1_wgrad_direct(int dtype, const void* x, int ldx, const void* dz, int lddz, float* dw, int B, int H, int W, int Cin, int Cout, int KS,
                          int accumulate, hipStream_t s) {
-  switch (dtype) {
-    case GCT2_F32: return conv_s1_wgrad_t<float>(x, ldx, dz, lddz, dw, B, H, W, Cin, Cout, KS, accumulate, s);
-    case GCT2_BF16: return conv_s1_wgrad_t<__bf16>(x, ldx, dz, lddz, dw, B, H, W, Cin, Cout, KS, accumulate, s);
-    default: return conv_s1_wgrad_t<_Float16>(x, ldx, dz, lddz, dw, B, H, W, Cin, Cout, KS, accumulate, s);
-  }
+  const size_t total = (size_t)KS * KS * Cin * Cout;
+  const int R = B * H * W;
+  int rsplit = (int)((262144 + total - 1) / total);
+  rsplit = max(1, min(rsplit, (R + 63) / 64));
+  if (!accumulate) (void)hipMemsetAsync(dw, 0, total * sizeof(float), s);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(direct_conv_s1_wgrad_kernel<T>, dim3((unsigned)((total + 255) / 256), 1, rsplit), dim3(256), 0, s,
+                       reinterpret_cast<const T*>(x), ldx, reinterpret_cast<const T*>(dz), lddz, dw, B, H, W, Cin, Cout, KS, rsplit);
+  });
+  return gct2_check_launch("conv2d_s1_wgrad");
 }

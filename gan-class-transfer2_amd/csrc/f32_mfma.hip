@@ -16,8 +16,6 @@
 #include "gct2_common.h"
 #include <algorithm>
 
-int wgrad_reduce(const float* ws, float* dw, size_t n, int nsplit, int accumulate, hipStream_t s);   // wgrad_mfma.hip
-
 namespace {
 
 constexpr int FBM = 128, FBK = 16, FLD = 144;        // tile rows, reduction elements per stage, LDS row (floats)

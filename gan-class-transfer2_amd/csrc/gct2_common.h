@@ -15,10 +15,6 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
 typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
 
-// host-side error plumbing (capi.hip)
-int gct2_fail(int code, const char* fmt, ...);
-int gct2_check_launch(const char* what);
-
 // the call context of include/gct2.h: caller-owned scratch + tile-selection knobs.  Host memory, used by ONE host thread at a time
 // (the one-shot ReLU plane and the launch log are written by the layer entry points).
 struct gct2_ctx {
@@ -58,8 +54,6 @@ struct gct2_ctx {
     *bytes = ws_bytes; return ws;
   }
 };
-// appends "token;" to the launch log of the ctx when it is enabled (capi.hip)
-void gct2_log(gct2_ctx& c, const char* fmt, ...);
 
 #ifdef GCT2_STAMP
 // Diagnostic build only (make stamp / EXTRA=-DGCT2_STAMP; gct2_build_flags() says so and product hosts refuse the library).
@@ -334,11 +328,6 @@ __device__ __forceinline__ bool xcd_tile(int id, int m_tiles, int inner, int chu
 }
 
 // the atomic fall-backs of the fused bias gradients add into their targets: overwritten targets start from zero
-// bias queue of a call context (tapgemm_mfma.hip): record the partial rows a launch left in the queue buffer / reduce everything recorded
-int pw_occupy(int workgroups, unsigned long long ticks, hipStream_t s);      // pointwise.hip: gct2_stream_occupy
-int tapgemm_dbq_push(gct2_ctx& c, const float* part, int rows, const TapGemmParams& p, hipStream_t s);
-int tapgemm_dbq_flush(gct2_ctx& c, hipStream_t s);
-int tapgemm_dbq_flush_for(gct2_ctx& c, const float* db, int n0, const float* db2, int n1, hipStream_t s);   // in front of an immediate writer
 inline void zero_overwritten_db(const TapGemmParams& p, hipStream_t s) {
   if (p.db && !(p.db_acc & 1) && p.db_split > 0) (void)hipMemsetAsync(p.db, 0, (size_t)p.db_split * sizeof(float), s);
   if (p.db2 && !(p.db_acc & 2) && p.N > p.db_split) (void)hipMemsetAsync(p.db2, 0, (size_t)(p.N - p.db_split) * sizeof(float), s);
@@ -376,3 +365,101 @@ struct WgradParams {
 // wgrad_mfma(): when `defer` is non-null and the launch left its result as workspace slabs, the slab reduction is NOT launched and
 // the slabs are described here (the caller folds them into the optimizer read); nslab = 0 means dw holds the gradient
 struct WgradSlabs { const float* base; int nslab; size_t stride; };
+
+// ---- host side: dtype dispatch ---------------------------------------------------------------------------------------------------
+// with_dtype(dtype, f) calls f(DTypeTag<T>{}) with T = float / __bf16 / _Float16 for GCT2_F32 / GCT2_BF16 / anything else (callers
+// validate the code; an unknown one takes the _Float16 arm); with_dtype16 is the same for the 16-bit-only matrix-core files.  A generic
+// lambda reads the type with `using T = typename decltype(tag)::type;` - the ONE place where a dtype code turns into a type.
+template <typename T> struct DTypeTag { using type = T; };
+template <typename F> inline auto with_dtype16(int dtype, F&& f) {
+  if (dtype == GCT2_BF16) return f(DTypeTag<__bf16>{});
+  return f(DTypeTag<_Float16>{});
+}
+template <typename F> inline auto with_dtype(int dtype, F&& f) {
+  if (dtype == GCT2_F32) return f(DTypeTag<float>{});
+  return with_dtype16(dtype, f);
+}
+
+// ---- host side: every function one translation unit defines and another one calls, declared HERE and nowhere else (each defining
+// file includes this header, so a definition that drifts from its declaration does not compile) ---------------------------------------
+// capi.hip: error text of the calling thread / "token;" appended to the launch log of the ctx when it is enabled / hipGetLastError
+int gct2_fail(int code, const char* fmt, ...);
+void gct2_log(gct2_ctx& c, const char* fmt, ...);
+int gct2_check_launch(const char* what);
+
+// tapgemm_mfma.hip: forward / input-gradient GEMMs on the 16-bit matrix cores; the ordered row reduction of the fused bias gradients;
+// bias queue of a call context: record the partial rows a launch left in the queue buffer / reduce everything recorded /
+// reduce what is queued for targets that an immediate writer is about to touch
+bool tapgemm_mfma_supported(int dtype, const TapGemmParams& p);
+int tapgemm_mfma(gct2_ctx& c, int dtype, int form, int epi, const TapGemmParams& p, hipStream_t s);
+int tapgemm_dbpart_reduce(const float* part, int rows, const TapGemmParams& p, hipStream_t s);
+int tapgemm_dbq_push(gct2_ctx& c, const float* part, int rows, const TapGemmParams& p, hipStream_t s);
+int tapgemm_dbq_flush(gct2_ctx& c, hipStream_t s);
+int tapgemm_dbq_flush_for(gct2_ctx& c, const float* db, int n0, const float* db2, int n1, hipStream_t s);
+
+// halo_mfma.hip
+bool halo_convT_wanted(const gct2_ctx& c, int epi, const TapGemmParams& p);
+int halo_convT(gct2_ctx& c, int dtype, int epi, TapGemmParams p, hipStream_t s);
+bool halo_head_supported(const gct2_ctx& c, int dtype, const TapGemmParams& p);
+int halo_head(gct2_ctx& c, int dtype, TapGemmParams p, float* dw, float* db, float* loss, float* db_up, int accumulate, hipStream_t s);
+
+// wgrad_mfma.hip (wgrad_reduce: dw (+)= the sum of nsplit slabs, in slab order)
+bool wgrad_mfma_supported(int dtype, const WgradParams& p);
+int wgrad_mfma(gct2_ctx& c, int dtype, WgradParams p, hipStream_t s, WgradSlabs* defer);
+int wgrad_reduce(const float* ws, float* dw, size_t n, int nsplit, int accumulate, hipStream_t s);
+
+// rgb_mfma.hip: the image layer (<= 4 channels on one side)
+bool rgb_fwd_supported(int dtype, const TapGemmParams& p);
+bool rgb_fwd_writes_bits(const TapGemmParams& p);
+int rgb_fwd(int dtype, const TapGemmParams& p, hipStream_t s);
+bool rgb_wgrad_supported(int dtype, const WgradParams& p);
+int rgb_wgrad(const gct2_ctx& c, int dtype, WgradParams p, hipStream_t s, WgradSlabs* defer);
+
+// f32_mfma.hip: fp32 on the fp32 matrix cores
+int f32_tapgemm(gct2_ctx& c, int form, int epi, TapGemmParams p, hipStream_t s);
+int f32_wgrad(gct2_ctx& c, WgradParams p, hipStream_t s, WgradSlabs* defer);
+
+// direct_kernels.hip: one thread per output, every dtype
+int tapgemm_direct(int dtype, int form, int epi, const TapGemmParams& p, hipStream_t s);
+int wgrad_direct(int dtype, WgradParams p, hipStream_t s);
+int conv_s1_direct(int dtype, bool dgrad, const void* x, int ldx, const void* w, const float* bias, const void* act, int ldact, void* y, int ldy,
+                   int B, int H, int W, int K, int N, int KS, int relu, int accumulate, hipStream_t s);
+int conv_s1_wgrad_direct(int dtype, const void* x, int ldx, const void* dz, int lddz, float* dw, int B, int H, int W, int Cin, int Cout, int KS,
+                         int accumulate, hipStream_t s);
+
+// pointwise.hip
+int pw_occupy(int workgroups, unsigned long long ticks, hipStream_t s);
+int pw_rng_uniform_int(uint64_t seed, uint64_t stream_id, uint64_t offset, int32_t* out, size_t n, int lo, int hi, hipStream_t s);
+int pw_rng_normal(uint64_t seed, uint64_t stream_id, uint64_t offset, float* out, size_t n, hipStream_t s);
+int pw_noise(int dtype, const float* x, const int32_t* t, const float* eps, void* out, int ldout, void* out2, int ldout2, int B, int HW,
+             int C, int steps, hipStream_t s);
+int pw_noise_rng(int dtype, const float* x, const int32_t* t, uint64_t seed, uint64_t stream_id, uint64_t offset, float* eps_out, void* out,
+                 int ldout, void* out2, int ldout2, int B, int HW, int C, int steps, hipStream_t s);
+int pw_dense_fwd(int dtype, const void* x, int ldx, const float* w, const float* b, float* y, int M, int Cin, int Cout, hipStream_t s);
+int pw_dense_bwd(int dtype, const void* x, int ldx, const float* w, const float* dy, void* dx, int lddx, float* dw, float* db, int M,
+                 int Cin, int Cout, int Cmask, int accumulate, hipStream_t s);
+int pw_head_finish(const float* part, int rows, float* dw, float* db, float* loss, float* db_dx, int ndw, int Cout, float inv_n,
+                   int accumulate, hipStream_t s);
+int pw_dense_head_train(const gct2_ctx& c, int dtype, const void* x, int ld, const float* w, const float* b, const float* target, float* pred,
+                        void* dx, int lddx, float* dw, float* db, float* loss, float* partials, int M, int Cin, int Cout, int Cmask,
+                        const float* ls, float* db_dx, const void* x2, int ldx2, int accumulate, hipStream_t s);
+int pw_diffusion_mix(int dtype, const float* x, const float* e, float a, float* fake, void* out, int ldout, void* out2, int ldout2,
+                     size_t npix, int C, hipStream_t s);
+int pw_diffusion_update(int mode, const float* pred, const float* fake, double a, double a1, float* x, float* e, size_t n, hipStream_t s);
+int pw_noise_edits(const float* eps, const float* dict, int K, float* out, int H, int W, int C, hipStream_t s);
+int pw_image_prepare(const uint8_t* src, const int64_t* offsets, const int32_t* dims, float* dst, int B, int size, hipStream_t s);
+int pw_mse(const float* pred, const float* target, float* dpred, float* loss, float* partials, size_t n, const float* ls, hipStream_t s);
+int pw_relu_mask(int dtype, const void* act, int ldact, void* d, int ldd, size_t npix, int C, hipStream_t s);
+int pw_add(int dtype, void* dst, int lddst, const void* src, int ldsrc, size_t npix, int C, hipStream_t s);
+int pw_mix_per_image(const float* x, const float* eps, const float* a, const float* c, float* out, int B, size_t per_image, hipStream_t s);
+int pw_colsum(int dtype, const void* dz, int ld, float* db, size_t M, int C, float sign, hipStream_t s);
+// slabs != null: the gradient of the first n_slab elements is the sum of nslab slabs (slab_stride floats apart), not g
+int pw_adam(float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n, float alpha, float b1, float b2, float eps,
+            float grad_mul, const gct2_loss_scale_state* ls, int zero_grad, hipStream_t s, const float* slabs = nullptr, int nslab = 0,
+            size_t slab_stride = 0, size_t n_slab = 0);
+int pw_cast(int dtype, const float* src, void* dst, size_t n, hipStream_t s);
+int pw_ls_init(gct2_loss_scale_state* st, float scale, hipStream_t s);
+int pw_ls_begin(gct2_loss_scale_state* st, float base_lr, int warmup_steps, float b1, float b2, hipStream_t s);
+int pw_ls_check(const float* g, size_t n, gct2_loss_scale_state* st, hipStream_t s);
+int pw_ls_update(gct2_loss_scale_state* st, int growth_interval, hipStream_t s);
+int pw_relu_bits(int dtype, const void* y, int ldy, size_t pixels, int channels, unsigned char* bits, int ldbits, hipStream_t s);

@@ -618,8 +618,6 @@ __global__ __launch_bounds__(512, 2) void halo_convT_kernel(TapGemmParams p) {
 
 }  // namespace
 
-int tapgemm_dbpart_reduce(const float* part, int rows, const TapGemmParams& p, hipStream_t s);   // tapgemm_mfma.hip
-
 // the halo kernel takes FORM_CONVT problems whose SMALL grid tiles into 16 x 16 patches: the Conv2DTranspose forward
 // (bias + ReLU) and the Conv2D input gradient (mask / accumulate / fused bias gradient)
 bool halo_convT_wanted(const gct2_ctx& c, int epi, const TapGemmParams& p) {
@@ -633,9 +631,6 @@ bool halo_convT_wanted(const gct2_ctx& c, int epi, const TapGemmParams& p) {
   const int tiles = p.B * (p.Hs >> 4) * (p.Ws >> 4) * ((p.N + 63) / 64);
   return p.N <= 256 && tiles >= 256;          // measured vs tapgemm: U0 fwd 177 -> 136 us, U1 fwd 126 -> 120, U2 fwd 124 -> 122, D1 dgrad 88 -> 81, D2 dgrad 70 -> 66
 }
-
-int pw_head_finish(const float* part, int rows, float* dw, float* db, float* loss, float* db_dx, int ndw, int Cout, float inv_n,
-                   int accumulate, hipStream_t s);     // pointwise.hip
 
 // UpShuffle_0 forward with the train-step head in its epilogue (EPI_HEAD): needs N = 64 (one n-tile: a wave owns every channel
 // of its pixels), the shape constraints of the halo kernel and room for one partial row per work-group in the workspace.
@@ -660,8 +655,10 @@ int halo_head(gct2_ctx& c, int dtype, TapGemmParams p, float* dw, float* db, flo
 #endif
   dim3 grid(8 * p.xcd_chunk);
   gct2_log(c, "halo:convT:head");
-  if (dtype == GCT2_BF16) hipLaunchKernelGGL((halo_convT_kernel<__bf16, EPI_HEAD>), grid, dim3(512), 0, s, p);
-  else hipLaunchKernelGGL((halo_convT_kernel<_Float16, EPI_HEAD>), grid, dim3(512), 0, s, p);
+  with_dtype16(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((halo_convT_kernel<T, EPI_HEAD>), grid, dim3(512), 0, s, p);
+  });
   if (int e = gct2_check_launch("halo_head")) return e;
   return pw_head_finish(c.ws, p.m_tiles, dw, db, loss, db_up, p.head.Cin * p.head.Cout, p.head.Cout, 1.0f / p.head.count, accumulate, s);
 }
@@ -693,13 +690,11 @@ int halo_convT(gct2_ctx& c, int dtype, int epi, TapGemmParams p, hipStream_t s) 
 #endif
   dim3 grid(8 * p.xcd_chunk * p.n_tiles);
   gct2_log(c, "halo:convT:%s%s", epi == EPI_BIAS_ACT ? "bias_act" : "mask", p.bits ? ":bits" : "");
-  if (epi == EPI_BIAS_ACT) {
-    if (dtype == GCT2_BF16) hipLaunchKernelGGL((halo_convT_kernel<__bf16, EPI_BIAS_ACT>), grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((halo_convT_kernel<_Float16, EPI_BIAS_ACT>), grid, dim3(512), 0, s, p);
-  } else {
-    if (dtype == GCT2_BF16) hipLaunchKernelGGL((halo_convT_kernel<__bf16, EPI_MASK>), grid, dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((halo_convT_kernel<_Float16, EPI_MASK>), grid, dim3(512), 0, s, p);
-  }
+  with_dtype16(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (epi == EPI_BIAS_ACT) hipLaunchKernelGGL((halo_convT_kernel<T, EPI_BIAS_ACT>), grid, dim3(512), 0, s, p);
+    else hipLaunchKernelGGL((halo_convT_kernel<T, EPI_MASK>), grid, dim3(512), 0, s, p);
+  });
   if (epi == EPI_BIAS_ACT && p.bits) c.relu_bits_done = 1;      // the epilogue wrote the ReLU bit plane
   if (p.dbws) {
     if (queued) { if (int e = tapgemm_dbq_push(c, queued, p.m_tiles, p, s)) return e; }

@@ -972,76 +972,61 @@ int pw_rng_normal(uint64_t seed, uint64_t stream_id, uint64_t offset, float* out
   hipLaunchKernelGGL(rng_normal_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, seed, stream_id, offset, out, n);
   return gct2_check_launch("rng_normal");
 }
-template <typename T>
-static int noise_t(const float* x, const int32_t* t, const float* eps, void* out, int ldout, void* out2, int ldout2, int B, int HW, int C,
-                   int steps, hipStream_t s) {
-  const size_t npix = (size_t)B * HW;
-  hipLaunchKernelGGL(noise_kernel<T>, dim3(blocks_for(npix * C, 256)), dim3(256), 0, s, x, t, eps, reinterpret_cast<T*>(out), ldout,
-                     reinterpret_cast<T*>(out2), ldout2, npix, HW, C, steps + 1);
-  return gct2_check_launch("noise_image");
-}
 int pw_noise(int dtype, const float* x, const int32_t* t, const float* eps, void* out, int ldout, void* out2, int ldout2, int B, int HW,
              int C, int steps, hipStream_t s) {
-  if (dtype == GCT2_F32) return noise_t<float>(x, t, eps, out, ldout, out2, ldout2, B, HW, C, steps, s);
-  if (dtype == GCT2_BF16) return noise_t<__bf16>(x, t, eps, out, ldout, out2, ldout2, B, HW, C, steps, s);
-  return noise_t<_Float16>(x, t, eps, out, ldout, out2, ldout2, B, HW, C, steps, s);
-}
-template <typename T>
-static int noise_rng_t(const float* x, const int32_t* t, uint64_t seed, uint64_t sid, uint64_t off, float* eps_out, void* out, int ldout,
-                       void* out2, int ldout2, int B, int HW, int C, int steps, hipStream_t s) {
   const size_t npix = (size_t)B * HW;
-  if constexpr (sizeof(T) == 2) {
-    // the train step's call: 3 channels into the packed 4-slot image and nothing else, whole groups of four pixels / three counters
-    if (C == 3 && ldout == 4 && !out2 && !eps_out && off % 12 == 0 && npix % 4 == 0 && HW % 4 == 0 && (uintptr_t)x % 16 == 0 &&
-        (uintptr_t)out % 16 == 0) {
-      hipLaunchKernelGGL(noise_rng_px4_kernel<T>, dim3(blocks_for(npix / 4, 256)), dim3(256), 0, s, x, t, seed, sid, off >> 2,
-                         reinterpret_cast<T*>(out), npix / 4, HW, steps + 1);
-      return gct2_check_launch("noise_image_rng");
-    }
-  }
-  hipLaunchKernelGGL(noise_rng_kernel<T>, dim3(blocks_for(npix * C / 4 + 2, 256)), dim3(256), 0, s, x, t, seed, sid, off, eps_out,
-                     reinterpret_cast<T*>(out), ldout, reinterpret_cast<T*>(out2), ldout2, npix * C, HW, C, steps + 1);
-  return gct2_check_launch("noise_image_rng");
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(noise_kernel<T>, dim3(blocks_for(npix * C, 256)), dim3(256), 0, s, x, t, eps, reinterpret_cast<T*>(out), ldout,
+                       reinterpret_cast<T*>(out2), ldout2, npix, HW, C, steps + 1);
+  });
+  return gct2_check_launch("noise_image");
 }
 int pw_noise_rng(int dtype, const float* x, const int32_t* t, uint64_t seed, uint64_t sid, uint64_t off, float* eps_out, void* out,
                  int ldout, void* out2, int ldout2, int B, int HW, int C, int steps, hipStream_t s) {
-  if (dtype == GCT2_F32) return noise_rng_t<float>(x, t, seed, sid, off, eps_out, out, ldout, out2, ldout2, B, HW, C, steps, s);
-  if (dtype == GCT2_BF16) return noise_rng_t<__bf16>(x, t, seed, sid, off, eps_out, out, ldout, out2, ldout2, B, HW, C, steps, s);
-  return noise_rng_t<_Float16>(x, t, seed, sid, off, eps_out, out, ldout, out2, ldout2, B, HW, C, steps, s);
-}
-template <typename T>
-static int dense_fwd_t(const void* x, int ldx, const float* w, const float* b, float* y, int M, int Cin, int Cout, hipStream_t s) {
-  hipLaunchKernelGGL(dense_fwd_kernel<T>, dim3(blocks_for(M, 256)), dim3(256), Cin * 4 * sizeof(float), s, reinterpret_cast<const T*>(x), ldx,
-                     w, b, y, M, Cin, Cout);
-  return gct2_check_launch("dense_fwd");
+  const size_t npix = (size_t)B * HW;
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if constexpr (sizeof(T) == 2) {
+      // the train step's call: 3 channels into the packed 4-slot image and nothing else, whole groups of four pixels / three counters
+      if (C == 3 && ldout == 4 && !out2 && !eps_out && off % 12 == 0 && npix % 4 == 0 && HW % 4 == 0 && (uintptr_t)x % 16 == 0 &&
+          (uintptr_t)out % 16 == 0) {
+        hipLaunchKernelGGL(noise_rng_px4_kernel<T>, dim3(blocks_for(npix / 4, 256)), dim3(256), 0, s, x, t, seed, sid, off >> 2,
+                           reinterpret_cast<T*>(out), npix / 4, HW, steps + 1);
+        return;
+      }
+    }
+    hipLaunchKernelGGL(noise_rng_kernel<T>, dim3(blocks_for(npix * C / 4 + 2, 256)), dim3(256), 0, s, x, t, seed, sid, off, eps_out,
+                       reinterpret_cast<T*>(out), ldout, reinterpret_cast<T*>(out2), ldout2, npix * C, HW, C, steps + 1);
+  });
+  return gct2_check_launch("noise_image_rng");
 }
 int pw_dense_fwd(int dtype, const void* x, int ldx, const float* w, const float* b, float* y, int M, int Cin, int Cout, hipStream_t s) {
-  if (dtype == GCT2_F32) return dense_fwd_t<float>(x, ldx, w, b, y, M, Cin, Cout, s);
-  if (dtype == GCT2_BF16) return dense_fwd_t<__bf16>(x, ldx, w, b, y, M, Cin, Cout, s);
-  return dense_fwd_t<_Float16>(x, ldx, w, b, y, M, Cin, Cout, s);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(dense_fwd_kernel<T>, dim3(blocks_for(M, 256)), dim3(256), Cin * 4 * sizeof(float), s, reinterpret_cast<const T*>(x),
+                       ldx, w, b, y, M, Cin, Cout);
+  });
+  return gct2_check_launch("dense_fwd");
 }
-template <typename T>
-static int dense_bwd_t(const void* x, int ldx, const float* w, const float* dy, void* dx, int lddx, float* dw, float* db, int M, int Cin,
-                       int Cout, int Cmask, int accumulate, hipStream_t s) {
+int pw_dense_bwd(int dtype, const void* x, int ldx, const float* w, const float* dy, void* dx, int lddx, float* dw, float* db, int M,
+                 int Cin, int Cout, int Cmask, int accumulate, hipStream_t s) {
   constexpr int PIX = 128;
   if (!accumulate) {            // the kernel adds its per-work-group sums with atomics
     (void)hipMemsetAsync(dw, 0, (size_t)Cin * Cout * sizeof(float), s);
     if (db) (void)hipMemsetAsync(db, 0, (size_t)Cout * sizeof(float), s);
   }
-  const size_t lds = (size_t)Cin * 16 + PIX * 16 + (size_t)PIX * Cin * sizeof(T);
   const int ntiles = (M + PIX - 1) / PIX;
   const int grid = ntiles < 1024 ? ntiles : 1024;
-  auto kern = dense_bwd_kernel<T, PIX>;
-  if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, reinterpret_cast<const T*>(x), ldx, w, dy, reinterpret_cast<T*>(dx), lddx, dw, db,
-                     M, Cin, Cout, Cmask);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const size_t lds = (size_t)Cin * 16 + PIX * 16 + (size_t)PIX * Cin * sizeof(T);
+    auto kern = dense_bwd_kernel<T, PIX>;
+    if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, reinterpret_cast<const T*>(x), ldx, w, dy, reinterpret_cast<T*>(dx), lddx, dw,
+                       db, M, Cin, Cout, Cmask);
+  });
   return gct2_check_launch("dense_bwd");
-}
-int pw_dense_bwd(int dtype, const void* x, int ldx, const float* w, const float* dy, void* dx, int lddx, float* dw, float* db, int M,
-                 int Cin, int Cout, int Cmask, int accumulate, hipStream_t s) {
-  if (dtype == GCT2_F32) return dense_bwd_t<float>(x, ldx, w, dy, dx, lddx, dw, db, M, Cin, Cout, Cmask, accumulate, s);
-  if (dtype == GCT2_BF16) return dense_bwd_t<__bf16>(x, ldx, w, dy, dx, lddx, dw, db, M, Cin, Cout, Cmask, accumulate, s);
-  return dense_bwd_t<_Float16>(x, ldx, w, dy, dx, lddx, dw, db, M, Cin, Cout, Cmask, accumulate, s);
 }
 // the ordered finish of the head's partial rows, also used by the UpShuffle_0 forward that carries the head in its epilogue
 int pw_head_finish(const float* part, int rows, float* dw, float* db, float* loss, float* db_dx, int ndw, int Cout, float inv_n,
@@ -1051,68 +1036,57 @@ int pw_head_finish(const float* part, int rows, float* dw, float* db, float* los
   return gct2_check_launch("dense_head_finish");
 }
 
-template <typename T>
-static int dense_head_train_t(const gct2_ctx& c, const void* x, int ld, const float* w, const float* b, const float* target, float* pred,
-                              void* dx, int lddx, float* dw, float* db, float* loss, float* partials, int M, int Cin, int Cout, int Cmask,
-                              const float* ls, float* db_dx, const void* x2, int ldx2, int accumulate, hipStream_t s) {
-  // matrix-core version: the reference head (64 masked U_0 channels + 3 image channels -> 3 outputs) with a workspace in the ctx
-  const size_t ws_bytes = c.ws_bytes;
-  float* ws = c.ws;
-  if (Cmask == 64 && Cin >= 64 && Cin <= (x2 ? 68 : 72) && (x2 || ld >= 72) && Cout <= 3) {
-    const int ngroups = (M + 15) / 16;
-    const int grid = std::min(512, (ngroups + 3) / 4);
-    if (ws && ws_bytes >= (size_t)grid * HEAD_ROW * sizeof(float)) {
-      hipLaunchKernelGGL(dense_head_mfma_kernel<T>, dim3(grid), dim3(256), 0, s, reinterpret_cast<const T*>(x), ld, w, b, target, pred,
-                         reinterpret_cast<T*>(dx), lddx, ws, M, Cin, Cout, ls, reinterpret_cast<const T*>(x2), ldx2);
-      hipLaunchKernelGGL(dense_head_finish_kernel, dim3(HEAD_ROW / 32), dim3(1024), 0, s, ws, grid, dw, db, loss, db_dx, Cin * Cout, Cout,
-                         1.0f / ((float)M * (float)Cout), accumulate);
-      return gct2_check_launch("dense_head_train");
-    }
-  }
-  if (x2) return gct2_fail(GCT2_EINVAL, "dense_head_train: a split input (x2) needs the matrix-core version: Cmask = 64, Cin <= 68, "
-                                        "Cout <= 3 and a registered workspace");
-  if (!accumulate) {            // the LDS-tile kernel adds its per-work-group sums with atomics
-    (void)hipMemsetAsync(dw, 0, (size_t)Cin * Cout * sizeof(float), s);
-    if (db) (void)hipMemsetAsync(db, 0, (size_t)Cout * sizeof(float), s);
-    if (db_dx) (void)hipMemsetAsync(db_dx, 0, (size_t)Cmask * sizeof(float), s);
-  }
-  constexpr int PIX = 256;
-  const size_t lds = (size_t)PIX * ld * 2 + (size_t)PIX * Cmask * 2 + PIX * 16 + (size_t)ld * 16;
-  const int ntiles = (M + PIX - 1) / PIX;
-  const int grid = ntiles < 1024 ? ntiles : 1024;
-  auto kern = dense_head_train_kernel<T, PIX>;
-  static size_t attr_lds = 0;
-  if (lds > attr_lds) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_lds = lds;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, reinterpret_cast<const T*>(x), ld, w, b, target, pred, reinterpret_cast<T*>(dx),
-                     lddx, dw, db, partials, M, Cin, Cout, Cmask, ls, db_dx);
-  hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0, s, partials, grid, loss, 1.0f / ((float)M * (float)Cout));
-  return gct2_check_launch("dense_head_train");
-}
 int pw_dense_head_train(const gct2_ctx& c, int dtype, const void* x, int ld, const float* w, const float* b, const float* target, float* pred,
                         void* dx, int lddx, float* dw, float* db, float* loss, float* partials, int M, int Cin, int Cout, int Cmask,
                         const float* ls, float* db_dx, const void* x2, int ldx2, int accumulate, hipStream_t s) {
-  if (dtype == GCT2_BF16)
-    return dense_head_train_t<__bf16>(c, x, ld, w, b, target, pred, dx, lddx, dw, db, loss, partials, M, Cin, Cout, Cmask, ls, db_dx, x2, ldx2,
-                                      accumulate, s);
-  return dense_head_train_t<_Float16>(c, x, ld, w, b, target, pred, dx, lddx, dw, db, loss, partials, M, Cin, Cout, Cmask, ls, db_dx, x2, ldx2,
-                                      accumulate, s);
-}
-template <typename T>
-static int diffusion_mix_t(const float* x, const float* e, float a, float* fake, void* out, int ldout, void* out2, int ldout2, size_t npix,
-                           int C, hipStream_t s) {
-  const size_t n = npix * C;
-  hipLaunchKernelGGL(diffusion_mix_kernel<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, x, e, sqrtf(a), sqrtf(1.f - a), fake,
-                     reinterpret_cast<T*>(out), ldout, reinterpret_cast<T*>(out2), ldout2, n, C);
-  return gct2_check_launch("diffusion_mix");
+  const size_t ws_bytes = c.ws_bytes;
+  float* ws = c.ws;
+  return with_dtype16(dtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    // matrix-core version: the reference head (64 masked U_0 channels + 3 image channels -> 3 outputs) with a workspace in the ctx
+    if (Cmask == 64 && Cin >= 64 && Cin <= (x2 ? 68 : 72) && (x2 || ld >= 72) && Cout <= 3) {
+      const int ngroups = (M + 15) / 16;
+      const int grid = std::min(512, (ngroups + 3) / 4);
+      if (ws && ws_bytes >= (size_t)grid * HEAD_ROW * sizeof(float)) {
+        hipLaunchKernelGGL(dense_head_mfma_kernel<T>, dim3(grid), dim3(256), 0, s, reinterpret_cast<const T*>(x), ld, w, b, target, pred,
+                           reinterpret_cast<T*>(dx), lddx, ws, M, Cin, Cout, ls, reinterpret_cast<const T*>(x2), ldx2);
+        hipLaunchKernelGGL(dense_head_finish_kernel, dim3(HEAD_ROW / 32), dim3(1024), 0, s, ws, grid, dw, db, loss, db_dx, Cin * Cout, Cout,
+                           1.0f / ((float)M * (float)Cout), accumulate);
+        return gct2_check_launch("dense_head_train");
+      }
+    }
+    if (x2) return gct2_fail(GCT2_EINVAL, "dense_head_train: a split input (x2) needs the matrix-core version: Cmask = 64, Cin <= 68, "
+                                          "Cout <= 3 and a registered workspace");
+    if (!accumulate) {            // the LDS-tile kernel adds its per-work-group sums with atomics
+      (void)hipMemsetAsync(dw, 0, (size_t)Cin * Cout * sizeof(float), s);
+      if (db) (void)hipMemsetAsync(db, 0, (size_t)Cout * sizeof(float), s);
+      if (db_dx) (void)hipMemsetAsync(db_dx, 0, (size_t)Cmask * sizeof(float), s);
+    }
+    constexpr int PIX = 256;
+    const size_t lds = (size_t)PIX * ld * 2 + (size_t)PIX * Cmask * 2 + PIX * 16 + (size_t)ld * 16;
+    const int ntiles = (M + PIX - 1) / PIX;
+    const int grid = ntiles < 1024 ? ntiles : 1024;
+    auto kern = dense_head_train_kernel<T, PIX>;
+    static size_t attr_lds = 0;
+    if (lds > attr_lds) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      attr_lds = lds;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, reinterpret_cast<const T*>(x), ld, w, b, target, pred, reinterpret_cast<T*>(dx),
+                       lddx, dw, db, partials, M, Cin, Cout, Cmask, ls, db_dx);
+    hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0, s, partials, grid, loss, 1.0f / ((float)M * (float)Cout));
+    return gct2_check_launch("dense_head_train");
+  });
 }
 int pw_diffusion_mix(int dtype, const float* x, const float* e, float a, float* fake, void* out, int ldout, void* out2, int ldout2,
                      size_t npix, int C, hipStream_t s) {
-  if (dtype == GCT2_F32) return diffusion_mix_t<float>(x, e, a, fake, out, ldout, out2, ldout2, npix, C, s);
-  if (dtype == GCT2_BF16) return diffusion_mix_t<__bf16>(x, e, a, fake, out, ldout, out2, ldout2, npix, C, s);
-  return diffusion_mix_t<_Float16>(x, e, a, fake, out, ldout, out2, ldout2, npix, C, s);
+  const size_t n = npix * C;
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(diffusion_mix_kernel<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, x, e, sqrtf(a), sqrtf(1.f - a), fake,
+                       reinterpret_cast<T*>(out), ldout, reinterpret_cast<T*>(out2), ldout2, n, C);
+  });
+  return gct2_check_launch("diffusion_mix");
 }
 int pw_diffusion_update(int mode, const float* pred, const float* fake, double a, double a1, float* x, float* e, size_t n, hipStream_t s) {
   const dim3 grid(blocks_for(n, 256)), block(256);
@@ -1140,59 +1114,51 @@ int pw_mse(const float* pred, const float* target, float* dpred, float* loss, fl
   hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0, s, partials, nb, loss, 1.0f / (float)n);
   return gct2_check_launch("mse_fwd_bwd");
 }
-template <typename T>
-static int relu_mask_t(const void* act, int ldact, void* d, int ldd, size_t npix, int C, hipStream_t s) {
-  hipLaunchKernelGGL(relu_mask_kernel<T>, dim3(blocks_for(npix * C, 256)), dim3(256), 0, s, reinterpret_cast<const T*>(act), ldact,
-                     reinterpret_cast<T*>(d), ldd, npix * C, C);
+int pw_relu_mask(int dtype, const void* act, int ldact, void* d, int ldd, size_t npix, int C, hipStream_t s) {
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(relu_mask_kernel<T>, dim3(blocks_for(npix * C, 256)), dim3(256), 0, s, reinterpret_cast<const T*>(act), ldact,
+                       reinterpret_cast<T*>(d), ldd, npix * C, C);
+  });
   return gct2_check_launch("relu_mask");
 }
-int pw_relu_mask(int dtype, const void* act, int ldact, void* d, int ldd, size_t npix, int C, hipStream_t s) {
-  if (dtype == GCT2_F32) return relu_mask_t<float>(act, ldact, d, ldd, npix, C, s);
-  if (dtype == GCT2_BF16) return relu_mask_t<__bf16>(act, ldact, d, ldd, npix, C, s);
-  return relu_mask_t<_Float16>(act, ldact, d, ldd, npix, C, s);
-}
-template <typename T>
-static int add_t(void* dst, int lddst, const void* src, int ldsrc, size_t npix, int C, hipStream_t s) {
-  hipLaunchKernelGGL(add_kernel<T>, dim3(blocks_for(npix * C, 256)), dim3(256), 0, s, reinterpret_cast<T*>(dst), lddst,
-                     reinterpret_cast<const T*>(src), ldsrc, npix * C, C);
-  return gct2_check_launch("add");
-}
 int pw_add(int dtype, void* dst, int lddst, const void* src, int ldsrc, size_t npix, int C, hipStream_t s) {
-  if (dtype == GCT2_F32) return add_t<float>(dst, lddst, src, ldsrc, npix, C, s);
-  if (dtype == GCT2_BF16) return add_t<__bf16>(dst, lddst, src, ldsrc, npix, C, s);
-  return add_t<_Float16>(dst, lddst, src, ldsrc, npix, C, s);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(add_kernel<T>, dim3(blocks_for(npix * C, 256)), dim3(256), 0, s, reinterpret_cast<T*>(dst), lddst,
+                       reinterpret_cast<const T*>(src), ldsrc, npix * C, C);
+  });
+  return gct2_check_launch("add");
 }
 int pw_mix_per_image(const float* x, const float* eps, const float* a, const float* c, float* out, int B, size_t per_image, hipStream_t s) {
   const size_t n = (size_t)B * per_image;
   hipLaunchKernelGGL(mix_per_image_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, x, eps, a, c, out, n, per_image);
   return gct2_check_launch("mix_per_image");
 }
-template <typename T>
-static int colsum_t(const void* dz, int ld, float* db, size_t M, int C, float sign, hipStream_t s) {
+int pw_colsum(int dtype, const void* dz, int ld, float* db, size_t M, int C, float sign, hipStream_t s) {
   const int ctiles = (C + 63) / 64;
   int rblocks = (int)((M + 511) / 512);
   const int cap = (1024 + ctiles - 1) / ctiles;
   if (rblocks > cap) rblocks = cap;
   if (rblocks < 1) rblocks = 1;
   const int rows_per_block = (int)((M + rblocks - 1) / rblocks);
-  if constexpr (sizeof(T) == 2) {
-    if (C % 8 == 0 && ld % 8 == 0 && (uintptr_t)dz % 16 == 0) {
-      hipLaunchKernelGGL(colsum_vec_kernel<T>, dim3(ctiles, rblocks), dim3(256), 0, s, reinterpret_cast<const T*>(dz), ld, db, M, C,
-                         rows_per_block, sign);
-      return gct2_check_launch("colsum_vec");
+  const dim3 grid(ctiles, rblocks);
+  return with_dtype(dtype, [&](auto tag) -> int {
+    using T = typename decltype(tag)::type;
+    const T* src = reinterpret_cast<const T*>(dz);
+    if constexpr (sizeof(T) == 2) {
+      if (C % 8 == 0 && ld % 8 == 0 && (uintptr_t)dz % 16 == 0) {
+        hipLaunchKernelGGL(colsum_vec_kernel<T>, grid, dim3(256), 0, s, src, ld, db, M, C, rows_per_block, sign);
+        return gct2_check_launch("colsum_vec");
+      }
     }
-  }
-  hipLaunchKernelGGL(colsum_kernel<T>, dim3(ctiles, rblocks), dim3(256), 0, s, reinterpret_cast<const T*>(dz), ld, db, M, C, rows_per_block, sign);
-  return gct2_check_launch("colsum");
-}
-int pw_colsum(int dtype, const void* dz, int ld, float* db, size_t M, int C, float sign, hipStream_t s) {
-  if (dtype == GCT2_F32) return colsum_t<float>(dz, ld, db, M, C, sign, s);
-  if (dtype == GCT2_BF16) return colsum_t<__bf16>(dz, ld, db, M, C, sign, s);
-  return colsum_t<_Float16>(dz, ld, db, M, C, sign, s);
+    hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(256), 0, s, src, ld, db, M, C, rows_per_block, sign);
+    return gct2_check_launch("colsum");
+  });
 }
 int pw_adam(float* p, float* m, float* v, float* g, void* shadow, int sdt, size_t n, float alpha, float b1, float b2, float eps,
-            float grad_mul, const gct2_loss_scale_state* ls, int zero_grad, hipStream_t s,
-            const float* slabs, int nslab, size_t slab_stride, size_t n_slab) {
+            float grad_mul, const gct2_loss_scale_state* ls, int zero_grad, hipStream_t s, const float* slabs, int nslab, size_t slab_stride,
+            size_t n_slab) {
   if (n == 0) return GCT2_OK;
   const int nb = blocks_for(n / 4 + 4, 256);
 #define GCT2_ADAM(S, HS) hipLaunchKernelGGL((adam_kernel<S, HS>), dim3(nb), dim3(256), 0, s, p, m, v, g, reinterpret_cast<S*>(shadow), n, alpha, b1, b2, eps, grad_mul, ls, zero_grad, slabs, nslab, slab_stride, n_slab)
@@ -1206,9 +1172,10 @@ int pw_adam(float* p, float* m, float* v, float* g, void* shadow, int sdt, size_
 int pw_cast(int dtype, const float* src, void* dst, size_t n, hipStream_t s) {
   if (n == 0) return GCT2_OK;
   const int nb = blocks_for(n, 256);
-  if (dtype == GCT2_BF16) hipLaunchKernelGGL(cast_kernel<__bf16>, dim3(nb), dim3(256), 0, s, src, reinterpret_cast<__bf16*>(dst), n);
-  else if (dtype == GCT2_F16) hipLaunchKernelGGL(cast_kernel<_Float16>, dim3(nb), dim3(256), 0, s, src, reinterpret_cast<_Float16*>(dst), n);
-  else hipLaunchKernelGGL(cast_kernel<float>, dim3(nb), dim3(256), 0, s, src, reinterpret_cast<float*>(dst), n);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(cast_kernel<T>, dim3(nb), dim3(256), 0, s, src, reinterpret_cast<T*>(dst), n);
+  });
   return gct2_check_launch("cast_from_f32");
 }
 int pw_ls_init(gct2_loss_scale_state* st, float scale, hipStream_t s) {
@@ -1250,9 +1217,10 @@ int pw_relu_bits(int dtype, const void* y, int ldy, size_t pixels, int channels,
   const size_t n = pixels * (size_t)groups;
   if (!n) return GCT2_OK;
   const dim3 grid((unsigned)((n + 255) / 256));
-  if (dtype == GCT2_F32) hipLaunchKernelGGL(relu_bits_kernel<float>, grid, dim3(256), 0, s, (const float*)y, ldy, pixels, groups, bits, ldbits);
-  else if (dtype == GCT2_BF16) hipLaunchKernelGGL(relu_bits_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)y, ldy, pixels, groups, bits, ldbits);
-  else hipLaunchKernelGGL(relu_bits_kernel<_Float16>, grid, dim3(256), 0, s, (const _Float16*)y, ldy, pixels, groups, bits, ldbits);
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(relu_bits_kernel<T>, grid, dim3(256), 0, s, (const T*)y, ldy, pixels, groups, bits, ldbits);
+  });
   return gct2_check_launch("relu_bits");
 }
 

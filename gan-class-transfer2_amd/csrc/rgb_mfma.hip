@@ -288,8 +288,10 @@ int rgb_fwd(int dtype, const TapGemmParams& p, hipStream_t s) {
   const int M = p.B * p.Hs * p.Ws;
   dim3 grid((M + 127) / 128, (p.N + 127) / 128);
   const size_t lds = 128 * 128 + 64 * 256;
-  if (dtype == GCT2_BF16) hipLaunchKernelGGL(rgb_fwd_kernel<__bf16>, grid, dim3(256), lds, s, p);
-  else hipLaunchKernelGGL(rgb_fwd_kernel<_Float16>, grid, dim3(256), lds, s, p);
+  with_dtype16(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(rgb_fwd_kernel<T>, grid, dim3(256), lds, s, p);
+  });
   return gct2_check_launch("rgb_fwd");
 }
 bool rgb_wgrad_supported(int dtype, const WgradParams& p) {
@@ -297,8 +299,6 @@ bool rgb_wgrad_supported(int dtype, const WgradParams& p) {
   if (p.Cb > 4 || p.Cs % 8 || p.ldsmall % 8 || (uintptr_t)p.small % 16) return false;
   return true;
 }
-int wgrad_reduce(const float* ws, float* dw, size_t n, int nsplit, int accumulate, hipStream_t s);   // wgrad_mfma.hip
-
 int rgb_wgrad(const gct2_ctx& c, int dtype, WgradParams p, hipStream_t s, WgradSlabs* defer) {
   if (defer) *defer = WgradSlabs{nullptr, 0, 0};
   const int R = p.B * p.Hs * p.Ws;
@@ -315,8 +315,10 @@ int rgb_wgrad(const gct2_ctx& c, int dtype, WgradParams p, hipStream_t s, WgradS
   p.ws = (ws && n % 4 == 0 && (uintptr_t)p.dw % 16 == 0 && n * sizeof(float) * splits <= ws_bytes) ? ws : nullptr;
   if (!p.ws && !p.accumulate) (void)hipMemsetAsync(p.dw, 0, n * sizeof(float), s);   // the atomic path adds into dw
   const size_t lds = 4 * 64 * 256;
-  if (dtype == GCT2_BF16) hipLaunchKernelGGL(rgb_wgrad_kernel<__bf16>, grid, dim3(256), lds, s, p);
-  else hipLaunchKernelGGL(rgb_wgrad_kernel<_Float16>, grid, dim3(256), lds, s, p);
+  with_dtype16(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(rgb_wgrad_kernel<T>, grid, dim3(256), lds, s, p);
+  });
   if (int e = gct2_check_launch("rgb_wgrad")) return e;
   // the slabs are never handed to the fused optimizer launch (`defer`): this tensor is tiny and the slabs are many, one thread per
   // element walking 512 slabs is latency-bound (29 us at the very end of the step); wgrad_reduce's wide form sums them in ~5 us

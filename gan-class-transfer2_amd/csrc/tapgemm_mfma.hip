@@ -821,9 +821,6 @@ bool tapgemm_mfma_supported(int dtype, const TapGemmParams& p) {
   return true;
 }
 
-bool halo_convT_wanted(const gct2_ctx& c, int epi, const TapGemmParams& p);      // halo_mfma.hip
-int halo_convT(gct2_ctx& c, int dtype, int epi, TapGemmParams p, hipStream_t s);
-
 // the ordered row reduction of the fused bias gradients, for the other translation units that leave partial rows
 // bias queue: record a row set / reduce everything recorded (two launches: overwriting targets, then adding ones)
 int tapgemm_dbq_flush(gct2_ctx& c, hipStream_t s) {
@@ -901,11 +898,9 @@ int tapgemm_mfma(gct2_ctx& c, int dtype, int form, int epi, const TapGemmParams&
   if (form == FORM_S1 || form == FORM_S1T) {
     if (epi != (form == FORM_S1 ? EPI_BIAS_ACT : EPI_MASK) || p.ks < 1 || p.ks > 5 || !(p.ks & 1))
       return gct2_fail(GCT2_EINVAL, "tapgemm_mfma: stride-1 form with kernel size %d / epilogue %d", p.ks, epi);
-    if (dtype == GCT2_BF16) return dispatch<__bf16>(c, form, epi, p, s);
-    return dispatch<_Float16>(c, form, epi, p, s);
+  } else if (form == FORM_CONVT && (c.tap_variant == 0 || c.halo_mode == 2) && halo_convT_wanted(c, epi, p)) {
+    // (a forced tile keeps the halo kernel out, unless the halo kernel is forced too: halo mode 2)
+    return halo_convT(c, dtype, epi, p, s);
   }
-  // (a forced tile keeps the halo kernel out, unless the halo kernel is forced too: halo mode 2)
-  if (form == FORM_CONVT && (c.tap_variant == 0 || c.halo_mode == 2) && halo_convT_wanted(c, epi, p)) return halo_convT(c, dtype, epi, p, s);
-  if (dtype == GCT2_BF16) return dispatch<__bf16>(c, form, epi, p, s);
-  return dispatch<_Float16>(c, form, epi, p, s);
+  return with_dtype16(dtype, [&](auto tag) { return dispatch<typename decltype(tag)::type>(c, form, epi, p, s); });
 }

@@ -779,33 +779,20 @@ int wgrad_mfma(gct2_ctx& c, int dtype, WgradParams p, hipStream_t s, WgradSlabs*
     (void)hipMemsetAsync(p.dw, 0, n * sizeof(float), s);
   }
   gct2_log(c, "wgrad:%s:rsplit=%d:%s", p.ks ? "s1" : (big_tile ? (variant == 4 ? "256q-r03" : (variant == 5 ? "256q-r04" : "256q")) : "128"), rsplit, p.ws ? "slabs" : (rsplit == 1 ? "owner" : "atomics"));
-  if (p.ks) {
-    if (dtype == GCT2_BF16) hipLaunchKernelGGL((wgrad_kernel<__bf16, true>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((wgrad_kernel<_Float16, true>), grid, dim3(256), 0, s, p);
-  } else if (big_tile) {
-    // stage-aligned geometry -> scalar address code and waves taking turns (see the kernel); other shapes keep the r03 stage order
-    const bool aligned = (p.Ws % 32 == 0 || (32 % p.Ws == 0 && p.Hs % (32 / p.Ws) == 0)) && variant != 4;
-    const bool pipe = aligned && variant != 5;       // r05: the next stage's fragments read under the multiplies (5 = the r04 order)
-    if (dtype == GCT2_BF16) {
-      if (pipe) hipLaunchKernelGGL((wgrad256q_kernel<__bf16, true, true, true>), grid, dim3(512), 0, s, p);
-      else if (aligned) hipLaunchKernelGGL((wgrad256q_kernel<__bf16, true, true>), grid, dim3(512), 0, s, p);
-      else hipLaunchKernelGGL((wgrad256q_kernel<__bf16, false, false>), grid, dim3(512), 0, s, p);
-    } else {
-      if (pipe) hipLaunchKernelGGL((wgrad256q_kernel<_Float16, true, true, true>), grid, dim3(512), 0, s, p);
-      else if (aligned) hipLaunchKernelGGL((wgrad256q_kernel<_Float16, true, true>), grid, dim3(512), 0, s, p);
-      else hipLaunchKernelGGL((wgrad256q_kernel<_Float16, false, false>), grid, dim3(512), 0, s, p);
-    }
-  } else {
-    // whole images of the small grid per 64-row step (tuning 16-23 = 6 keeps the general form for the bit-identity test)
-    const bool imgal = 64 % (p.Hs * p.Ws) == 0 && variant != 6;
-    if (dtype == GCT2_BF16) {
-      if (imgal) hipLaunchKernelGGL((wgrad_kernel<__bf16, false, true>), grid, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((wgrad_kernel<__bf16>), grid, dim3(256), 0, s, p);
-    } else {
-      if (imgal) hipLaunchKernelGGL((wgrad_kernel<_Float16, false, true>), grid, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((wgrad_kernel<_Float16>), grid, dim3(256), 0, s, p);
-    }
-  }
+  // stage-aligned geometry -> scalar address code and waves taking turns (see the kernel); other shapes keep the r03 stage order
+  const bool aligned = (p.Ws % 32 == 0 || (32 % p.Ws == 0 && p.Hs % (32 / p.Ws) == 0)) && variant != 4;
+  const bool pipe = aligned && variant != 5;       // r05: the next stage's fragments read under the multiplies (5 = the r04 order)
+  // whole images of the small grid per 64-row step (tuning 16-23 = 6 keeps the general form for the bit-identity test)
+  const bool imgal = 64 % (p.Hs * p.Ws) == 0 && variant != 6;
+  with_dtype16(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (p.ks) hipLaunchKernelGGL((wgrad_kernel<T, true>), grid, dim3(256), 0, s, p);
+    else if (big_tile && pipe) hipLaunchKernelGGL((wgrad256q_kernel<T, true, true, true>), grid, dim3(512), 0, s, p);
+    else if (big_tile && aligned) hipLaunchKernelGGL((wgrad256q_kernel<T, true, true>), grid, dim3(512), 0, s, p);
+    else if (big_tile) hipLaunchKernelGGL((wgrad256q_kernel<T, false, false>), grid, dim3(512), 0, s, p);
+    else if (imgal) hipLaunchKernelGGL((wgrad_kernel<T, false, true>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((wgrad_kernel<T>), grid, dim3(256), 0, s, p);
+  });
   if (p.ws && defer && !p.accumulate) *defer = WgradSlabs{p.ws, rsplit, n};     // the caller's optimizer kernel sums the slabs
   else if (p.ws) hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, p.ws, p.dw, n / 4, rsplit, p.accumulate);
   return gct2_check_launch("wgrad_mfma");

@@ -866,6 +866,39 @@ def test_noise_with_inkernel_rng_is_bit_identical(gpu):
     assert torch.equal(packed[:, :3], bb[:, 4:7]) and float(packed[:, 3].float().abs().max()) == 0
 
 
+def test_noise_with_inkernel_rng_fp32(gpu):
+    """the fp32 instance of gct2_noise_image_rng (the bf16 one is above, the fp16 one below): the same draws and the same unfused mix
+    as gct2_rng_normal + gct2_noise_image, hence the same bits; a stream position inside a Philox counter, rows of 8 and a packed copy"""
+    B, HW, C, steps, off = 3, 50, 3, 200, 12345
+    n = B * HW * C
+    x = torch.rand(B, HW, C, device=gpu) * 2 - 1
+    t = torch.tensor([1, 77, 200], dtype=torch.int32, device=gpu)
+    eps = torch.zeros(n, device=gpu)
+    lib().call("gct2_rng_normal", 99, 2, off, eps.data_ptr(), n, stream())
+    a = torch.zeros(B * HW, 8, device=gpu); bb = torch.zeros_like(a)
+    lib().call("gct2_noise_image", F32, x.data_ptr(), t.data_ptr(), eps.data_ptr(), a.data_ptr() + 4 * 4, 8, None, 0, B, HW, C, steps, stream())
+    eps2 = torch.zeros(n, device=gpu)
+    packed = torch.zeros(B * HW, 4, device=gpu)
+    lib().call("gct2_noise_image_rng", F32, x.data_ptr(), t.data_ptr(), 99, 2, off, eps2.data_ptr(), bb.data_ptr() + 4 * 4, 8,
+               packed.data_ptr(), 4, B, HW, C, steps, stream())
+    torch.cuda.synchronize()
+    assert torch.equal(a, bb) and torch.equal(eps, eps2) and float(a[:, 4:7].abs().max()) > 0
+    assert torch.equal(packed[:, :3], bb[:, 4:7]) and float(packed[:, 3].abs().max()) == 0
+
+
+@pytest.mark.parametrize("dt", [F32, BF16, F16])
+def test_cast_from_f32(gpu, dt):
+    """gct2_cast_from_f32 in every dtype: one round-to-nearest-even conversion per element (a copy in fp32), exactly what torch's
+    .to() computes; 601 elements = a ragged last work-group, the element behind them stays as it was"""
+    n = 601
+    rng = np.random.default_rng(23)
+    src = torch.tensor(rng.standard_normal(n) * 10.0 ** rng.integers(-3, 3, n), dtype=torch.float32, device=gpu)
+    dst = torch.full((n + 1,), 5.0, dtype=TDT[dt], device=gpu)
+    lib().call("gct2_cast_from_f32", dt, src.data_ptr(), dst.data_ptr(), n, stream())
+    torch.cuda.synchronize()
+    assert torch.equal(dst[:n], src.to(TDT[dt])) and float(dst[n]) == 5.0
+
+
 @pytest.mark.parametrize("dt", [BF16, F16])
 def test_noise_rng_four_pixel_path_is_bit_identical(gpu, dt):
     """r06: the train step's call of gct2_noise_image_rng (3 channels into the packed 4-slot image, nothing else, stream position a
@@ -1081,7 +1114,7 @@ def _packbits(y, C):
 
 @pytest.mark.parametrize("words", [False, True])
 @pytest.mark.parametrize("case", ["conv_wide", "conv_narrow_view", "conv_splitk", "conv_rgb_staged", "conv_rgb_small", "conv_f32",
-                                  "convT_halo", "convT_tap", "convT_splitk"])
+                                  "convT_halo", "convT_tap", "convT_splitk", "conv_narrow_view_f16"])
 def test_relu_bit_plane_written_by_forward_calls(gpu, case, words):
     """gct2_ctx_set_relu_bits before a forward call: the call also leaves bits = (y > 0), one byte per 8 channels, written by the
     16-byte epilogues (tap GEMM, halo kernel, image layer) or derived from the stored y on the other paths (8-byte epilogue of an
@@ -1089,10 +1122,11 @@ def test_relu_bit_plane_written_by_forward_calls(gpu, case, words):
     plane is one-shot (a second call without a new registration leaves the bytes alone); bytes outside the view stay untouched.
     words: a 4-byte aligned plane (the engine's): the four lane rows of a pixel merge their bytes into one 32-bit store."""
     L = lib()
-    dt = F32 if case == "conv_f32" else BF16
+    dt = F32 if case == "conv_f32" else F16 if case.endswith("_f16") else BF16      # (the derived plane exists in every dtype)
     kind = "convT" if case.startswith("convT") else "conv"
     B, H, W, Cin, Cout, ld_extra, tuning = {
         "conv_wide": (2, 32, 32, 64, 128, 8, 0), "conv_narrow_view": (2, 16, 16, 64, 64, 4, 0), "conv_splitk": (2, 8, 8, 128, 256, 0, 0),
+        "conv_narrow_view_f16": (2, 16, 16, 64, 64, 4, 0),
         "conv_rgb_staged": (2, 32, 32, 3, 128, 0, 0), "conv_rgb_small": (2, 32, 32, 3, 64, 0, 0), "conv_f32": (1, 16, 16, 16, 32, 0, 0),
         "convT_halo": (2, 16, 16, 64, 64, 8, 2 << 24), "convT_tap": (2, 16, 16, 64, 128, 0, 1 << 24), "convT_splitk": (2, 4, 4, 256, 128, 0, 0),
     }[case]

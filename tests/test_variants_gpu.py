@@ -87,17 +87,20 @@ def test_conv2d_s1_kernels(gpu, dt, shape, with_ctx):
     assert L.load().gct2_conv2d_s1_fwd(None, dt, 16, Cin, 16, None, 16, Cout, B, H, W, Cin, Cout, 2, 1, None) == 1      # even kernel size
 
 
-def test_small_helpers(gpu):
+@pytest.mark.parametrize("dtype", [F32, BF16, F16], ids=["f32", "bf16", "f16"])
+def test_small_helpers(gpu, dtype):
+    """gct2_relu_mask and gct2_add in every dtype, 50 pixels x 12 channels in rows of 16 (the columns behind the channels stay as they
+    were), exactly: the mask is a select, the sum one fp32 add rounded once - what torch computes on the same rounded inputs"""
     import gan_class_transfer2_amd as g
     L = g._lib
     rng = np.random.default_rng(4)
-    act = torch.tensor(rng.standard_normal((50, 12)), dtype=torch.bfloat16, device=gpu)
-    d = torch.tensor(rng.standard_normal((50, 16)), dtype=torch.bfloat16, device=gpu)
+    act = torch.tensor(rng.standard_normal((50, 12)), dtype=TDT[dtype], device=gpu)
+    d = torch.tensor(rng.standard_normal((50, 16)), dtype=TDT[dtype], device=gpu)
     ref = d.clone(); ref[:, :12] = torch.where(act > 0, d[:, :12], torch.zeros_like(d[:, :12]))
-    L.call("gct2_relu_mask", BF16, act.data_ptr(), 12, d.data_ptr(), 16, 50, 12, stream())
-    a = torch.tensor(rng.standard_normal((50, 12)), dtype=torch.float32, device=gpu); b = torch.tensor(rng.standard_normal((50, 12)), dtype=torch.float32, device=gpu)
-    want = a + b
-    L.call("gct2_add", F32, a.data_ptr(), 12, b.data_ptr(), 12, 50, 12, stream())
+    L.call("gct2_relu_mask", dtype, act.data_ptr(), 12, d.data_ptr(), 16, 50, 12, stream())
+    a = torch.tensor(rng.standard_normal((50, 16)), dtype=TDT[dtype], device=gpu); b = torch.tensor(rng.standard_normal((50, 12)), dtype=TDT[dtype], device=gpu)
+    want = a.clone(); want[:, :12] = (a[:, :12].float() + b.float()).to(TDT[dtype])
+    L.call("gct2_add", dtype, a.data_ptr(), 16, b.data_ptr(), 12, 50, 12, stream())
     x = torch.tensor(rng.standard_normal((3, 40)), dtype=torch.float32, device=gpu); e = torch.tensor(rng.standard_normal((3, 40)), dtype=torch.float32, device=gpu)
     ca = torch.tensor([0.5, 0.0, 2.0], device=gpu); cc = torch.tensor([1.0, -1.0, 0.25], device=gpu); out = torch.zeros(3, 40, device=gpu)
     L.call("gct2_mix_per_image", x.data_ptr(), e.data_ptr(), ca.data_ptr(), cc.data_ptr(), out.data_ptr(), 3, 40, stream())
