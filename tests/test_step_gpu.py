@@ -374,6 +374,39 @@ def test_fp16_loss_scaling_step(gpu):
         assert abs(np.abs(upd).mean() / np.abs(upd_ref).mean() - 1) <= 0.05, k
 
 
+def test_fp16_overflow_inside_the_reverse_pass_skips_the_step(gpu):
+    """test_fp16_loss_scaling_step's configuration, but nobody writes inf into the gradient arena: the loss
+    scale is re-initialised (gct2_loss_scale_init) to 2^28, the smallest power of two at which the oracle's scaled fp16 gradients
+    exceed 65504 somewhere (asserted: finite at 2^27, non-finite at 2^28), so the overflow is born in a 16-bit store of the reverse
+    pass and has to travel through the input- and weight-gradient kernels to gct2_scale_check_finite.  The step must be skipped:
+    parameters bit-equal, iterations unchanged, scale halved."""
+    import gan_class_transfer2_amd as g
+    cfg = O.OracleConfig(size=32, pixel_size=64, max_size=128, octaves=3, batch_size=4, warm_up=3)
+    params = O.init_params(cfg, seed=5)
+    x, t_int, eps = O.synthetic_batch(cfg, seed=3)
+    with np.errstate(over="ignore", invalid="ignore"):
+        finite = {e: all(np.isfinite(v).all() for v in O.trainer_step(params, x, t_int, eps, cfg, operand_round="f16", loss_scale=2.0 ** e)[2].values())
+                  for e in (27, 28)}
+    assert finite == {27: True, 28: False}
+    eng = make_engine(cfg, 2, gpu, loss_scaling=True)
+    eng.set_params(params)
+    X, T, Ep = torch.tensor(x, dtype=torch.float32, device=gpu), torch.tensor(t_int), torch.tensor(eps, dtype=torch.float32)
+    eng.train_step(X, T, Ep, apply=False)                       # one applied step first: iterations = 1
+    eng.check_finite(); eng.apply_adam(); eng.finish_step()
+    torch.cuda.synchronize()
+    assert eng.iterations == 1 and eng.loss_scale() == (2.0 ** 15, 1)
+    p1 = eng.get_params()
+    g._lib.call("gct2_loss_scale_init", eng.ls_state.data_ptr(), 2.0 ** 28, torch.cuda.current_stream().cuda_stream)
+    eng.iterations = 1                                          # (the init call starts a fresh state)
+    eng.train_step(X, T, Ep, apply=False)
+    eng.check_finite(); eng.apply_adam(); eng.finish_step()
+    torch.cuda.synchronize()
+    assert not bool(torch.isfinite(eng.arena.g).all())          # the overflow reached the gradient arena by itself
+    p2 = eng.get_params()
+    assert all(np.array_equal(p2[k], p1[k]) for k in p1)
+    assert eng.iterations == 1 and eng.loss_scale() == (2.0 ** 27, 0)
+
+
 def test_checkpoint_roundtrip_continues(gpu, tmp_path):
     """state serialisation: 2 steps, save, load into a fresh engine, 1 more step on each -> the same loss
     bit for bit (same parameters, same device RNG positions) and the same parameters / Adam slots afterwards (reference widths:
