@@ -573,6 +573,18 @@ int gct2_cast_from_f32(int dtype, const float* src, void* dst, size_t n, void* s
   return pw_cast(dtype, src, dst, n, S(stream));
 }
 
+int gct2_ema_update(float* ema, const float* p, void* ema_shadow, int shadow_dtype, size_t n, float momentum, float one_minus,
+                    const gct2_loss_scale_state* ls, void* stream) {
+  if (!ema || !p) return gct2_fail(GCT2_EINVAL, "ema_update: null pointer");
+  if (n == 0) return gct2_fail(GCT2_EINVAL, "ema_update: n == 0");
+  if (ema_shadow && shadow_dtype != GCT2_BF16 && shadow_dtype != GCT2_F16)
+    return gct2_fail(GCT2_EINVAL, "ema_update: a shadow needs a 16-bit dtype (GCT2_BF16 / GCT2_F16), got %d", shadow_dtype);
+  if (((uintptr_t)ema | (uintptr_t)p) % 16 || (ema_shadow && (uintptr_t)ema_shadow % 8))
+    return gct2_fail(GCT2_EINVAL, "ema_update: ema and p must be 16-byte aligned, the shadow 8-byte aligned");
+  if (!(momentum >= 0.f && momentum <= 1.f)) return gct2_fail(GCT2_EINVAL, "ema_update: momentum %g outside [0, 1]", (double)momentum);
+  return pw_ema(ema, p, ema_shadow, shadow_dtype, n, momentum, one_minus, ls, S(stream));
+}
+
 int gct2_loss_scale_init(gct2_loss_scale_state* st, float initial_scale, void* stream) {
   if (!st || !(initial_scale > 0.f)) return gct2_fail(GCT2_EINVAL, "loss_scale_init: null state or non-positive scale");
   return pw_ls_init(st, initial_scale, S(stream));

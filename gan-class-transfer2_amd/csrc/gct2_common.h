@@ -457,6 +457,9 @@ int pw_colsum(int dtype, const void* dz, int ld, float* db, size_t M, int C, flo
 int pw_adam(float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n, float alpha, float b1, float b2, float eps,
             float grad_mul, const gct2_loss_scale_state* ls, int zero_grad, hipStream_t s, const float* slabs = nullptr, int nslab = 0,
             size_t slab_stride = 0, size_t n_slab = 0);
+// Keras' optimizer EMA over a flat range: ema = momentum * ema + one_minus * p, the new value also in the 16-bit shadow (may be null)
+int pw_ema(float* ema, const float* p, void* shadow, int shadow_dtype, size_t n, float momentum, float one_minus,
+           const gct2_loss_scale_state* ls, hipStream_t s);
 int pw_cast(int dtype, const float* src, void* dst, size_t n, hipStream_t s);
 int pw_ls_init(gct2_loss_scale_state* st, float scale, hipStream_t s);
 int pw_ls_begin(gct2_loss_scale_state* st, float base_lr, int warmup_steps, float b1, float b2, hipStream_t s);

@@ -913,6 +913,41 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
   }
 }
 
+// ---- Keras' optimizer EMA over a flat arena: average = momentum * average + (1 - momentum) * var [TF] --------------------------
+template <typename S, bool HAS_SHADOW>
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, S* __restrict__ shadow, size_t n,
+                                                  float momentum, float one_minus, const gct2_loss_scale_state* __restrict__ ls) {
+  // two products and one sum, each rounded to fp32 (no FMA contraction: as for adam_keras_update, the bits must not depend on what
+  // hipcc fuses).  ls != NULL (LossScaleOptimizer): a skipped step leaves the averages alone - nothing is written.
+#pragma clang fp contract(off)
+  if (ls && ls->found_inf != 0) return;
+  const size_t n4 = n >> 2;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    // touched once per step, like the optimizer's arenas: streaming accesses
+    f32x4_t ev = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(ema) + i);
+    const f32x4_t pv = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(p) + i);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const float a = momentum * ev[k], b = one_minus * pv[k];
+      ev[k] = a + b;
+    }
+    __builtin_nontemporal_store(ev, reinterpret_cast<f32x4_t*>(ema) + i);
+    if constexpr (HAS_SHADOW) {
+      const u32x2_t o = {pack2<S>(ev[0], ev[1]), pack2<S>(ev[2], ev[3])};
+      reinterpret_cast<u32x2_t*>(shadow)[i] = o;
+    }
+  }
+  // tail (n % 4 elements)
+  const size_t i = (n4 << 2) + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    const float a = momentum * ema[i], b = one_minus * p[i];
+    const float e = a + b;
+    ema[i] = e;
+    if constexpr (HAS_SHADOW) shadow[i] = from_f32<S>(e);
+  }
+}
+
 template <typename S>
 __global__ void cast_kernel(const float* __restrict__ src, S* __restrict__ dst, size_t n) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -1168,6 +1203,17 @@ int pw_adam(float* p, float* m, float* v, float* g, void* shadow, int sdt, size_
   else GCT2_ADAM(float, true);
 #undef GCT2_ADAM
   return gct2_check_launch("adam_keras_multi");
+}
+int pw_ema(float* ema, const float* p, void* shadow, int sdt, size_t n, float momentum, float one_minus, const gct2_loss_scale_state* ls,
+           hipStream_t s) {
+  if (n == 0) return GCT2_OK;
+  const int nb = blocks_for(n / 4 + 4, 256);
+#define GCT2_EMA(S, HS) hipLaunchKernelGGL((ema_kernel<S, HS>), dim3(nb), dim3(256), 0, s, ema, p, reinterpret_cast<S*>(shadow), n, momentum, one_minus, ls)
+  if (!shadow) GCT2_EMA(float, false);
+  else if (sdt == GCT2_BF16) GCT2_EMA(__bf16, true);
+  else GCT2_EMA(_Float16, true);
+#undef GCT2_EMA
+  return gct2_check_launch("ema_update");
 }
 int pw_cast(int dtype, const float* src, void* dst, size_t n, hipStream_t s) {
   if (n == 0) return GCT2_OK;

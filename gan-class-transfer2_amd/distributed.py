@@ -259,6 +259,11 @@ class ShardedDataParallelStep:
     kernels behind the last bucket's reduce-scatter / all-gather."""
 
     def __init__(self, engine, bucket_elems: int = 4 << 20, group=None, force_exchange: bool = False, tail_layers: int = 3):
+        if getattr(engine, "use_ema", False):
+            raise ValueError("ShardedDataParallelStep holds only a shard of the fp32 parameters per rank: it cannot keep the engine's "
+                             "parameter averages (Adam(use_ema=True)); use DataParallelStep, or switch them off")
+        engine._ema_forbidden = ("this engine is driven by ShardedDataParallelStep, which holds only a shard of the fp32 parameters per "
+                                 "rank: parameter averages (enable_ema) are not available there")
         self.engine, self.group = engine, group
         A = engine.arena
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1

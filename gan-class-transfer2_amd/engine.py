@@ -25,6 +25,7 @@ import torch
 from . import _lib
 from ._lib import BF16, F16, F32, Slot, call
 from .trainer_math import TrainerState, glorot_limit
+from .trainer_math import ema_coefficients as TM_ema_coefficients
 
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 
@@ -112,6 +113,11 @@ class ParamArena:
         # the engine may hold optimizer launches back (UNetEngine.defer_adam: the Adam step of the layers the forward pass needs last
         # runs inside the NEXT forward pass): whoever looks at p / m / v / shadow through these properties gets them flushed first
         self.before_read: Optional[Callable[[], None]] = None
+        # the exponential moving average of p and its compute-dtype copy (TrainerState.enable_ema allocates them; None while EMA is
+        # off) and which of the two weight sets wptr / pptr hand out (TrainerState.ema_weights)
+        self._ema: Optional[torch.Tensor] = None
+        self._ema_shadow: Optional[torch.Tensor] = None
+        self._read_ema = False
 
     def _sync(self) -> None:
         if self.before_read is not None:
@@ -132,6 +138,14 @@ class ParamArena:
     @property
     def shadow(self) -> Optional[torch.Tensor]:
         self._sync(); return self._shadow
+
+    @property
+    def ema(self) -> Optional[torch.Tensor]:
+        self._sync(); return self._ema
+
+    @property
+    def ema_shadow(self) -> Optional[torch.Tensor]:
+        self._sync(); return self._ema_shadow
 
     LAYOUT = 2        # bumped when the order of tensors inside the arenas changes (state_dict carries it)
 
@@ -166,12 +180,13 @@ class ParamArena:
     def wptr(self, name: str) -> int:
         """device pointer of the compute-dtype operand copy of a weight."""
         o = self.offsets[name]                    # (raw storage: the engine orders its own launches against pending updates)
-        if self._shadow is None:
-            return self._p.data_ptr() + 4 * o
-        return self._shadow.data_ptr() + 2 * o
+        p, shadow = (self._ema, self._ema_shadow) if self._read_ema else (self._p, self._shadow)
+        if shadow is None:
+            return p.data_ptr() + 4 * o
+        return shadow.data_ptr() + 2 * o
 
     def pptr(self, name: str) -> int:
-        return self._p.data_ptr() + 4 * self.offsets[name]
+        return (self._ema if self._read_ema else self._p).data_ptr() + 4 * self.offsets[name]
 
     def gptr(self, name: str) -> int:
         return self.g.data_ptr() + 4 * self.offsets[name]
@@ -284,7 +299,8 @@ class UNetEngine(TrainerState):
                  base_lr: float = 2e-5, warm_up: int = 2000, beta_1: float = 0.9, beta_2: float = 0.999,
                  epsilon: float = 1e-7, loss_scaling: bool = False, seed: int = 1234, rng_seed: int = 0,
                  workspace_mb: int = 64, predict_x: bool = True, predict_scaled_epsilon: bool = False,
-                 prediction_weighting: bool = False, ordinary_differential_equation: bool = False, f32_matrix: bool = False):
+                 prediction_weighting: bool = False, ordinary_differential_equation: bool = False, f32_matrix: bool = False,
+                 use_ema: bool = False, ema_momentum: float = 0.99):
         super().__init__(dtype, device, steps, base_lr, warm_up, beta_1, beta_2, epsilon, loss_scaling, rng_seed, predict_x,
                          predict_scaled_epsilon, prediction_weighting, ordinary_differential_equation, f32_matrix)
         self.topo = topo
@@ -349,6 +365,9 @@ class UNetEngine(TrainerState):
         self._pending_event = None
         self._flush_event = None
         self._pending_names: set = set()
+        # the averages of the held-back layers follow their optimizer launches: (arena ranges, momentum, 1 - momentum) of the step
+        # that held them back (TrainerState.finish_step covers the rest of the arena at the end of that step)
+        self._pending_ema: Optional[tuple] = None
         self._defer_ctxs: Dict[str, "_lib.Context"] = {}
         self._defer_ws: Dict[str, torch.Tensor] = {}
         self.arena.before_read = self.flush_deferred
@@ -376,6 +395,8 @@ class UNetEngine(TrainerState):
         # only run while a step is being recorded - it puts that state where a full step leaves it (distributed.py)
         self.post_replay: Optional[Callable[[], None]] = None
         self._grads_in_arena = True    # False after a step whose fused optimizer consumed weight-gradient slabs in place
+        if use_ema:
+            self.enable_ema(ema_momentum)
 
     # ------------------------------------------------------------------------------------------
     def stream_for(self, role: str) -> "torch.cuda.Stream":
@@ -430,6 +451,63 @@ class UNetEngine(TrainerState):
         for _, layer, args in self._pending:
             call("gct2_adam_apply", ctypes.addressof(args), A.gptr(layer + ".w"), A.numel(layer + ".w"), stream)
         self._pending = []
+        if self._pending_ema is not None:                       # right behind the launches that wrote these parameters, on their stream
+            ranges, m, c = self._pending_ema
+            self._pending_ema = None
+            if self.use_ema:
+                for lo, hi in ranges:
+                    self._ema_launch(lo, hi, m, c, None, stream)
+
+    # ---- the parameter averages (TrainerState.enable_ema) --------------------------------------------------------------------
+    def _ema_source(self) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        return self.arena._p, self.arena._shadow
+
+    def _ema_tensors(self) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+        return self.arena._ema, self.arena._ema_shadow
+
+    def _ema_attach(self, ema: Optional[torch.Tensor], ema_shadow: Optional[torch.Tensor]) -> None:
+        self.arena._ema, self.arena._ema_shadow = ema, ema_shadow
+        # whatever baked in the addresses of the previous averages goes with them: the step plans (their gct2_ema_update records;
+        # the key only says THAT a step averages, and a later enable_ema allocates anew) and the sampler's captures of the averaged weights
+        self._plans.clear()
+        self._plan_seen.clear()
+        graphs = getattr(self, "_forward_graphs", None)
+        if graphs:
+            for gk in [k for k in graphs if k[2]]:
+                del graphs[gk]
+
+    def _ema_select(self, on: bool) -> None:
+        self.arena._read_ema = bool(on)
+
+    def _ema_selected(self) -> bool:
+        return self.arena._read_ema
+
+    def _ema_partition(self) -> Tuple[List[Tuple[int, int]], List[Tuple[int, int]]]:
+        """(ranges whose optimizer launches of this step are enqueued, ranges of the layers this step holds back - defer_adam: the
+        arena's prefix - with adjacent ones merged); together they cover the arena exactly once"""
+        A = self.arena
+        held: List[Tuple[int, int]] = []
+        for lo, hi in sorted(A.layer_ranges[layer] for _, layer, _ in self._pending):
+            if held and held[-1][1] == lo:
+                held[-1] = (held[-1][0], hi)
+            else:
+                held.append((lo, hi))
+        now, at = [], 0
+        for lo, hi in held:
+            if lo > at:
+                now.append((at, lo))
+            at = hi
+        if at < A.total:
+            now.append((at, A.total))
+        return now, held
+
+    def _ema_step_update(self) -> None:
+        """the step-end launches over what is enqueued; the held-back ranges wait in _pending_ema with THIS step's momentum"""
+        m, c = TM_ema_coefficients(self.ema_momentum)
+        now, held = self._ema_partition()
+        self._pending_ema = (tuple(held), m, c) if held else None
+        for lo, hi in now:
+            self._ema_launch(lo, hi, m, c, self._ls_ptr(), self._stream())
 
     def flush_deferred(self) -> None:
         """run whatever optimizer launches the last train step held back, on the current stream (no-op when nothing is pending).
@@ -897,6 +975,7 @@ class UNetEngine(TrainerState):
         (no host synchronisation).  t_int / eps may be injected for parity runs (SURVEY.md §8c RNG)."""
         if x.dim() != 4 or x.shape[-1] != 3:
             raise ValueError(f"expected an NHWC batch [B,H,W,3], got {tuple(x.shape)}")
+        self._refuse_training_on_averages()
         if x.dtype != torch.float32 or not x.is_contiguous() or x.device != self.device:
             x = x.to(self.device, torch.float32).contiguous()
         B, H, W, _ = x.shape
@@ -970,7 +1049,7 @@ class UNetEngine(TrainerState):
                 # baked into recorded arguments (gct2_adam_keras_multi, gct2_loss_scale_begin) or restored into the per-layer
                 # gct2_adam_args by every replay: Trainer.compile() may legally rewrite them between steps
                 self.dtype, float(self.beta_1), float(self.beta_2), float(self.epsilon), float(self.base_lr), int(self.warm_up),
-                id(self.post_replay), self._side.cuda_stream,
+                id(self.post_replay), self._side.cuda_stream, self.use_ema, float(self.ema_momentum),
                 self._chain_stream.cuda_stream if self._chain_stream is not None else 0)
 
     def _planned_step(self, b: _Buffers, x: torch.Tensor, apply: bool, inline: bool, cur: "torch.cuda.Stream") -> torch.Tensor:
@@ -992,6 +1071,7 @@ class UNetEngine(TrainerState):
             # back to where it was, the half-built plan is dropped, and the caller sees the exception with the engine as before the
             # call (offsets and counters stayed advanced, _pending named launches whose slabs were never produced)
             before = dict(pending=list(self._pending), pending_names=set(self._pending_names), pending_event=self._pending_event,
+                          pending_ema=self._pending_ema,
                           bits_valid=b.bits_valid, grads_in_arena=self._grads_in_arena, post_backward_ran=self.post_backward_ran,
                           structs={l: bytes(a) for l, a in self._adam_args.items()})
             sp = _StepPlan(b)
@@ -1003,13 +1083,14 @@ class UNetEngine(TrainerState):
                 self.rng_offset_t, self.rng_offset_eps, self._iterations = off_t, off_eps, its
                 self._pending, self._pending_names = before["pending"], before["pending_names"]
                 self._pending_event, b.bits_valid = before["pending_event"], before["bits_valid"]
+                self._pending_ema = before["pending_ema"]
                 self._grads_in_arena, self.post_backward_ran = before["grads_in_arena"], before["post_backward_ran"]
                 for l, raw in before["structs"].items():
                     ctypes.memmove(ctypes.addressof(self._adam_args[l]), raw, len(raw))
                 self._plan_seen[key] = self.plan_after - 1     # (the next step of this shape tries again)
                 raise
             sp.plan.end()
-            sp.after = dict(pending=list(self._pending), pending_names=set(self._pending_names), bits_valid=b.bits_valid,
+            sp.after = dict(pending=list(self._pending), pending_names=set(self._pending_names), pending_ema=self._pending_ema, bits_valid=b.bits_valid,
                             grads_in_arena=self._grads_in_arena, fused_layers=list(getattr(self, "_fused_layers", [])))
             # the per-layer gct2_adam_args structs are shared with eager steps (which may fill them differently: another deferral
             # set, another range): a replay puts the recorded inputs back first
@@ -1056,12 +1137,17 @@ class UNetEngine(TrainerState):
         self.rng_offset_eps += sp.d_off_eps
         self._iterations += sp.d_its
         self._pending, self._pending_names, self._pending_event = list(a["pending"]), set(a["pending_names"]), None
+        self._pending_ema = a["pending_ema"]
         sp.b.bits_valid, self._grads_in_arena = a["bits_valid"], a["grads_in_arena"]
         if self.post_replay is not None:
             self.post_replay()
         return sp.loss
 
-    def predict(self, noised: torch.Tensor) -> torch.Tensor:
+    def predict(self, noised: torch.Tensor, use_ema: bool = False) -> torch.Tensor:
+        """use_ema: evaluate the averaged weights (ema_weights()) instead of the raw iterate"""
+        if use_ema:
+            with self.ema_weights():
+                return self.predict(noised)
         B, H, W, _ = noised.shape
         b = self.buffers(B, H, W)
         self.load_input_into_r0(b, noised)
@@ -1082,6 +1168,9 @@ class UNetEngine(TrainerState):
               "topology": torch.tensor([self.topo.pixel_size, self.topo.max_size, self.topo.octaves, A.total, A.LAYOUT], dtype=torch.int64)}
         if self.ls_state is not None:
             sd["loss_scale_state"] = self.ls_state.cpu()
+        if self.use_ema:                # (only then: without the averages the dictionary is what it always was)
+            sd["arena.ema"] = A.ema.cpu()
+            sd["ema_momentum"] = torch.tensor([float(self.ema_momentum)], dtype=torch.float64)      # (restored by load_state_dict)
         return sd
 
     def named_state_dict(self) -> Dict[str, torch.Tensor]:
@@ -1091,7 +1180,7 @@ class UNetEngine(TrainerState):
         sd = self.state_dict()
         A, out = self.arena, {k: v for k, v in sd.items() if not k.startswith("arena.") and k != "topology"}
         out["topology"] = sd["topology"][:3].clone()
-        for slot in ("p", "m", "v"):
+        for slot in ("p", "m", "v") + (("ema",) if "arena.ema" in sd else ()):
             flat = sd["arena." + slot]
             for name, o in A.offsets.items():
                 out[f"{slot}/{name}"] = flat[o:o + A.numel(name)].view(A.shapes[name]).clone()
@@ -1101,7 +1190,8 @@ class UNetEngine(TrainerState):
         A = self.arena
         if [int(v) for v in sd["topology"][:3]] != [self.topo.pixel_size, self.topo.max_size, self.topo.octaves]:
             raise ValueError(f"checkpoint topology {[int(v) for v in sd['topology'][:3]]} != engine")
-        flat = {slot: torch.zeros(A.total, dtype=torch.float32) for slot in ("p", "m", "v")}
+        slots = ("p", "m", "v") + (("ema",) if any(k.startswith("ema/") for k in sd) else ())
+        flat = {slot: torch.zeros(A.total, dtype=torch.float32) for slot in slots}
         for slot in flat:
             for name, o in A.offsets.items():
                 t = sd[f"{slot}/{name}"]
@@ -1141,6 +1231,9 @@ class UNetEngine(TrainerState):
             raise ValueError(f"checkpoint topology / layout {have} != engine {want}")
         if ("loss_scale_state" in sd) != (self.ls_state is not None):
             raise ValueError("checkpoint and engine disagree on dynamic loss scaling (mixed_precision, train.py:34)")
+        if "arena.ema" in sd and not self.use_ema:
+            raise ValueError("the checkpoint holds parameter averages (Adam(use_ema=True)) and this engine keeps none: switch them on "
+                             "(enable_ema) before loading - they are not dropped silently")
         for name in ("p", "m", "v"):
             getattr(A, name).copy_(sd["arena." + name].to(self.device, torch.float32))
         A.g.zero_()
@@ -1149,6 +1242,12 @@ class UNetEngine(TrainerState):
             self.ls_state.copy_(sd["loss_scale_state"].to(self.device))
         self.iterations = its
         A.refresh_shadow(self._stream())
+        if self.use_ema:               # a checkpoint written without averages: they start from the loaded parameters (as enable_ema does)
+            A.ema.copy_(sd["arena.ema"].to(self.device, torch.float32) if "arena.ema" in sd else A._p)
+            if A._ema_shadow is not None:
+                call("gct2_cast_from_f32", self.dtype, A._ema.data_ptr(), A._ema_shadow.data_ptr(), A.total, self._stream())
+            if "ema_momentum" in sd:       # the averages continue as they were kept (a later compile() may still change it)
+                self.ema_momentum = float(sd["ema_momentum"][0])
         self._masters_sharded = False                          # the arenas are whole again (a sharded wrapper sets it at its next step)
 
     def save_checkpoint(self, path: str) -> None:

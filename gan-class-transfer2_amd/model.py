@@ -92,10 +92,19 @@ class WarmUp:
 
 class Adam:
     """tf.keras.optimizers.Adam hyper-parameters (train.py:75); the update itself is
-    gct2_adam_keras_multi (epsilon added to sqrt(v))."""
+    gct2_adam_keras_multi (epsilon added to sqrt(v)).  use_ema / ema_momentum [TF]: the engine keeps an exponential
+    moving average of the parameters (gct2_ema_update after every applied step); finalize_variable_values() overwrites the
+    parameters with it, predict(..., use_ema=True) and log_sample(..., use_ema=True) read it."""
 
-    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, use_ema=False, ema_momentum=0.99,
+                 ema_overwrite_frequency=None):
+        if ema_overwrite_frequency is not None:
+            raise NotImplementedError("ema_overwrite_frequency: periodic overwriting is not built; call "
+                                      "optimizer.finalize_variable_values() where the parameters should become the averages")
+        if use_ema and not (0.0 <= float(ema_momentum) <= 1.0):
+            raise ValueError(f"ema_momentum must lie in [0, 1], got {ema_momentum!r}")
         self.learning_rate, self.beta_1, self.beta_2, self.epsilon = learning_rate, beta_1, beta_2, epsilon
+        self.use_ema, self.ema_momentum, self.ema_overwrite_frequency = bool(use_ema), ema_momentum, None
         self.loss_scaling = False
         self._engine = None            # bound by Trainer.compile / train_step: the step counter lives with the engine
 
@@ -106,6 +115,13 @@ class Adam:
 
     def lr(self, step: int) -> float:
         return self.learning_rate(step) if callable(self.learning_rate) else float(self.learning_rate)
+
+    def finalize_variable_values(self, var_list=None) -> None:
+        """Keras' end-of-training hook [TF]: the model's parameters become their averages (var_list is ignored: the engine holds
+        one arena)."""
+        if self._engine is None:
+            raise RuntimeError("finalize_variable_values: the optimizer is not bound to an engine yet (compile, then train)")
+        self._engine.ema_overwrite()
 
 
 class LossScaleOptimizer:
@@ -118,6 +134,9 @@ class LossScaleOptimizer:
     def __getattr__(self, k):
         return getattr(self.inner, k)
 
+    def finalize_variable_values(self, var_list=None) -> None:
+        self.inner.finalize_variable_values(var_list)
+
 
 def default_optimizer():
     """train.py:75,82-83"""
@@ -127,7 +146,8 @@ def default_optimizer():
 
 def engine_hyper_parameters(optimizer) -> Dict[str, object]:
     """an optimizer (train.py:75, 82-83) as the engines' hyper-parameter attributes / constructor arguments; a learning rate
-    that is neither a WarmUp nor a constant leaves base_lr and warm_up out"""
+    that is neither a WarmUp nor a constant leaves base_lr and warm_up out; use_ema / ema_momentum are there only when the optimizer
+    averages (without them the dictionary is what it was before the averages existed)"""
     inner = getattr(optimizer, "inner", optimizer)
     kw = dict(beta_1=inner.beta_1, beta_2=inner.beta_2, epsilon=inner.epsilon)
     lr = inner.learning_rate
@@ -135,6 +155,8 @@ def engine_hyper_parameters(optimizer) -> Dict[str, object]:
         kw.update(base_lr=lr.base, warm_up=lr.warmup_steps)
     elif not callable(lr):
         kw.update(base_lr=float(lr), warm_up=0)
+    if getattr(inner, "use_ema", False):
+        kw.update(use_ema=True, ema_momentum=float(inner.ema_momentum))
     return kw
 
 
@@ -515,8 +537,14 @@ class Trainer(Layer):
         """train.py:511-514"""
         if self.denoiser.engine is not None and optimizer is not None:
             eng, inner = self.denoiser.engine, getattr(optimizer, "inner", optimizer)
-            for k, v in engine_hyper_parameters(optimizer).items():
-                setattr(eng, k, v)
+            hp = engine_hyper_parameters(optimizer)
+            for k, v in hp.items():
+                if k not in ("use_ema", "ema_momentum"):
+                    setattr(eng, k, v)
+            if hp.get("use_ema"):                         # the averages start from the parameters as they stand now
+                eng.enable_ema(hp["ema_momentum"])
+            elif getattr(eng, "use_ema", False):
+                eng.disable_ema()
             if inner.loss_scaling and eng.ls_state is None:
                 eng.enable_loss_scaling()                 # train.py:505-514: the model is called before compile
             elif not inner.loss_scaling and eng.ls_state is not None:

@@ -10,6 +10,7 @@ planned forward pass of UNetEngine at batch 1 and 6 (captured once into a HIP gr
 variants of train.py:20, 26, 27 - VariantEngine.predict, layer by layer.  Returns the tensors the reference hands to tf.summary."""
 from __future__ import annotations
 
+import contextlib
 import warnings
 from typing import Callable, Dict, Optional, Tuple
 
@@ -45,7 +46,8 @@ class _Sampler:
         # kept on the engine: the reference calls log_sample once per epoch, the buffer sets and arenas (hence the graphs) live on.
         # A graph bakes in the workspace pointers and the tile choices of the engine's call context at capture time: the cache is
         # keyed on the context's version (bumped by every set_workspace / set_tuning / force_direct) and holds the buffer set
-        # itself, so neither a re-tuned context nor a recycled id() can replay a stale graph.
+        # itself, so neither a re-tuned context nor a recycled id() can replay a stale graph.  A graph also bakes in the weight
+        # pointers: the key carries the weight set (raw / averaged, engine.ema_weights()), so each set replays its own capture.
         if self.planned and not hasattr(eng, "_forward_graphs"):
             eng._forward_graphs = {}
         self._inputs: Dict[int, torch.Tensor] = {}
@@ -53,11 +55,11 @@ class _Sampler:
     # ---- network evaluation ---------------------------------------------------------------------------------------------
     def _graph_for(self, b):
         eng = self.eng
-        cache: Dict[Tuple[int, int], Tuple[object, object]] = eng._forward_graphs
-        version = eng.ctx.version
+        cache: Dict[Tuple[int, int, bool], Tuple[object, object]] = eng._forward_graphs
+        version, averaged = eng.ctx.version, bool(eng._ema_reading)
         for key in [k for k in cache if k[1] != version]:       # the context changed: every captured graph is stale
             del cache[key]
-        hit = cache.get((id(b), version))
+        hit = cache.get((id(b), version, averaged))
         if hit is not None and hit[1] is b:
             return hit[0]
         eng.forward(b)                          # (also the first evaluation: whatever lazy set-up there is happens here)
@@ -71,7 +73,7 @@ class _Sampler:
             warnings.warn(f"log_sample: HIP graph capture of the forward pass was refused ({e}); using plain launches")
             self.use_graph = False
             return None
-        cache[(id(b), version)] = (g, b)
+        cache[(id(b), version, averaged)] = (g, b)
         return None                             # this evaluation has already run (the warm-up call above)
 
     def evaluate(self, B: int) -> torch.Tensor:
@@ -86,7 +88,7 @@ class _Sampler:
             eng.forward(b)
             return b.pred
         cache = eng._forward_graphs
-        hit = cache.get((id(b), eng.ctx.version))
+        hit = cache.get((id(b), eng.ctx.version, bool(eng._ema_reading)))
         if hit is not None and hit[1] is b:
             hit[0].replay()
         else:
@@ -146,12 +148,20 @@ def _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_different
 def log_sample(denoiser: "M.Denoiser", example_image: torch.Tensor, example: torch.Tensor, dictionary: torch.Tensor,
                steps: Optional[int] = None, test_step: Optional[int] = None, predict_x: Optional[bool] = None,
                predict_scaled_epsilon: Optional[bool] = None, ordinary_differential_equation: Optional[bool] = None,
-               use_graph: bool = True) -> Dict[str, torch.Tensor]:
+               use_graph: bool = True, use_ema: bool = False) -> Dict[str, torch.Tensor]:
     """example_image [1,H,W,3] fp32 in [-1,1) (train.py:305); example [1,2,H,W,3] ~ N(0,1) (train.py:306);
-    dictionary [H,W,2**bits_per_pixel,3] ~ N(0,1) (train.py:308-311); all on the HIP device."""
+    dictionary [H,W,2**bits_per_pixel,3] ~ N(0,1) (train.py:308-311); all on the HIP device.
+    use_ema: every network evaluation reads the engine's parameter averages (Adam(use_ema=True)) instead of the raw iterate."""
+    eng = denoiser.ensure_engine()
+    with (eng.ema_weights() if use_ema else contextlib.nullcontext()):
+        return _log_sample(eng, example_image, example, dictionary, steps, test_step, predict_x, predict_scaled_epsilon,
+                           ordinary_differential_equation, use_graph)
+
+
+def _log_sample(eng, example_image, example, dictionary, steps, test_step, predict_x, predict_scaled_epsilon,
+                ordinary_differential_equation, use_graph) -> Dict[str, torch.Tensor]:
     steps = M.steps if steps is None else steps
     test_step = M.test_step if test_step is None else test_step
-    eng = denoiser.ensure_engine()
     mode = _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_differential_equation)
     dev = eng.device
     f32 = lambda t: t.to(dev, torch.float32).contiguous()
@@ -206,9 +216,10 @@ def log_sample(denoiser: "M.Denoiser", example_image: torch.Tensor, example: tor
     return out
 
 
-def make_log_sample(denoiser: "M.Denoiser", example_image, example, dictionary, sink: Callable[[int, Dict[str, torch.Tensor]], None]):
+def make_log_sample(denoiser: "M.Denoiser", example_image, example, dictionary, sink: Callable[[int, Dict[str, torch.Tensor]], None],
+                    use_ema: bool = False):
     """callback with the reference's signature `log_sample(epochs, logs)` (train.py:323, 519-521); `sink(epoch, images)` stands
-    for the TensorBoard summary writer."""
+    for the TensorBoard summary writer.  use_ema: sample from the parameter averages."""
     def cb(epochs, logs):
-        sink(epochs, log_sample(denoiser, example_image, example, dictionary))
+        sink(epochs, log_sample(denoiser, example_image, example, dictionary, use_ema=use_ema))
     return cb

@@ -8,6 +8,7 @@ holds the values bit for bit.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Optional, Sequence, Tuple
 
@@ -75,6 +76,12 @@ def objective_coefficients(t_int: torch.Tensor, steps: int, predict_x: bool = Tr
     return zero, c.contiguous(), one
 
 
+def ema_coefficients(momentum: float) -> Tuple[float, float]:
+    """(momentum, 1 - momentum) as the two float32 factors of Keras' optimizer EMA [TF]: Python forms 1 - momentum in double and the
+    product with a float32 tensor rounds it once - so does the host here (gct2_ema_update takes both factors)."""
+    return float(np.float32(momentum)), float(np.float32(1.0 - float(momentum)))
+
+
 OBJECTIVE_SWITCHES = ("predict_x", "predict_scaled_epsilon", "prediction_weighting", "ordinary_differential_equation")
 
 
@@ -82,6 +89,26 @@ class TrainerState:
     """what a train-step engine holds besides its network: constructor arguments checked, then plain attributes that
     `Trainer.compile()` may rewrite between steps (base_lr, warm_up, beta_1, beta_2, epsilon) and `Trainer` sets before every
     step (the four objective switches of train.py:29-32; defaults = the reference's: the network predicts the clean image)."""
+
+    # exponential moving average of the parameters (Keras Adam(use_ema=True) [TF]): off by default (class-level defaults: an engine
+    # that never switches it on carries no state for it); enable_ema() / disable_ema() write them.  The averages themselves and the
+    # switch between the two weight sets live where weight pointers are resolved (ParamArena / _Net): the three names below read them
+    use_ema, ema_momentum = False, 0.99
+
+    @property
+    def _ema(self) -> Optional[torch.Tensor]:
+        """fp32, arena length; None while the averages are off"""
+        return self._ema_tensors()[0]
+
+    @property
+    def _ema_shadow(self) -> Optional[torch.Tensor]:
+        """compute dtype (None in fp32 mode and while the averages are off)"""
+        return self._ema_tensors()[1]
+
+    @property
+    def _ema_reading(self) -> bool:
+        """inside ema_weights(): the forward launches read the averages"""
+        return self._ema_selected()
 
     def __init__(self, dtype: int, device: Optional[torch.device], steps: int, base_lr: float, warm_up: int, beta_1: float,
                  beta_2: float, epsilon: float, loss_scaling: bool, rng_seed: int, predict_x: bool, predict_scaled_epsilon: bool,
@@ -191,7 +218,84 @@ class TrainerState:
         if self.ls_state is not None:
             call("gct2_scale_check_finite", grads_ptr, n, self.ls_state.data_ptr(), self._stream() if stream is None else stream)
 
+    # ---- exponential moving average of the parameters (tf.keras.optimizers.Adam(use_ema=True, ema_momentum=...)) [TF] -----------
+    # what an engine provides: _ema_source() -> (fp32 parameter arena, compute-dtype copy or None), raw storage;
+    # _ema_tensors() -> (averages, their compute-dtype copy or None) and _ema_attach(ema, ema_shadow), which stores them with whoever
+    # resolves weight pointers (ParamArena / _Net); _ema_select(on) / _ema_selected(), the switch between the two weight sets
+    def flush_deferred(self) -> None:
+        """optimizer launches an engine holds back (UNetEngine.defer_adam); nothing to do for an engine that holds none back"""
+
+    def enable_ema(self, momentum: float = 0.99) -> None:
+        """switch the parameter averages on (or change their momentum): average = momentum * average + (1 - momentum) * var after
+        every APPLIED optimizer step.  The averages start as copies of the current parameters and of their compute-dtype copy, as
+        Keras >= 2.11 creates them with initial_value=var; that is [TF] behaviour and parity-unpinned (there is no TensorFlow
+        here).  Optimizer launches the engine holds back are flushed first: they belong to a step made with the old setting."""
+        m = float(momentum)
+        if not (0.0 <= m <= 1.0):
+            raise ValueError(f"ema_momentum must lie in [0, 1], got {momentum!r}")
+        why = getattr(self, "_ema_forbidden", None)
+        if why:
+            raise ValueError(why)
+        if self._ema_reading:
+            raise _lib.Gct2Error("enable_ema inside ema_weights()")
+        self.flush_deferred()
+        if self._ema is None:
+            p, shadow = self._ema_source()
+            self._ema_attach(p.clone(), shadow.clone() if shadow is not None else None)
+        self.use_ema, self.ema_momentum = True, m
+
+    def disable_ema(self) -> None:
+        """drop the averages (their memory goes with them)"""
+        if self._ema_reading:
+            raise _lib.Gct2Error("disable_ema inside ema_weights()")
+        self.flush_deferred()
+        self.use_ema = False
+        self._ema_attach(None, None)
+
+    def _ema_launch(self, lo: int, hi: int, momentum: float, one_minus: float, ls_ptr: Optional[int], stream: int) -> None:
+        p, _ = self._ema_source()
+        sh = self._ema_shadow
+        call("gct2_ema_update", self._ema.data_ptr() + 4 * lo, p.data_ptr() + 4 * lo, None if sh is None else sh.data_ptr() + 2 * lo,
+             self.dtype, hi - lo, momentum, one_minus, ls_ptr, stream)
+
+    def _ema_step_update(self) -> None:
+        """every optimizer launch of the step is enqueued when finish_step() runs: one launch over the arena (UNetEngine, which may
+        hold some back, splits it)"""
+        m, c = ema_coefficients(self.ema_momentum)
+        self._ema_launch(0, self._ema.numel(), m, c, self._ls_ptr(), self._stream())
+
+    def ema_overwrite(self) -> None:
+        """Keras' finalize_variable_values: the parameters (and their compute-dtype copy) become the averages, as device copies"""
+        if not self.use_ema:
+            raise ValueError("ema_overwrite: the engine keeps no averages (Adam(use_ema=True) / enable_ema())")
+        self.flush_deferred()
+        p, shadow = self._ema_source()
+        p.copy_(self._ema)
+        if shadow is not None:
+            shadow.copy_(self._ema_shadow)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """inside, every forward launch (predict, the sampler) reads the averaged kernels, biases and Dense head instead of the raw
+        iterate; train_step refuses.  The raw weights are back on exit, also after an exception."""
+        if not self.use_ema:
+            raise ValueError("ema_weights: the engine keeps no averages (Adam(use_ema=True) / enable_ema())")
+        if self._ema_reading:
+            raise _lib.Gct2Error("ema_weights() is already active")
+        self.flush_deferred()
+        self._ema_select(True)
+        try:
+            yield self
+        finally:
+            self._ema_select(False)
+
+    def _refuse_training_on_averages(self) -> None:
+        if self._ema_reading:
+            raise _lib.Gct2Error("train_step inside ema_weights(): the step would differentiate the averaged weights")
+
     def finish_step(self) -> None:
+        if self.use_ema:                   # after every Adam launch of the step, in front of the loss-scale update (found_inf gates it)
+            self._ema_step_update()
         if self.ls_state is not None:      # applied_steps (= optimizer.iterations) advances on the device, only if finite
             call("gct2_loss_scale_update", self.ls_state.data_ptr(), LOSS_SCALE_GROWTH_INTERVAL, self._stream())
         else:

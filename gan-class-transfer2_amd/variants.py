@@ -47,16 +47,21 @@ class _Net:
         self.p, self.m, self.v, self.g = z(torch.float32), z(torch.float32), z(torch.float32), z(torch.float32)
         self.op = z(TORCH_DTYPE[self.dtype]) if self.dtype != F32 else self.p
         self.shapes = dict(self.specs)
+        # the exponential moving average of p and of the operand copy (TrainerState.enable_ema; None while EMA is off) and which
+        # of the two weight sets optr / pptr hand out (TrainerState.ema_weights)
+        self.ema = self.ema_op = None
+        self.read_ema = False
 
     def view(self, arena: torch.Tensor, name: str) -> torch.Tensor:
         o, shp = self.offsets[name], self.shapes[name]
         return arena[o:o + int(np.prod(shp))].view(shp)
 
     def optr(self, name: str) -> int:       # operand (compute dtype) pointer
-        return self.op.data_ptr() + self.offsets[name] * self.op.element_size()
+        op = self.ema_op if self.read_ema else self.op
+        return op.data_ptr() + self.offsets[name] * op.element_size()
 
     def pptr(self, name: str) -> int:
-        return self.p.data_ptr() + 4 * self.offsets[name]
+        return (self.ema if self.read_ema else self.p).data_ptr() + 4 * self.offsets[name]
 
     def gptr(self, name: str) -> int:
         return self.g.data_ptr() + 4 * self.offsets[name]
@@ -267,7 +272,8 @@ class VariantEngine(TrainerState):
                  device: Optional[torch.device] = None, steps: int = 200, base_lr: float = 2e-5, warm_up: int = 2000, beta_1: float = 0.9,
                  beta_2: float = 0.999, epsilon: float = 1e-7, loss_scaling: bool = False, seed: int = 1234, rng_seed: int = 0,
                  predict_x: bool = True, predict_scaled_epsilon: bool = False, prediction_weighting: bool = False,
-                 ordinary_differential_equation: bool = False, f32_matrix: bool = False):
+                 ordinary_differential_equation: bool = False, f32_matrix: bool = False, use_ema: bool = False,
+                 ema_momentum: float = 0.99):
         super().__init__(dtype, device, steps, base_lr, warm_up, beta_1, beta_2, epsilon, loss_scaling, rng_seed, predict_x,
                          predict_scaled_epsilon, prediction_weighting, ordinary_differential_equation, f32_matrix)
         self.octaves = octaves
@@ -282,6 +288,24 @@ class VariantEngine(TrainerState):
         self.partials = torch.zeros(1024, dtype=torch.float32, device=self.device)
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.last = {}
+        if use_ema:
+            self.enable_ema(ema_momentum)
+
+    # ---- the parameter averages (TrainerState.enable_ema) -------------------------------------------------------------------
+    def _ema_source(self):
+        return self.net.p, (self.net.op if self.dtype != F32 else None)
+
+    def _ema_tensors(self):
+        return self.net.ema, (self.net.ema_op if self.dtype != F32 else None)
+
+    def _ema_attach(self, ema, ema_shadow) -> None:
+        self.net.ema, self.net.ema_op = ema, (ema_shadow if self.dtype != F32 else ema)
+
+    def _ema_select(self, on: bool) -> None:
+        self.net.read_ema = bool(on)
+
+    def _ema_selected(self) -> bool:
+        return self.net.read_ema
 
     # ---- parameters ---------------------------------------------------------------------------------------------------------
     @property
@@ -350,6 +374,7 @@ class VariantEngine(TrainerState):
         """backward=False: Trainer.call (train.py:223-272), the loss of a freshly noised batch without gradients."""
         if x.dim() != 4 or x.shape[-1] != 3:
             raise ValueError(f"expected an NHWC batch [B,H,W,3], got {tuple(x.shape)}")
+        self._refuse_training_on_averages()
         x = x.to(self.device, torch.float32).contiguous()
         B, H, W, _ = x.shape
         if H % (2 ** self.octaves) or W % (2 ** self.octaves):
@@ -382,5 +407,9 @@ class VariantEngine(TrainerState):
              0.0 if self.ls_state is not None else self.adam_alpha(), self.beta_1, self.beta_2, self.epsilon, 1.0, self._ls_ptr(), 0, s)
         self.finish_step()
 
-    def predict(self, noised: torch.Tensor) -> torch.Tensor:
+    def predict(self, noised: torch.Tensor, use_ema: bool = False) -> torch.Tensor:
+        """use_ema: evaluate the averaged weights (ema_weights()) instead of the raw iterate"""
+        if use_ema:
+            with self.ema_weights():
+                return self.predict(noised)
         return self.top.fwd(noised.to(self.device, TORCH_DTYPE[self.dtype]).contiguous())

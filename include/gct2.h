@@ -37,7 +37,7 @@ enum {
 };
 
 /* library / device identification ------------------------------------------------------------ */
-int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed) */
+int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive)) */
 /* how the library was built: 0 for the product build; bit 0 (GCT2_BUILD_STAMP) = diagnostic build with in-kernel phase stamps
  * (make EXTRA=-DGCT2_STAMP).  Product hosts (the Python binding, bench.py, the tests) refuse a library whose flags are not 0. */
 enum { GCT2_BUILD_STAMP = 1 };
@@ -372,6 +372,18 @@ int gct2_loss_scale_update(gct2_loss_scale_state* state, int growth_interval, vo
 int gct2_adam_keras_multi(float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype,
                           size_t n, float alpha, float beta1, float beta2, float eps, float grad_mul,
                           const gct2_loss_scale_state* ls, int zero_grad, void* stream);
+
+/* Keras' optimizer EMA [TF] (Adam(use_ema=True, ema_momentum=...)): average = momentum * average + (1 - momentum) * var,
+ * elementwise, fp32: new = fl(fl(momentum * ema) + fl(one_minus * p)), two products and one sum, no contraction.
+ * ema, p: fp32 [n], 16-byte aligned.
+ * ema_shadow (may be NULL): copy of the NEW ema in shadow_dtype (GCT2_BF16 / GCT2_F16), 8-byte aligned, written in the same pass
+ *   (round to nearest even, overflow to +-inf: the bits gct2_cast_from_f32 writes).
+ * one_minus: the host forms 1 - momentum in double and rounds once, as Python does in the reference stack.
+ * ls (may be NULL): when ls->found_inf != 0 NOTHING is written (a skipped LossScaleOptimizer step leaves the averages alone).
+ * GCT2_EINVAL before any launch: NULL ema / p, n == 0, misaligned pointers, a shadow with shadow_dtype GCT2_F32 or unknown,
+ * momentum outside [0, 1] or not finite. */
+int gct2_ema_update(float* ema, const float* p, void* ema_shadow, int shadow_dtype, size_t n, float momentum, float one_minus,
+                    const gct2_loss_scale_state* ls, void* stream);
 
 /* fp32 -> dtype cast of a flat array (initial weight shadows). */
 int gct2_cast_from_f32(int dtype, const float* src, void* dst, size_t n, void* stream);
