@@ -585,6 +585,58 @@ int gct2_ema_update(float* ema, const float* p, void* ema_shadow, int shadow_dty
   return pw_ema(ema, p, ema_shadow, shadow_dtype, n, momentum, one_minus, ls, S(stream));
 }
 
+int gct2_sumsq_layout(const uint64_t* begin, const uint64_t* count, int nseg, gct2_sumsq_seg* out, size_t* npartials) {
+  if (!begin || !count || !out || !npartials) return gct2_fail(GCT2_EINVAL, "sumsq_layout: null pointer");
+  if (nseg < 1 || nseg > GCT2_SUMSQ_MAX_SEGMENTS)
+    return gct2_fail(GCT2_EINVAL, "sumsq_layout: nseg = %d outside [1, %d]", nseg, GCT2_SUMSQ_MAX_SEGMENTS);
+  uint64_t total = 0;
+  for (int s = 0; s < nseg; s++) {                 // everything is checked before anything is filled
+    if (count[s] == 0) return gct2_fail(GCT2_EINVAL, "sumsq_layout: segment %d is empty", s);
+    if (begin[s] % 4) return gct2_fail(GCT2_EINVAL, "sumsq_layout: segment %d begins at %llu, not a multiple of 4 elements", s, (unsigned long long)begin[s]);
+    if (begin[s] + count[s] < begin[s]) return gct2_fail(GCT2_EINVAL, "sumsq_layout: segment %d wraps around", s);
+    if (s && begin[s] < begin[s - 1]) return gct2_fail(GCT2_EINVAL, "sumsq_layout: segment %d begins before segment %d (ascending order)", s, s - 1);
+    if (s && begin[s] < begin[s - 1] + count[s - 1]) return gct2_fail(GCT2_EINVAL, "sumsq_layout: segments %d and %d overlap", s - 1, s);
+    total += (count[s] + GCT2_SUMSQ_CHUNK - 1) / GCT2_SUMSQ_CHUNK;
+  }
+  if (total > 0x7fffffffull) return gct2_fail(GCT2_EINVAL, "sumsq_layout: %llu partials are more than one launch covers", (unsigned long long)total);
+  uint64_t first = 0;
+  for (int s = 0; s < nseg; s++) {
+    out[s].begin = begin[s]; out[s].count = count[s]; out[s].first_partial = first;
+    first += (count[s] + GCT2_SUMSQ_CHUNK - 1) / GCT2_SUMSQ_CHUNK;
+  }
+  *npartials = (size_t)first;
+  return GCT2_OK;
+}
+
+int gct2_grad_sumsq(const float* g, const gct2_sumsq_seg* segs, int nseg, size_t npartials, float grad_mul, gct2_loss_scale_state* ls,
+                    double* partials, double* sumsq, void* stream) {
+  if (!g || !segs || !partials || !sumsq) return gct2_fail(GCT2_EINVAL, "grad_sumsq: null pointer");
+  if (nseg < 1 || nseg > GCT2_SUMSQ_MAX_SEGMENTS)
+    return gct2_fail(GCT2_EINVAL, "grad_sumsq: nseg = %d outside [1, %d]", nseg, GCT2_SUMSQ_MAX_SEGMENTS);
+  if (npartials == 0 || npartials < (size_t)nseg || npartials > 0x7fffffffull)
+    return gct2_fail(GCT2_EINVAL, "grad_sumsq: npartials = %zu is not what gct2_sumsq_layout reports for %d segments", npartials, nseg);
+  if ((uintptr_t)g % 16 || ((uintptr_t)segs | (uintptr_t)partials | (uintptr_t)sumsq) % 8)
+    return gct2_fail(GCT2_EINVAL, "grad_sumsq: g must be 16-byte aligned, segs / partials / sumsq 8-byte aligned");
+  return pw_grad_sumsq(g, segs, nseg, npartials, grad_mul, ls, partials, sumsq, S(stream));
+}
+
+int gct2_adam_keras_clipped(float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n, float alpha, float beta1,
+                            float beta2, float eps, float grad_mul, const gct2_loss_scale_state* ls, int clip_mode, float clip,
+                            const double* sumsq, void* stream) {
+  if (!p || !m || !v || !g) return gct2_fail(GCT2_EINVAL, "adam_keras_clipped: null pointer");
+  if (n == 0) return gct2_fail(GCT2_EINVAL, "adam_keras_clipped: n == 0");
+  if (shadow && shadow_dtype != GCT2_BF16 && shadow_dtype != GCT2_F16)
+    return gct2_fail(GCT2_EINVAL, "adam_keras_clipped: a shadow needs a 16-bit dtype (GCT2_BF16 / GCT2_F16), got %d", shadow_dtype);
+  if (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g) % 16 || (shadow && (uintptr_t)shadow % 8) || (uintptr_t)sumsq % 8)
+    return gct2_fail(GCT2_EINVAL, "adam_keras_clipped: p, m, v and g must be 16-byte aligned, the shadow and sumsq 8-byte aligned");
+  if (clip_mode < GCT2_CLIP_NONE || clip_mode > GCT2_CLIP_GLOBAL_NORM) return gct2_fail(GCT2_EINVAL, "adam_keras_clipped: unknown clip_mode %d", clip_mode);
+  if (clip_mode != GCT2_CLIP_NONE && !(clip > 0.f && clip <= 3.402823466e38f))
+    return gct2_fail(GCT2_EINVAL, "adam_keras_clipped: clip = %g must be finite and > 0", (double)clip);
+  if ((clip_mode == GCT2_CLIP_NORM || clip_mode == GCT2_CLIP_GLOBAL_NORM) && !sumsq)
+    return gct2_fail(GCT2_EINVAL, "adam_keras_clipped: clip_mode %d needs sumsq (gct2_grad_sumsq)", clip_mode);
+  return pw_adam_clipped(p, m, v, g, shadow, shadow_dtype, n, alpha, beta1, beta2, eps, grad_mul, ls, clip_mode, clip, sumsq, S(stream));
+}
+
 int gct2_loss_scale_init(gct2_loss_scale_state* st, float initial_scale, void* stream) {
   if (!st || !(initial_scale > 0.f)) return gct2_fail(GCT2_EINVAL, "loss_scale_init: null state or non-positive scale");
   return pw_ls_init(st, initial_scale, S(stream));

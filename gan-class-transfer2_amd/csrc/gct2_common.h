@@ -460,6 +460,12 @@ int pw_adam(float* p, float* m, float* v, float* g, void* shadow, int shadow_dty
 // Keras' optimizer EMA over a flat range: ema = momentum * ema + one_minus * p, the new value also in the 16-bit shadow (may be null)
 int pw_ema(float* ema, const float* p, void* shadow, int shadow_dtype, size_t n, float momentum, float one_minus,
            const gct2_loss_scale_state* ls, hipStream_t s);
+// gradient clipping: per-segment and total sum of squares of the scaled gradient in fp64 (two launches, fixed summation order; sets
+// ls->found_inf like pw_ls_check) / pw_adam from the arena with the clipping step of `mode` between g' and the update
+int pw_grad_sumsq(const float* g, const gct2_sumsq_seg* segs, int nseg, size_t npartials, float grad_mul, gct2_loss_scale_state* ls,
+                  double* partials, double* sumsq, hipStream_t s);
+int pw_adam_clipped(float* p, float* m, float* v, const float* g, void* shadow, int shadow_dtype, size_t n, float alpha, float b1, float b2,
+                    float eps, float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip, const double* sumsq, hipStream_t s);
 int pw_cast(int dtype, const float* src, void* dst, size_t n, hipStream_t s);
 int pw_ls_init(gct2_loss_scale_state* st, float scale, hipStream_t s);
 int pw_ls_begin(gct2_loss_scale_state* st, float base_lr, int warmup_steps, float b1, float b2, hipStream_t s);

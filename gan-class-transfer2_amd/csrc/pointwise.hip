@@ -988,6 +988,136 @@ __global__ void ls_update_kernel(gct2_loss_scale_state* s, int growth_interval) 
   s->inv_scale = 1.f / s->scale;
 }
 
+// ---- gradient clipping (Keras clipnorm / global_clipnorm / clipvalue [TF]) ----------------------------------------------------
+// stage one of gct2_grad_sumsq: work-group c owns partial c = one chunk of GCT2_SUMSQ_CHUNK elements (the last chunk of a segment
+// may be shorter) and never reads outside its segment.  g' = fl32(g * k) as adam_kernel forms it; the square (exact) and every sum
+// in fp64, in a fixed order: a thread over its own elements in address order, the 64 lanes of a wave by an xor butterfly (both
+// operands of every add are the same pair on both lanes, so all lanes hold the same bits), the four waves in wave order.
+__global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ g, const gct2_sumsq_seg* __restrict__ segs, int nseg,
+                                                            float grad_mul, gct2_loss_scale_state* ls, double* __restrict__ partials) {
+#pragma clang fp contract(off)
+  const uint64_t c = blockIdx.x;
+  int lo = 0, hi = nseg - 1;                       // the last segment whose first partial is <= c (uniform over the work-group)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (segs[mid].first_partial <= c) lo = mid; else hi = mid - 1;
+  }
+  const uint64_t off = (c - segs[lo].first_partial) * (uint64_t)GCT2_SUMSQ_CHUNK, count = segs[lo].count;
+  const uint64_t len = off >= count ? 0 : (count - off < (uint64_t)GCT2_SUMSQ_CHUNK ? count - off : (uint64_t)GCT2_SUMSQ_CHUNK);
+  const float* __restrict__ src = g + segs[lo].begin + off;       // 16-byte aligned: begin and the chunk are multiples of 4 elements
+  const float k = (ls ? ls->inv_scale : 1.f) * grad_mul;
+  const uint32_t n4 = (uint32_t)(len >> 2);
+  double acc = 0.0;
+  bool bad = false;
+#pragma unroll 4
+  for (uint32_t i = threadIdx.x; i < n4; i += 256) {
+    const f32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(src) + i);     // read once per step: streaming
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      bad |= !(fabsf(v[e]) <= 3.402823466e38f);    // the RAW element: false for inf and nan (ls_check_kernel's test)
+      const double x = (double)(v[e] * k);
+      acc = acc + x * x;
+    }
+  }
+  if (threadIdx.x < (uint32_t)(len & 3)) {         // tail (len % 4 elements)
+    const float r = src[((size_t)n4 << 2) + threadIdx.x];
+    bad |= !(fabsf(r) <= 3.402823466e38f);
+    const double x = (double)(r * k);
+    acc = acc + x * x;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) acc = acc + __shfl_xor(acc, d, 64);
+  const bool wave_bad = __any(bad);
+  __shared__ double ws[4];
+  if ((threadIdx.x & 63) == 0) {
+    ws[threadIdx.x >> 6] = acc;
+    if (ls && wave_bad) atomicOr(&ls->found_inf, 1);      // the flag gct2_scale_check_finite sets (an integer atomic: order-free)
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) partials[c] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
+// stage two: one work-group; thread s adds the partials of segment s in index order, then thread 0 adds the segments in segment order
+__global__ __launch_bounds__(256) void sumsq_final_kernel(const gct2_sumsq_seg* __restrict__ segs, int nseg, const double* __restrict__ partials,
+                                                          double* __restrict__ sumsq) {
+  __shared__ double seg_sum[GCT2_SUMSQ_MAX_SEGMENTS];
+  for (int s = threadIdx.x; s < nseg; s += 256) {
+    const uint64_t np = (segs[s].count + GCT2_SUMSQ_CHUNK - 1) / GCT2_SUMSQ_CHUNK;
+    const double* __restrict__ src = partials + segs[s].first_partial;
+    double acc = 0.0;
+    for (uint64_t i = 0; i < np; i++) acc = acc + src[i];
+    seg_sum[s] = acc;
+    sumsq[s] = acc;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double acc = 0.0;
+    for (int s = 0; s < nseg; s++) acc = acc + seg_sum[s];
+    sumsq[nseg] = acc;
+  }
+}
+
+// the step between g' and adam_keras_update; `a` is the launch-uniform operand of the mode (clipped_adam_kernel forms it once)
+__device__ __forceinline__ float clip_grad(float g, int mode, float clip, float a) {
+#pragma clang fp contract(off)
+  switch (mode) {
+    case GCT2_CLIP_VALUE: return g < -clip ? -clip : (g > clip ? clip : g);      // a NaN fails both comparisons and stays (TF's minimum / maximum)
+    case GCT2_CLIP_NORM: { const float t = g * clip; return t / a; }             // tf.clip_by_norm: (g * clip) / max(l2, clip)
+    case GCT2_CLIP_GLOBAL_NORM: return g * a;                                    // tf.clip_by_global_norm: g * scale
+    default: return g;
+  }
+}
+// adam_kernel (same geometry, streaming accesses, shadow write, ls skip and ls->alpha; the gradient comes from g only and is never
+// zeroed) with clip_grad between g' and the update
+template <typename S, bool HAS_SHADOW>
+__global__ __launch_bounds__(256) void clipped_adam_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                                           const float* __restrict__ g, S* __restrict__ shadow, size_t n, float alpha,
+                                                           float b1, float b2, float eps, float grad_mul,
+                                                           const gct2_loss_scale_state* __restrict__ ls, int mode, float clip,
+                                                           const double* __restrict__ sumsq) {
+#pragma clang fp contract(off)
+  if (ls && ls->found_inf != 0) return;            // a skipped step writes nothing
+  const float inv_scale = (ls ? ls->inv_scale : 1.f) * grad_mul;
+  if (ls) alpha = ls->alpha;
+  float a = 0.f;
+  if (mode == GCT2_CLIP_NORM) {
+    const double ss = *sumsq;
+    const float l2 = ss > 0.0 ? (float)sqrt(ss) : 1.f;
+    a = fmaxf(l2, clip);
+  } else if (mode == GCT2_CLIP_GLOBAL_NORM) {
+    const float nrm = (float)sqrt(*sumsq);         // the double square root, rounded once to fp32
+    a = fabsf(nrm) <= 3.402823466e38f ? clip * fminf(1.f / nrm, 1.f / clip) : __builtin_nanf("");
+  }
+  const size_t n4 = n >> 2;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const float ob1 = 1.f - b1, ob2 = 1.f - b2;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const f32x4_t gv = reinterpret_cast<const f32x4_t*>(g)[i];
+    f32x4_t pv = __builtin_nontemporal_load(reinterpret_cast<f32x4_t*>(p) + i), mv = __builtin_nontemporal_load(reinterpret_cast<f32x4_t*>(m) + i),
+            vv = __builtin_nontemporal_load(reinterpret_cast<f32x4_t*>(v) + i);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      float pp = pv[k], mm = mv[k], v1 = vv[k];
+      adam_keras_update(pp, mm, v1, clip_grad(gv[k] * inv_scale, mode, clip, a), alpha, b1, ob1, b2, ob2, eps);
+      pv[k] = pp; mv[k] = mm; vv[k] = v1;
+    }
+    __builtin_nontemporal_store(pv, reinterpret_cast<f32x4_t*>(p) + i);
+    __builtin_nontemporal_store(mv, reinterpret_cast<f32x4_t*>(m) + i);
+    __builtin_nontemporal_store(vv, reinterpret_cast<f32x4_t*>(v) + i);
+    if constexpr (HAS_SHADOW) {
+      const u32x2_t o = {pack2<S>(pv[0], pv[1]), pack2<S>(pv[2], pv[3])};
+      reinterpret_cast<u32x2_t*>(shadow)[i] = o;
+    }
+  }
+  // tail (n % 4 elements)
+  const size_t i = (n4 << 2) + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    float mm = m[i], vv = v[i], pp = p[i];
+    adam_keras_update(pp, mm, vv, clip_grad(g[i] * inv_scale, mode, clip, a), alpha, b1, ob1, b2, ob2, eps);
+    m[i] = mm; v[i] = vv; p[i] = pp;
+    if constexpr (HAS_SHADOW) shadow[i] = from_f32<S>(pp);
+  }
+}
+
 inline int blocks_for(size_t n, int per_block) {
   size_t b = (n + per_block - 1) / per_block;
   return (int)(b < 1 ? 1 : (b > (size_t)kMaxBlocks ? kMaxBlocks : b));
@@ -1214,6 +1344,23 @@ int pw_ema(float* ema, const float* p, void* shadow, int sdt, size_t n, float mo
   else GCT2_EMA(_Float16, true);
 #undef GCT2_EMA
   return gct2_check_launch("ema_update");
+}
+int pw_grad_sumsq(const float* g, const gct2_sumsq_seg* segs, int nseg, size_t npartials, float grad_mul, gct2_loss_scale_state* ls,
+                  double* partials, double* sumsq, hipStream_t s) {
+  hipLaunchKernelGGL(sumsq_partial_kernel, dim3((unsigned)npartials), dim3(256), 0, s, g, segs, nseg, grad_mul, ls, partials);
+  if (int e = gct2_check_launch("grad_sumsq")) return e;
+  hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, s, segs, nseg, partials, sumsq);
+  return gct2_check_launch("grad_sumsq");
+}
+int pw_adam_clipped(float* p, float* m, float* v, const float* g, void* shadow, int sdt, size_t n, float alpha, float b1, float b2, float eps,
+                    float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip, const double* sumsq, hipStream_t s) {
+  const int nb = blocks_for(n / 4 + 4, 256);
+#define GCT2_ADAM(S, HS) hipLaunchKernelGGL((clipped_adam_kernel<S, HS>), dim3(nb), dim3(256), 0, s, p, m, v, g, reinterpret_cast<S*>(shadow), n, alpha, b1, b2, eps, grad_mul, ls, mode, clip, sumsq)
+  if (!shadow) GCT2_ADAM(float, false);
+  else if (sdt == GCT2_BF16) GCT2_ADAM(__bf16, true);
+  else GCT2_ADAM(_Float16, true);
+#undef GCT2_ADAM
+  return gct2_check_launch("adam_keras_clipped");
 }
 int pw_cast(int dtype, const float* src, void* dst, size_t n, hipStream_t s) {
   if (n == 0) return GCT2_OK;

@@ -154,6 +154,17 @@ def _one_stream_less(engine, exchange: bool) -> None:
         engine.chain_priority = False
 
 
+def _refuse_clipping(engine, who: str) -> None:
+    """gradient clipping (Adam(clipnorm / global_clipnorm / clipvalue)) is single-GPU only: a global norm needs every bucket reduced
+    before the first update, which the bucketed exchange - updates start while later buckets are still in flight - does not give;
+    that scheduling change is not built.  Refuses an engine that clips and makes its set_clipping refuse from here on."""
+    if getattr(engine, "clip_mode", 0) != 0:
+        raise ValueError(f"{who} updates bucket by bucket while later gradients are still being exchanged: it cannot clip gradients "
+                         "(Adam(clipnorm / global_clipnorm / clipvalue)); switch clipping off (set_clipping())")
+    engine._clip_forbidden = (f"this engine is driven by {who}, which updates bucket by bucket while later gradients are still being "
+                              "exchanged: gradient clipping (set_clipping) is not available there")
+
+
 class DataParallelStep:
     """drives UNetEngine.train_step on every rank with overlapped gradient all-reduce.
 
@@ -163,6 +174,7 @@ class DataParallelStep:
     UNetEngine.backward has waited for the dgrad launches of every earlier layer - the last readers of their weights."""
 
     def __init__(self, engine, bucket_elems: int = 4 << 20, group=None, force_exchange: bool = False):
+        _refuse_clipping(engine, "DataParallelStep")
         self.engine = engine
         A = engine.arena
         self.reducer = BucketedAllReducer(A.g, A.ready_order(), A.layer_ranges, bucket_elems, group, force_exchange, engine=engine)
@@ -259,6 +271,7 @@ class ShardedDataParallelStep:
     kernels behind the last bucket's reduce-scatter / all-gather."""
 
     def __init__(self, engine, bucket_elems: int = 4 << 20, group=None, force_exchange: bool = False, tail_layers: int = 3):
+        _refuse_clipping(engine, "ShardedDataParallelStep")
         if getattr(engine, "use_ema", False):
             raise ValueError("ShardedDataParallelStep holds only a shard of the fp32 parameters per rank: it cannot keep the engine's "
                              "parameter averages (Adam(use_ema=True)); use DataParallelStep, or switch them off")

@@ -955,6 +955,12 @@ class UNetEngine(TrainerState):
     def _apply_adam(self, lo: int = 0, hi: Optional[int] = None, grad_div: float = 1.0, stream: Optional[int] = None) -> None:
         A, s = self.arena, (self._stream() if stream is None else stream)
         hi = A.total if hi is None else hi
+        if self.clip_mode != _lib.CLIP_NONE:
+            if self._clip_by_norm() and (lo, hi) != (0, A.total):
+                raise ValueError(f"apply_adam({lo}, {hi}) with clipnorm / global_clipnorm: a norm needs every gradient of the arena "
+                                 f"[0, {A.total}) reduced before the first update; clipping under a bucketed exchange is not built")
+            self._adam_clipped(A._p, A._m, A._v, A.g, A._shadow, lo, hi, 1.0 / grad_div, s)
+            return
         # with loss scaling the kernel takes inv_scale / found_inf / alpha from the device-resident state (the step counter that
         # alpha depends on only advances on applied steps); otherwise alpha comes from the host's counter
         ls_ptr = self._ls_ptr()
@@ -963,6 +969,13 @@ class UNetEngine(TrainerState):
         call("gct2_adam_keras_multi", A._p.data_ptr() + 4 * lo, A._m.data_ptr() + 4 * lo, A._v.data_ptr() + 4 * lo,
              A.g.data_ptr() + 4 * lo, shadow, self.dtype, hi - lo, Slot("alpha", alpha), self.beta_1, self.beta_2,
              self.epsilon, 1.0 / grad_div, ls_ptr, 0, s)
+
+    def _clip_segments(self) -> List[Tuple[int, int]]:
+        A = self.arena
+        return sorted((o, A.numel(name)) for name, o in A.offsets.items())
+
+    def _clip_device(self) -> torch.device:
+        return self.arena.g.device
 
     def check_finite(self, lo: int = 0, hi: Optional[int] = None, stream: Optional[int] = None) -> None:
         hi = self.arena.total if hi is None else hi
@@ -980,7 +993,7 @@ class UNetEngine(TrainerState):
             x = x.to(self.device, torch.float32).contiguous()
         B, H, W, _ = x.shape
         b = self.buffers(B, H, W)
-        inline = apply and self.fuse_adam and self.ls_state is None
+        inline = apply and self.fuse_adam and self.ls_state is None and self.clip_mode == _lib.CLIP_NONE
         self.post_backward_ran = self.post_backward is not None and not apply
         cur = torch.cuda.current_stream(self.device)
         if self._flush_event is not None:                      # a flush on another stream (predict / state_dict there): the step waits once
@@ -1033,7 +1046,8 @@ class UNetEngine(TrainerState):
             self.post_backward()
         if apply:
             if not inline:
-                self.check_finite()
+                if not self._clip_by_norm():                   # (a norm-clipped step: gct2_grad_sumsq sets found_inf in its one pass)
+                    self.check_finite()
                 self.apply_adam()
             self.finish_step()
         return loss
@@ -1049,7 +1063,7 @@ class UNetEngine(TrainerState):
                 # baked into recorded arguments (gct2_adam_keras_multi, gct2_loss_scale_begin) or restored into the per-layer
                 # gct2_adam_args by every replay: Trainer.compile() may legally rewrite them between steps
                 self.dtype, float(self.beta_1), float(self.beta_2), float(self.epsilon), float(self.base_lr), int(self.warm_up),
-                id(self.post_replay), self._side.cuda_stream, self.use_ema, float(self.ema_momentum),
+                id(self.post_replay), self._side.cuda_stream, self.use_ema, float(self.ema_momentum), self.clip_mode, float(self.clip),
                 self._chain_stream.cuda_stream if self._chain_stream is not None else 0)
 
     def _planned_step(self, b: _Buffers, x: torch.Tensor, apply: bool, inline: bool, cur: "torch.cuda.Stream") -> torch.Tensor:

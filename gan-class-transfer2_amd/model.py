@@ -17,8 +17,9 @@ import torch
 
 from . import _lib
 from . import trainer_math
-from ._lib import BF16, F16, F32, call
+from ._lib import BF16, CLIP_NONE, F16, F32, call
 from .engine import TORCH_DTYPE, Topology, UNetEngine
+from .trainer_math import clipping_mode
 
 # ---- train.py:17-36 ---------------------------------------------------------------------------------
 size = 256
@@ -94,10 +95,14 @@ class Adam:
     """tf.keras.optimizers.Adam hyper-parameters (train.py:75); the update itself is
     gct2_adam_keras_multi (epsilon added to sqrt(v)).  use_ema / ema_momentum [TF]: the engine keeps an exponential
     moving average of the parameters (gct2_ema_update after every applied step); finalize_variable_values() overwrites the
-    parameters with it, predict(..., use_ema=True) and log_sample(..., use_ema=True) read it."""
+    parameters with it, predict(..., use_ema=True) and log_sample(..., use_ema=True) read it.  clipnorm / global_clipnorm /
+    clipvalue [TF]: the engine clips the gradients per variable, all together or per element (gct2_grad_sumsq,
+    gct2_adam_keras_clipped) on its non-fused optimizer path."""
 
     def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, use_ema=False, ema_momentum=0.99,
-                 ema_overwrite_frequency=None):
+                 ema_overwrite_frequency=None, clipnorm=None, global_clipnorm=None, clipvalue=None):
+        clipping_mode(clipnorm, global_clipnorm, clipvalue)        # Keras' rule: at most one of the three, each > 0 (ValueError)
+        self.clipnorm, self.global_clipnorm, self.clipvalue = clipnorm, global_clipnorm, clipvalue
         if ema_overwrite_frequency is not None:
             raise NotImplementedError("ema_overwrite_frequency: periodic overwriting is not built; call "
                                       "optimizer.finalize_variable_values() where the parameters should become the averages")
@@ -157,7 +162,19 @@ def engine_hyper_parameters(optimizer) -> Dict[str, object]:
         kw.update(base_lr=float(lr), warm_up=0)
     if getattr(inner, "use_ema", False):
         kw.update(use_ema=True, ema_momentum=float(inner.ema_momentum))
+    mode, clip = clipping_mode(*(getattr(inner, k, None) for k in CLIP_ARGUMENTS))
+    if mode != CLIP_NONE:
+        kw.update(clip_mode=mode, clip=clip)
     return kw
+
+
+CLIP_ARGUMENTS = ("clipnorm", "global_clipnorm", "clipvalue")
+
+
+def clipping_arguments(optimizer) -> Dict[str, object]:
+    """the optimizer's three clipping arguments as keyword arguments of an engine's set_clipping (all None: off)"""
+    inner = getattr(optimizer, "inner", optimizer)
+    return {k: getattr(inner, k, None) for k in CLIP_ARGUMENTS}
 
 
 def alpha_dash(t):
@@ -509,7 +526,11 @@ class Trainer(Layer):
             if "base_lr" not in kw:
                 raise NotImplementedError("only WarmUp or constant learning rates are supported")
             kw["loss_scaling"] = bool(getattr(opt, "inner", opt).loss_scaling)
+        clipped = kw.pop("clip_mode", None) is not None
+        kw.pop("clip", None)
         eng = self.denoiser.ensure_engine(**kw)
+        if clipped:                                      # (a fresh engine: clipping is a setting, not a constructor argument)
+            eng.set_clipping(**clipping_arguments(opt))
         # train.py:238-252 reads the objective globals every time Trainer.call runs: an engine built earlier (by denoiser(...),
         # trainable_variables, the log_sample callback) follows the switches as they stand now
         for k, v in objective_switches().items():
@@ -539,8 +560,10 @@ class Trainer(Layer):
             eng, inner = self.denoiser.engine, getattr(optimizer, "inner", optimizer)
             hp = engine_hyper_parameters(optimizer)
             for k, v in hp.items():
-                if k not in ("use_ema", "ema_momentum"):
+                if k not in ("use_ema", "ema_momentum", "clip_mode", "clip"):
                     setattr(eng, k, v)
+            if "clip_mode" in hp or getattr(eng, "clip_mode", CLIP_NONE) != CLIP_NONE:
+                eng.set_clipping(**clipping_arguments(optimizer))      # (an optimizer without clipping switches it off)
             if hp.get("use_ema"):                         # the averages start from the parameters as they stand now
                 eng.enable_ema(hp["ema_momentum"])
             elif getattr(eng, "use_ema", False):

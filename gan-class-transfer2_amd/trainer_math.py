@@ -9,6 +9,7 @@ holds the values bit for bit.
 from __future__ import annotations
 
 import contextlib
+import ctypes as C
 import math
 from typing import Optional, Sequence, Tuple
 
@@ -16,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import F32, call
+from ._lib import F32, Slot, call
 
 LOSS_SCALE_GROWTH_INTERVAL = 2000   # tf.keras.mixed_precision.LossScaleOptimizer's dynamic_growth_steps default [TF]
 
@@ -82,6 +83,24 @@ def ema_coefficients(momentum: float) -> Tuple[float, float]:
     return float(np.float32(momentum)), float(np.float32(1.0 - float(momentum)))
 
 
+def clipping_mode(clipnorm=None, global_clipnorm=None, clipvalue=None) -> Tuple[int, float]:
+    """Keras' three optimizer clipping arguments [TF] as (gct2_adam_keras_clipped mode, threshold): at most one of them, each finite
+    and > 0 (ValueError otherwise); all None is (CLIP_NONE, 0.0)"""
+    given = [(k, m, v) for k, m, v in (("clipnorm", _lib.CLIP_NORM, clipnorm), ("global_clipnorm", _lib.CLIP_GLOBAL_NORM, global_clipnorm),
+                                       ("clipvalue", _lib.CLIP_VALUE, clipvalue)) if v is not None]
+    if len(given) > 1:
+        raise ValueError(f"at most one of clipnorm, global_clipnorm and clipvalue can be set, got {', '.join(k for k, _, _ in given)}")
+    if not given:
+        return _lib.CLIP_NONE, 0.0
+    name, mode, value = given[0]
+    value = float(value)
+    with np.errstate(all="ignore"):
+        as_f32 = float(np.float32(value))                # what the C ABI receives
+    if not (value > 0.0 and as_f32 > 0.0 and math.isfinite(as_f32)):
+        raise ValueError(f"{name} must be a finite float32 > 0, got {given[0][2]!r}")
+    return mode, value
+
+
 OBJECTIVE_SWITCHES = ("predict_x", "predict_scaled_epsilon", "prediction_weighting", "ordinary_differential_equation")
 
 
@@ -94,6 +113,10 @@ class TrainerState:
     # that never switches it on carries no state for it); enable_ema() / disable_ema() write them.  The averages themselves and the
     # switch between the two weight sets live where weight pointers are resolved (ParamArena / _Net): the three names below read them
     use_ema, ema_momentum = False, 0.99
+    # gradient clipping (Keras Adam(clipnorm / global_clipnorm / clipvalue) [TF]): off by default, set_clipping() writes the pair; the
+    # reduction's segment table and buffers (_clip_reduction) exist only after the first norm-clipped step
+    clip_mode, clip = _lib.CLIP_NONE, 0.0
+    _clip_table = None
 
     @property
     def _ema(self) -> Optional[torch.Tensor]:
@@ -217,6 +240,64 @@ class TrainerState:
     def _check_finite(self, grads_ptr: int, n: int, stream: Optional[int] = None) -> None:
         if self.ls_state is not None:
             call("gct2_scale_check_finite", grads_ptr, n, self.ls_state.data_ptr(), self._stream() if stream is None else stream)
+
+    # ---- gradient clipping (tf.keras.optimizers.Adam(clipnorm=..., global_clipnorm=..., clipvalue=...)) [TF] --------------------------
+    # what an engine provides: _clip_segments() -> one (begin, count) per parameter tensor inside its gradient arena, in arena order
+    # and without the alignment padding; _clip_device() -> where that arena lives
+    def set_clipping(self, clipnorm: Optional[float] = None, global_clipnorm: Optional[float] = None, clipvalue: Optional[float] = None) -> None:
+        """Keras' rule: at most one of the three, each > 0 and finite (ValueError); all None switches clipping off.  A hyper-parameter
+        like beta_1: it holds from the next step on and is not part of a checkpoint.  Optimizer launches the engine holds back are
+        flushed first: they belong to a step made with the old setting."""
+        mode, value = clipping_mode(clipnorm, global_clipnorm, clipvalue)
+        why = getattr(self, "_clip_forbidden", None)
+        if why and mode != _lib.CLIP_NONE:
+            raise ValueError(why)
+        self.flush_deferred()
+        self.clip_mode, self.clip = mode, value
+
+    def _clip_by_norm(self) -> bool:
+        """the step reduces the gradient arena first (gct2_grad_sumsq, which also sets the loss-scale state's found_inf)"""
+        return self.clip_mode in (_lib.CLIP_NORM, _lib.CLIP_GLOBAL_NORM)
+
+    def _clip_reduction(self):
+        """(device segment table, nseg, npartials, partials, sumsq, [(begin, count)]) of gct2_grad_sumsq: laid out by
+        gct2_sumsq_layout, uploaded and allocated on first use, kept for the engine's lifetime (step plans hold the addresses)"""
+        if self._clip_table is None:
+            segs = [(int(b), int(c)) for b, c in self._clip_segments()]
+            n = len(segs)
+            begin, count = (C.c_uint64 * n)(*[b for b, _ in segs]), (C.c_uint64 * n)(*[c for _, c in segs])
+            out, npartials = (C.c_uint64 * (3 * n))(), C.c_size_t(0)
+            _lib.check(_lib.load().gct2_sumsq_layout(begin, count, n, out, C.byref(npartials)), "gct2_sumsq_layout")
+            dev = self._clip_device()
+            table = torch.tensor(list(out), dtype=torch.int64).to(dev)          # gct2_sumsq_seg[n]: three 64-bit words each
+            self._clip_table = (table, n, int(npartials.value), torch.zeros(npartials.value, dtype=torch.float64, device=dev),
+                                torch.zeros(n + 1, dtype=torch.float64, device=dev), segs)
+        return self._clip_table
+
+    def _adam_clipped(self, p: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tensor, shadow: Optional[torch.Tensor], lo: int, hi: int,
+                      grad_mul: float, stream: int) -> None:
+        """the optimizer launches of a clipped step over arenas (tensors; shadow None in fp32 mode): clipvalue = one
+        gct2_adam_keras_clipped over [lo, hi).  The norm modes take the whole arena, [lo, hi) = [0, total): global_clipnorm =
+        gct2_grad_sumsq, then one launch over [0, total) reading the total; clipnorm = gct2_grad_sumsq, then one launch per tensor
+        over exactly its elements, reading its own sum"""
+        ls_ptr = self._ls_ptr()
+        alpha = 0.0 if self.ls_state is not None else self.adam_alpha()
+
+        def launch(lo: int, n: int, sumsq_ptr: Optional[int]) -> None:
+            call("gct2_adam_keras_clipped", p.data_ptr() + 4 * lo, m.data_ptr() + 4 * lo, v.data_ptr() + 4 * lo, g.data_ptr() + 4 * lo,
+                 None if shadow is None else shadow.data_ptr() + 2 * lo, self.dtype, n, Slot("alpha", alpha), self.beta_1, self.beta_2,
+                 self.epsilon, grad_mul, ls_ptr, self.clip_mode, float(self.clip), sumsq_ptr, stream)
+
+        if not self._clip_by_norm():
+            launch(lo, hi - lo, None)
+            return
+        table, nseg, npartials, partials, sumsq, segs = self._clip_reduction()
+        call("gct2_grad_sumsq", g.data_ptr(), table.data_ptr(), nseg, npartials, grad_mul, ls_ptr, partials.data_ptr(), sumsq.data_ptr(), stream)
+        if self.clip_mode == _lib.CLIP_GLOBAL_NORM:
+            launch(lo, hi - lo, sumsq.data_ptr() + 8 * nseg)
+        else:
+            for s, (begin, n) in enumerate(segs):
+                launch(begin, n, sumsq.data_ptr() + 8 * s)
 
     # ---- exponential moving average of the parameters (tf.keras.optimizers.Adam(use_ema=True, ema_momentum=...)) [TF] -----------
     # what an engine provides: _ema_source() -> (fp32 parameter arena, compute-dtype copy or None), raw storage;

@@ -307,6 +307,13 @@ class VariantEngine(TrainerState):
     def _ema_selected(self) -> bool:
         return self.net.read_ema
 
+    # ---- gradient clipping (TrainerState.set_clipping) ----------------------------------------------------------------------
+    def _clip_segments(self):
+        return sorted((self.net.offsets[name], int(np.prod(shp))) for name, shp in self.net.specs)
+
+    def _clip_device(self):
+        return self.net.g.device
+
     # ---- parameters ---------------------------------------------------------------------------------------------------------
     @property
     def shapes(self) -> Dict[str, Tuple[int, ...]]:
@@ -401,6 +408,12 @@ class VariantEngine(TrainerState):
 
     def apply_adam(self) -> None:
         N, s = self.net, self.net.stream()
+        if self.clip_mode != _lib.CLIP_NONE:
+            if not self._clip_by_norm():                       # (a norm-clipped step: gct2_grad_sumsq sets found_inf in its one pass)
+                self._check_finite(N.g.data_ptr(), N.g.numel(), s)
+            self._adam_clipped(N.p, N.m, N.v, N.g, N.op if self.dtype != F32 else None, 0, N.p.numel(), 1.0, s)
+            self.finish_step()
+            return
         self._check_finite(N.g.data_ptr(), N.g.numel(), s)
         shadow = N.op.data_ptr() if self.dtype != F32 else None
         call("gct2_adam_keras_multi", N.p.data_ptr(), N.m.data_ptr(), N.v.data_ptr(), N.g.data_ptr(), shadow, self.dtype, N.p.numel(),

@@ -37,7 +37,7 @@ enum {
 };
 
 /* library / device identification ------------------------------------------------------------ */
-int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive)) */
+int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive); v17 + gct2_sumsq_layout, gct2_grad_sumsq, gct2_adam_keras_clipped (additive)) */
 /* how the library was built: 0 for the product build; bit 0 (GCT2_BUILD_STAMP) = diagnostic build with in-kernel phase stamps
  * (make EXTRA=-DGCT2_STAMP).  Product hosts (the Python binding, bench.py, the tests) refuse a library whose flags are not 0. */
 enum { GCT2_BUILD_STAMP = 1 };
@@ -384,6 +384,56 @@ int gct2_adam_keras_multi(float* p, float* m, float* v, float* g, void* shadow, 
  * momentum outside [0, 1] or not finite. */
 int gct2_ema_update(float* ema, const float* p, void* ema_shadow, int shadow_dtype, size_t n, float momentum, float one_minus,
                     const gct2_loss_scale_state* ls, void* stream);
+
+/* ---- gradient clipping [TF]: Keras' optimizer arguments clipvalue / clipnorm / global_clipnorm (opt-in; train.py uses none) ----
+ * GCT2_CLIP_VALUE clips every element, GCT2_CLIP_NORM every variable to an L2 norm (tf.clip_by_norm), GCT2_CLIP_GLOBAL_NORM all
+ * variables together (tf.clip_by_global_norm).  The two norm modes read a sum of squares that gct2_grad_sumsq leaves on the device. */
+#define GCT2_CLIP_NONE 0
+#define GCT2_CLIP_VALUE 1
+#define GCT2_CLIP_NORM 2
+#define GCT2_CLIP_GLOBAL_NORM 3
+#define GCT2_SUMSQ_CHUNK 32768           /* elements one fp64 partial covers (one work-group of stage one; a multiple of 4) */
+#define GCT2_SUMSQ_MAX_SEGMENTS 1024     /* largest nseg of gct2_sumsq_layout / gct2_grad_sumsq */
+/* one variable inside the fp32 gradient arena: elements [begin, begin + count), its partials at [first_partial, first_partial +
+ * ceil(count / GCT2_SUMSQ_CHUNK)) */
+typedef struct { uint64_t begin, count, first_partial; } gct2_sumsq_seg;
+
+/* host only, no launch: checks the segments, then fills out[nseg] and *npartials (the length of gct2_grad_sumsq's `partials`).
+ * Each segment gets ceil(count / GCT2_SUMSQ_CHUNK) partials; first_partial is the running prefix.
+ * GCT2_EINVAL, nothing filled: a NULL pointer, nseg outside [1, GCT2_SUMSQ_MAX_SEGMENTS], count == 0, begin % 4 != 0 (a chunk is
+ * read with 16-byte loads), segments not in ascending order or overlapping. */
+int gct2_sumsq_layout(const uint64_t* begin, const uint64_t* count, int nseg, gct2_sumsq_seg* out, size_t* npartials);
+
+/* sumsq[s] = sum over segment s of (double)g'^2 for s < nseg, sumsq[nseg] = sumsq[0] + ... + sumsq[nseg-1] in segment order, where
+ *   k = fl32((ls ? ls->inv_scale : 1) * grad_mul),  g' = fl32(g * k)   - the g' of gct2_adam_keras_multi.
+ * The square (exact: an fp32 value squared fits fp64) and every addition are fp64.  Stage one (one launch, npartials work-groups of
+ * 256 threads) leaves one partial per chunk - a chunk never straddles a segment, and elements outside every segment are never read
+ * (padding and neighbouring buffers may hold NaN); stage two (one work-group) adds a segment's partials in index order and the
+ * segments in segment order.  No floating-point atomics: the bits depend on the input alone, not on the order work-groups arrive in
+ * or on the stream.
+ * g: fp32, 16-byte aligned; segs: device copy of gct2_sumsq_layout's out[nseg]; partials: device [npartials]; sumsq: device
+ * [nseg + 1]; all three 8-byte aligned.
+ * ls (may be NULL): ls->found_inf |= any(!isfinite(RAW g inside a segment)) - the flag gct2_scale_check_finite sets, so a
+ *   norm-clipped loss-scaled step needs no separate pass over the gradients.
+ * GCT2_EINVAL before any launch: NULL g / segs / partials / sumsq, nseg outside [1, GCT2_SUMSQ_MAX_SEGMENTS], npartials == 0 or
+ * < nseg, misaligned pointers. */
+int gct2_grad_sumsq(const float* g, const gct2_sumsq_seg* segs, int nseg, size_t npartials, float grad_mul, gct2_loss_scale_state* ls,
+                    double* partials, double* sumsq, void* stream);
+
+/* gct2_adam_keras_multi (zero_grad = 0; same geometry, shadow write, ls skip and ls->alpha) with one step between g' and the update,
+ * fp32, no contraction:
+ *   GCT2_CLIP_NONE:        g'' = g'                                  (the bits of gct2_adam_keras_multi)
+ *   GCT2_CLIP_VALUE:       g'' = min(max(g', -clip), clip)           (a NaN stays NaN, as TF's minimum / maximum)
+ *   GCT2_CLIP_NORM:        l2 = *sumsq > 0 ? (float)sqrt(*sumsq) : 1;  g'' = fl(fl(g' * clip) / max(l2, clip))
+ *   GCT2_CLIP_GLOBAL_NORM: nrm = (float)sqrt(*sumsq);  scale = isfinite(nrm) ? fl(clip * min(1 / nrm, 1 / clip)) : NaN;
+ *                          g'' = fl(g' * scale)   (as in TF, a scale that is not exactly 1 below the threshold is accepted)
+ * sqrt is the double one, rounded once to fp32.  sumsq: ONE fp64 value on the device (gct2_grad_sumsq's sumsq + s for a variable,
+ * sumsq + nseg for the global norm), 8-byte aligned; NULL for NONE / VALUE.  shadow (may be NULL): GCT2_BF16 / GCT2_F16 copy of p.
+ * GCT2_EINVAL before any launch: NULL p / m / v / g, n == 0, misaligned pointers, a shadow with shadow_dtype GCT2_F32 or unknown,
+ * unknown clip_mode, clip not finite or <= 0 in a clipping mode, a norm mode with sumsq == NULL. */
+int gct2_adam_keras_clipped(float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n,
+                            float alpha, float beta1, float beta2, float eps, float grad_mul,
+                            const gct2_loss_scale_state* ls, int clip_mode, float clip, const double* sumsq, void* stream);
 
 /* fp32 -> dtype cast of a flat array (initial weight shadows). */
 int gct2_cast_from_f32(int dtype, const float* src, void* dst, size_t n, void* stream);
