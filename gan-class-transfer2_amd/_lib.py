@@ -19,6 +19,9 @@ BUILD_STAMP = 1
 # gct2_adam_keras_clipped modes and the reduction's constants (include/gct2.h)
 CLIP_NONE, CLIP_VALUE, CLIP_NORM, CLIP_GLOBAL_NORM = 0, 1, 2, 3
 SUMSQ_CHUNK, SUMSQ_MAX_SEGMENTS = 32768, 1024
+# gct2_optimizer_apply kinds (Adam has its own entry points) and gct2_loss_scale_begin_schedule schedules (include/gct2.h)
+OPT_ADAM, OPT_SGD, OPT_RMSPROP = 0, 1, 2
+SCHEDULE_WARMUP, SCHEDULE_INVERSE_TIME_DECAY = 0, 1
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgct2.so")
@@ -94,9 +97,11 @@ SIGNATURES = {
     "gct2_sumsq_layout": [_vp, _vp, _i, _vp, C.POINTER(C.c_size_t)],
     "gct2_grad_sumsq": [_vp, _vp, _i, _sz, _f, _vp, _vp, _vp, _vp],
     "gct2_adam_keras_clipped": [_vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _f, _f, _f, _vp, _i, _f, _vp, _vp],
+    "gct2_optimizer_apply": [_i, _vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _i, _f, _f, _f, _vp, _i, _f, _vp, _vp],
     "gct2_cast_from_f32": [_i, _vp, _vp, _sz, _vp],
     "gct2_loss_scale_init": [_vp, _f, _vp],
     "gct2_loss_scale_begin": [_vp, _f, _i, _f, _f, _vp],
+    "gct2_loss_scale_begin_schedule": [_vp, _i, _f, _f, _f, _i, _i, _f, _f, _vp],
     "gct2_scale_check_finite": [_vp, _sz, _vp, _vp],
     "gct2_loss_scale_update": [_vp, _i, _vp],
     "gct2_plan_create": [C.POINTER(C.c_void_p)],

@@ -637,6 +637,30 @@ int gct2_adam_keras_clipped(float* p, float* m, float* v, float* g, void* shadow
   return pw_adam_clipped(p, m, v, g, shadow, shadow_dtype, n, alpha, beta1, beta2, eps, grad_mul, ls, clip_mode, clip, sumsq, S(stream));
 }
 
+int gct2_optimizer_apply(int kind, float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,
+                         int nesterov, float rho, float epsilon, float grad_mul, const gct2_loss_scale_state* ls, int clip_mode, float clip,
+                         const double* sumsq, void* stream) {
+  if (kind != GCT2_OPT_SGD && kind != GCT2_OPT_RMSPROP)
+    return gct2_fail(GCT2_EINVAL, "optimizer_apply: unknown kind %d (GCT2_OPT_SGD / GCT2_OPT_RMSPROP; Adam is gct2_adam_keras_clipped)", kind);
+  if (!(momentum >= 0.f && momentum <= 1.f)) return gct2_fail(GCT2_EINVAL, "optimizer_apply: momentum %g outside [0, 1]", (double)momentum);
+  if (kind == GCT2_OPT_RMSPROP && !(rho >= 0.f && rho <= 1.f)) return gct2_fail(GCT2_EINVAL, "optimizer_apply: rho %g outside [0, 1]", (double)rho);
+  if (kind == GCT2_OPT_RMSPROP && !(epsilon >= 0.f)) return gct2_fail(GCT2_EINVAL, "optimizer_apply: epsilon %g < 0", (double)epsilon);
+  const bool use_m = momentum > 0.f, use_v = kind == GCT2_OPT_RMSPROP;
+  if (!p || !g || (use_m && !m) || (use_v && !v)) return gct2_fail(GCT2_EINVAL, "optimizer_apply: null pointer");
+  if (n == 0) return gct2_fail(GCT2_EINVAL, "optimizer_apply: n == 0");
+  if (shadow && shadow_dtype != GCT2_BF16 && shadow_dtype != GCT2_F16)
+    return gct2_fail(GCT2_EINVAL, "optimizer_apply: a shadow needs a 16-bit dtype (GCT2_BF16 / GCT2_F16), got %d", shadow_dtype);
+  if (((uintptr_t)p | (uintptr_t)g | (use_m ? (uintptr_t)m : 0) | (use_v ? (uintptr_t)v : 0)) % 16 || (shadow && (uintptr_t)shadow % 8) ||
+      (uintptr_t)sumsq % 8)
+    return gct2_fail(GCT2_EINVAL, "optimizer_apply: p, g and the slots in use must be 16-byte aligned, the shadow and sumsq 8-byte aligned");
+  if (clip_mode < GCT2_CLIP_NONE || clip_mode > GCT2_CLIP_GLOBAL_NORM) return gct2_fail(GCT2_EINVAL, "optimizer_apply: unknown clip_mode %d", clip_mode);
+  if (clip_mode != GCT2_CLIP_NONE && !(clip > 0.f && clip <= 3.402823466e38f))
+    return gct2_fail(GCT2_EINVAL, "optimizer_apply: clip = %g must be finite and > 0", (double)clip);
+  if ((clip_mode == GCT2_CLIP_NORM || clip_mode == GCT2_CLIP_GLOBAL_NORM) && !sumsq)
+    return gct2_fail(GCT2_EINVAL, "optimizer_apply: clip_mode %d needs sumsq (gct2_grad_sumsq)", clip_mode);
+  return pw_optimizer(kind, p, m, v, g, shadow, shadow_dtype, n, lr, momentum, nesterov, rho, epsilon, grad_mul, ls, clip_mode, clip, sumsq, S(stream));
+}
+
 int gct2_loss_scale_init(gct2_loss_scale_state* st, float initial_scale, void* stream) {
   if (!st || !(initial_scale > 0.f)) return gct2_fail(GCT2_EINVAL, "loss_scale_init: null state or non-positive scale");
   return pw_ls_init(st, initial_scale, S(stream));
@@ -644,6 +668,19 @@ int gct2_loss_scale_init(gct2_loss_scale_state* st, float initial_scale, void* s
 int gct2_loss_scale_begin(gct2_loss_scale_state* st, float base_lr, int warmup_steps, float beta1, float beta2, void* stream) {
   if (!st || warmup_steps < 0) return gct2_fail(GCT2_EINVAL, "loss_scale_begin: null state or negative warm-up");
   return pw_ls_begin(st, base_lr, warmup_steps, beta1, beta2, S(stream));
+}
+int gct2_loss_scale_begin_schedule(gct2_loss_scale_state* st, int schedule, float initial, float steps, float decay_rate, int staircase,
+                                   int bias_correction, float beta1, float beta2, void* stream) {
+  if (!st) return gct2_fail(GCT2_EINVAL, "loss_scale_begin_schedule: null state");
+  if (schedule == GCT2_SCHEDULE_WARMUP) {
+    if (!(steps >= 0.f && steps <= 16777216.f) || steps != (float)(int)steps)
+      return gct2_fail(GCT2_EINVAL, "loss_scale_begin_schedule: warm-up steps %g must be a whole number in [0, 2^24]", (double)steps);
+  } else if (schedule == GCT2_SCHEDULE_INVERSE_TIME_DECAY) {
+    if (!(steps > 0.f)) return gct2_fail(GCT2_EINVAL, "loss_scale_begin_schedule: decay_steps %g must be > 0", (double)steps);
+  } else {
+    return gct2_fail(GCT2_EINVAL, "loss_scale_begin_schedule: unknown schedule %d", schedule);
+  }
+  return pw_ls_begin_schedule(st, schedule, initial, steps, decay_rate, staircase, bias_correction, beta1, beta2, S(stream));
 }
 int gct2_scale_check_finite(const float* g, size_t n, gct2_loss_scale_state* st, void* stream) {
   if (!g || !st) return gct2_fail(GCT2_EINVAL, "scale_check_finite: null pointer");

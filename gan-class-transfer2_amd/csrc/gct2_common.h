@@ -466,9 +466,15 @@ int pw_grad_sumsq(const float* g, const gct2_sumsq_seg* segs, int nseg, size_t n
                   double* partials, double* sumsq, hipStream_t s);
 int pw_adam_clipped(float* p, float* m, float* v, const float* g, void* shadow, int shadow_dtype, size_t n, float alpha, float b1, float b2,
                     float eps, float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip, const double* sumsq, hipStream_t s);
+// Keras SGD / RMSprop over a flat range (kind: GCT2_OPT_SGD / GCT2_OPT_RMSPROP): pw_adam_clipped's geometry over the slots the kind uses
+int pw_optimizer(int kind, float* p, float* m, float* v, const float* g, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,
+                 int nesterov, float rho, float eps, float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip, const double* sumsq,
+                 hipStream_t s);
 int pw_cast(int dtype, const float* src, void* dst, size_t n, hipStream_t s);
 int pw_ls_init(gct2_loss_scale_state* st, float scale, hipStream_t s);
 int pw_ls_begin(gct2_loss_scale_state* st, float base_lr, int warmup_steps, float b1, float b2, hipStream_t s);
+int pw_ls_begin_schedule(gct2_loss_scale_state* st, int schedule, float initial, float steps, float decay_rate, int staircase, int bias_correction,
+                         float b1, float b2, hipStream_t s);
 int pw_ls_check(const float* g, size_t n, gct2_loss_scale_state* st, hipStream_t s);
 int pw_ls_update(gct2_loss_scale_state* st, int growth_interval, hipStream_t s);
 int pw_relu_bits(int dtype, const void* y, int ldy, size_t pixels, int channels, unsigned char* bits, int ldbits, hipStream_t s);

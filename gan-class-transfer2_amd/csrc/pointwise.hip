@@ -1118,6 +1118,126 @@ __global__ __launch_bounds__(256) void clipped_adam_kernel(float* __restrict__ p
   }
 }
 
+// ---- Keras SGD / RMSprop over a flat arena [TF] (include/gct2.h gct2_optimizer_apply) ---------------------------------------------
+// one element of the kind's update; m / v are touched only where USE_M / KIND say so.  Every product, sum, quotient and root is
+// rounded once (no contraction), in the order the header gives
+template <int KIND, bool USE_M>
+__device__ __forceinline__ void optimizer_update(float& p, float& m, float& v, float g, float lr, float momentum, bool nesterov, float rho,
+                                                 float orho, float eps) {
+#pragma clang fp contract(off)
+  const float step = lr * g;
+  if constexpr (KIND == GCT2_OPT_SGD) {
+    if constexpr (USE_M) {
+      const float a = momentum * m;
+      m = a - step;
+      if (nesterov) {
+        const float b = momentum * m;
+        p = p + (b - step);
+      } else {
+        p = p + m;
+      }
+    } else {
+      p = p - step;
+    }
+  } else {
+    const float v1 = rho * v, g2 = g * g;
+    const float v2 = orho * g2;
+    v = v1 + v2;
+    if constexpr (USE_M) {
+      const float a = momentum * m, den = sqrtf(v + eps);
+      m = a + step / den;
+      p = p - m;
+    } else {
+      const float den = sqrtf(v) + eps;
+      p = p - step / den;
+    }
+  }
+}
+// clipped_adam_kernel's geometry (256 threads, f32x4 main loop and a scalar tail, streaming accesses on what is touched once per step,
+// the shadow packed two per dword, ls skip and ls->alpha, clip_grad between g' and the update) over the slots the kind uses: m only
+// with momentum, v only for RMSprop - the other pointers are never dereferenced (they may be null)
+template <int KIND, bool USE_M, typename S, bool HAS_SHADOW>
+__global__ __launch_bounds__(256) void optimizer_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                                        const float* __restrict__ g, S* __restrict__ shadow, size_t n, float lr,
+                                                        float momentum, int nesterov, float rho, float eps, float grad_mul,
+                                                        const gct2_loss_scale_state* __restrict__ ls, int mode, float clip,
+                                                        const double* __restrict__ sumsq) {
+#pragma clang fp contract(off)
+  constexpr bool USE_V = KIND == GCT2_OPT_RMSPROP;
+  if (ls && ls->found_inf != 0) return;            // a skipped step writes nothing
+  const float inv_scale = (ls ? ls->inv_scale : 1.f) * grad_mul;
+  if (ls) lr = ls->alpha;
+  float a = 0.f;
+  if (mode == GCT2_CLIP_NORM) {
+    const double ss = *sumsq;
+    const float l2 = ss > 0.0 ? (float)sqrt(ss) : 1.f;
+    a = fmaxf(l2, clip);
+  } else if (mode == GCT2_CLIP_GLOBAL_NORM) {
+    const float nrm = (float)sqrt(*sumsq);
+    a = fabsf(nrm) <= 3.402823466e38f ? clip * fminf(1.f / nrm, 1.f / clip) : __builtin_nanf("");
+  }
+  const bool nes = nesterov != 0;
+  const float orho = 1.f - rho;
+  const size_t n4 = n >> 2;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const f32x4_t gv = reinterpret_cast<const f32x4_t*>(g)[i];
+    f32x4_t pv = __builtin_nontemporal_load(reinterpret_cast<f32x4_t*>(p) + i);
+    f32x4_t mv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (USE_M) mv = __builtin_nontemporal_load(reinterpret_cast<f32x4_t*>(m) + i);
+    if constexpr (USE_V) vv = __builtin_nontemporal_load(reinterpret_cast<f32x4_t*>(v) + i);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      float pp = pv[k], mm = mv[k], v1 = vv[k];
+      optimizer_update<KIND, USE_M>(pp, mm, v1, clip_grad(gv[k] * inv_scale, mode, clip, a), lr, momentum, nes, rho, orho, eps);
+      pv[k] = pp; mv[k] = mm; vv[k] = v1;
+    }
+    __builtin_nontemporal_store(pv, reinterpret_cast<f32x4_t*>(p) + i);
+    if constexpr (USE_M) __builtin_nontemporal_store(mv, reinterpret_cast<f32x4_t*>(m) + i);
+    if constexpr (USE_V) __builtin_nontemporal_store(vv, reinterpret_cast<f32x4_t*>(v) + i);
+    if constexpr (HAS_SHADOW) {
+      const u32x2_t o = {pack2<S>(pv[0], pv[1]), pack2<S>(pv[2], pv[3])};
+      reinterpret_cast<u32x2_t*>(shadow)[i] = o;
+    }
+  }
+  // tail (n % 4 elements)
+  const size_t i = (n4 << 2) + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    float pp = p[i], mm = 0.f, vv = 0.f;
+    if constexpr (USE_M) mm = m[i];
+    if constexpr (USE_V) vv = v[i];
+    optimizer_update<KIND, USE_M>(pp, mm, vv, clip_grad(g[i] * inv_scale, mode, clip, a), lr, momentum, nes, rho, orho, eps);
+    p[i] = pp;
+    if constexpr (USE_M) m[i] = mm;
+    if constexpr (USE_V) v[i] = vv;
+    if constexpr (HAS_SHADOW) shadow[i] = from_f32<S>(pp);
+  }
+}
+
+// gct2_loss_scale_begin_schedule: ls_begin_kernel for either schedule, with or without Adam's bias correction; float32 in Keras' order
+__global__ void ls_begin_schedule_kernel(gct2_loss_scale_state* s, int schedule, float initial, float steps, float decay_rate, int staircase,
+                                         int bias_correction, float b1, float b2) {
+#pragma clang fp contract(off)
+  s->found_inf = 0;
+  const int k = s->applied_steps;
+  float lr;
+  if (schedule == GCT2_SCHEDULE_WARMUP) {
+    const int warmup_steps = (int)steps;
+    lr = k < warmup_steps ? initial * (float)(k + 1) / (float)(warmup_steps + 1) : initial;
+  } else {
+    float q = (float)k / steps;
+    if (staircase) q = floorf(q);
+    const float r = decay_rate * q;
+    lr = initial / (1.f + r);
+  }
+  if (bias_correction) {
+    const double t = (double)(k + 1);
+    s->alpha = (float)((double)lr * sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t)));
+  } else {
+    s->alpha = lr;
+  }
+}
+
 inline int blocks_for(size_t n, int per_block) {
   size_t b = (n + per_block - 1) / per_block;
   return (int)(b < 1 ? 1 : (b > (size_t)kMaxBlocks ? kMaxBlocks : b));
@@ -1362,6 +1482,18 @@ int pw_adam_clipped(float* p, float* m, float* v, const float* g, void* shadow, 
 #undef GCT2_ADAM
   return gct2_check_launch("adam_keras_clipped");
 }
+int pw_optimizer(int kind, float* p, float* m, float* v, const float* g, void* shadow, int sdt, size_t n, float lr, float momentum, int nesterov,
+                 float rho, float eps, float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip, const double* sumsq, hipStream_t s) {
+  const int nb = blocks_for(n / 4 + 4, 256);
+  const bool use_m = momentum > 0.f;
+#define GCT2_OPT(K, M, S, HS) hipLaunchKernelGGL((optimizer_kernel<K, M, S, HS>), dim3(nb), dim3(256), 0, s, p, m, v, g, reinterpret_cast<S*>(shadow), n, lr, momentum, nesterov, rho, eps, grad_mul, ls, mode, clip, sumsq)
+#define GCT2_OPT_SHADOW(K, M) do { if (!shadow) GCT2_OPT(K, M, float, false); else if (sdt == GCT2_BF16) GCT2_OPT(K, M, __bf16, true); else GCT2_OPT(K, M, _Float16, true); } while (0)
+  if (kind == GCT2_OPT_SGD) { if (use_m) GCT2_OPT_SHADOW(GCT2_OPT_SGD, true); else GCT2_OPT_SHADOW(GCT2_OPT_SGD, false); }
+  else { if (use_m) GCT2_OPT_SHADOW(GCT2_OPT_RMSPROP, true); else GCT2_OPT_SHADOW(GCT2_OPT_RMSPROP, false); }
+#undef GCT2_OPT_SHADOW
+#undef GCT2_OPT
+  return gct2_check_launch("optimizer_apply");
+}
 int pw_cast(int dtype, const float* src, void* dst, size_t n, hipStream_t s) {
   if (n == 0) return GCT2_OK;
   const int nb = blocks_for(n, 256);
@@ -1378,6 +1510,11 @@ int pw_ls_init(gct2_loss_scale_state* st, float scale, hipStream_t s) {
 int pw_ls_begin(gct2_loss_scale_state* st, float base_lr, int warmup_steps, float b1, float b2, hipStream_t s) {
   hipLaunchKernelGGL(ls_begin_kernel, dim3(1), dim3(1), 0, s, st, base_lr, warmup_steps, b1, b2);
   return gct2_check_launch("loss_scale_begin");
+}
+int pw_ls_begin_schedule(gct2_loss_scale_state* st, int schedule, float initial, float steps, float decay_rate, int staircase, int bias_correction,
+                         float b1, float b2, hipStream_t s) {
+  hipLaunchKernelGGL(ls_begin_schedule_kernel, dim3(1), dim3(1), 0, s, st, schedule, initial, steps, decay_rate, staircase, bias_correction, b1, b2);
+  return gct2_check_launch("loss_scale_begin_schedule");
 }
 int pw_ls_check(const float* g, size_t n, gct2_loss_scale_state* st, hipStream_t s) {
   if (n == 0) return GCT2_OK;

@@ -165,6 +165,17 @@ def _refuse_clipping(engine, who: str) -> None:
                               "exchanged: gradient clipping (set_clipping) is not available there")
 
 
+def _refuse_optimizer(engine, who: str) -> str:
+    """Keras SGD / RMSprop (set_optimizer) are single-GPU only: no multi-rank step has been run or tested with them.  Refuses an engine
+    whose kind is not Adam; returns the message with which the engine's set_optimizer refuses another kind from then on (the caller
+    stores it as engine._optimizer_forbidden once nothing else refuses the engine)."""
+    if getattr(engine, "optimizer_kind", "adam") != "adam":
+        raise ValueError(f"{who} has only been built and tested with Adam: it cannot drive an engine whose optimizer is "
+                         f"{engine.optimizer_kind} (set_optimizer('adam') while no step has been applied)")
+    return (f"this engine is driven by {who}, which has only been built and tested with Adam: SGD and RMSprop (set_optimizer) are not "
+            "available there")
+
+
 class DataParallelStep:
     """drives UNetEngine.train_step on every rank with overlapped gradient all-reduce.
 
@@ -174,7 +185,9 @@ class DataParallelStep:
     UNetEngine.backward has waited for the dgrad launches of every earlier layer - the last readers of their weights."""
 
     def __init__(self, engine, bucket_elems: int = 4 << 20, group=None, force_exchange: bool = False):
+        adam_only = _refuse_optimizer(engine, "DataParallelStep")
         _refuse_clipping(engine, "DataParallelStep")
+        engine._optimizer_forbidden = adam_only
         self.engine = engine
         A = engine.arena
         self.reducer = BucketedAllReducer(A.g, A.ready_order(), A.layer_ranges, bucket_elems, group, force_exchange, engine=engine)
@@ -271,12 +284,14 @@ class ShardedDataParallelStep:
     kernels behind the last bucket's reduce-scatter / all-gather."""
 
     def __init__(self, engine, bucket_elems: int = 4 << 20, group=None, force_exchange: bool = False, tail_layers: int = 3):
+        adam_only = _refuse_optimizer(engine, "ShardedDataParallelStep")
         _refuse_clipping(engine, "ShardedDataParallelStep")
         if getattr(engine, "use_ema", False):
             raise ValueError("ShardedDataParallelStep holds only a shard of the fp32 parameters per rank: it cannot keep the engine's "
                              "parameter averages (Adam(use_ema=True)); use DataParallelStep, or switch them off")
         engine._ema_forbidden = ("this engine is driven by ShardedDataParallelStep, which holds only a shard of the fp32 parameters per "
                                  "rank: parameter averages (enable_ema) are not available there")
+        engine._optimizer_forbidden = adam_only
         self.engine, self.group = engine, group
         A = engine.arena
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1

@@ -26,6 +26,7 @@ from . import _lib
 from ._lib import BF16, F16, F32, Slot, call
 from .trainer_math import TrainerState, glorot_limit
 from .trainer_math import ema_coefficients as TM_ema_coefficients
+from .trainer_math import OPTIMIZER_KINDS as _OPTIMIZER_CODES
 
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 
@@ -947,7 +948,7 @@ class UNetEngine(TrainerState):
 
     # ---- optimizer (train.py:50-65,75) -----------------------------------------------------------
     def apply_adam(self, lo: int = 0, hi: Optional[int] = None, grad_div: float = 1.0, stream: Optional[int] = None) -> None:
-        """Keras Adam on arena range [lo, hi); does not advance `iterations` (see finish_step).
+        """the optimizer (Keras Adam; SGD / RMSprop after set_optimizer) on arena range [lo, hi); does not advance `iterations` (see finish_step).
         grad_div > 1 folds the data-parallel mean (sum over ranks / world size) into the gradient read."""
         self.flush_deferred()
         self._apply_adam(lo, hi, grad_div, stream)
@@ -955,11 +956,12 @@ class UNetEngine(TrainerState):
     def _apply_adam(self, lo: int = 0, hi: Optional[int] = None, grad_div: float = 1.0, stream: Optional[int] = None) -> None:
         A, s = self.arena, (self._stream() if stream is None else stream)
         hi = A.total if hi is None else hi
-        if self.clip_mode != _lib.CLIP_NONE:
+        if self.clip_mode != _lib.CLIP_NONE or self.optimizer_kind != "adam":
             if self._clip_by_norm() and (lo, hi) != (0, A.total):
                 raise ValueError(f"apply_adam({lo}, {hi}) with clipnorm / global_clipnorm: a norm needs every gradient of the arena "
                                  f"[0, {A.total}) reduced before the first update; clipping under a bucketed exchange is not built")
-            self._adam_clipped(A._p, A._m, A._v, A.g, A._shadow, lo, hi, 1.0 / grad_div, s)
+            launches = self._adam_clipped if self.optimizer_kind == "adam" else self._optimizer_launches       # (SGD / RMSprop, clipped or not)
+            launches(A._p, A._m, A._v, A.g, A._shadow, lo, hi, 1.0 / grad_div, s)
             return
         # with loss scaling the kernel takes inv_scale / found_inf / alpha from the device-resident state (the step counter that
         # alpha depends on only advances on applied steps); otherwise alpha comes from the host's counter
@@ -993,7 +995,7 @@ class UNetEngine(TrainerState):
             x = x.to(self.device, torch.float32).contiguous()
         B, H, W, _ = x.shape
         b = self.buffers(B, H, W)
-        inline = apply and self.fuse_adam and self.ls_state is None and self.clip_mode == _lib.CLIP_NONE
+        inline = apply and self.fuse_adam and self.ls_state is None and self.clip_mode == _lib.CLIP_NONE and self.optimizer_kind == "adam"
         self.post_backward_ran = self.post_backward is not None and not apply
         cur = torch.cuda.current_stream(self.device)
         if self._flush_event is not None:                      # a flush on another stream (predict / state_dict there): the step waits once
@@ -1064,6 +1066,7 @@ class UNetEngine(TrainerState):
                 # gct2_adam_args by every replay: Trainer.compile() may legally rewrite them between steps
                 self.dtype, float(self.beta_1), float(self.beta_2), float(self.epsilon), float(self.base_lr), int(self.warm_up),
                 id(self.post_replay), self._side.cuda_stream, self.use_ema, float(self.ema_momentum), self.clip_mode, float(self.clip),
+                self.optimizer_kind, float(self.momentum), bool(self.nesterov), float(self.rho), self.lr_schedule,
                 self._chain_stream.cuda_stream if self._chain_stream is not None else 0)
 
     def _planned_step(self, b: _Buffers, x: torch.Tensor, apply: bool, inline: bool, cur: "torch.cuda.Stream") -> torch.Tensor:
@@ -1123,7 +1126,7 @@ class UNetEngine(TrainerState):
         P.set("x", x.data_ptr())
         P.set("off_t", self.rng_offset_t)
         P.set("off_eps", self.rng_offset_eps)
-        alpha = self.adam_alpha() if self.ls_state is None else 0.0
+        alpha = self.step_size() if self.ls_state is None else 0.0
         P.set("alpha", alpha)
         sp.x_ref = x                                            # keeps the batch alive until the next step replaces it
         hook = self.grad_ready_hook
@@ -1169,8 +1172,9 @@ class UNetEngine(TrainerState):
 
     # ---- state serialisation (the reference has none, train.py:499-503 only logs) ----------------
     def state_dict(self) -> Dict[str, torch.Tensor]:
-        """everything a run needs to continue bit-identically: fp32 parameters and Adam slots (one arena each, layout =
-        ParamArena.offsets), optimizer iterations, RNG stream positions, loss-scale state.  CPU tensors, safetensors-ready."""
+        """everything a run needs to continue bit-identically: fp32 parameters and optimizer slots (one arena each, layout =
+        ParamArena.offsets), optimizer iterations, RNG stream positions, loss-scale state and, for SGD / RMSprop, "optimizer" = [kind
+        code, momentum, nesterov, rho] (load_state_dict checks the kind).  CPU tensors, safetensors-ready."""
         if getattr(self, "_masters_sharded", False):
             raise _lib.Gct2Error("the fp32 parameters and Adam slots of this engine are sharded over the data-parallel ranks "
                                  "(ShardedDataParallelStep): use its state_dict() / save_checkpoint() (they gather first), or call "
@@ -1182,6 +1186,9 @@ class UNetEngine(TrainerState):
               "topology": torch.tensor([self.topo.pixel_size, self.topo.max_size, self.topo.octaves, A.total, A.LAYOUT], dtype=torch.int64)}
         if self.ls_state is not None:
             sd["loss_scale_state"] = self.ls_state.cpu()
+        if self.optimizer_kind != "adam":       # (only then: an Adam engine's dictionary is what it always was)
+            sd["optimizer"] = torch.tensor([_OPTIMIZER_CODES[self.optimizer_kind], float(self.momentum), float(bool(self.nesterov)), float(self.rho)],
+                                           dtype=torch.float64)
         if self.use_ema:                # (only then: without the averages the dictionary is what it always was)
             sd["arena.ema"] = A.ema.cpu()
             sd["ema_momentum"] = torch.tensor([float(self.ema_momentum)], dtype=torch.float64)      # (restored by load_state_dict)
@@ -1245,6 +1252,10 @@ class UNetEngine(TrainerState):
             raise ValueError(f"checkpoint topology / layout {have} != engine {want}")
         if ("loss_scale_state" in sd) != (self.ls_state is not None):
             raise ValueError("checkpoint and engine disagree on dynamic loss scaling (mixed_precision, train.py:34)")
+        kind = {c: k for k, c in _OPTIMIZER_CODES.items()}.get(int(sd["optimizer"][0]), "?") if "optimizer" in sd else "adam"
+        if kind != self.optimizer_kind:
+            raise ValueError(f"the checkpoint was written by a {kind} optimizer and this engine runs {self.optimizer_kind}: the slots m / v "
+                             "mean different things (set_optimizer before loading)")
         if "arena.ema" in sd and not self.use_ema:
             raise ValueError("the checkpoint holds parameter averages (Adam(use_ema=True)) and this engine keeps none: switch them on "
                              "(enable_ema) before loading - they are not dropped silently")

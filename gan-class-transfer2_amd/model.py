@@ -1,7 +1,7 @@
 """Host-side mirror of the reference's Python model/train-loop surface (train.py:17-283, 498-523).
 
 Same names, constructor arguments and defaults as /root/reference/train.py so a user of that script finds
-`WarmUp`, `alpha_dash`, `Residual`, `Block`, `UpShuffle`, `DownShuffle`, `identity`, `Denoiser`, `Trainer`,
+`WarmUp`, `Adam`, `SGD`, `RMSprop`, `InverseTimeDecay`, `alpha_dash`, `Residual`, `Block`, `UpShuffle`, `DownShuffle`, `identity`, `Denoiser`, `Trainer`,
 `compile`/`fit` and the module-level hyper-parameters here; tensors are NHWC torch tensors on the HIP device
 and all arithmetic runs in libgct2.so (include/gct2.h).  There is no TensorFlow and no CPU fallback.
 
@@ -91,16 +91,27 @@ class WarmUp:
         return trainer_math.warmup_lr(step, self.base, self.warmup_steps)
 
 
-class Adam:
-    """tf.keras.optimizers.Adam hyper-parameters (train.py:75); the update itself is
-    gct2_adam_keras_multi (epsilon added to sqrt(v)).  use_ema / ema_momentum [TF]: the engine keeps an exponential
-    moving average of the parameters (gct2_ema_update after every applied step); finalize_variable_values() overwrites the
-    parameters with it, predict(..., use_ema=True) and log_sample(..., use_ema=True) read it.  clipnorm / global_clipnorm /
-    clipvalue [TF]: the engine clips the gradients per variable, all together or per element (gct2_grad_sumsq,
-    gct2_adam_keras_clipped) on its non-fused optimizer path."""
+class InverseTimeDecay:
+    """tf.keras.optimizers.schedules.InverseTimeDecay [TF] (train.py:70, 73): lr(step) = initial / (1 + decay_rate * step / decay_steps),
+    the quotient floored when staircase; float32 in Keras' order (trainer_math.inverse_time_decay_lr)."""
 
-    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, use_ema=False, ema_momentum=0.99,
-                 ema_overwrite_frequency=None, clipnorm=None, global_clipnorm=None, clipvalue=None):
+    def __init__(self, initial_learning_rate, decay_steps, decay_rate, staircase=False):
+        trainer_math.inverse_time_decay_schedule(initial_learning_rate, decay_steps, decay_rate, staircase)      # decay_steps > 0 (ValueError)
+        self.initial_learning_rate, self.decay_steps, self.decay_rate, self.staircase = initial_learning_rate, decay_steps, decay_rate, staircase
+
+    def __call__(self, step):
+        return trainer_math.inverse_time_decay_lr(step, self.initial_learning_rate, self.decay_steps, self.decay_rate, self.staircase)
+
+
+class Optimizer:
+    """what tf.keras optimizers share [TF]: the learning rate (a constant, WarmUp or InverseTimeDecay), use_ema / ema_momentum (the
+    engine keeps an exponential moving average of the parameters, gct2_ema_update after every applied step; finalize_variable_values()
+    overwrites the parameters with it, predict(..., use_ema=True) and log_sample(..., use_ema=True) read it), the three clipping
+    arguments clipnorm / global_clipnorm / clipvalue (the engine clips per variable, all together or per element on its non-fused
+    optimizer path) and `iterations`."""
+
+    def __init__(self, learning_rate, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None, clipnorm=None, global_clipnorm=None,
+                 clipvalue=None):
         clipping_mode(clipnorm, global_clipnorm, clipvalue)        # Keras' rule: at most one of the three, each > 0 (ValueError)
         self.clipnorm, self.global_clipnorm, self.clipvalue = clipnorm, global_clipnorm, clipvalue
         if ema_overwrite_frequency is not None:
@@ -108,7 +119,7 @@ class Adam:
                                       "optimizer.finalize_variable_values() where the parameters should become the averages")
         if use_ema and not (0.0 <= float(ema_momentum) <= 1.0):
             raise ValueError(f"ema_momentum must lie in [0, 1], got {ema_momentum!r}")
-        self.learning_rate, self.beta_1, self.beta_2, self.epsilon = learning_rate, beta_1, beta_2, epsilon
+        self.learning_rate = learning_rate
         self.use_ema, self.ema_momentum, self.ema_overwrite_frequency = bool(use_ema), ema_momentum, None
         self.loss_scaling = False
         self._engine = None            # bound by Trainer.compile / train_step: the step counter lives with the engine
@@ -129,10 +140,44 @@ class Adam:
         self._engine.ema_overwrite()
 
 
+class Adam(Optimizer):
+    """tf.keras.optimizers.Adam hyper-parameters (train.py:75); the update itself is gct2_adam_keras_multi (epsilon added to sqrt(v),
+    SURVEY.md A.6) - fused behind the weight gradients on one replica, gct2_adam_keras_clipped when the gradients are clipped."""
+
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, use_ema=False, ema_momentum=0.99,
+                 ema_overwrite_frequency=None, clipnorm=None, global_clipnorm=None, clipvalue=None):
+        super().__init__(learning_rate, use_ema, ema_momentum, ema_overwrite_frequency, clipnorm, global_clipnorm, clipvalue)
+        self.beta_1, self.beta_2, self.epsilon = beta_1, beta_2, epsilon
+
+
+class SGD(Optimizer):
+    """tf.keras.optimizers.SGD [TF] (train.py:69-70): plain, with momentum (Keras' velocity form) or Nesterov momentum; the update is
+    gct2_optimizer_apply on the engine's non-fused optimizer path (include/gct2.h has the formulas; parity with TensorFlow unpinned)."""
+
+    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None,
+                 clipnorm=None, global_clipnorm=None, clipvalue=None):
+        trainer_math.optimizer_hyper("sgd", momentum, nesterov)     # momentum in [0, 1] (ValueError)
+        super().__init__(learning_rate, use_ema, ema_momentum, ema_overwrite_frequency, clipnorm, global_clipnorm, clipvalue)
+        self.momentum, self.nesterov = momentum, bool(nesterov)
+
+
+class RMSprop(Optimizer):
+    """tf.keras.optimizers.RMSprop [TF] (train.py:73): epsilon outside the root without momentum, inside it with (optimizer_v2's two
+    paths); gct2_optimizer_apply on the engine's non-fused optimizer path.  centered=True needs a third slot and is not built."""
+
+    def __init__(self, learning_rate=0.001, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False, use_ema=False, ema_momentum=0.99,
+                 ema_overwrite_frequency=None, clipnorm=None, global_clipnorm=None, clipvalue=None):
+        trainer_math.optimizer_hyper("rmsprop", momentum, False, rho, epsilon)      # momentum, rho in [0, 1], epsilon >= 0 (ValueError)
+        if centered:
+            raise NotImplementedError("RMSprop(centered=True) keeps a third slot per parameter (the mean gradient), which is not built")
+        super().__init__(learning_rate, use_ema, ema_momentum, ema_overwrite_frequency, clipnorm, global_clipnorm, clipvalue)
+        self.rho, self.momentum, self.epsilon, self.centered = rho, momentum, epsilon, False
+
+
 class LossScaleOptimizer:
     """tf.keras.mixed_precision.LossScaleOptimizer (train.py:82-83): dynamic loss scaling."""
 
-    def __init__(self, inner_optimizer: Adam):
+    def __init__(self, inner_optimizer: Optimizer):
         self.inner = inner_optimizer
         self.inner.loss_scaling = True
 
@@ -150,14 +195,22 @@ def default_optimizer():
 
 
 def engine_hyper_parameters(optimizer) -> Dict[str, object]:
-    """an optimizer (train.py:75, 82-83) as the engines' hyper-parameter attributes / constructor arguments; a learning rate
-    that is neither a WarmUp nor a constant leaves base_lr and warm_up out; use_ema / ema_momentum are there only when the optimizer
-    averages (without them the dictionary is what it was before the averages existed)"""
+    """an optimizer (train.py:67-78, 82-83) as the engines' hyper-parameter attributes / constructor arguments; a WarmUp or a constant
+    gives base_lr and warm_up, an InverseTimeDecay gives lr_schedule, any other learning rate gives neither; SGD / RMSprop give
+    optimizer_kind with their own hyper-parameters; use_ema / ema_momentum and clip_mode / clip are there only when the optimizer
+    averages / clips (for the default optimizer the dictionary is what it always was)"""
     inner = getattr(optimizer, "inner", optimizer)
-    kw = dict(beta_1=inner.beta_1, beta_2=inner.beta_2, epsilon=inner.epsilon)
+    if isinstance(inner, SGD):
+        kw = dict(optimizer_kind="sgd", momentum=float(inner.momentum), nesterov=bool(inner.nesterov))
+    elif isinstance(inner, RMSprop):
+        kw = dict(optimizer_kind="rmsprop", rho=float(inner.rho), momentum=float(inner.momentum), epsilon=inner.epsilon)
+    else:
+        kw = dict(beta_1=inner.beta_1, beta_2=inner.beta_2, epsilon=inner.epsilon)
     lr = inner.learning_rate
     if isinstance(lr, WarmUp):
         kw.update(base_lr=lr.base, warm_up=lr.warmup_steps)
+    elif isinstance(lr, InverseTimeDecay):
+        kw.update(lr_schedule=trainer_math.inverse_time_decay_schedule(lr.initial_learning_rate, lr.decay_steps, lr.decay_rate, lr.staircase))
     elif not callable(lr):
         kw.update(base_lr=float(lr), warm_up=0)
     if getattr(inner, "use_ema", False):
@@ -169,6 +222,21 @@ def engine_hyper_parameters(optimizer) -> Dict[str, object]:
 
 
 CLIP_ARGUMENTS = ("clipnorm", "global_clipnorm", "clipvalue")
+
+
+OPTIMIZER_ARGUMENTS = ("momentum", "nesterov", "rho")
+
+
+def apply_optimizer_kind(eng, hp: Dict[str, object]) -> None:
+    """kind and schedule of engine_hyper_parameters' dictionary on an engine (set_optimizer's rule: another kind only while no step
+    has been applied); a dictionary with base_lr and without lr_schedule means WarmUp / a constant, one with neither (a learning rate
+    the engines do not know) leaves the schedule as it is, as it leaves base_lr and warm_up"""
+    kind = hp.get("optimizer_kind", "adam")
+    if kind != getattr(eng, "optimizer_kind", "adam") or kind != "adam":
+        eng.set_optimizer(kind, **{k: hp[k] for k in OPTIMIZER_ARGUMENTS if k in hp})
+    if ("lr_schedule" in hp or "base_lr" in hp) and hp.get("lr_schedule") != getattr(eng, "lr_schedule", None):
+        eng.flush_deferred()
+        eng.lr_schedule = hp.get("lr_schedule")
 
 
 def clipping_arguments(optimizer) -> Dict[str, object]:
@@ -502,6 +570,11 @@ class Denoiser(Layer):
         return self.middle(x)
 
 
+def _supported_learning_rate(hp: Dict[str, object]) -> None:
+    if "base_lr" not in hp and "lr_schedule" not in hp:
+        raise NotImplementedError("only WarmUp, InverseTimeDecay or constant learning rates are supported")
+
+
 class LambdaCallback:
     """tf.keras.callbacks.LambdaCallback(on_epoch_begin=...) (train.py:519-521)."""
 
@@ -523,14 +596,16 @@ class Trainer(Layer):
         kw = {}
         if opt is not None and self.denoiser.engine is None:
             kw = engine_hyper_parameters(opt)
-            if "base_lr" not in kw:
-                raise NotImplementedError("only WarmUp or constant learning rates are supported")
+            _supported_learning_rate(kw)
             kw["loss_scaling"] = bool(getattr(opt, "inner", opt).loss_scaling)
         clipped = kw.pop("clip_mode", None) is not None
         kw.pop("clip", None)
+        kind = {k: kw.pop(k) for k in ("optimizer_kind", "lr_schedule") + OPTIMIZER_ARGUMENTS if k in kw}
         eng = self.denoiser.ensure_engine(**kw)
         if clipped:                                      # (a fresh engine: clipping is a setting, not a constructor argument)
             eng.set_clipping(**clipping_arguments(opt))
+        if kind:                                         # (... and so are the optimizer kind and a schedule other than WarmUp)
+            apply_optimizer_kind(eng, kind)
         # train.py:238-252 reads the objective globals every time Trainer.call runs: an engine built earlier (by denoiser(...),
         # trainable_variables, the log_sample callback) follows the switches as they stand now
         for k, v in objective_switches().items():
@@ -559,8 +634,9 @@ class Trainer(Layer):
         if self.denoiser.engine is not None and optimizer is not None:
             eng, inner = self.denoiser.engine, getattr(optimizer, "inner", optimizer)
             hp = engine_hyper_parameters(optimizer)
+            apply_optimizer_kind(eng, hp)                 # (first: a refused change of kind leaves the engine as it was)
             for k, v in hp.items():
-                if k not in ("use_ema", "ema_momentum", "clip_mode", "clip"):
+                if k not in ("use_ema", "ema_momentum", "clip_mode", "clip", "optimizer_kind", "lr_schedule") + OPTIMIZER_ARGUMENTS:
                     setattr(eng, k, v)
             if "clip_mode" in hp or getattr(eng, "clip_mode", CLIP_NONE) != CLIP_NONE:
                 eng.set_clipping(**clipping_arguments(optimizer))      # (an optimizer without clipping switches it off)

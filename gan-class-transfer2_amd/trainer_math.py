@@ -1,6 +1,6 @@
 """The host-side arithmetic of the reference's `Trainer` (train.py:50-93, 223-272), once, for every engine.
 
-Pure functions (no GPU needed): the noise schedule, the WarmUp learning rate, the Adam step size, the Glorot limit and the
+Pure functions (no GPU needed): the noise schedule, the WarmUp and InverseTimeDecay learning rates, the Adam step size, the Glorot limit and the
 per-image coefficients of the objective.  `TrainerState` is what `UNetEngine` and `VariantEngine` inherit: the hyper-parameters,
 the objective switches, the RNG stream positions, the step counter and the dynamic loss-scale state with its three calls.
 The order of the float32 operations in every formula is the reference's; the golden fixture of tests/test_trainer_math_cpu.py
@@ -32,6 +32,17 @@ def warmup_lr(k: int, base_lr: float, warm_up: int) -> float:
     if k < warm_up:
         return float(np.float32(base_lr) * np.float32(k + 1) / np.float32(warm_up + 1))
     return float(np.float32(base_lr))
+
+
+def inverse_time_decay_lr(k: int, initial: float, decay_steps: float, decay_rate: float, staircase: bool = False) -> float:
+    """tf.keras.optimizers.schedules.InverseTimeDecay.__call__ [TF] at optimizer.iterations = k, float32 arithmetic in Keras' order:
+    q = k / decay_steps (floored when staircase), lr = initial / (1 + decay_rate * q); gct2_loss_scale_begin_schedule computes the
+    same on the device when the step counter lives there."""
+    f = np.float32
+    q = f(k) / f(decay_steps)
+    if staircase:
+        q = np.floor(q)
+    return float(f(initial) / (f(1.0) + f(decay_rate) * q))
 
 
 def adam_step_size(lr: float, k: int, beta_1: float, beta_2: float) -> float:
@@ -101,6 +112,31 @@ def clipping_mode(clipnorm=None, global_clipnorm=None, clipvalue=None) -> Tuple[
     return mode, value
 
 
+OPTIMIZER_KINDS = {"adam": _lib.OPT_ADAM, "sgd": _lib.OPT_SGD, "rmsprop": _lib.OPT_RMSPROP}
+
+
+def optimizer_hyper(kind: str = "adam", momentum: float = 0.0, nesterov: bool = False, rho: float = 0.9, epsilon: Optional[float] = None):
+    """the hyper-parameters of an optimizer kind, checked the way tf.keras checks them (ValueError): (kind, momentum, nesterov, rho)
+    and, only when given, epsilon"""
+    if kind not in OPTIMIZER_KINDS:
+        raise ValueError(f"unknown optimizer kind {kind!r} (one of {', '.join(OPTIMIZER_KINDS)})")
+    momentum, rho = float(momentum), float(rho)
+    if not (0.0 <= momentum <= 1.0):
+        raise ValueError(f"momentum must lie in [0, 1], got {momentum!r}")
+    if not (0.0 <= rho <= 1.0):
+        raise ValueError(f"rho must lie in [0, 1], got {rho!r}")
+    if epsilon is not None and not (float(epsilon) >= 0.0):
+        raise ValueError(f"epsilon must be >= 0, got {epsilon!r}")
+    return kind, momentum, bool(nesterov), rho
+
+
+def inverse_time_decay_schedule(initial: float, decay_steps: float, decay_rate: float, staircase: bool = False) -> tuple:
+    """the engines' lr_schedule tuple of an InverseTimeDecay (ValueError unless decay_steps > 0)"""
+    if not (float(decay_steps) > 0.0):
+        raise ValueError(f"decay_steps must be > 0, got {decay_steps!r}")
+    return ("inverse_time_decay", float(initial), float(decay_steps), float(decay_rate), bool(staircase))
+
+
 OBJECTIVE_SWITCHES = ("predict_x", "predict_scaled_epsilon", "prediction_weighting", "ordinary_differential_equation")
 
 
@@ -117,6 +153,11 @@ class TrainerState:
     # reduction's segment table and buffers (_clip_reduction) exist only after the first norm-clipped step
     clip_mode, clip = _lib.CLIP_NONE, 0.0
     _clip_table = None
+    # the optimizer (train.py:67-78): Keras Adam by default; set_optimizer() switches to "sgd" (momentum, nesterov) or "rmsprop" (rho,
+    # momentum, the engine's epsilon), which run on the non-fused optimizer path through gct2_optimizer_apply.  lr_schedule: None =
+    # WarmUp of base_lr / warm_up (a constant is warm_up = 0), or ("inverse_time_decay", initial, decay_steps, decay_rate, staircase)
+    optimizer_kind, momentum, nesterov, rho = "adam", 0.0, False, 0.9
+    lr_schedule: Optional[tuple] = None
 
     @property
     def _ema(self) -> Optional[torch.Tensor]:
@@ -188,11 +229,33 @@ class TrainerState:
 
     # ---- optimizer (train.py:50-65,75) ---------------------------------------------------------------------------------------
     def learning_rate(self, k: Optional[int] = None) -> float:
-        return warmup_lr(self.iterations if k is None else k, self.base_lr, self.warm_up)
+        k = self.iterations if k is None else k
+        if self.lr_schedule is not None:
+            return inverse_time_decay_lr(k, *self.lr_schedule[1:])
+        return warmup_lr(k, self.base_lr, self.warm_up)
 
     def adam_alpha(self, k: Optional[int] = None) -> float:
         k = self.iterations if k is None else k
         return adam_step_size(self.learning_rate(k), k, self.beta_1, self.beta_2)
+
+    def step_size(self, k: Optional[int] = None) -> float:
+        """what multiplies the update of step k: Adam folds its bias correction into it, SGD and RMSprop take the learning rate"""
+        return self.adam_alpha(k) if self.optimizer_kind == "adam" else self.learning_rate(k)
+
+    def set_optimizer(self, kind: str = "adam", momentum: float = 0.0, nesterov: bool = False, rho: float = 0.9) -> None:
+        """the optimizer kind and the hyper-parameters only SGD / RMSprop have (epsilon is the engine's, as for Adam).  Another KIND is
+        allowed while no step has been applied: afterwards the slots hold the other optimizer's state (the rule of dropping loss
+        scaling).  Optimizer launches the engine holds back are flushed first: they belong to a step made with the old setting."""
+        kind, momentum, nesterov, rho = optimizer_hyper(kind, momentum, nesterov, rho)
+        if kind != self.optimizer_kind:
+            why = getattr(self, "_optimizer_forbidden", None)
+            if why and kind != "adam":
+                raise ValueError(why)
+            if self.iterations != 0:
+                raise _lib.Gct2Error(f"the engine has already applied {self.iterations} steps with {self.optimizer_kind}: its slots hold that "
+                                     f"optimizer's state, the kind cannot become {kind} now")
+        self.flush_deferred()
+        self.optimizer_kind, self.momentum, self.nesterov, self.rho = kind, momentum, nesterov, rho
 
     # ---- dynamic loss scaling (train.py:82-83) -------------------------------------------------------------------------------
     def enable_loss_scaling(self, initial_scale: float = 2.0 ** 15) -> None:
@@ -233,9 +296,19 @@ class TrainerState:
         return self.ls_state.data_ptr() if self.ls_state is not None else None
 
     def begin_step(self) -> None:
-        if self.ls_state is not None:
+        if self.ls_state is None:
+            return
+        adam = self.optimizer_kind == "adam"
+        if adam and self.lr_schedule is None:              # the default step keeps its call
             call("gct2_loss_scale_begin", self.ls_state.data_ptr(), float(self.base_lr), int(self.warm_up), float(self.beta_1),
                  float(self.beta_2), self._stream())
+        elif self.lr_schedule is None:
+            call("gct2_loss_scale_begin_schedule", self.ls_state.data_ptr(), _lib.SCHEDULE_WARMUP, float(self.base_lr), float(self.warm_up),
+                 0.0, 0, int(adam), float(self.beta_1), float(self.beta_2), self._stream())
+        else:
+            _, initial, decay_steps, decay_rate, staircase = self.lr_schedule
+            call("gct2_loss_scale_begin_schedule", self.ls_state.data_ptr(), _lib.SCHEDULE_INVERSE_TIME_DECAY, initial, decay_steps,
+                 decay_rate, int(staircase), int(adam), float(self.beta_1), float(self.beta_2), self._stream())
 
     def _check_finite(self, grads_ptr: int, n: int, stream: Optional[int] = None) -> None:
         if self.ls_state is not None:
@@ -287,6 +360,33 @@ class TrainerState:
             call("gct2_adam_keras_clipped", p.data_ptr() + 4 * lo, m.data_ptr() + 4 * lo, v.data_ptr() + 4 * lo, g.data_ptr() + 4 * lo,
                  None if shadow is None else shadow.data_ptr() + 2 * lo, self.dtype, n, Slot("alpha", alpha), self.beta_1, self.beta_2,
                  self.epsilon, grad_mul, ls_ptr, self.clip_mode, float(self.clip), sumsq_ptr, stream)
+
+        if not self._clip_by_norm():
+            launch(lo, hi - lo, None)
+            return
+        table, nseg, npartials, partials, sumsq, segs = self._clip_reduction()
+        call("gct2_grad_sumsq", g.data_ptr(), table.data_ptr(), nseg, npartials, grad_mul, ls_ptr, partials.data_ptr(), sumsq.data_ptr(), stream)
+        if self.clip_mode == _lib.CLIP_GLOBAL_NORM:
+            launch(lo, hi - lo, sumsq.data_ptr() + 8 * nseg)
+        else:
+            for s, (begin, n) in enumerate(segs):
+                launch(begin, n, sumsq.data_ptr() + 8 * s)
+
+    def _optimizer_launches(self, p: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tensor, shadow: Optional[torch.Tensor], lo: int,
+                            hi: int, grad_mul: float, stream: int) -> None:
+        """_adam_clipped for the kinds of gct2_optimizer_apply (SGD, RMSprop), clipped or not: the same sequence - gct2_grad_sumsq
+        first for the two norm modes, then the update once over [lo, hi) or, for clipnorm, once per tensor - with only the slots the
+        kind uses handed to the kernel"""
+        ls_ptr = self._ls_ptr()
+        lr = 0.0 if self.ls_state is not None else self.step_size()
+        kind = OPTIMIZER_KINDS[self.optimizer_kind]
+        use_m, use_v = float(self.momentum) > 0.0, kind == _lib.OPT_RMSPROP
+
+        def launch(lo: int, n: int, sumsq_ptr: Optional[int]) -> None:
+            call("gct2_optimizer_apply", kind, p.data_ptr() + 4 * lo, m.data_ptr() + 4 * lo if use_m else None,
+                 v.data_ptr() + 4 * lo if use_v else None, g.data_ptr() + 4 * lo, None if shadow is None else shadow.data_ptr() + 2 * lo,
+                 self.dtype, n, Slot("alpha", lr), float(self.momentum), int(bool(self.nesterov)), float(self.rho), float(self.epsilon),
+                 grad_mul, ls_ptr, self.clip_mode, float(self.clip), sumsq_ptr, stream)
 
         if not self._clip_by_norm():
             launch(lo, hi - lo, None)

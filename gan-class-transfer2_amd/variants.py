@@ -408,10 +408,11 @@ class VariantEngine(TrainerState):
 
     def apply_adam(self) -> None:
         N, s = self.net, self.net.stream()
-        if self.clip_mode != _lib.CLIP_NONE:
+        if self.clip_mode != _lib.CLIP_NONE or self.optimizer_kind != "adam":
             if not self._clip_by_norm():                       # (a norm-clipped step: gct2_grad_sumsq sets found_inf in its one pass)
                 self._check_finite(N.g.data_ptr(), N.g.numel(), s)
-            self._adam_clipped(N.p, N.m, N.v, N.g, N.op if self.dtype != F32 else None, 0, N.p.numel(), 1.0, s)
+            launches = self._adam_clipped if self.optimizer_kind == "adam" else self._optimizer_launches       # (SGD / RMSprop, clipped or not)
+            launches(N.p, N.m, N.v, N.g, N.op if self.dtype != F32 else None, 0, N.p.numel(), 1.0, s)
             self.finish_step()
             return
         self._check_finite(N.g.data_ptr(), N.g.numel(), s)

@@ -37,7 +37,7 @@ enum {
 };
 
 /* library / device identification ------------------------------------------------------------ */
-int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive); v17 + gct2_sumsq_layout, gct2_grad_sumsq, gct2_adam_keras_clipped (additive)) */
+int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive); v17 + gct2_sumsq_layout, gct2_grad_sumsq, gct2_adam_keras_clipped (additive); v17 + gct2_optimizer_apply, gct2_loss_scale_begin_schedule (additive)) */
 /* how the library was built: 0 for the product build; bit 0 (GCT2_BUILD_STAMP) = diagnostic build with in-kernel phase stamps
  * (make EXTRA=-DGCT2_STAMP).  Product hosts (the Python binding, bench.py, the tests) refuse a library whose flags are not 0. */
 enum { GCT2_BUILD_STAMP = 1 };
@@ -347,7 +347,7 @@ int gct2_mse_fwd_bwd(const float* pred, const float* target, float* dpred, float
 typedef struct {
   float scale; float inv_scale; int32_t good_steps; int32_t found_inf;
   int32_t applied_steps;   /* optimizer.iterations */
-  float alpha;             /* lr(applied_steps) * sqrt(1-b2^t)/(1-b1^t), t = applied_steps+1: written by loss_scale_begin */
+  float alpha;             /* lr(applied_steps) * sqrt(1-b2^t)/(1-b1^t), t = applied_steps+1: written by loss_scale_begin; the plain lr(applied_steps) for SGD / RMSprop (loss_scale_begin_schedule) */
   int32_t reserved[2];
 } gct2_loss_scale_state;
 int gct2_loss_scale_init(gct2_loss_scale_state* state, float initial_scale, void* stream);
@@ -434,6 +434,46 @@ int gct2_grad_sumsq(const float* g, const gct2_sumsq_seg* segs, int nseg, size_t
 int gct2_adam_keras_clipped(float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n,
                             float alpha, float beta1, float beta2, float eps, float grad_mul,
                             const gct2_loss_scale_state* ls, int clip_mode, float clip, const double* sumsq, void* stream);
+
+/* ---- Keras SGD and RMSprop [TF] (train.py:67-78, the optimizer lines the reference keeps commented out) ----------------------
+ * One entry point over a flat arena range, beside gct2_adam_keras_clipped and with its geometry, shadow write, ls skip and clipping
+ * step: g' = fl(g * fl((ls ? ls->inv_scale : 1) * grad_mul)), g'' = the clipped g' exactly as gct2_adam_keras_clipped forms it, and
+ * lr = ls ? ls->alpha : lr.  Then, all in fp32, every operation rounded once, no contraction:
+ *   GCT2_OPT_SGD, momentum == 0:      p = p - fl(lr * g'')
+ *   GCT2_OPT_SGD, momentum > 0:       m = fl(fl(momentum * m) - fl(lr * g''))           (Keras ApplyKerasMomentum, m = the velocity)
+ *                 nesterov == 0:      p = p + m
+ *                 nesterov != 0:      p = p + fl(fl(momentum * m) - fl(lr * g''))       (with the NEW m)
+ *   GCT2_OPT_RMSPROP:                 v = fl(fl(rho * v) + fl(fl(1 - rho) * fl(g'' * g'')))
+ *                 momentum == 0:      p = p - fl(fl(lr * g'') / fl(fl(sqrt(v)) + epsilon))            (epsilon outside the root)
+ *                 momentum > 0:       m = fl(fl(momentum * m) + fl(fl(lr * g'') / fl(sqrt(fl(v + epsilon)))));  p = p - m
+ *                                                                                       (the fused ApplyRMSProp: epsilon inside the root)
+ * These are the formulas of tf.keras optimizer_v2 (the TF 2.4 - 2.6 era) [TF]; PARITY UNPINNED, like Adam's epsilon placement.
+ * A slot that a kind does not use is neither read nor written and may be NULL: m for momentum == 0, v for GCT2_OPT_SGD.  That is
+ * what the entry point is for: plain SGD moves 14 - 16 bytes per parameter where Adam moves 30.
+ * ls->found_inf != 0: NOTHING is written.  shadow (may be NULL): GCT2_BF16 / GCT2_F16 copy of the new p.  sumsq as for
+ * gct2_adam_keras_clipped.  RMSprop's centered variant needs a third slot and is not built.
+ * GCT2_EINVAL before any launch: unknown kind (GCT2_OPT_ADAM included: Adam stays where it is), NULL p / g or a NULL slot the kind
+ * uses, n == 0, misaligned pointers, a shadow with shadow_dtype GCT2_F32 or unknown, momentum or rho outside [0, 1], epsilon < 0,
+ * and the clipping checks of gct2_adam_keras_clipped. */
+#define GCT2_OPT_ADAM 0
+#define GCT2_OPT_SGD 1
+#define GCT2_OPT_RMSPROP 2
+int gct2_optimizer_apply(int kind, float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n,
+                         float lr, float momentum, int nesterov, float rho, float epsilon, float grad_mul,
+                         const gct2_loss_scale_state* ls, int clip_mode, float clip, const double* sumsq, void* stream);
+
+/* gct2_loss_scale_begin for any schedule and optimizer: found_inf = 0 and state->alpha = the step size of THIS step at
+ * k = state->applied_steps, in float32 and in Keras' order:
+ *   GCT2_SCHEDULE_WARMUP (train.py:57-65):   lr = k < steps ? fl(fl(initial * (k + 1)) / (steps + 1)) : initial
+ *                                            (steps = warmup_steps, a whole number; decay_rate and staircase are ignored)
+ *   GCT2_SCHEDULE_INVERSE_TIME_DECAY [TF]:   q = fl((float)k / steps);  staircase: q = floorf(q);
+ *                                            lr = fl(initial / fl(1 + fl(decay_rate * q)))           (steps = decay_steps > 0)
+ * bias_correction != 0 (Adam): alpha = (float)(lr * sqrt(1 - beta2^t) / (1 - beta1^t)), t = k + 1, as gct2_loss_scale_begin;
+ * bias_correction == 0 (SGD, RMSprop): alpha = lr exactly, beta1 / beta2 are ignored.  No other field of the state is written. */
+#define GCT2_SCHEDULE_WARMUP 0
+#define GCT2_SCHEDULE_INVERSE_TIME_DECAY 1
+int gct2_loss_scale_begin_schedule(gct2_loss_scale_state* state, int schedule, float initial, float steps, float decay_rate,
+                                   int staircase, int bias_correction, float beta1, float beta2, void* stream);
 
 /* fp32 -> dtype cast of a flat array (initial weight shadows). */
 int gct2_cast_from_f32(int dtype, const float* src, void* dst, size_t n, void* stream);
