@@ -22,6 +22,8 @@ SUMSQ_CHUNK, SUMSQ_MAX_SEGMENTS = 32768, 1024
 # gct2_optimizer_apply kinds (Adam has its own entry points) and gct2_loss_scale_begin_schedule schedules (include/gct2.h)
 OPT_ADAM, OPT_SGD, OPT_RMSPROP = 0, 1, 2
 SCHEDULE_WARMUP, SCHEDULE_INVERSE_TIME_DECAY = 0, 1
+# gct2_loss_fwd_bwd kinds (include/gct2.h; the four returns of Trainer.call, train.py:254-280)
+LOSS_MSE, LOSS_L1, LOSS_MSE_POOLED, LOSS_DCT = 0, 1, 2, 3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgct2.so")
@@ -92,6 +94,8 @@ SIGNATURES = {
     "gct2_noise_image": [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "gct2_noise_image_rng": [_i, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "gct2_mse_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp],
+    "gct2_loss_scratch": [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)],
+    "gct2_loss_fwd_bwd": [_i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp],
     "gct2_adam_keras_multi": [_vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _f, _f, _f, _vp, _i, _vp],
     "gct2_ema_update": [_vp, _vp, _vp, _i, _sz, _f, _f, _vp, _vp],
     "gct2_sumsq_layout": [_vp, _vp, _i, _vp, C.POINTER(C.c_size_t)],
@@ -181,7 +185,7 @@ def call(name: str, *args) -> None:
 
 # the entry points a plan can hold (csrc/plan.hip ENTRIES): everything that enqueues work on a stream + the one-shot ReLU plane
 PLANNABLE = frozenset(n for n, sig in SIGNATURES.items() if n == "gct2_ctx_set_relu_bits" or (
-    not n.startswith(("gct2_ctx_", "gct2_plan_", "gct2_loss_scale_init")) and n not in ("gct2_abi_version", "gct2_build_flags", "gct2_device_check", "gct2_stream_occupy", "gct2_sumsq_layout")))
+    not n.startswith(("gct2_ctx_", "gct2_plan_", "gct2_loss_scale_init")) and n not in ("gct2_abi_version", "gct2_build_flags", "gct2_device_check", "gct2_stream_occupy", "gct2_sumsq_layout", "gct2_loss_scratch")))
 _recording = None      # the Plan that is recording calls right now (one host thread drives an engine: _lib.call is not re-entrant)
 _FLOAT_STRUCT = struct.Struct("<f")
 _DOUBLE_STRUCT = struct.Struct("<d")

@@ -552,6 +552,46 @@ int gct2_mse_fwd_bwd(const float* pred, const float* target, float* dpred, float
   return pw_mse(pred, target, dpred, loss, partials, n, loss_scale_ptr, S(stream));
 }
 
+// shape rules of a loss kind (shared by gct2_loss_scratch and gct2_loss_fwd_bwd)
+static int check_loss_shape(const char* fn, int kind, int B, int H, int W, int C) {
+  if (kind < GCT2_LOSS_MSE || kind > GCT2_LOSS_DCT) return gct2_fail(GCT2_EINVAL, "%s: unknown loss kind %d", fn, kind);
+  if (B <= 0 || H <= 0 || W <= 0 || C < 1 || C > 4) return gct2_fail(GCT2_EINVAL, "%s: B=%d H=%d W=%d must be positive, C=%d in 1..4", fn, B, H, W, C);
+  if (kind == GCT2_LOSS_MSE_POOLED && ((H & 15) || (W & 15)))
+    return gct2_fail(GCT2_EINVAL, "%s: H=%d W=%d must be multiples of 16 (avg_pool2d(16, 16, 'SAME') without padding)", fn, H, W);
+  if (kind == GCT2_LOSS_MSE_POOLED && (size_t)B * (H / 16) * (W / 16) > ((size_t)1 << 28))
+    return gct2_fail(GCT2_EINVAL, "%s: too many 16 x 16 cells", fn);
+  if (kind == GCT2_LOSS_DCT && (H != W || (H & 3))) return gct2_fail(GCT2_EINVAL, "%s: the DCT loss needs H == W == size, a multiple of 4 (H=%d W=%d)", fn, H, W);
+  if (kind == GCT2_LOSS_DCT && ((size_t)H * W * C >= ((size_t)1 << 31) || (size_t)B * ((H + 127) / 128) * (((size_t)W * C + 127) / 128) > ((size_t)1 << 28)))
+    return gct2_fail(GCT2_EINVAL, "%s: image too large for the DCT loss", fn);
+  return GCT2_OK;
+}
+
+int gct2_loss_scratch(int kind, int B, int H, int W, int C, size_t* floats) {
+  if (!floats) return gct2_fail(GCT2_EINVAL, "loss_scratch: null output pointer");
+  if (int e = check_loss_shape("loss_scratch", kind, B, H, W, C)) return e;
+  return loss_scratch_floats(kind, B, H, W, C, nullptr, floats);
+}
+
+int gct2_loss_fwd_bwd(int kind, const float* pred, const float* target, float* dpred, float* loss, float* scratch, size_t scratch_floats,
+                      int B, int H, int W, int C, const float* basis, const float* loss_scale_ptr, void* stream) {
+  if (int e = check_loss_shape("loss_fwd_bwd", kind, B, H, W, C)) return e;
+  if (!pred || !target || !loss || !scratch) return gct2_fail(GCT2_EINVAL, "loss_fwd_bwd: null pointer");
+  if (kind == GCT2_LOSS_DCT && !basis) return gct2_fail(GCT2_EINVAL, "loss_fwd_bwd: the DCT loss needs a basis");
+  if (((uintptr_t)pred | (uintptr_t)target | (uintptr_t)dpred | (uintptr_t)loss | (uintptr_t)loss_scale_ptr) % 4 || (uintptr_t)scratch % 16 ||
+      (kind == GCT2_LOSS_DCT && (uintptr_t)basis % 16))
+    return gct2_fail(GCT2_EINVAL, "loss_fwd_bwd: scratch and basis must be 16-byte aligned, the other pointers 4-byte aligned");
+  size_t need = 0;
+  loss_scratch_floats(kind, B, H, W, C, nullptr, &need);
+  if (scratch_floats < need) return gct2_fail(GCT2_EINVAL, "loss_fwd_bwd: %zu floats of scratch, this kind and shape need %zu (gct2_loss_scratch)", scratch_floats, need);
+  const size_t n = (size_t)B * H * W * C;
+  switch (kind) {
+    case GCT2_LOSS_MSE: return pw_mse(pred, target, dpred, loss, scratch, n, loss_scale_ptr, S(stream));
+    case GCT2_LOSS_L1: return loss_l1(pred, target, dpred, loss, scratch, n, loss_scale_ptr, S(stream));
+    case GCT2_LOSS_MSE_POOLED: return loss_pooled(pred, target, dpred, loss, scratch, B, H, W, C, loss_scale_ptr, S(stream));
+    default: return loss_dct(pred, target, dpred, loss, scratch, B, H, C, basis, loss_scale_ptr, S(stream));
+  }
+}
+
 int gct2_adam_keras_multi(float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n, float alpha, float beta1,
                           float beta2, float eps, float grad_mul, const gct2_loss_scale_state* ls, int zero_grad, void* stream) {
   if (!p || !m || !v || !g) return gct2_fail(GCT2_EINVAL, "adam_keras_multi: null pointer");

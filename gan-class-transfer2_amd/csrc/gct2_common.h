@@ -419,6 +419,15 @@ int rgb_wgrad(const gct2_ctx& c, int dtype, WgradParams p, hipStream_t s, WgradS
 int f32_tapgemm(gct2_ctx& c, int form, int epi, TapGemmParams p, hipStream_t s);
 int f32_wgrad(gct2_ctx& c, WgradParams p, hipStream_t s, WgradSlabs* defer);
 
+// loss_kernels.hip: the training losses besides the plain MSE (gct2_loss_fwd_bwd); loss_scratch_floats: the scratch a kind needs and
+// how much of it holds the partial sums
+int loss_scratch_floats(int kind, int B, int H, int W, int C, size_t* partial_floats, size_t* floats);
+int loss_l1(const float* pred, const float* target, float* dpred, float* loss, float* scratch, size_t n, const float* ls, hipStream_t s);
+int loss_pooled(const float* pred, const float* target, float* dpred, float* loss, float* scratch, int B, int H, int W, int C, const float* ls,
+                hipStream_t s);
+int loss_dct(const float* pred, const float* target, float* dpred, float* loss, float* scratch, int B, int S, int C, const float* basis,
+             const float* ls, hipStream_t s);
+
 // direct_kernels.hip: one thread per output, every dtype
 int tapgemm_direct(int dtype, int form, int epi, const TapGemmParams& p, hipStream_t s);
 int wgrad_direct(int dtype, WgradParams p, hipStream_t s);

@@ -294,7 +294,7 @@ __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ pred
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const float d = pred[i] - target[i];
     acc = fmaf(d, d, acc);
-    dpred[i] = d * scale;
+    if (dpred) dpred[i] = d * scale;              // (null: gct2_loss_fwd_bwd's loss-only call)
   }
   for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
   __shared__ float ws[4];

@@ -584,6 +584,7 @@ class UNetEngine(TrainerState):
         b.t_int = z(B, dtype=torch.int32)
         b.loss = z(1, dtype=torch.float32)
         b.partials = z(1024, dtype=torch.float32)
+        b.loss_store = {}               # scratch (and the DCT basis) of the non-default training losses, allocated on first use
         self._bufs[key] = b
         return b
 
@@ -711,8 +712,14 @@ class UNetEngine(TrainerState):
              M, t.fu(0) + 3, 3, s)
         return b.pred
 
-    def loss_and_dpred(self, b: _Buffers, target: torch.Tensor, target_is_x: bool = False) -> torch.Tensor:
-        """fp32 MSE against the clean image (predict_x, train.py:243-244,262-272) and its gradient."""
+    def loss_and_dpred(self, b: _Buffers, target: torch.Tensor, target_is_x: bool = False, grad: bool = True) -> torch.Tensor:
+        """the training loss against the target (train.py:262-280) and its gradient: fp32 MSE against the clean image by default
+        (predict_x, train.py:243-244, 272); training_loss "l1" / "mse_pooled" / "dct" through gct2_loss_fwd_bwd, with grad=False
+        (Trainer.call: no gradients) as its loss-only form."""
+        if self.training_loss != "mse":
+            self._loss_launch(b.loss_store, b.pred, Slot("x", target.data_ptr()) if target_is_x else target.data_ptr(),
+                              b.dpred if grad else None, b.loss, self._stream())
+            return b.loss
         ls_ptr = self._ls_ptr()
         call("gct2_mse_fwd_bwd", b.pred.data_ptr(), Slot("x", target.data_ptr()) if target_is_x else target.data_ptr(), b.dpred.data_ptr(), b.loss.data_ptr(),
              b.partials.data_ptr(), b.pred.numel(), ls_ptr, self._stream())
@@ -729,19 +736,23 @@ class UNetEngine(TrainerState):
              b.H * b.W * 3, self._stream())
         return b.target, w
 
-    def weighted_loss_and_dpred(self, b: _Buffers, target: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-        """prediction_weighting (train.py:250-252): loss = mean((w_b pred - target)^2); dpred = w_b * dloss/d(w_b pred)."""
+    def weighted_loss_and_dpred(self, b: _Buffers, target: torch.Tensor, w: torch.Tensor, grad: bool = True) -> torch.Tensor:
+        """prediction_weighting (train.py:250-252): loss = loss_fn(w_b pred, target) - the MSE mean((w_b pred - target)^2) by default;
+        dpred = w_b * dloss/d(w_b pred)."""
         n = b.H * b.W * 3
         call("gct2_mix_per_image", b.pred.data_ptr(), None, w.data_ptr(), None, b.pred.data_ptr(), b.B, n, self._stream())
-        loss = self.loss_and_dpred(b, target)
+        loss = self.loss_and_dpred(b, target, grad=grad)
+        if not grad and self.training_loss != "mse":           # (the loss-only call wrote no gradient)
+            return loss
         call("gct2_mix_per_image", b.dpred.data_ptr(), None, w.data_ptr(), None, b.dpred.data_ptr(), b.B, n, self._stream())
         return loss
 
     def fused_head_ok(self) -> bool:
         """the matrix-core head with the split input (R_0's UpShuffle_0 channels + the packed image): the reference topology
-        (Fu_0 = 64) in a 16-bit mode with a workspace; anything else runs dense_fwd + mse_fwd_bwd + dense_bwd."""
+        (Fu_0 = 64) in a 16-bit mode with a workspace and the MSE loss the head kernels carry; anything else runs dense_fwd + the loss
+        (gct2_mse_fwd_bwd, or gct2_loss_fwd_bwd for the other training losses) + dense_bwd."""
         return (self.use_fused_head and self.dtype != F32 and self.topo.fu(0) == 64 and self.workspace is not None
-                and not self.objective_weighted())
+                and not self.objective_weighted() and self.training_loss == "mse")
 
     def head_train(self, b: _Buffers, target: torch.Tensor, target_is_x: bool = False) -> torch.Tensor:
         """Dense(3) + fp32 MSE + both of their gradients in one pass over R_0 (gct2_dense_head_train)."""
@@ -1066,7 +1077,7 @@ class UNetEngine(TrainerState):
                 # gct2_adam_args by every replay: Trainer.compile() may legally rewrite them between steps
                 self.dtype, float(self.beta_1), float(self.beta_2), float(self.epsilon), float(self.base_lr), int(self.warm_up),
                 id(self.post_replay), self._side.cuda_stream, self.use_ema, float(self.ema_momentum), self.clip_mode, float(self.clip),
-                self.optimizer_kind, float(self.momentum), bool(self.nesterov), float(self.rho), self.lr_schedule,
+                self.optimizer_kind, float(self.momentum), bool(self.nesterov), float(self.rho), self.lr_schedule, self.training_loss,
                 self._chain_stream.cuda_stream if self._chain_stream is not None else 0)
 
     def _planned_step(self, b: _Buffers, x: torch.Tensor, apply: bool, inline: bool, cur: "torch.cuda.Stream") -> torch.Tensor:

@@ -41,6 +41,11 @@ ordinary_differential_equation = False
 
 mixed_precision = False
 
+# train.py:254-280: which of Trainer.call's `return` lines is live - "mse" (train.py:272, the reference as committed), "l1"
+# (train.py:268-270), "mse_pooled" (train.py:274-280: plus the MSE of 16 x 16 average pools) or "dct" (train.py:254-260, 265: the
+# frequency-weighted 2-D DCT of the residual, squared and averaged); trainer_math.TRAINING_LOSSES
+training_loss = "mse"
+
 warm_up = 2_000
 
 # MI355X knob: None -> float32, or float16 when mixed_precision (train.py:38); "bfloat16" selects the
@@ -592,6 +597,8 @@ class Trainer(Layer):
         self.loss_fn = None
 
     def _engine(self) -> UNetEngine:
+        trainer_math.training_loss_code(training_loss)   # an unknown name: ValueError, before anything is built or changed
+        loss_kind = training_loss
         opt = self.optimizer
         kw = {}
         if opt is not None and self.denoiser.engine is None:
@@ -610,6 +617,7 @@ class Trainer(Layer):
         # trainable_variables, the log_sample callback) follows the switches as they stand now
         for k, v in objective_switches().items():
             setattr(eng, k, v)
+        eng.training_loss = loss_kind                    # (... and the `return` of train.py:265-280 that is live now)
         return eng
 
     def call(self, x):
@@ -623,11 +631,11 @@ class Trainer(Layer):
         eng.noise_into_r0(b, x, unfused_head=True)     # forward(head=True) reads the image channels from R_0 itself
         eng.forward(b)
         if eng.default_objective():
-            return eng.loss_and_dpred(b, x).clone()[0]
+            return eng.loss_and_dpred(b, x, grad=False).clone()[0]
         target, w = eng.make_target(b, x)              # train.py:238-252
         if eng.objective_weighted():
-            return eng.weighted_loss_and_dpred(b, target, w).clone()[0]
-        return eng.loss_and_dpred(b, target).clone()[0]
+            return eng.weighted_loss_and_dpred(b, target, w, grad=False).clone()[0]
+        return eng.loss_and_dpred(b, target, grad=False).clone()[0]
 
     def compile(self, optimizer, loss):
         """train.py:511-514"""

@@ -11,6 +11,7 @@ variants of train.py:20, 26, 27 - VariantEngine.predict, layer by layer.  Return
 from __future__ import annotations
 
 import contextlib
+import gc
 import warnings
 from typing import Callable, Dict, Optional, Tuple
 
@@ -63,6 +64,11 @@ class _Sampler:
         if hit is not None and hit[1] is b:
             return hit[0]
         eng.forward(b)                          # (also the first evaluation: whatever lazy set-up there is happens here)
+        # dead engines hold reference cycles (and with them step plans, events, graphs, device tensors): the cyclic collector must not
+        # finalise them INSIDE the capture (torch.cuda.graph no longer collects on entry) - collect now, keep it off until the capture ends
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
         try:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
@@ -73,6 +79,9 @@ class _Sampler:
             warnings.warn(f"log_sample: HIP graph capture of the forward pass was refused ({e}); using plain launches")
             self.use_graph = False
             return None
+        finally:
+            if gc_was_on:
+                gc.enable()
         cache[(id(b), version, averaged)] = (g, b)
         return None                             # this evaluation has already run (the warm-up call above)
 

@@ -139,6 +139,27 @@ def inverse_time_decay_schedule(initial: float, decay_steps: float, decay_rate: 
 
 OBJECTIVE_SWITCHES = ("predict_x", "predict_scaled_epsilon", "prediction_weighting", "ordinary_differential_equation")
 
+# the four ways Trainer.call turns target - prediction into the scalar Keras minimises (train.py:254-280: the author moves a `return`)
+TRAINING_LOSSES = ("mse", "l1", "mse_pooled", "dct")
+_LOSS_CODES = {"mse": _lib.LOSS_MSE, "l1": _lib.LOSS_L1, "mse_pooled": _lib.LOSS_MSE_POOLED, "dct": _lib.LOSS_DCT}
+
+
+def training_loss_code(name: str) -> int:
+    """the gct2_loss_fwd_bwd kind of a TRAINING_LOSSES name (ValueError for anything else)"""
+    if name not in _LOSS_CODES:
+        raise ValueError(f"unknown training_loss {name!r} (one of {', '.join(TRAINING_LOSSES)})")
+    return _LOSS_CODES[name]
+
+
+def dct_basis(size: int) -> np.ndarray:
+    """G of gct2_loss_fwd_bwd's DCT kind for the reference's dct2d (train.py:254-260): tf.signal.dct(norm='ortho') [TF] times
+    frequency_weights = 1 / (k + 1), G[k, m] = 1/(k+1) * sigma_k * cos(pi (2m + 1) k / (2 size)), sigma_0 = sqrt(1/size), else
+    sqrt(2/size); formed in float64 and rounded once to float32 [size, size]."""
+    k = np.arange(size, dtype=np.float64)[:, None]
+    m = np.arange(size, dtype=np.float64)[None, :]
+    sigma = np.where(k == 0, math.sqrt(1.0 / size), math.sqrt(2.0 / size))
+    return (sigma / (k + 1.0) * np.cos(np.pi * (2.0 * m + 1.0) * k / (2.0 * size))).astype(np.float32)
+
 
 class TrainerState:
     """what a train-step engine holds besides its network: constructor arguments checked, then plain attributes that
@@ -158,6 +179,10 @@ class TrainerState:
     # WarmUp of base_lr / warm_up (a constant is warm_up = 0), or ("inverse_time_decay", initial, decay_steps, decay_rate, staircase)
     optimizer_kind, momentum, nesterov, rho = "adam", 0.0, False, 0.9
     lr_schedule: Optional[tuple] = None
+    # the training loss (train.py:254-280): one of TRAINING_LOSSES; `Trainer` sets it before every step from the module global.  "mse"
+    # is gct2_mse_fwd_bwd (or the fused heads) as ever; the other kinds go through gct2_loss_fwd_bwd, whose scratch (and the DCT basis)
+    # an engine allocates on first use of such a kind (_loss_resources)
+    training_loss = "mse"
 
     @property
     def _ema(self) -> Optional[torch.Tensor]:
@@ -226,6 +251,29 @@ class TrainerState:
 
     def objective_coefficients(self, t_int: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         return objective_coefficients(t_int, self.steps, *(getattr(self, k) for k in OBJECTIVE_SWITCHES))
+
+    # ---- the training losses besides the plain MSE (train.py:254-280) -------------------------------------------------------------
+    def _loss_resources(self, store: dict, B: int, H: int, W: int, Cc: int = 3) -> Tuple[int, torch.Tensor, Optional[torch.Tensor]]:
+        """(kind code, scratch, basis or None) of gct2_loss_fwd_bwd for the current training_loss and this shape: allocated on first use
+        and kept in `store` (a buffer set's, or the variant engine's).  A shape the kind refuses (pooled MSE off the 16-pixel grid, a
+        DCT of a non-square image) raises here, before anything is launched."""
+        code = training_loss_code(self.training_loss)
+        key = (code, B, H, W, Cc)
+        if key not in store:
+            need = C.c_size_t(0)
+            _lib.check(self.lib.gct2_loss_scratch(code, B, H, W, Cc, C.byref(need)), "gct2_loss_scratch")
+            scratch = torch.zeros(need.value, dtype=torch.float32, device=self.device)
+            basis = torch.from_numpy(dct_basis(H)).to(self.device) if code == _lib.LOSS_DCT else None
+            store[key] = (scratch, basis)
+        return (code,) + store[key]
+
+    def _loss_launch(self, store: dict, pred: torch.Tensor, target, dpred: Optional[torch.Tensor], loss: torch.Tensor, stream: int) -> None:
+        """gct2_loss_fwd_bwd of the current (non-"mse") training_loss on an fp32 [B,H,W,C] prediction; target: a device address or a Slot
+        holding one; dpred = None: the loss only"""
+        B, H, W, Cc = pred.shape
+        code, scratch, basis = self._loss_resources(store, B, H, W, Cc)
+        call("gct2_loss_fwd_bwd", code, pred.data_ptr(), target, dpred.data_ptr() if dpred is not None else None, loss.data_ptr(),
+             scratch.data_ptr(), scratch.numel(), B, H, W, Cc, basis.data_ptr() if basis is not None else None, self._ls_ptr(), stream)
 
     # ---- optimizer (train.py:50-65,75) ---------------------------------------------------------------------------------------
     def learning_rate(self, k: Optional[int] = None) -> float:

@@ -287,6 +287,7 @@ class VariantEngine(TrainerState):
         self.glorot_init(seed)
         self.partials = torch.zeros(1024, dtype=torch.float32, device=self.device)
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._loss_store: dict = {}     # scratch (and the DCT basis) of the non-default training losses, by kind and shape
         self.last = {}
         if use_ema:
             self.enable_ema(ema_momentum)
@@ -395,7 +396,10 @@ class VariantEngine(TrainerState):
         if w is not None:
             call("gct2_mix_per_image", pred.data_ptr(), None, w.data_ptr(), None, pred.data_ptr(), B, H * W * 3, s)
         dpred = torch.empty_like(pred)
-        call("gct2_mse_fwd_bwd", pred.data_ptr(), target.data_ptr(), dpred.data_ptr(), self.loss.data_ptr(), self.partials.data_ptr(), n, self._ls_ptr(), s)
+        if self.training_loss != "mse":                        # train.py:265-280 (no gradient when there is no reverse pass)
+            self._loss_launch(self._loss_store, pred, target.data_ptr(), dpred if backward else None, self.loss, s)
+        else:
+            call("gct2_mse_fwd_bwd", pred.data_ptr(), target.data_ptr(), dpred.data_ptr(), self.loss.data_ptr(), self.partials.data_ptr(), n, self._ls_ptr(), s)
         if w is not None:
             call("gct2_mix_per_image", dpred.data_ptr(), None, w.data_ptr(), None, dpred.data_ptr(), B, H * W * 3, s)
         self.last.update(pred=pred, noised=noised)

@@ -37,7 +37,7 @@ enum {
 };
 
 /* library / device identification ------------------------------------------------------------ */
-int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive); v17 + gct2_sumsq_layout, gct2_grad_sumsq, gct2_adam_keras_clipped (additive); v17 + gct2_optimizer_apply, gct2_loss_scale_begin_schedule (additive)) */
+int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive); v17 + gct2_sumsq_layout, gct2_grad_sumsq, gct2_adam_keras_clipped (additive); v17 + gct2_optimizer_apply, gct2_loss_scale_begin_schedule (additive); v17 + gct2_loss_scratch, gct2_loss_fwd_bwd (additive)) */
 /* how the library was built: 0 for the product build; bit 0 (GCT2_BUILD_STAMP) = diagnostic build with in-kernel phase stamps
  * (make EXTRA=-DGCT2_STAMP).  Product hosts (the Python binding, bench.py, the tests) refuse a library whose flags are not 0. */
 enum { GCT2_BUILD_STAMP = 1 };
@@ -339,6 +339,45 @@ int gct2_image_prepare(const uint8_t* src, const int64_t* offsets, const int32_t
  * loss_scale_ptr: device pointer to the current loss scale (fp16 mode) or NULL for 1. */
 int gct2_mse_fwd_bwd(const float* pred, const float* target, float* dpred, float* loss,
                      float* partials, size_t n, const float* loss_scale_ptr, void* stream);
+
+/* ---- the other training losses Trainer.call carries (train.py:254-280; the author switches between them by moving a `return`) ----
+ * One entry point for the four ways the reference turns target - pred into the scalar Keras minimises.  pred, target, dpred: fp32
+ * [B,H,W,C] contiguous, C in 1..4; n = B*H*W*C; d = fl32(target - pred); s = *loss_scale_ptr, or 1 when it is NULL (as in
+ * gct2_mse_fwd_bwd).  dpred == NULL: the loss only (Trainer.call without gradients) - nothing but `loss` and `scratch` is written.
+ * Host constants are formed in double and rounded once to fp32; the pointwise arithmetic is fp32, every operation rounded on its own
+ * (no contraction); no floating-point atomics: work-groups leave partial sums (fp64) in `scratch`, one launch adds them in index
+ * order, and loss = (float) of a double expression of the sums - the bits depend on the inputs alone.
+ *   GCT2_LOSS_MSE         exactly gct2_mse_fwd_bwd's launches and bits, with the first 1024 floats of scratch as its `partials`.
+ *   GCT2_LOSS_L1          loss = S / n, S = sum max(d, -d);  dpred = fl(s * (d >= -d ? -c : c)), c = (float)(1.0 / n).  A tie sends
+ *                         the gradient to the first operand of the reference's maximum(t - p, p - t) and a NaN to the second: TF's
+ *                         _MaximumGrad (x >= y) [TF]; PARITY UNPINNED like the other [TF] rules.
+ *   GCT2_LOSS_MSE_POOLED  H and W multiples of 16 (avg_pool2d(16, 16, 'SAME') then pads nothing; anything else: GCT2_EINVAL).  qsum =
+ *                         the sum of d over a pixel's 16 x 16 cell and channel, n2 = B*(H/16)*(W/16)*C:
+ *                         loss = S1 / n + S2 / n2, S1 = sum d^2, S2 = sum over cells and channels of (qsum / 256)^2;
+ *                         dpred = fl(s * fl(fl(d * c1) + fl(qsum * c2))), c1 = (float)(-2.0 / n), c2 = (float)(-2.0 / (65536.0 * n2)).
+ *                         The reference pools target and pred separately and subtracts the pools; pooling d differs from that only
+ *                         in rounding.
+ *   GCT2_LOSS_DCT         H == W == size, a multiple of 4.  basis = G, fp32 [size,size] row-major, supplied by the caller (the library
+ *                         never evaluates a cosine).  Per image and channel, D = d[b,:,:,c]:  E = G D G^T,  loss = (sum E^2) / n,
+ *                         dpred[b,:,:,c] = fl(s * fl(V * c1)),  V = G^T E G,  c1 = (float)(-2.0 / n).  Four fp32 matrix products per
+ *                         plane on the fp32 matrix cores (each an fmaf chain over ascending reduction index), hopping
+ *                         d -> scratch -> dpred -> scratch -> dpred.  The reference's G (trainer_math.dct_basis) is
+ *                         tf.signal.dct(norm='ortho') times frequency_weights: G[k,m] = 1/(k+1) * sigma_k * cos(pi (2m+1) k / (2 size)),
+ *                         sigma_0 = sqrt(1/size), else sqrt(2/size); dct2d leaves its result spatially transposed, which the mean
+ *                         does not see.
+ * scratch: device floats, 16-byte aligned, at least what gct2_loss_scratch reports for the kind and shape (the partial sums; for the
+ * DCT also one [B,H,W,C] plane set).  GCT2_EINVAL before any launch: unknown kind, non-positive dims or C outside 1..4, the shape
+ * rules above, NULL pred / target / loss / scratch, basis == NULL for the DCT, misaligned pointers (scratch and basis 16 bytes, the
+ * rest 4), scratch_floats below gct2_loss_scratch's figure. */
+#define GCT2_LOSS_MSE 0          /* train.py:272 */
+#define GCT2_LOSS_L1 1           /* train.py:268-270 */
+#define GCT2_LOSS_MSE_POOLED 2   /* train.py:274-280 */
+#define GCT2_LOSS_DCT 3          /* train.py:254-260, 265 */
+/* host only, no launch: floats of device scratch gct2_loss_fwd_bwd needs for this kind and shape */
+int gct2_loss_scratch(int kind, int B, int H, int W, int C, size_t* floats);
+int gct2_loss_fwd_bwd(int kind, const float* pred, const float* target, float* dpred, float* loss,
+                      float* scratch, size_t scratch_floats, int B, int H, int W, int C,
+                      const float* basis, const float* loss_scale_ptr, void* stream);
 
 /* ---- mixed precision (train.py:34,43-45,82-83) ------------------------------------------------ */
 /* device-resident state of Keras' LossScaleOptimizer [TF] plus the optimizer step counter it gates: a skipped step (inf/nan
