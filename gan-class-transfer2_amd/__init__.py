@@ -9,4 +9,5 @@ from .sampler import log_sample, make_log_sample  # noqa: F401
 from ._lib import BF16, F16, F32, Gct2Error       # noqa: F401
 from .engine import Topology, UNetEngine          # noqa: F401
 from .model import (Adam, Block, Dense, Denoiser, DownShuffle, InverseTimeDecay, LambdaCallback, LossScaleOptimizer,  # noqa: F401
-                    RMSprop, Residual, SGD, Sequential, Trainer, UpShuffle, WarmUp, alpha_dash, configure, identity)
+                    RMSprop, Residual, SGD, Sequential, Trainer, UpShuffle, WarmUp, alpha_dash, configure, identity, regularizers,
+                    sign_gradient)

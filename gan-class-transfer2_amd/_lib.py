@@ -22,6 +22,8 @@ SUMSQ_CHUNK, SUMSQ_MAX_SEGMENTS = 32768, 1024
 # gct2_optimizer_apply kinds (Adam has its own entry points) and gct2_loss_scale_begin_schedule schedules (include/gct2.h)
 OPT_ADAM, OPT_SGD, OPT_RMSPROP = 0, 1, 2
 SCHEDULE_WARMUP, SCHEDULE_INVERSE_TIME_DECAY = 0, 1
+# gct2_optimizer_apply_reg gradient transformers (include/gct2.h; train.py:47-48 sign_gradient)
+GRAD_NONE, GRAD_SIGN = 0, 1
 # gct2_loss_fwd_bwd kinds (include/gct2.h; the four returns of Trainer.call, train.py:254-280)
 LOSS_MSE, LOSS_L1, LOSS_MSE_POOLED, LOSS_DCT = 0, 1, 2, 3
 
@@ -102,6 +104,9 @@ SIGNATURES = {
     "gct2_grad_sumsq": [_vp, _vp, _i, _sz, _f, _vp, _vp, _vp, _vp],
     "gct2_adam_keras_clipped": [_vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _f, _f, _f, _vp, _i, _f, _vp, _vp],
     "gct2_optimizer_apply": [_i, _vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _i, _f, _f, _f, _vp, _i, _f, _vp, _vp],
+    "gct2_optimizer_apply_reg": [_i, _vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _i, _f, _f, _f, _vp, _i, _f, _vp, _f, _i, _vp],
+    "gct2_grad_sumsq_l2": [_vp, _vp, _vp, _vp, _i, _sz, _f, _vp, _vp, _vp, _vp],
+    "gct2_l2_penalty": [_vp, _vp, _f, _vp, _vp, _vp],
     "gct2_cast_from_f32": [_i, _vp, _vp, _sz, _vp],
     "gct2_loss_scale_init": [_vp, _f, _vp],
     "gct2_loss_scale_begin": [_vp, _f, _i, _f, _f, _vp],

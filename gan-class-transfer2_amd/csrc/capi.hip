@@ -701,6 +701,55 @@ int gct2_optimizer_apply(int kind, float* p, float* m, float* v, float* g, void*
   return pw_optimizer(kind, p, m, v, g, shadow, shadow_dtype, n, lr, momentum, nesterov, rho, epsilon, grad_mul, ls, clip_mode, clip, sumsq, S(stream));
 }
 
+int gct2_optimizer_apply_reg(int kind, float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,
+                             int nesterov, float rho, float epsilon, float grad_mul, const gct2_loss_scale_state* ls, int clip_mode, float clip,
+                             const double* sumsq, float l2_coeff, int transform, void* stream) {
+  if (kind != GCT2_OPT_ADAM && kind != GCT2_OPT_SGD && kind != GCT2_OPT_RMSPROP)
+    return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: unknown kind %d (GCT2_OPT_ADAM / GCT2_OPT_SGD / GCT2_OPT_RMSPROP)", kind);
+  const bool adam = kind == GCT2_OPT_ADAM;         // (momentum = beta1, rho = beta2: unchecked, as gct2_adam_keras_clipped leaves them)
+  if (!adam && !(momentum >= 0.f && momentum <= 1.f)) return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: momentum %g outside [0, 1]", (double)momentum);
+  if (kind == GCT2_OPT_RMSPROP && !(rho >= 0.f && rho <= 1.f)) return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: rho %g outside [0, 1]", (double)rho);
+  if (kind == GCT2_OPT_RMSPROP && !(epsilon >= 0.f)) return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: epsilon %g < 0", (double)epsilon);
+  const bool use_m = adam || momentum > 0.f, use_v = kind != GCT2_OPT_SGD;
+  if (!p || !g || (use_m && !m) || (use_v && !v)) return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: null pointer");
+  if (n == 0) return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: n == 0");
+  if (shadow && shadow_dtype != GCT2_BF16 && shadow_dtype != GCT2_F16)
+    return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: a shadow needs a 16-bit dtype (GCT2_BF16 / GCT2_F16), got %d", shadow_dtype);
+  if (((uintptr_t)p | (uintptr_t)g | (use_m ? (uintptr_t)m : 0) | (use_v ? (uintptr_t)v : 0)) % 16 || (shadow && (uintptr_t)shadow % 8) ||
+      (uintptr_t)sumsq % 8)
+    return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: p, g and the slots in use must be 16-byte aligned, the shadow and sumsq 8-byte aligned");
+  if (clip_mode < GCT2_CLIP_NONE || clip_mode > GCT2_CLIP_GLOBAL_NORM) return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: unknown clip_mode %d", clip_mode);
+  if (clip_mode != GCT2_CLIP_NONE && !(clip > 0.f && clip <= 3.402823466e38f))
+    return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: clip = %g must be finite and > 0", (double)clip);
+  if ((clip_mode == GCT2_CLIP_NORM || clip_mode == GCT2_CLIP_GLOBAL_NORM) && !sumsq)
+    return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: clip_mode %d needs sumsq (gct2_grad_sumsq / gct2_grad_sumsq_l2)", clip_mode);
+  if (transform != GCT2_GRAD_NONE && transform != GCT2_GRAD_SIGN) return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: unknown transform %d", transform);
+  if (!(l2_coeff >= 0.f && l2_coeff <= 3.402823466e38f))
+    return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: l2_coeff = %g must be finite and >= 0", (double)l2_coeff);
+  return pw_optimizer_reg(kind, p, m, v, g, shadow, shadow_dtype, n, lr, momentum, nesterov, rho, epsilon, grad_mul, ls, clip_mode, clip, sumsq,
+                          l2_coeff, transform, S(stream));
+}
+
+int gct2_grad_sumsq_l2(const float* g, const float* p, const gct2_sumsq_seg* segs, const float* seg_coeff, int nseg, size_t npartials,
+                       float grad_mul, gct2_loss_scale_state* ls, double* partials, double* sumsq, void* stream) {
+  if (!g || !p || !segs || !seg_coeff || !partials || !sumsq) return gct2_fail(GCT2_EINVAL, "grad_sumsq_l2: null pointer");
+  if (nseg < 1 || nseg > GCT2_SUMSQ_MAX_SEGMENTS)
+    return gct2_fail(GCT2_EINVAL, "grad_sumsq_l2: nseg = %d outside [1, %d]", nseg, GCT2_SUMSQ_MAX_SEGMENTS);
+  if (npartials == 0 || npartials < (size_t)nseg || npartials > 0x7fffffffull)
+    return gct2_fail(GCT2_EINVAL, "grad_sumsq_l2: npartials = %zu is not what gct2_sumsq_layout reports for %d segments", npartials, nseg);
+  if (((uintptr_t)g | (uintptr_t)p) % 16 || ((uintptr_t)segs | (uintptr_t)partials | (uintptr_t)sumsq) % 8 || (uintptr_t)seg_coeff % 4)
+    return gct2_fail(GCT2_EINVAL, "grad_sumsq_l2: g and p must be 16-byte aligned, segs / partials / sumsq 8-byte, seg_coeff 4-byte aligned");
+  return pw_grad_sumsq_l2(g, p, segs, seg_coeff, nseg, npartials, grad_mul, ls, partials, sumsq, S(stream));
+}
+
+int gct2_l2_penalty(const float* loss, const double* S_, float l2, float* penalty_out, float* total_out, void* stream) {
+  if (!loss || !S_ || !penalty_out || !total_out) return gct2_fail(GCT2_EINVAL, "l2_penalty: null pointer");
+  if ((uintptr_t)S_ % 8 || ((uintptr_t)loss | (uintptr_t)penalty_out | (uintptr_t)total_out) % 4)
+    return gct2_fail(GCT2_EINVAL, "l2_penalty: S must be 8-byte aligned, loss / penalty_out / total_out 4-byte aligned");
+  if (!(l2 >= 0.f && l2 <= 3.402823466e38f)) return gct2_fail(GCT2_EINVAL, "l2_penalty: l2 = %g must be finite and >= 0", (double)l2);
+  return pw_l2_penalty(loss, S_, l2, penalty_out, total_out, S(stream));
+}
+
 int gct2_loss_scale_init(gct2_loss_scale_state* st, float initial_scale, void* stream) {
   if (!st || !(initial_scale > 0.f)) return gct2_fail(GCT2_EINVAL, "loss_scale_init: null state or non-positive scale");
   return pw_ls_init(st, initial_scale, S(stream));

@@ -479,6 +479,14 @@ int pw_adam_clipped(float* p, float* m, float* v, const float* g, void* shadow, 
 int pw_optimizer(int kind, float* p, float* m, float* v, const float* g, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,
                  int nesterov, float rho, float eps, float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip, const double* sumsq,
                  hipStream_t s);
+// pw_optimizer for all three kinds (GCT2_OPT_ADAM: lr = alpha, momentum = beta1, rho = beta2) with the penalty gradient l2c * p in front of
+// the clipping step and the gradient transformer behind it; pw_grad_sumsq over the regularized gradient; the reported penalty
+int pw_optimizer_reg(int kind, float* p, float* m, float* v, const float* g, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,
+                     int nesterov, float rho, float eps, float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip, const double* sumsq,
+                     float l2c, int transform, hipStream_t s);
+int pw_grad_sumsq_l2(const float* g, const float* p, const gct2_sumsq_seg* segs, const float* seg_coeff, int nseg, size_t npartials,
+                     float grad_mul, gct2_loss_scale_state* ls, double* partials, double* sumsq, hipStream_t s);
+int pw_l2_penalty(const float* loss, const double* S, float l2, float* penalty, float* total, hipStream_t s);
 int pw_cast(int dtype, const float* src, void* dst, size_t n, hipStream_t s);
 int pw_ls_init(gct2_loss_scale_state* st, float scale, hipStream_t s);
 int pw_ls_begin(gct2_loss_scale_state* st, float base_lr, int warmup_steps, float b1, float b2, hipStream_t s);

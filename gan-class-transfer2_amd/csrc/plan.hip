@@ -35,6 +35,7 @@ const Entry ENTRIES[] = {
     GCT2_ENTRY(gct2_convT4s2_fwd), GCT2_ENTRY(gct2_convT4s2_fwd_head_train), GCT2_ENTRY(gct2_convT4s2_dgrad), GCT2_ENTRY(gct2_convT4s2_wgrad),
     GCT2_ENTRY(gct2_adam_apply), GCT2_ENTRY(gct2_adam_keras_multi), GCT2_ENTRY(gct2_ema_update),
     GCT2_ENTRY(gct2_grad_sumsq), GCT2_ENTRY(gct2_adam_keras_clipped), GCT2_ENTRY(gct2_optimizer_apply), GCT2_ENTRY(gct2_loss_scale_begin_schedule),
+    GCT2_ENTRY(gct2_optimizer_apply_reg), GCT2_ENTRY(gct2_grad_sumsq_l2), GCT2_ENTRY(gct2_l2_penalty),
     GCT2_ENTRY(gct2_conv2d_s1_fwd), GCT2_ENTRY(gct2_conv2d_s1_dgrad), GCT2_ENTRY(gct2_conv2d_s1_wgrad),
     GCT2_ENTRY(gct2_relu_mask), GCT2_ENTRY(gct2_add), GCT2_ENTRY(gct2_mix_per_image),
     GCT2_ENTRY(gct2_dense_fwd), GCT2_ENTRY(gct2_dense_bwd), GCT2_ENTRY(gct2_dense_head_train),

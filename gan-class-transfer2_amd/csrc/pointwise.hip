@@ -993,7 +993,11 @@ __global__ void ls_update_kernel(gct2_loss_scale_state* s, int growth_interval) 
 // may be shorter) and never reads outside its segment.  g' = fl32(g * k) as adam_kernel forms it; the square (exact) and every sum
 // in fp64, in a fixed order: a thread over its own elements in address order, the 64 lanes of a wave by an xor butterfly (both
 // operands of every add are the same pair on both lanes, so all lanes hold the same bits), the four waves in wave order.
-__global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ g, const gct2_sumsq_seg* __restrict__ segs, int nseg,
+// L2 (gct2_grad_sumsq_l2): the element squared is g_r = fl(g' + fl(seg_coeff[s] * p)), the regularized gradient the update kernel forms;
+// a segment whose coefficient is 0 skips the add (and the read of p).  found_inf still comes from the raw g alone.
+template <bool L2>
+__global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ g, const float* __restrict__ p,
+                                                            const gct2_sumsq_seg* __restrict__ segs, const float* __restrict__ seg_coeff, int nseg,
                                                             float grad_mul, gct2_loss_scale_state* ls, double* __restrict__ partials) {
 #pragma clang fp contract(off)
   const uint64_t c = blockIdx.x;
@@ -1006,23 +1010,33 @@ __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restr
   const uint64_t len = off >= count ? 0 : (count - off < (uint64_t)GCT2_SUMSQ_CHUNK ? count - off : (uint64_t)GCT2_SUMSQ_CHUNK);
   const float* __restrict__ src = g + segs[lo].begin + off;       // 16-byte aligned: begin and the chunk are multiples of 4 elements
   const float k = (ls ? ls->inv_scale : 1.f) * grad_mul;
+  float coef = 0.f;
+  const float* __restrict__ psrc = nullptr;
+  if constexpr (L2) { coef = seg_coeff[lo]; psrc = p + segs[lo].begin + off; }
+  const bool reg = L2 && coef != 0.f;              // uniform over the work-group
   const uint32_t n4 = (uint32_t)(len >> 2);
   double acc = 0.0;
   bool bad = false;
 #pragma unroll 4
   for (uint32_t i = threadIdx.x; i < n4; i += 256) {
     const f32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(src) + i);     // read once per step: streaming
+    f32x4_t w = {0.f, 0.f, 0.f, 0.f};
+    if (reg) w = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(psrc) + i);
 #pragma unroll
     for (int e = 0; e < 4; e++) {
       bad |= !(fabsf(v[e]) <= 3.402823466e38f);    // the RAW element: false for inf and nan (ls_check_kernel's test)
-      const double x = (double)(v[e] * k);
+      float x32 = v[e] * k;
+      if (reg) { const float t = coef * w[e]; x32 = x32 + t; }
+      const double x = (double)x32;
       acc = acc + x * x;
     }
   }
   if (threadIdx.x < (uint32_t)(len & 3)) {         // tail (len % 4 elements)
     const float r = src[((size_t)n4 << 2) + threadIdx.x];
     bad |= !(fabsf(r) <= 3.402823466e38f);
-    const double x = (double)(r * k);
+    float x32 = r * k;
+    if (reg) { const float t = coef * psrc[((size_t)n4 << 2) + threadIdx.x]; x32 = x32 + t; }
+    const double x = (double)x32;
     acc = acc + x * x;
   }
 #pragma unroll
@@ -1056,7 +1070,21 @@ __global__ __launch_bounds__(256) void sumsq_final_kernel(const gct2_sumsq_seg* 
   }
 }
 
-// the step between g' and adam_keras_update; `a` is the launch-uniform operand of the mode (clipped_adam_kernel forms it once)
+// the launch-uniform operand of a norm mode, formed once per thread from the ONE fp64 sum of squares the launch reads
+__device__ __forceinline__ float clip_operand(int mode, float clip, const double* __restrict__ sumsq) {
+#pragma clang fp contract(off)
+  if (mode == GCT2_CLIP_NORM) {
+    const double ss = *sumsq;
+    const float l2 = ss > 0.0 ? (float)sqrt(ss) : 1.f;
+    return fmaxf(l2, clip);
+  }
+  if (mode == GCT2_CLIP_GLOBAL_NORM) {
+    const float nrm = (float)sqrt(*sumsq);         // the double square root, rounded once to fp32
+    return fabsf(nrm) <= 3.402823466e38f ? clip * fminf(1.f / nrm, 1.f / clip) : __builtin_nanf("");
+  }
+  return 0.f;
+}
+// the step between g' and adam_keras_update; `a` is the launch-uniform operand of the mode (clip_operand)
 __device__ __forceinline__ float clip_grad(float g, int mode, float clip, float a) {
 #pragma clang fp contract(off)
   switch (mode) {
@@ -1078,15 +1106,7 @@ __global__ __launch_bounds__(256) void clipped_adam_kernel(float* __restrict__ p
   if (ls && ls->found_inf != 0) return;            // a skipped step writes nothing
   const float inv_scale = (ls ? ls->inv_scale : 1.f) * grad_mul;
   if (ls) alpha = ls->alpha;
-  float a = 0.f;
-  if (mode == GCT2_CLIP_NORM) {
-    const double ss = *sumsq;
-    const float l2 = ss > 0.0 ? (float)sqrt(ss) : 1.f;
-    a = fmaxf(l2, clip);
-  } else if (mode == GCT2_CLIP_GLOBAL_NORM) {
-    const float nrm = (float)sqrt(*sumsq);         // the double square root, rounded once to fp32
-    a = fabsf(nrm) <= 3.402823466e38f ? clip * fminf(1.f / nrm, 1.f / clip) : __builtin_nanf("");
-  }
+  const float a = clip_operand(mode, clip, sumsq);
   const size_t n4 = n >> 2;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const float ob1 = 1.f - b1, ob2 = 1.f - b2;
@@ -1167,15 +1187,7 @@ __global__ __launch_bounds__(256) void optimizer_kernel(float* __restrict__ p, f
   if (ls && ls->found_inf != 0) return;            // a skipped step writes nothing
   const float inv_scale = (ls ? ls->inv_scale : 1.f) * grad_mul;
   if (ls) lr = ls->alpha;
-  float a = 0.f;
-  if (mode == GCT2_CLIP_NORM) {
-    const double ss = *sumsq;
-    const float l2 = ss > 0.0 ? (float)sqrt(ss) : 1.f;
-    a = fmaxf(l2, clip);
-  } else if (mode == GCT2_CLIP_GLOBAL_NORM) {
-    const float nrm = (float)sqrt(*sumsq);
-    a = fabsf(nrm) <= 3.402823466e38f ? clip * fminf(1.f / nrm, 1.f / clip) : __builtin_nanf("");
-  }
+  const float a = clip_operand(mode, clip, sumsq);
   const bool nes = nesterov != 0;
   const float orho = 1.f - rho;
   const size_t n4 = n >> 2;
@@ -1212,6 +1224,84 @@ __global__ __launch_bounds__(256) void optimizer_kernel(float* __restrict__ p, f
     if constexpr (USE_V) v[i] = vv;
     if constexpr (HAS_SHADOW) shadow[i] = from_f32<S>(pp);
   }
+}
+
+// ---- L2 weight regularizer and sign transformer in front of any kind's update (include/gct2.h gct2_optimizer_apply_reg) -----------
+// Keras' gradient_transformers=[sign_gradient] (train.py:47-48): tf.sign - a NaN stays NaN, -0 gives +0
+__device__ __forceinline__ float sign_grad(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : (x == 0.f ? 0.f : x)); }
+// g' -> the gradient the update reads: the penalty gradient fl(l2c * p) added (skipped, not computed, when l2c == 0), clip_grad, then
+// the transformer (Keras' _transform_gradients order [TF]); l2c and transform are launch-uniform
+__device__ __forceinline__ float reg_grad(float g1, float p, float l2c, int transform, int mode, float clip, float a) {
+#pragma clang fp contract(off)
+  if (l2c != 0.f) {
+    const float t = l2c * p;
+    g1 = g1 + t;
+  }
+  g1 = clip_grad(g1, mode, clip, a);
+  return transform == GCT2_GRAD_SIGN ? sign_grad(g1) : g1;
+}
+// optimizer_kernel over all three kinds (GCT2_OPT_ADAM: lr = alpha, momentum = beta1, rho = beta2, both slots in use) with reg_grad
+// where the siblings have clip_grad; adam_keras_update and optimizer_update are the siblings' own
+template <int KIND, bool USE_M, typename S, bool HAS_SHADOW>
+__global__ __launch_bounds__(256) void reg_optimizer_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                                            const float* __restrict__ g, S* __restrict__ shadow, size_t n, float lr,
+                                                            float momentum, int nesterov, float rho, float eps, float grad_mul,
+                                                            const gct2_loss_scale_state* __restrict__ ls, int mode, float clip,
+                                                            const double* __restrict__ sumsq, float l2c, int transform) {
+#pragma clang fp contract(off)
+  constexpr bool USE_V = KIND != GCT2_OPT_SGD;
+  if (ls && ls->found_inf != 0) return;            // a skipped step writes nothing
+  const float inv_scale = (ls ? ls->inv_scale : 1.f) * grad_mul;
+  if (ls) lr = ls->alpha;
+  const float a = clip_operand(mode, clip, sumsq);
+  const bool nes = nesterov != 0;
+  const float omom = 1.f - momentum, orho = 1.f - rho;       // (Adam: 1 - beta1, 1 - beta2)
+  auto update = [&](float& pp, float& mm, float& vv, float gg) {
+    if constexpr (KIND == GCT2_OPT_ADAM) adam_keras_update(pp, mm, vv, gg, lr, momentum, omom, rho, orho, eps);
+    else optimizer_update<KIND, USE_M>(pp, mm, vv, gg, lr, momentum, nes, rho, orho, eps);
+  };
+  const size_t n4 = n >> 2;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const f32x4_t gv = reinterpret_cast<const f32x4_t*>(g)[i];
+    f32x4_t pv = __builtin_nontemporal_load(reinterpret_cast<f32x4_t*>(p) + i);
+    f32x4_t mv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (USE_M) mv = __builtin_nontemporal_load(reinterpret_cast<f32x4_t*>(m) + i);
+    if constexpr (USE_V) vv = __builtin_nontemporal_load(reinterpret_cast<f32x4_t*>(v) + i);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      float pp = pv[k], mm = mv[k], v1 = vv[k];
+      update(pp, mm, v1, reg_grad(gv[k] * inv_scale, pp, l2c, transform, mode, clip, a));
+      pv[k] = pp; mv[k] = mm; vv[k] = v1;
+    }
+    __builtin_nontemporal_store(pv, reinterpret_cast<f32x4_t*>(p) + i);
+    if constexpr (USE_M) __builtin_nontemporal_store(mv, reinterpret_cast<f32x4_t*>(m) + i);
+    if constexpr (USE_V) __builtin_nontemporal_store(vv, reinterpret_cast<f32x4_t*>(v) + i);
+    if constexpr (HAS_SHADOW) {
+      const u32x2_t o = {pack2<S>(pv[0], pv[1]), pack2<S>(pv[2], pv[3])};
+      reinterpret_cast<u32x2_t*>(shadow)[i] = o;
+    }
+  }
+  // tail (n % 4 elements)
+  const size_t i = (n4 << 2) + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    float pp = p[i], mm = 0.f, vv = 0.f;
+    if constexpr (USE_M) mm = m[i];
+    if constexpr (USE_V) vv = v[i];
+    update(pp, mm, vv, reg_grad(g[i] * inv_scale, pp, l2c, transform, mode, clip, a));
+    p[i] = pp;
+    if constexpr (USE_M) m[i] = mm;
+    if constexpr (USE_V) v[i] = vv;
+    if constexpr (HAS_SHADOW) shadow[i] = from_f32<S>(pp);
+  }
+}
+// gct2_l2_penalty: what Keras' train_step reports beside the data term, one thread, fp64 until the last rounding
+__global__ void l2_penalty_kernel(const float* __restrict__ loss, const double* __restrict__ S, float l2, float* __restrict__ penalty,
+                                  float* __restrict__ total) {
+#pragma clang fp contract(off)
+  const double r = (double)l2 * *S;
+  *penalty = (float)r;
+  *total = (float)((double)*loss + r);
 }
 
 // gct2_loss_scale_begin_schedule: ls_begin_kernel for either schedule, with or without Adam's bias correction; float32 in Keras' order
@@ -1467,10 +1557,22 @@ int pw_ema(float* ema, const float* p, void* shadow, int sdt, size_t n, float mo
 }
 int pw_grad_sumsq(const float* g, const gct2_sumsq_seg* segs, int nseg, size_t npartials, float grad_mul, gct2_loss_scale_state* ls,
                   double* partials, double* sumsq, hipStream_t s) {
-  hipLaunchKernelGGL(sumsq_partial_kernel, dim3((unsigned)npartials), dim3(256), 0, s, g, segs, nseg, grad_mul, ls, partials);
+  hipLaunchKernelGGL(sumsq_partial_kernel<false>, dim3((unsigned)npartials), dim3(256), 0, s, g, (const float*)nullptr, segs, (const float*)nullptr,
+                     nseg, grad_mul, ls, partials);
   if (int e = gct2_check_launch("grad_sumsq")) return e;
   hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, s, segs, nseg, partials, sumsq);
   return gct2_check_launch("grad_sumsq");
+}
+int pw_grad_sumsq_l2(const float* g, const float* p, const gct2_sumsq_seg* segs, const float* seg_coeff, int nseg, size_t npartials,
+                     float grad_mul, gct2_loss_scale_state* ls, double* partials, double* sumsq, hipStream_t s) {
+  hipLaunchKernelGGL(sumsq_partial_kernel<true>, dim3((unsigned)npartials), dim3(256), 0, s, g, p, segs, seg_coeff, nseg, grad_mul, ls, partials);
+  if (int e = gct2_check_launch("grad_sumsq_l2")) return e;
+  hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, s, segs, nseg, partials, sumsq);
+  return gct2_check_launch("grad_sumsq_l2");
+}
+int pw_l2_penalty(const float* loss, const double* S, float l2, float* penalty, float* total, hipStream_t s) {
+  hipLaunchKernelGGL(l2_penalty_kernel, dim3(1), dim3(1), 0, s, loss, S, l2, penalty, total);
+  return gct2_check_launch("l2_penalty");
 }
 int pw_adam_clipped(float* p, float* m, float* v, const float* g, void* shadow, int sdt, size_t n, float alpha, float b1, float b2, float eps,
                     float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip, const double* sumsq, hipStream_t s) {
@@ -1493,6 +1595,20 @@ int pw_optimizer(int kind, float* p, float* m, float* v, const float* g, void* s
 #undef GCT2_OPT_SHADOW
 #undef GCT2_OPT
   return gct2_check_launch("optimizer_apply");
+}
+int pw_optimizer_reg(int kind, float* p, float* m, float* v, const float* g, void* shadow, int sdt, size_t n, float lr, float momentum,
+                     int nesterov, float rho, float eps, float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip, const double* sumsq,
+                     float l2c, int transform, hipStream_t s) {
+  const int nb = blocks_for(n / 4 + 4, 256);
+  const bool use_m = momentum > 0.f;
+#define GCT2_REG(K, M, S, HS) hipLaunchKernelGGL((reg_optimizer_kernel<K, M, S, HS>), dim3(nb), dim3(256), 0, s, p, m, v, g, reinterpret_cast<S*>(shadow), n, lr, momentum, nesterov, rho, eps, grad_mul, ls, mode, clip, sumsq, l2c, transform)
+#define GCT2_REG_SHADOW(K, M) do { if (!shadow) GCT2_REG(K, M, float, false); else if (sdt == GCT2_BF16) GCT2_REG(K, M, __bf16, true); else GCT2_REG(K, M, _Float16, true); } while (0)
+  if (kind == GCT2_OPT_ADAM) GCT2_REG_SHADOW(GCT2_OPT_ADAM, true);
+  else if (kind == GCT2_OPT_SGD) { if (use_m) GCT2_REG_SHADOW(GCT2_OPT_SGD, true); else GCT2_REG_SHADOW(GCT2_OPT_SGD, false); }
+  else { if (use_m) GCT2_REG_SHADOW(GCT2_OPT_RMSPROP, true); else GCT2_REG_SHADOW(GCT2_OPT_RMSPROP, false); }
+#undef GCT2_REG_SHADOW
+#undef GCT2_REG
+  return gct2_check_launch("optimizer_apply_reg");
 }
 int pw_cast(int dtype, const float* src, void* dst, size_t n, hipStream_t s) {
   if (n == 0) return GCT2_OK;

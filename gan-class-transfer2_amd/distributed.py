@@ -165,6 +165,18 @@ def _refuse_clipping(engine, who: str) -> None:
                               "exchanged: gradient clipping (set_clipping) is not available there")
 
 
+def _refuse_regularizer(engine, who: str) -> str:
+    """the L2 weight regularizer and the gradient transformer (set_regularizer / set_gradient_transform) are single-GPU only: they run
+    on the non-fused optimizer path through gct2_optimizer_apply_reg, which no multi-rank step has been run or tested with.  Refuses an
+    engine with either setting on; returns the message with which both setters refuse from then on (the caller stores it as
+    engine._reg_forbidden once nothing else refuses the engine)."""
+    if getattr(engine, "l2", 0.0) > 0.0 or getattr(engine, "grad_transform", "none") != "none":
+        raise ValueError(f"{who} has not been built or tested with an L2 regularizer or a gradient transformer: switch them off "
+                         "(set_regularizer(None), set_gradient_transform('none'))")
+    return (f"this engine is driven by {who}, which has not been built or tested with them: the L2 regularizer (set_regularizer) and "
+            "gradient transformers (set_gradient_transform) are not available there")
+
+
 def _refuse_optimizer(engine, who: str) -> str:
     """Keras SGD / RMSprop (set_optimizer) are single-GPU only: no multi-rank step has been run or tested with them.  Refuses an engine
     whose kind is not Adam; returns the message with which the engine's set_optimizer refuses another kind from then on (the caller
@@ -186,8 +198,10 @@ class DataParallelStep:
 
     def __init__(self, engine, bucket_elems: int = 4 << 20, group=None, force_exchange: bool = False):
         adam_only = _refuse_optimizer(engine, "DataParallelStep")
+        no_reg = _refuse_regularizer(engine, "DataParallelStep")
         _refuse_clipping(engine, "DataParallelStep")
         engine._optimizer_forbidden = adam_only
+        engine._reg_forbidden = no_reg
         self.engine = engine
         A = engine.arena
         self.reducer = BucketedAllReducer(A.g, A.ready_order(), A.layer_ranges, bucket_elems, group, force_exchange, engine=engine)
@@ -285,6 +299,7 @@ class ShardedDataParallelStep:
 
     def __init__(self, engine, bucket_elems: int = 4 << 20, group=None, force_exchange: bool = False, tail_layers: int = 3):
         adam_only = _refuse_optimizer(engine, "ShardedDataParallelStep")
+        no_reg = _refuse_regularizer(engine, "ShardedDataParallelStep")
         _refuse_clipping(engine, "ShardedDataParallelStep")
         if getattr(engine, "use_ema", False):
             raise ValueError("ShardedDataParallelStep holds only a shard of the fp32 parameters per rank: it cannot keep the engine's "
@@ -292,6 +307,7 @@ class ShardedDataParallelStep:
         engine._ema_forbidden = ("this engine is driven by ShardedDataParallelStep, which holds only a shard of the fp32 parameters per "
                                  "rank: parameter averages (enable_ema) are not available there")
         engine._optimizer_forbidden = adam_only
+        engine._reg_forbidden = no_reg
         self.engine, self.group = engine, group
         A = engine.arena
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1

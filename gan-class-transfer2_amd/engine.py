@@ -967,11 +967,13 @@ class UNetEngine(TrainerState):
     def _apply_adam(self, lo: int = 0, hi: Optional[int] = None, grad_div: float = 1.0, stream: Optional[int] = None) -> None:
         A, s = self.arena, (self._stream() if stream is None else stream)
         hi = A.total if hi is None else hi
-        if self.clip_mode != _lib.CLIP_NONE or self.optimizer_kind != "adam":
+        if self.clip_mode != _lib.CLIP_NONE or self.optimizer_kind != "adam" or self._regularized():
             if self._clip_by_norm() and (lo, hi) != (0, A.total):
                 raise ValueError(f"apply_adam({lo}, {hi}) with clipnorm / global_clipnorm: a norm needs every gradient of the arena "
                                  f"[0, {A.total}) reduced before the first update; clipping under a bucketed exchange is not built")
             launches = self._adam_clipped if self.optimizer_kind == "adam" else self._optimizer_launches       # (SGD / RMSprop, clipped or not)
+            if self._regularized():                             # (an L2 regularizer or a gradient transformer: every kind, one entry point)
+                launches = self._reg_launches
             launches(A._p, A._m, A._v, A.g, A._shadow, lo, hi, 1.0 / grad_div, s)
             return
         # with loss scaling the kernel takes inv_scale / found_inf / alpha from the device-resident state (the step counter that
@@ -1006,7 +1008,8 @@ class UNetEngine(TrainerState):
             x = x.to(self.device, torch.float32).contiguous()
         B, H, W, _ = x.shape
         b = self.buffers(B, H, W)
-        inline = apply and self.fuse_adam and self.ls_state is None and self.clip_mode == _lib.CLIP_NONE and self.optimizer_kind == "adam"
+        inline = (apply and self.fuse_adam and self.ls_state is None and self.clip_mode == _lib.CLIP_NONE and self.optimizer_kind == "adam"
+                  and not self._regularized())
         self.post_backward_ran = self.post_backward is not None and not apply
         cur = torch.cuda.current_stream(self.device)
         if self._flush_event is not None:                      # a flush on another stream (predict / state_dict there): the step waits once
@@ -1021,6 +1024,8 @@ class UNetEngine(TrainerState):
         if not inline:
             self.flush_deferred()                              # (a fused step schedules them inside its forward pass instead)
         self.begin_step()
+        if self.l2 > 0.0:                                      # the penalty's sum of squares, from the weights this forward pass reads
+            self._penalty_begin(self._stream())
         default_obj = self.default_objective()
         if t_int is None and eps is None:
             # the normal training path: eps never touches HBM (unless the target is built from it, train.py:238-252)
@@ -1045,6 +1050,8 @@ class UNetEngine(TrainerState):
                 loss = self.weighted_loss_and_dpred(b, target, w)
             else:
                 loss = self.head_train(b, target, default_obj) if fused else self.loss_and_dpred(b, target, default_obj)
+        if self.l2 > 0.0:                                      # Keras reports loss + the regularization losses; b.loss keeps the data term
+            loss = self._penalty_finish(loss, self._stream())
         # single GPU without loss scaling: Adam rides the side stream inside backward(); the loss-scaled step has to see
         # every gradient (finite check) before any update
         self.flush_deferred()                                  # (no-op after a forward pass that scheduled them; covers octaves < 4 corner cases)
@@ -1078,6 +1085,7 @@ class UNetEngine(TrainerState):
                 self.dtype, float(self.beta_1), float(self.beta_2), float(self.epsilon), float(self.base_lr), int(self.warm_up),
                 id(self.post_replay), self._side.cuda_stream, self.use_ema, float(self.ema_momentum), self.clip_mode, float(self.clip),
                 self.optimizer_kind, float(self.momentum), bool(self.nesterov), float(self.rho), self.lr_schedule, self.training_loss,
+                float(self.l2), self.grad_transform,
                 self._chain_stream.cuda_stream if self._chain_stream is not None else 0)
 
     def _planned_step(self, b: _Buffers, x: torch.Tensor, apply: bool, inline: bool, cur: "torch.cuda.Stream") -> torch.Tensor:

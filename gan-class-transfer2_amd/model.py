@@ -46,6 +46,11 @@ mixed_precision = False
 # frequency-weighted 2-D DCT of the residual, squared and averaged); trainer_math.TRAINING_LOSSES
 training_loss = "mse"
 
+# train.py:80: `regularizer = None  # tf.keras.regularizers.l2(1e-6)` - the kernel_regularizer and bias_regularizer of every
+# Conv2D, Conv2DTranspose and of the Dense(3) head (not of Residual's projection, train.py:107).  None, or regularizers.l2(...);
+# Trainer reads it before every step, like training_loss
+regularizer = None
+
 warm_up = 2_000
 
 # MI355X knob: None -> float32, or float16 when mixed_precision (train.py:38); "bfloat16" selects the
@@ -85,6 +90,47 @@ def preferred_dtype_code() -> int:
 
 
 # ---- optimizer pieces (train.py:47-83) -----------------------------------------------------------------
+class L2:
+    """tf.keras.regularizers.L2 [TF]: the penalty l2 * sum(w^2) per regularized tensor; the engines add its gradient 2 l2 w inside the
+    optimizer kernels (gct2_optimizer_apply_reg) and report the penalty with the loss"""
+
+    def __init__(self, l2=0.01):
+        trainer_math.l2_coefficients(l2)                           # finite and >= 0 (ValueError)
+        self.l2 = l2
+
+
+class regularizers:
+    """the tf.keras.regularizers namespace as far as train.py:80 uses it"""
+    L2 = L2
+    l2 = L2
+
+
+def regularizer_l2(value) -> Optional[float]:
+    """the module global `regularizer` as an engine's set_regularizer argument: None, or the factor of a regularizers.l2(...)"""
+    if value is None:
+        return None
+    if not isinstance(value, L2):
+        raise NotImplementedError(f"regularizer = {value!r}: only None and regularizers.l2(...) are built (no l1, l1_l2 or callables)")
+    return value.l2
+
+
+def sign_gradient(gradient):
+    """train.py:47-48: [(tf.sign(g), v) for (g, v) in gradient] on (tensor, variable) pairs.  As an optimizer's
+    gradient_transformers=[sign_gradient] it is recognised by identity and runs inside the optimizer kernel."""
+    return [(torch.sign(g), v) for (g, v) in gradient]
+
+
+def gradient_transform_name(gradient_transformers) -> str:
+    """an optimizer's gradient_transformers argument as an engine's set_gradient_transform name: None or [] is "none",
+    [sign_gradient] is "sign"; arbitrary callables are not built"""
+    if gradient_transformers is None or (isinstance(gradient_transformers, (list, tuple)) and len(gradient_transformers) == 0):
+        return "none"
+    if isinstance(gradient_transformers, (list, tuple)) and len(gradient_transformers) == 1 and gradient_transformers[0] is sign_gradient:
+        return "sign"
+    raise NotImplementedError("gradient_transformers: only None, [] and [sign_gradient] are built (the transformer runs inside the "
+                              "optimizer kernel; arbitrary callables are not supported)")
+
+
 class WarmUp:
     """train.py:50-65: lr(step) = base*(step+1)/(warmup_steps+1) while step < warmup_steps, else base."""
 
@@ -113,11 +159,13 @@ class Optimizer:
     engine keeps an exponential moving average of the parameters, gct2_ema_update after every applied step; finalize_variable_values()
     overwrites the parameters with it, predict(..., use_ema=True) and log_sample(..., use_ema=True) read it), the three clipping
     arguments clipnorm / global_clipnorm / clipvalue (the engine clips per variable, all together or per element on its non-fused
-    optimizer path) and `iterations`."""
+    optimizer path), gradient_transformers (None or [sign_gradient], run behind the clipping step) and `iterations`."""
 
     def __init__(self, learning_rate, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None, clipnorm=None, global_clipnorm=None,
-                 clipvalue=None):
+                 clipvalue=None, gradient_transformers=None):
         clipping_mode(clipnorm, global_clipnorm, clipvalue)        # Keras' rule: at most one of the three, each > 0 (ValueError)
+        gradient_transform_name(gradient_transformers)             # None, [] or [sign_gradient] (NotImplementedError)
+        self.gradient_transformers = gradient_transformers
         self.clipnorm, self.global_clipnorm, self.clipvalue = clipnorm, global_clipnorm, clipvalue
         if ema_overwrite_frequency is not None:
             raise NotImplementedError("ema_overwrite_frequency: periodic overwriting is not built; call "
@@ -150,8 +198,9 @@ class Adam(Optimizer):
     SURVEY.md A.6) - fused behind the weight gradients on one replica, gct2_adam_keras_clipped when the gradients are clipped."""
 
     def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, use_ema=False, ema_momentum=0.99,
-                 ema_overwrite_frequency=None, clipnorm=None, global_clipnorm=None, clipvalue=None):
-        super().__init__(learning_rate, use_ema, ema_momentum, ema_overwrite_frequency, clipnorm, global_clipnorm, clipvalue)
+                 ema_overwrite_frequency=None, clipnorm=None, global_clipnorm=None, clipvalue=None, gradient_transformers=None):
+        super().__init__(learning_rate, use_ema, ema_momentum, ema_overwrite_frequency, clipnorm, global_clipnorm, clipvalue,
+                         gradient_transformers)
         self.beta_1, self.beta_2, self.epsilon = beta_1, beta_2, epsilon
 
 
@@ -160,9 +209,10 @@ class SGD(Optimizer):
     gct2_optimizer_apply on the engine's non-fused optimizer path (include/gct2.h has the formulas; parity with TensorFlow unpinned)."""
 
     def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None,
-                 clipnorm=None, global_clipnorm=None, clipvalue=None):
+                 clipnorm=None, global_clipnorm=None, clipvalue=None, gradient_transformers=None):
         trainer_math.optimizer_hyper("sgd", momentum, nesterov)     # momentum in [0, 1] (ValueError)
-        super().__init__(learning_rate, use_ema, ema_momentum, ema_overwrite_frequency, clipnorm, global_clipnorm, clipvalue)
+        super().__init__(learning_rate, use_ema, ema_momentum, ema_overwrite_frequency, clipnorm, global_clipnorm, clipvalue,
+                         gradient_transformers)
         self.momentum, self.nesterov = momentum, bool(nesterov)
 
 
@@ -171,11 +221,12 @@ class RMSprop(Optimizer):
     paths); gct2_optimizer_apply on the engine's non-fused optimizer path.  centered=True needs a third slot and is not built."""
 
     def __init__(self, learning_rate=0.001, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False, use_ema=False, ema_momentum=0.99,
-                 ema_overwrite_frequency=None, clipnorm=None, global_clipnorm=None, clipvalue=None):
+                 ema_overwrite_frequency=None, clipnorm=None, global_clipnorm=None, clipvalue=None, gradient_transformers=None):
         trainer_math.optimizer_hyper("rmsprop", momentum, False, rho, epsilon)      # momentum, rho in [0, 1], epsilon >= 0 (ValueError)
         if centered:
             raise NotImplementedError("RMSprop(centered=True) keeps a third slot per parameter (the mean gradient), which is not built")
-        super().__init__(learning_rate, use_ema, ema_momentum, ema_overwrite_frequency, clipnorm, global_clipnorm, clipvalue)
+        super().__init__(learning_rate, use_ema, ema_momentum, ema_overwrite_frequency, clipnorm, global_clipnorm, clipvalue,
+                         gradient_transformers)
         self.rho, self.momentum, self.epsilon, self.centered = rho, momentum, epsilon, False
 
 
@@ -202,8 +253,8 @@ def default_optimizer():
 def engine_hyper_parameters(optimizer) -> Dict[str, object]:
     """an optimizer (train.py:67-78, 82-83) as the engines' hyper-parameter attributes / constructor arguments; a WarmUp or a constant
     gives base_lr and warm_up, an InverseTimeDecay gives lr_schedule, any other learning rate gives neither; SGD / RMSprop give
-    optimizer_kind with their own hyper-parameters; use_ema / ema_momentum and clip_mode / clip are there only when the optimizer
-    averages / clips (for the default optimizer the dictionary is what it always was)"""
+    optimizer_kind with their own hyper-parameters; use_ema / ema_momentum, clip_mode / clip and grad_transform are there only when the
+    optimizer averages / clips / transforms (for the default optimizer the dictionary is what it always was)"""
     inner = getattr(optimizer, "inner", optimizer)
     if isinstance(inner, SGD):
         kw = dict(optimizer_kind="sgd", momentum=float(inner.momentum), nesterov=bool(inner.nesterov))
@@ -223,6 +274,9 @@ def engine_hyper_parameters(optimizer) -> Dict[str, object]:
     mode, clip = clipping_mode(*(getattr(inner, k, None) for k in CLIP_ARGUMENTS))
     if mode != CLIP_NONE:
         kw.update(clip_mode=mode, clip=clip)
+    transform = gradient_transform_name(getattr(inner, "gradient_transformers", None))
+    if transform != "none":
+        kw.update(grad_transform=transform)
     return kw
 
 
@@ -605,19 +659,25 @@ class Trainer(Layer):
             kw = engine_hyper_parameters(opt)
             _supported_learning_rate(kw)
             kw["loss_scaling"] = bool(getattr(opt, "inner", opt).loss_scaling)
+        l2 = regularizer_l2(regularizer)                 # anything but None / regularizers.l2: NotImplementedError, before anything is built
         clipped = kw.pop("clip_mode", None) is not None
         kw.pop("clip", None)
+        transform = kw.pop("grad_transform", None)
         kind = {k: kw.pop(k) for k in ("optimizer_kind", "lr_schedule") + OPTIMIZER_ARGUMENTS if k in kw}
         eng = self.denoiser.ensure_engine(**kw)
         if clipped:                                      # (a fresh engine: clipping is a setting, not a constructor argument)
             eng.set_clipping(**clipping_arguments(opt))
         if kind:                                         # (... and so are the optimizer kind and a schedule other than WarmUp)
             apply_optimizer_kind(eng, kind)
+        if transform is not None:                        # (... and the gradient transformer)
+            eng.set_gradient_transform(transform)
         # train.py:238-252 reads the objective globals every time Trainer.call runs: an engine built earlier (by denoiser(...),
         # trainable_variables, the log_sample callback) follows the switches as they stand now
         for k, v in objective_switches().items():
             setattr(eng, k, v)
         eng.training_loss = loss_kind                    # (... and the `return` of train.py:265-280 that is live now)
+        if trainer_math.l2_coefficients(l2)[0] != getattr(eng, "l2", 0.0):     # (... and the regularizer of train.py:80)
+            eng.set_regularizer(l2)
         return eng
 
     def call(self, x):
@@ -644,10 +704,12 @@ class Trainer(Layer):
             hp = engine_hyper_parameters(optimizer)
             apply_optimizer_kind(eng, hp)                 # (first: a refused change of kind leaves the engine as it was)
             for k, v in hp.items():
-                if k not in ("use_ema", "ema_momentum", "clip_mode", "clip", "optimizer_kind", "lr_schedule") + OPTIMIZER_ARGUMENTS:
+                if k not in ("use_ema", "ema_momentum", "clip_mode", "clip", "grad_transform", "optimizer_kind", "lr_schedule") + OPTIMIZER_ARGUMENTS:
                     setattr(eng, k, v)
             if "clip_mode" in hp or getattr(eng, "clip_mode", CLIP_NONE) != CLIP_NONE:
                 eng.set_clipping(**clipping_arguments(optimizer))      # (an optimizer without clipping switches it off)
+            if hp.get("grad_transform", "none") != getattr(eng, "grad_transform", "none"):
+                eng.set_gradient_transform(hp.get("grad_transform", "none"))      # (... and one without a transformer, that)
             if hp.get("use_ema"):                         # the averages start from the parameters as they stand now
                 eng.enable_ema(hp["ema_momentum"])
             elif getattr(eng, "use_ema", False):

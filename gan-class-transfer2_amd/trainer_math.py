@@ -137,6 +137,37 @@ def inverse_time_decay_schedule(initial: float, decay_steps: float, decay_rate: 
     return ("inverse_time_decay", float(initial), float(decay_steps), float(decay_rate), bool(staircase))
 
 
+# Keras' gradient_transformers as the engines know them: none, or train.py:47-48's sign_gradient (gct2_optimizer_apply_reg transform)
+GRADIENT_TRANSFORMS = {"none": _lib.GRAD_NONE, "sign": _lib.GRAD_SIGN}
+
+
+def l2_coefficients(l2) -> Tuple[float, float]:
+    """tf.keras.regularizers.l2(l2) [TF] as (l2 held as float32, c = (float)(2.0 * (double)(float)l2)): the factor of the reported
+    penalty l2 * sum(w^2) and the factor of its gradient 2 l2 w (gct2_optimizer_apply_reg's l2_coeff).  None is (0.0, 0.0), off;
+    negative or not finite in float32 is a ValueError"""
+    if l2 is None:
+        return 0.0, 0.0
+    with np.errstate(all="ignore"):
+        held = float(np.float32(float(l2)))
+        c = float(np.float32(2.0 * held))
+    if not (float(l2) >= 0.0 and math.isfinite(held) and math.isfinite(c)):
+        raise ValueError(f"the l2 regularization factor must be a finite float32 >= 0, got {l2!r}")
+    return held, c
+
+
+def coefficient_runs(segs, coeffs, total: int):
+    """[(begin, end, coefficient)]: the maximal runs of neighbouring tensors with the same coefficient, together covering [0, total) -
+    a run starts at its first tensor (the first run at 0) and ends where the next begins, alignment padding included"""
+    runs = []
+    for (begin, _), c in zip(segs, coeffs):
+        if not runs:
+            runs.append([0, total, c])
+        elif runs[-1][2] != c:
+            runs[-1][1] = begin
+            runs.append([begin, total, c])
+    return [tuple(r) for r in runs]
+
+
 OBJECTIVE_SWITCHES = ("predict_x", "predict_scaled_epsilon", "prediction_weighting", "ordinary_differential_equation")
 
 # the four ways Trainer.call turns target - prediction into the scalar Keras minimises (train.py:254-280: the author moves a `return`)
@@ -183,6 +214,14 @@ class TrainerState:
     # is gct2_mse_fwd_bwd (or the fused heads) as ever; the other kinds go through gct2_loss_fwd_bwd, whose scratch (and the DCT basis)
     # an engine allocates on first use of such a kind (_loss_resources)
     training_loss = "mse"
+    # the L2 weight regularizer (train.py:80, tf.keras.regularizers.l2 as kernel_regularizer and bias_regularizer [TF]) and the
+    # optimizer's gradient transformer (train.py:47-48, 71-74: sign_gradient): off by default, set_regularizer() /
+    # set_gradient_transform() write them.  `l2` is the factor as the float32 Keras holds.  With either on, the step takes the
+    # non-fused optimizer path through gct2_optimizer_apply_reg; the penalty's reduction, its two output scalars and the per-tensor
+    # coefficient tables exist only after the first regularized step
+    l2, grad_transform = 0.0, "none"
+    _l2_state = None
+    _reg_tables = None
 
     @property
     def _ema(self) -> Optional[torch.Tensor]:
@@ -384,16 +423,19 @@ class TrainerState:
         """(device segment table, nseg, npartials, partials, sumsq, [(begin, count)]) of gct2_grad_sumsq: laid out by
         gct2_sumsq_layout, uploaded and allocated on first use, kept for the engine's lifetime (step plans hold the addresses)"""
         if self._clip_table is None:
-            segs = [(int(b), int(c)) for b, c in self._clip_segments()]
-            n = len(segs)
-            begin, count = (C.c_uint64 * n)(*[b for b, _ in segs]), (C.c_uint64 * n)(*[c for _, c in segs])
-            out, npartials = (C.c_uint64 * (3 * n))(), C.c_size_t(0)
-            _lib.check(_lib.load().gct2_sumsq_layout(begin, count, n, out, C.byref(npartials)), "gct2_sumsq_layout")
-            dev = self._clip_device()
-            table = torch.tensor(list(out), dtype=torch.int64).to(dev)          # gct2_sumsq_seg[n]: three 64-bit words each
-            self._clip_table = (table, n, int(npartials.value), torch.zeros(npartials.value, dtype=torch.float64, device=dev),
-                                torch.zeros(n + 1, dtype=torch.float64, device=dev), segs)
+            self._clip_table = self._sumsq_tables(self._clip_segments())
         return self._clip_table
+
+    def _sumsq_tables(self, segments):
+        segs = [(int(b), int(c)) for b, c in segments]
+        n = len(segs)
+        begin, count = (C.c_uint64 * n)(*[b for b, _ in segs]), (C.c_uint64 * n)(*[c for _, c in segs])
+        out, npartials = (C.c_uint64 * (3 * n))(), C.c_size_t(0)
+        _lib.check(_lib.load().gct2_sumsq_layout(begin, count, n, out, C.byref(npartials)), "gct2_sumsq_layout")
+        dev = self._clip_device()
+        table = torch.tensor(list(out), dtype=torch.int64).to(dev)          # gct2_sumsq_seg[n]: three 64-bit words each
+        return (table, n, int(npartials.value), torch.zeros(npartials.value, dtype=torch.float64, device=dev),
+                torch.zeros(n + 1, dtype=torch.float64, device=dev), segs)
 
     def _adam_clipped(self, p: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tensor, shadow: Optional[torch.Tensor], lo: int, hi: int,
                       grad_mul: float, stream: int) -> None:
@@ -446,6 +488,119 @@ class TrainerState:
         else:
             for s, (begin, n) in enumerate(segs):
                 launch(begin, n, sumsq.data_ptr() + 8 * s)
+
+    # ---- L2 weight regularizer and gradient transformer (train.py:47-48, 71-74, 80) [TF] ------------------------------------------------
+    # what an engine provides besides the clipping hooks: _l2_segments() -> the (begin, count) of the tensors that carry the
+    # regularizer (default: every tensor; VariantEngine leaves Residual's bias-free projection out, train.py:107)
+    def set_regularizer(self, l2: Optional[float] = None) -> None:
+        """tf.keras.regularizers.l2(l2) on every kernel, bias and the Dense head [TF]: None or 0 switches it off, a negative or
+        non-finite factor is a ValueError.  A setting like set_clipping: it holds from the next step on and is not part of a
+        checkpoint.  Optimizer launches the engine holds back are flushed first: they belong to a step made with the old setting."""
+        held, _ = l2_coefficients(l2)
+        why = getattr(self, "_reg_forbidden", None)
+        if why and held > 0.0:
+            raise ValueError(why)
+        self.flush_deferred()
+        self.l2 = held
+
+    def set_gradient_transform(self, name: str = "none") -> None:
+        """the optimizer's gradient_transformers: "none", or "sign" (train.py:47-48), applied behind the clipping step as Keras'
+        _transform_gradients does [TF].  A setting like set_regularizer."""
+        if name not in GRADIENT_TRANSFORMS:
+            raise ValueError(f"unknown gradient transform {name!r} (one of {', '.join(GRADIENT_TRANSFORMS)})")
+        why = getattr(self, "_reg_forbidden", None)
+        if why and name != "none":
+            raise ValueError(why)
+        self.flush_deferred()
+        self.grad_transform = name
+
+    def _regularized(self) -> bool:
+        """the step's optimizer launches are gct2_optimizer_apply_reg's (and the step is not fused)"""
+        return self.l2 > 0.0 or self.grad_transform != "none"
+
+    def _l2_segments(self):
+        return self._clip_segments()
+
+    @property
+    def regularization_loss(self) -> Optional[torch.Tensor]:
+        """the penalty l2 * sum(w^2) of the last regularized train step, fp32 [1] on the device (None while the regularizer is off)"""
+        return self._l2_state[1] if self.l2 > 0.0 and self._l2_state is not None else None
+
+    def _reg_table(self, total: int):
+        """(segments, per-tensor coefficients, runs, device copy of the coefficients) for the current l2: built on first use and kept
+        for the engine's lifetime (step plans hold the device address)"""
+        _, c = l2_coefficients(self.l2)
+        if self._reg_tables is None:
+            self._reg_tables = {}
+        if c not in self._reg_tables:
+            segs = [(int(b), int(n)) for b, n in self._clip_segments()]
+            carry = {(int(b), int(n)) for b, n in self._l2_segments()} if c > 0.0 else set()
+            assert carry <= set(segs), "_l2_segments() must name tensors of _clip_segments()"
+            coeffs = [c if seg in carry else 0.0 for seg in segs]
+            self._reg_tables[c] = (segs, coeffs, coefficient_runs(segs, coeffs, total),
+                                   torch.tensor(coeffs, dtype=torch.float32).to(self._clip_device()))
+        return self._reg_tables[c]
+
+    def _reg_launches(self, p: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tensor, shadow: Optional[torch.Tensor], lo: int,
+                      hi: int, grad_mul: float, stream: int) -> None:
+        """_adam_clipped / _optimizer_launches of a step with a regularizer or a transformer, for every kind: the same sequence through
+        gct2_optimizer_apply_reg - the reduction first for the two norm modes (gct2_grad_sumsq_l2 over the regularized gradient as soon
+        as a coefficient is non-zero), then the update once per run of neighbouring tensors with the same coefficient inside [lo, hi)
+        (ONE launch where every tensor carries the regularizer) or, for clipnorm, once per tensor"""
+        ls_ptr = self._ls_ptr()
+        lr = 0.0 if self.ls_state is not None else self.step_size()
+        kind = OPTIMIZER_KINDS[self.optimizer_kind]
+        adam = kind == _lib.OPT_ADAM
+        use_m, use_v = adam or float(self.momentum) > 0.0, kind != _lib.OPT_SGD
+        first, second = (self.beta_1, self.beta_2) if adam else (self.momentum, self.rho)      # (Adam's betas ride in these positions)
+        transform = GRADIENT_TRANSFORMS[self.grad_transform]
+        segs, coeffs, runs, dev_coeffs = self._reg_table(p.numel())
+
+        def launch(lo: int, n: int, sumsq_ptr: Optional[int], coeff: float) -> None:
+            call("gct2_optimizer_apply_reg", kind, p.data_ptr() + 4 * lo, m.data_ptr() + 4 * lo if use_m else None,
+                 v.data_ptr() + 4 * lo if use_v else None, g.data_ptr() + 4 * lo, None if shadow is None else shadow.data_ptr() + 2 * lo,
+                 self.dtype, n, Slot("alpha", lr), float(first), int(bool(self.nesterov)), float(second), float(self.epsilon),
+                 grad_mul, ls_ptr, self.clip_mode, float(self.clip), sumsq_ptr, coeff, transform, stream)
+
+        total_ptr = None
+        if self._clip_by_norm():
+            table, nseg, npartials, partials, sumsq, _ = self._clip_reduction()
+            if any(coeffs):
+                call("gct2_grad_sumsq_l2", g.data_ptr(), p.data_ptr(), table.data_ptr(), dev_coeffs.data_ptr(), nseg, npartials, grad_mul,
+                     ls_ptr, partials.data_ptr(), sumsq.data_ptr(), stream)
+            else:
+                call("gct2_grad_sumsq", g.data_ptr(), table.data_ptr(), nseg, npartials, grad_mul, ls_ptr, partials.data_ptr(),
+                     sumsq.data_ptr(), stream)
+            if self.clip_mode == _lib.CLIP_NORM:
+                for s, ((begin, n), coeff) in enumerate(zip(segs, coeffs)):
+                    launch(begin, n, sumsq.data_ptr() + 8 * s, coeff)
+                return
+            total_ptr = sumsq.data_ptr() + 8 * nseg
+        for begin, end, coeff in runs:
+            begin, end = max(begin, lo), min(end, hi)
+            if end > begin:
+                launch(begin, end - begin, total_ptr, coeff)
+
+    def _fp32_parameters(self) -> torch.Tensor:
+        """the raw fp32 parameter arena, laid out like the gradient arena (what the engines also hand to the averages: _ema_source)"""
+        return self._ema_source()[0]
+
+    def _penalty_begin(self, stream: int) -> None:
+        """head of a regularized step: S = the fp64 sum of squares of the regularized tensors as the forward pass is about to read them
+        (gct2_grad_sumsq pointed at the fp32 parameter arena, over a segment table, partials and sums of its own)"""
+        if self._l2_state is None:
+            dev = self._clip_device()
+            self._l2_state = (self._sumsq_tables(self._l2_segments()), torch.zeros(1, dtype=torch.float32, device=dev),
+                              torch.zeros(1, dtype=torch.float32, device=dev))
+        (table, nseg, npartials, partials, sumsq, _), _, _ = self._l2_state
+        p = self._fp32_parameters()
+        call("gct2_grad_sumsq", p.data_ptr(), table.data_ptr(), nseg, npartials, 1.0, None, partials.data_ptr(), sumsq.data_ptr(), stream)
+
+    def _penalty_finish(self, loss: torch.Tensor, stream: int) -> torch.Tensor:
+        """behind the loss: what Keras' train_step reports, loss + l2 * S (gct2_l2_penalty); the data term stays where it is"""
+        (_, nseg, _, _, sumsq, _), penalty, total = self._l2_state
+        call("gct2_l2_penalty", loss.data_ptr(), sumsq.data_ptr() + 8 * nseg, float(self.l2), penalty.data_ptr(), total.data_ptr(), stream)
+        return total
 
     # ---- exponential moving average of the parameters (tf.keras.optimizers.Adam(use_ema=True, ema_momentum=...)) [TF] -----------
     # what an engine provides: _ema_source() -> (fp32 parameter arena, compute-dtype copy or None), raw storage;

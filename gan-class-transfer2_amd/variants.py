@@ -35,6 +35,7 @@ class _Net:
         self.offsets: Dict[str, int] = {}
         self.total = 0
         self.ctx = ctx
+        self.unregularized: set = set()      # tensors built without kernel_regularizer (Residual's projection, train.py:107)
 
     def declare(self, name: str, shape: Tuple[int, ...]) -> str:
         self.specs.append((name, shape))
@@ -123,6 +124,7 @@ class _Proj:
     def __init__(self, net: _Net, name: str, cin: int, cout: int):
         self.net, self.cin, self.cout = net, cin, cout
         self.w = net.declare(name + ".w", (cin, cout))
+        net.unregularized.add(self.w)        # train.py:107: Dense(input_shape[-1], use_bias=False), no regularizer
 
     def fwd(self, x):
         n, (B, H, W, C) = self.net, x.shape
@@ -315,6 +317,10 @@ class VariantEngine(TrainerState):
     def _clip_device(self):
         return self.net.g.device
 
+    def _l2_segments(self):
+        """every kernel, bias and the head carry the regularizer; Residual's bias-free projection is built without one (train.py:107)"""
+        return sorted((self.net.offsets[name], int(np.prod(shp))) for name, shp in self.net.specs if name not in self.net.unregularized)
+
     # ---- parameters ---------------------------------------------------------------------------------------------------------
     @property
     def shapes(self) -> Dict[str, Tuple[int, ...]]:
@@ -390,6 +396,9 @@ class VariantEngine(TrainerState):
         s = self.net.stream()
         n = B * H * W * 3
         self.begin_step()
+        regularized = backward and self.l2 > 0.0               # (Trainer.call reports the data term, as calling the Keras model does)
+        if regularized:
+            self._penalty_begin(s)
         noised, t_int, eps = self._noised(x, t_int, eps)
         pred = self.top.fwd(noised)
         target, w = self._objective(x, t_int, eps)
@@ -405,17 +414,20 @@ class VariantEngine(TrainerState):
         self.last.update(pred=pred, noised=noised)
         if not backward:
             return self.loss
+        loss = self._penalty_finish(self.loss, s) if regularized else self.loss
         self.top.bwd(dpred)
         if apply:
             self.apply_adam()
-        return self.loss
+        return loss
 
     def apply_adam(self) -> None:
         N, s = self.net, self.net.stream()
-        if self.clip_mode != _lib.CLIP_NONE or self.optimizer_kind != "adam":
+        if self.clip_mode != _lib.CLIP_NONE or self.optimizer_kind != "adam" or self._regularized():
             if not self._clip_by_norm():                       # (a norm-clipped step: gct2_grad_sumsq sets found_inf in its one pass)
                 self._check_finite(N.g.data_ptr(), N.g.numel(), s)
             launches = self._adam_clipped if self.optimizer_kind == "adam" else self._optimizer_launches       # (SGD / RMSprop, clipped or not)
+            if self._regularized():                             # (an L2 regularizer or a gradient transformer: every kind, one entry point)
+                launches = self._reg_launches
             launches(N.p, N.m, N.v, N.g, N.op if self.dtype != F32 else None, 0, N.p.numel(), 1.0, s)
             self.finish_step()
             return

@@ -37,7 +37,7 @@ enum {
 };
 
 /* library / device identification ------------------------------------------------------------ */
-int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive); v17 + gct2_sumsq_layout, gct2_grad_sumsq, gct2_adam_keras_clipped (additive); v17 + gct2_optimizer_apply, gct2_loss_scale_begin_schedule (additive); v17 + gct2_loss_scratch, gct2_loss_fwd_bwd (additive)) */
+int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive); v17 + gct2_sumsq_layout, gct2_grad_sumsq, gct2_adam_keras_clipped (additive); v17 + gct2_optimizer_apply, gct2_loss_scale_begin_schedule (additive); v17 + gct2_loss_scratch, gct2_loss_fwd_bwd (additive); v17 + gct2_optimizer_apply_reg, gct2_grad_sumsq_l2, gct2_l2_penalty (additive)) */
 /* how the library was built: 0 for the product build; bit 0 (GCT2_BUILD_STAMP) = diagnostic build with in-kernel phase stamps
  * (make EXTRA=-DGCT2_STAMP).  Product hosts (the Python binding, bench.py, the tests) refuse a library whose flags are not 0. */
 enum { GCT2_BUILD_STAMP = 1 };
@@ -500,6 +500,50 @@ int gct2_adam_keras_clipped(float* p, float* m, float* v, float* g, void* shadow
 int gct2_optimizer_apply(int kind, float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n,
                          float lr, float momentum, int nesterov, float rho, float epsilon, float grad_mul,
                          const gct2_loss_scale_state* ls, int clip_mode, float clip, const double* sumsq, void* stream);
+
+/* ---- L2 weight regularizer and gradient transformer [TF] (train.py:47-48, 71-74, 80: SGD(..., gradient_transformers=[sign_gradient])
+ * and regularizer = tf.keras.regularizers.l2(1e-6), both commented out there) -------------------------------------------------------
+ * Both sit between the raw gradient and the kind's update, where the clipping step sits.  All fp32, every operation rounded once, no
+ * contraction; g' = fl(g * fl((ls ? ls->inv_scale : 1) * grad_mul)) as everywhere:
+ *   1. penalty gradient (Keras adds l2 * sum(w^2) to the loss, so autodiff adds 2 l2 w):  c = (float)(2.0 * (double)(float)l2) formed by
+ *      the host,  g_r = fl(g' + fl(c * p))  with p the parameter BEFORE this step's update.  c == 0: the add is skipped, not computed -
+ *      the bits are those of the unregularized kernels, the sign of a zero and a non-finite p included.
+ *   2. clipping of g_r exactly as gct2_adam_keras_clipped clips g' (for the norm modes *sumsq is the sum of squares of g_r:
+ *      gct2_grad_sumsq_l2).
+ *   3. transformer (Keras' _transform_gradients clips first, then runs gradient_transformers [TF]):
+ *      GCT2_GRAD_SIGN: x > 0 ? 1 : x < 0 ? -1 : x == 0 ? +0.0f : x   (tf.sign: a NaN stays NaN, -0.0 gives +0.0)
+ *   4. the kind's update, unchanged: GCT2_OPT_ADAM as gct2_adam_keras_clipped (lr = alpha, momentum = beta1, rho = beta2, epsilon;
+ *      nesterov ignored; both slots in use), GCT2_OPT_SGD / GCT2_OPT_RMSPROP as gct2_optimizer_apply.
+ * Geometry, streaming accesses, shadow write, ls skip (found_inf comes from the raw g alone: nothing here sets it) and ls->alpha as
+ * gct2_optimizer_apply; a slot a kind does not use is neither read nor written and may be NULL.  The gradient arena is never written:
+ * it keeps holding the data-term gradient.  PARITY UNPINNED w.r.t. TensorFlow.
+ * GCT2_EINVAL before any launch: the checks of gct2_optimizer_apply (kind may also be GCT2_OPT_ADAM, then m and v are required and
+ * momentum / rho are the unchecked betas), unknown transform, l2_coeff not finite or < 0. */
+#define GCT2_GRAD_NONE 0
+#define GCT2_GRAD_SIGN 1
+int gct2_optimizer_apply_reg(int kind, float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n,
+                             float lr, float momentum, int nesterov, float rho, float epsilon, float grad_mul,
+                             const gct2_loss_scale_state* ls, int clip_mode, float clip, const double* sumsq,
+                             float l2_coeff, int transform, void* stream);
+
+/* gct2_grad_sumsq over the regularized gradient: the element squared and summed in segment s is
+ *   x = fl(fl(g * k) + fl(seg_coeff[s] * p)),   k as for gct2_grad_sumsq,
+ * the g_r of gct2_optimizer_apply_reg with l2_coeff = seg_coeff[s].  seg_coeff: device float[nseg], 4-byte aligned; an entry of 0 skips
+ * the add (and the read of p) for that segment - such a segment's sum is gct2_grad_sumsq's, which is how tensors without a regularizer
+ * (Residual's bias-free projection, train.py:107) are kept out.  p: fp32, 16-byte aligned, laid out like g (segs index both).  The same
+ * two stages, the same fixed fp64 order, no floating-point atomics, nothing outside a segment is read in g or p;
+ * ls->found_inf |= any(!isfinite(RAW g)) - a large or non-finite p does not set it.
+ * GCT2_EINVAL before any launch: as gct2_grad_sumsq, plus NULL or misaligned p / seg_coeff. */
+int gct2_grad_sumsq_l2(const float* g, const float* p, const gct2_sumsq_seg* segs, const float* seg_coeff, int nseg, size_t npartials,
+                       float grad_mul, gct2_loss_scale_state* ls, double* partials, double* sumsq, void* stream);
+
+/* what Keras' train_step reports with a regularizer, loss + sum of the regularization losses:
+ *   *penalty_out = (float)((double)l2 * *S),   *total_out = (float)((double)*loss + (double)l2 * *S)
+ * S: ONE fp64 value on the device, the sum of (double)p^2 over the regularized tensors - gct2_grad_sumsq pointed at the parameter arena
+ * with grad_mul = 1 and ls = NULL leaves it in sumsq[nseg].  l2: the regularizer's float32 coefficient (not doubled).  loss: fp32 [1],
+ * read only; penalty_out, total_out: fp32 [1] each.  One thread; the product and the sum in fp64, each result rounded once to fp32.
+ * GCT2_EINVAL before any launch: a NULL or misaligned pointer (S 8-byte, the others 4-byte), l2 not finite or < 0. */
+int gct2_l2_penalty(const float* loss, const double* S, float l2, float* penalty_out, float* total_out, void* stream);
 
 /* gct2_loss_scale_begin for any schedule and optimizer: found_inf = 0 and state->alpha = the step size of THIS step at
  * k = state->applied_steps, in float32 and in Keras' order:

@@ -1,0 +1,511 @@
+"""CPU tier of the L2 weight regularizer and the sign transformer (train.py:47-48, 71-74, 80): the restatement of tests/reg_cases.py
+against torch autograd and by hand, the public names and their argument checks, the translation into the engines' settings, the
+host-side state (TrainerState) and its call lists, the binding of the three new C entry points and every rejection they make before
+a launch - none of which needs a device.
+
+The rejection rows run in a fresh child process (this file as a script) whose environment hides the GPUs, as
+tests/test_capi_contract_cpu.py runs its table: the pointers are fake addresses, and a row that slipped through its checks must find
+no device to launch on."""
+import ctypes
+import importlib.util
+import json
+import os
+import subprocess
+import sys
+import types
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+P = 4096                    # a fake, 16-byte aligned device address: every launching call below is rejected before anything reads it
+S = P + 65536               # ... and an 8-byte aligned one for sumsq
+EINVAL, ENODEV = 1, 3
+F32, BF16 = 0, 1
+INF, NAN = float("inf"), float("nan")
+
+
+# ---- the rejection table (child process) ------------------------------------------------------------------------------------------
+def _reg(**o):
+    a = dict(kind=2, p=P, m=P + 4096, v=P + 8192, g=P + 12288, shadow=None, dtype=F32, n=1024, lr=1e-3, momentum=0.9, nesterov=0, rho=0.9,
+             eps=1e-7, grad_mul=1.0, ls=None, mode=0, clip=0.0, sumsq=None, l2_coeff=2e-6, transform=0, stream=None)
+    assert not set(o) - set(a)
+    a.update(o)
+    return ["gct2_optimizer_apply_reg", list(a.values())]
+
+
+def _sumsq(**o):
+    a = dict(g=P, p=P + 4096, segs=S, seg_coeff=S + 4096, nseg=4, npartials=4, grad_mul=1.0, ls=None, partials=S + 8192, sumsq=S + 12288, stream=None)
+    assert not set(o) - set(a)
+    a.update(o)
+    return ["gct2_grad_sumsq_l2", list(a.values())]
+
+
+def _pen(**o):
+    a = dict(loss=P, S=S, l2=1e-6, penalty=P + 4, total=P + 8, stream=None)
+    assert not set(o) - set(a)
+    a.update(o)
+    return ["gct2_l2_penalty", list(a.values())]
+
+
+CASES = [
+    # ---- gct2_optimizer_apply_reg: the checks of gct2_optimizer_apply (Adam is a kind here) ...
+    (_reg(kind=3), "optimizer_apply_reg: unknown kind 3"),
+    (_reg(kind=-1), "optimizer_apply_reg: unknown kind -1"),
+    (_reg(momentum=-0.5), "momentum -0.5 outside [0, 1]"),
+    (_reg(momentum=1.5), "momentum 1.5 outside [0, 1]"),
+    (_reg(momentum=NAN), "outside [0, 1]"),
+    (_reg(rho=1.5), "rho 1.5 outside [0, 1]"),
+    (_reg(eps=-1.0), "epsilon -1 < 0"),
+    (_reg(p=None), "null pointer"),
+    (_reg(g=None), "null pointer"),
+    (_reg(m=None), "null pointer"),                                  # RMSprop with momentum uses both slots
+    (_reg(v=None), "null pointer"),
+    (_reg(kind=1, m=None), "null pointer"),                          # SGD with momentum uses m
+    (_reg(kind=0, m=None), "null pointer"),                          # Adam uses both, whatever beta_1 is
+    (_reg(kind=0, momentum=0.0, m=None), "null pointer"),
+    (_reg(kind=0, v=None), "null pointer"),
+    (_reg(n=0), "n == 0"),
+    (_reg(p=P + 8), "16-byte aligned"),
+    (_reg(g=P + 12288 + 4), "16-byte aligned"),
+    (_reg(m=P + 4096 + 4), "16-byte aligned"),
+    (_reg(kind=0, v=P + 8192 + 8), "16-byte aligned"),
+    (_reg(shadow=P + 16384 + 4, dtype=BF16), "8-byte aligned"),
+    (_reg(mode=3, clip=1.0, sumsq=S + 4), "8-byte aligned"),
+    (_reg(shadow=P + 16384, dtype=F32), "16-bit dtype"),
+    (_reg(mode=4, clip=1.0), "unknown clip_mode 4"),
+    (_reg(mode=1, clip=0.0), "must be finite and > 0"),
+    (_reg(mode=2, clip=INF, sumsq=S), "must be finite and > 0"),
+    (_reg(mode=2, clip=1.0), "clip_mode 2 needs sumsq"),
+    (_reg(mode=3, clip=1.0), "clip_mode 3 needs sumsq"),
+    # ... plus its own
+    (_reg(transform=2), "unknown transform 2"),
+    (_reg(transform=-1), "unknown transform -1"),
+    (_reg(l2_coeff=-1e-6), "l2_coeff = -1e-06 must be finite and >= 0"),
+    (_reg(l2_coeff=INF), "must be finite and >= 0"),
+    (_reg(l2_coeff=NAN), "must be finite and >= 0"),
+    (_reg(kind=7, transform=9), "unknown kind 7"),                   # two mistakes: the earlier check names the call
+    (_reg(transform=9, l2_coeff=-1.0), "unknown transform 9"),
+    # ---- gct2_grad_sumsq_l2
+    (_sumsq(g=None), "grad_sumsq_l2: null pointer"),
+    (_sumsq(p=None), "grad_sumsq_l2: null pointer"),
+    (_sumsq(segs=None), "grad_sumsq_l2: null pointer"),
+    (_sumsq(seg_coeff=None), "grad_sumsq_l2: null pointer"),
+    (_sumsq(partials=None), "grad_sumsq_l2: null pointer"),
+    (_sumsq(sumsq=None), "grad_sumsq_l2: null pointer"),
+    (_sumsq(nseg=0), "nseg = 0 outside [1, 1024]"),
+    (_sumsq(nseg=1025, npartials=1025), "nseg = 1025 outside [1, 1024]"),
+    (_sumsq(npartials=0), "npartials = 0 is not what gct2_sumsq_layout reports"),
+    (_sumsq(npartials=3), "npartials = 3 is not what gct2_sumsq_layout reports"),
+    (_sumsq(g=P + 4), "g and p must be 16-byte aligned"),
+    (_sumsq(p=P + 4096 + 8), "g and p must be 16-byte aligned"),
+    (_sumsq(sumsq=S + 12288 + 4), "16-byte aligned"),
+    (_sumsq(seg_coeff=S + 4096 + 2), "seg_coeff 4-byte aligned"),
+    # ---- gct2_l2_penalty
+    (_pen(loss=None), "l2_penalty: null pointer"),
+    (_pen(S=None), "l2_penalty: null pointer"),
+    (_pen(penalty=None), "l2_penalty: null pointer"),
+    (_pen(total=None), "l2_penalty: null pointer"),
+    (_pen(S=S + 4), "S must be 8-byte aligned"),
+    (_pen(loss=P + 2), "4-byte aligned"),
+    (_pen(l2=-1e-6), "l2 = -1e-06 must be finite and >= 0"),
+    (_pen(l2=INF), "must be finite and >= 0"),
+    (_pen(l2=NAN), "must be finite and >= 0"),
+]
+
+
+def _child():
+    """runs CASES against the library and prints one JSON line: {"device": code of gct2_device_check, "results": [[code, text], ...]}"""
+    spec = importlib.util.spec_from_file_location("gct2_lib", os.path.join(ROOT, "gan-class-transfer2_amd", "_lib.py"))
+    L = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(L)
+    lib = L.load()
+    out = {"device": lib.gct2_device_check(), "results": []}
+    if out["device"] == ENODEV:
+        for (fn, args), _text in CASES:
+            code = getattr(lib, fn)(*args)
+            out["results"].append([code, lib.gct2_last_error().decode()])
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    _child()
+    sys.exit(0)
+
+import pytest                                               # noqa: E402  (the child above needs neither pytest nor the package)
+import torch                                                # noqa: E402
+
+import clip_cases as K                                      # noqa: E402
+import reg_cases as RC                                      # noqa: E402
+import gan_class_transfer2_amd as g                         # noqa: E402
+from gan_class_transfer2_amd import trainer_math as TM      # noqa: E402
+
+
+def test_the_three_entry_points_reject_bad_arguments_without_a_device():
+    env = dict(os.environ)
+    env.update(HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    r = subprocess.run([sys.executable, os.path.abspath(__file__)], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 0, r.stderr[-4000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    if out["device"] != ENODEV:
+        pytest.skip(f"a device is visible to the child process (gct2_device_check() = {out['device']}): fake pointers are not sent to it")
+    assert len(out["results"]) == len(CASES) >= 55
+    prefix = {"gct2_optimizer_apply_reg": "optimizer_apply_reg: ", "gct2_grad_sumsq_l2": "grad_sumsq_l2: ", "gct2_l2_penalty": "l2_penalty: "}
+    wrong = [(i, fn, text, got) for i, (((fn, _a), text), got) in enumerate(zip(CASES, out["results"]))
+             if got[0] != EINVAL or not got[1].startswith(prefix[fn]) or text not in got[1]]
+    assert not wrong, wrong
+
+
+# ---- the restatement ----------------------------------------------------------------------------------------------------------------
+def test_coefficient_is_exact_for_the_reference_factor():
+    c = RC.coefficient(1e-6)
+    assert c.dtype == np.float32
+    held = np.float32(1e-6)
+    assert c == np.float32(2.0 * float(held)) and float(c) == 2.0 * float(held)        # doubling a float32 is exact
+    assert c.view(np.int32) == held.view(np.int32) + (1 << 23)                        # the same mantissa, the exponent one up
+    assert TM.l2_coefficients(1e-6) == (float(held), float(c)) and TM.l2_coefficients(None) == (0.0, 0.0) == TM.l2_coefficients(0)
+    assert float(RC.coefficient(0.125)) == 0.25
+    for bad in (-1e-6, INF, NAN, 3e38):                                  # (3e38 is finite, its double is not)
+        with pytest.raises(ValueError, match="l2 regularization factor"):
+            TM.l2_coefficients(bad)
+
+
+def test_penalty_gradient_equals_autograd_of_the_penalty():
+    """Keras adds l2 * sum(w^2) to the loss; its autograd gradient is 2 l2 w - in float32, torch forms (2 w) * l2 or w * (2 l2):
+    both are c * w exactly, because doubling is exact in binary floating point"""
+    rng = np.random.default_rng(3)
+    w = rng.standard_normal(4099).astype(np.float32)
+    gdata = rng.standard_normal(4099).astype(np.float32)
+    for l2 in (1e-6, 0.3, 0.125):
+        t = torch.tensor(w, requires_grad=True)
+        (torch.tensor(np.float32(l2)) * (t * t).sum()).backward()
+        c = RC.coefficient(l2)
+        assert np.array_equal(t.grad.numpy().view(np.int32), (c * w).view(np.int32)), l2
+        # ... and the regularized gradient is the data term plus that, one rounding each
+        t = torch.tensor(w, requires_grad=True)
+        ((torch.tensor(gdata) * t).sum() + torch.tensor(np.float32(l2)) * (t * t).sum()).backward()
+        assert np.array_equal(t.grad.numpy().view(np.int32), RC.regularized(gdata, w, c).view(np.int32)), l2
+    assert RC.regularized(gdata, w, 0.0) is not None and np.shares_memory(RC.regularized(gdata, w, 0.0), gdata)      # c == 0: nothing is added
+
+
+def test_a_zero_coefficient_skips_the_add_also_for_a_non_finite_parameter():
+    gp = np.array([1.0, -0.0, 0.0, 2.0], dtype=np.float32)
+    p = np.array([INF, 5.0, -INF, NAN], dtype=np.float32)
+    out = RC.regularized(gp, p, 0.0)
+    assert np.array_equal(out.view(np.int32), gp.view(np.int32))                       # 0 * inf would have been NaN
+    assert np.isnan(RC.regularized(gp, p, 1e-6)[[0, 2, 3]]).sum() == 1                 # (with the add: +-inf or NaN)
+
+
+def test_sign_semantics():
+    tiny = np.float32(1e-45)                                           # the smallest subnormal
+    x = np.array([0.0, -0.0, NAN, INF, -INF, tiny, -tiny, 3.5, -2e-38], dtype=np.float32)
+    got = RC.sign(x)
+    want = np.array([0.0, 0.0, NAN, 1.0, -1.0, 1.0, -1.0, 1.0, -1.0], dtype=np.float32)
+    assert got.dtype == np.float32 and np.isnan(got[2])
+    ok = ~np.isnan(want)
+    assert np.array_equal(got[ok].view(np.int32), want[ok].view(np.int32))             # -0 gives +0: the bits, not only the value
+    assert np.array_equal(got[ok], torch.sign(torch.tensor(x)).numpy()[ok])            # tf.sign / torch.sign agree on the values
+    # Keras' order: the transformer sees the CLIPPED gradient (a clipped value keeps its sign; a NaN stays NaN through both)
+    g2 = RC.gradient(np.array([3.0, -3.0, NAN, 0.25], np.float32), np.zeros(4, np.float32), 0.0, RC.GRAD_SIGN, K.CLIP_VALUE, 0.5)
+    assert np.array_equal(g2[[0, 1, 3]], [1.0, -1.0, 1.0]) and np.isnan(g2[2])
+
+
+def test_exact_cancellation_pins_the_sign_of_zero():
+    g0 = np.zeros(16, dtype=np.float32)
+    p0 = np.linspace(-2, 2, 16).astype(np.float32)
+    c = RC.coefficient(0.3)
+    at = RC.plant_zeros_and_cancellations(g0, p0, [(0, 16)], c, (0.5, 2.0 ** -8))
+    assert at == [3, 4]
+    for k, i in zip((0.5, 2.0 ** -8), at):
+        s = RC.regularized(K.scaled(g0, k), p0, c)
+        assert s[i] == 0 and not np.signbit(s[i])                      # x + (-x) = +0 in round-to-nearest
+    s = RC.regularized(K.scaled(g0, 0.5), p0, c)
+    assert (s[0] == 0 and not np.signbit(s[0])) and (s[1] == 0 and np.signbit(s[1])) and s[2] == c
+    assert not np.signbit(RC.sign(s)[1])                               # ... and the sign of -0 is +0
+
+
+def test_penalty_by_hand():
+    pen, total = RC.penalty(np.float32(0.5), np.float64(1e6), 1e-6)
+    assert pen.dtype == total.dtype == np.float32
+    assert pen == np.float32(float(np.float32(1e-6)) * 1e6) and total == np.float32(0.5 + float(np.float32(1e-6)) * 1e6)
+    # the sum is formed in float64: adding the ROUNDED penalty to the loss would differ here
+    loss, S, l2 = np.float32(1.0), np.float64(3.0), 2.0 ** -25
+    pen, total = RC.penalty(loss, S, l2)
+    assert total == np.float32(1.0 + 3.0 * 2.0 ** -25) and pen == np.float32(3.0 * 2.0 ** -25)
+    assert RC.penalty(np.float32(0.25), np.float64(123.0), 0.0) == (0.0, 0.25)
+
+
+def test_restatement_update_dispatch():
+    rng = np.random.default_rng(1)
+    p, m, v, gr = (rng.standard_normal(64).astype(np.float32) for _ in range(4))
+    v = np.abs(v)
+    hyper = dict(beta_1=0.9, beta_2=0.999, epsilon=1e-7)
+    a = RC.apply(RC.ADAM, p, m, v, gr, 1e-3, hyper, c=RC.coefficient(0.3))
+    b = K.adam(p, m, v, gr + RC.coefficient(0.3) * p, 1e-3, 0.9, 0.999, 1e-7)
+    assert all(np.array_equal(x, y) for x, y in zip(a, b))
+    a = RC.apply(RC.SGD, p, None, None, gr, 1e-4, {}, transform=RC.GRAD_SIGN)
+    assert np.array_equal(a[0], p - np.float32(1e-4) * np.sign(gr)) and a[1] is None and a[2] is None
+
+
+# ---- the public names ---------------------------------------------------------------------------------------------------------------
+def test_sign_gradient_on_pairs():
+    gs = [torch.tensor([3.0, -0.5, 0.0, -0.0]), torch.tensor([[-INF, 2.0]])]
+    vs = [object(), object()]
+    out = g.sign_gradient(list(zip(gs, vs)))
+    assert [v for _, v in out] == vs
+    assert torch.equal(out[0][0], torch.tensor([1.0, -1.0, 0.0, 0.0])) and torch.equal(out[1][0], torch.tensor([[-1.0, 1.0]]))
+    assert torch.equal(out[0][0], torch.tensor(RC.sign(gs[0].numpy())))               # the kernel's transformer, on the finite values
+    assert g.model.sign_gradient is g.sign_gradient
+
+
+def test_optimizer_keyword_handling():
+    for Opt in (g.Adam, g.SGD, g.RMSprop, lambda **kw: g.model.Optimizer(1e-3, **kw)):
+        assert Opt().gradient_transformers is None
+        assert Opt(gradient_transformers=[]).gradient_transformers == []
+        assert Opt(gradient_transformers=[g.sign_gradient]).gradient_transformers == [g.sign_gradient]
+        for bad in ([lambda pairs: pairs], [g.sign_gradient, g.sign_gradient], g.sign_gradient, [torch.sign], "sign"):
+            with pytest.raises(NotImplementedError, match="gradient_transformers"):
+                Opt(gradient_transformers=bad)
+    # the reference's line as written (train.py:71-74)
+    opt = g.SGD(0.0001, gradient_transformers=[g.sign_gradient])
+    assert (opt.learning_rate, opt.momentum, opt.nesterov) == (0.0001, 0.0, False)
+    assert g.LossScaleOptimizer(opt).gradient_transformers == [g.sign_gradient]
+    name = g.model.gradient_transform_name
+    assert (name(None), name([]), name(()), name([g.sign_gradient]), name((g.sign_gradient,))) == ("none", "none", "none", "sign", "sign")
+
+
+def test_regularizers_namespace():
+    r = g.regularizers.l2(1e-6)
+    assert r.l2 == 1e-6 and isinstance(r, g.regularizers.L2) and g.regularizers.l2().l2 == 0.01           # Keras' default factor
+    assert g.regularizers.l2(l2=0.5).l2 == 0.5
+    for bad in (-1.0, INF, NAN):
+        with pytest.raises(ValueError, match="l2 regularization factor"):
+            g.regularizers.l2(bad)
+    rl2 = g.model.regularizer_l2
+    assert rl2(None) is None and rl2(r) == 1e-6
+    for bad in (1e-6, "l2", lambda w: 0.0, types.SimpleNamespace(l2=1e-6), types.SimpleNamespace(l1=1e-6)):
+        with pytest.raises(NotImplementedError, match="regularizer"):
+            rl2(bad)
+    assert g.model.regularizer is None                                 # train.py:80 as committed
+
+
+def test_engine_hyper_parameters():
+    hp = g.model.engine_hyper_parameters
+    # the default optimizer's dictionary is the literal it always was; None and [] add nothing
+    assert hp(g.model.default_optimizer()) == dict(beta_1=0.9, beta_2=0.999, epsilon=1e-7, base_lr=2e-5, warm_up=g.model.warm_up)
+    assert hp(g.Adam(g.WarmUp(2e-5, 7), gradient_transformers=[])) == dict(beta_1=0.9, beta_2=0.999, epsilon=1e-7, base_lr=2e-5, warm_up=7)
+    assert hp(g.SGD(0.25, 0.5, True)) == dict(optimizer_kind="sgd", momentum=0.5, nesterov=True, base_lr=0.25, warm_up=0)
+    assert hp(g.SGD(0.0001, gradient_transformers=[g.sign_gradient])) == dict(optimizer_kind="sgd", momentum=0.0, nesterov=False, base_lr=0.0001,
+                                                                              warm_up=0, grad_transform="sign")
+    assert hp(g.LossScaleOptimizer(g.RMSprop(1e-3, gradient_transformers=[g.sign_gradient], clipvalue=0.5)))["grad_transform"] == "sign"
+
+
+# ---- the host-side state ------------------------------------------------------------------------------------------------------------
+class Stub(TM.TrainerState):
+    """TrainerState without a device: the attributes its optimizer methods read, tensors replaced by address holders"""
+    dtype = BF16
+
+    def __init__(self, segs=((0, 100), (128, 60), (192, 8), (256, 40)), unregularized=()):
+        self.base_lr, self.warm_up, self.beta_1, self.beta_2, self.epsilon = 1e-2, 0, 0.9, 0.999, 1e-7
+        self._iterations, self.ls_state, self.loss_scaling = 0, None, False
+        self.flushed, self.segs, self.unregularized = 0, list(segs), set(unregularized)
+
+    def flush_deferred(self):
+        self.flushed += 1
+
+    def _ema_tensors(self):
+        return None, None
+
+    def _clip_segments(self):
+        return list(self.segs)
+
+    def _l2_segments(self):
+        return [s for s in self.segs if s not in self.unregularized]
+
+    def _clip_device(self):
+        return torch.device("cpu")
+
+
+class Ptr:
+    def __init__(self, base, n=320):
+        self.base, self.n = base, n
+
+    def data_ptr(self):
+        return self.base
+
+    def numel(self):
+        return self.n
+
+
+def test_trainer_state_settings():
+    e = Stub()
+    assert (e.l2, e.grad_transform, e.regularization_loss) == (0.0, "none", None) and not e._regularized()
+    assert not {"l2", "grad_transform", "_l2_state", "_reg_tables"} & set(vars(e))      # class-level defaults: nothing new is carried
+    e.set_regularizer(1e-6)
+    assert e.l2 == float(np.float32(1e-6)) and e._regularized() and e.flushed == 1
+    e.set_regularizer(None)
+    assert e.l2 == 0.0 and not e._regularized()
+    e.set_regularizer(0)
+    assert e.l2 == 0.0
+    e.set_gradient_transform("sign")
+    assert e.grad_transform == "sign" and e._regularized() and e.flushed == 4
+    e.set_gradient_transform("none")
+    assert not e._regularized()
+    for bad in (-1e-6, INF, NAN):
+        with pytest.raises(ValueError, match="l2 regularization factor"):
+            e.set_regularizer(bad)
+    with pytest.raises(ValueError, match="unknown gradient transform"):
+        e.set_gradient_transform("abs")
+    assert (e.l2, e.grad_transform, e.flushed) == (0.0, "none", 5)                       # refused before anything was flushed or written
+    # an engine driven by a data-parallel wrapper keeps both off (switching them off stays allowed)
+    e._reg_forbidden = "driven by a wrapper"
+    for change in (lambda: e.set_regularizer(1e-6), lambda: e.set_gradient_transform("sign")):
+        with pytest.raises(ValueError, match="driven by a wrapper"):
+            change()
+    e.set_regularizer(None); e.set_gradient_transform("none")
+
+
+def test_wrappers_refuse_a_regularized_engine():
+    from gan_class_transfer2_amd.distributed import _refuse_regularizer
+    e = Stub()
+    why = _refuse_regularizer(e, "DataParallelStep")
+    assert "DataParallelStep" in why and not hasattr(e, "_reg_forbidden")
+    e.set_regularizer(1e-6)
+    with pytest.raises(ValueError, match="DataParallelStep"):
+        _refuse_regularizer(e, "DataParallelStep")
+    e.set_regularizer(None)
+    e.set_gradient_transform("sign")
+    with pytest.raises(ValueError, match="ShardedDataParallelStep"):
+        _refuse_regularizer(e, "ShardedDataParallelStep")
+
+
+def test_plan_key_covers_both_settings_and_a_checkpoint_neither():
+    """_plan_key on a stand-in whose every other attribute is constant: changing either setting changes the key, changing it back
+    restores it.  (That a checkpoint carries neither is checked on a real engine, tests/test_reg_gpu.py.)"""
+    from unittest import mock
+    eng = mock.MagicMock()
+    eng.l2, eng.grad_transform = 0.0, "none"
+    key = lambda: g.UNetEngine._plan_key(eng, "buffers", True, False, eng.stream)
+    off = key()
+    assert key() == off
+    eng.l2 = float(np.float32(1e-6))
+    with_l2 = key()
+    eng.l2 = float(np.float32(4e-6))
+    assert len({off, with_l2, key()}) == 3
+    eng.l2, eng.grad_transform = 0.0, "sign"
+    assert key() not in (off, with_l2)
+    eng.grad_transform = "none"
+    assert key() == off
+
+
+def test_coefficient_runs():
+    runs = TM.coefficient_runs
+    segs = [(0, 100), (128, 60), (192, 8), (256, 40)]
+    assert runs(segs, [0.5, 0.5, 0.5, 0.5], 320) == [(0, 320, 0.5)]                    # every tensor alike: ONE run over the arena
+    assert runs(segs, [0.5, 0.0, 0.0, 0.5], 320) == [(0, 128, 0.5), (128, 256, 0.0), (256, 320, 0.5)]
+    assert runs(segs, [0.0, 0.5, 0.0, 0.5], 320) == [(0, 128, 0.0), (128, 192, 0.5), (192, 256, 0.0), (256, 320, 0.5)]
+
+
+def _launch_list(monkeypatch, e, lo=0, hi=320):
+    calls = []
+    monkeypatch.setattr(TM, "call", lambda name, *a: calls.append((name, [x.value if type(x) is g._lib.Slot else x for x in a])))
+    p, m, v, gr, sh = Ptr(0x10000), Ptr(0x20000), Ptr(0x30000), Ptr(0x40000), Ptr(0x50000)
+    e._reg_launches(p, m, v, gr, sh, lo, hi, 0.5, 77)
+    return calls
+
+
+def test_launch_lists(monkeypatch):
+    c = TM.l2_coefficients(1e-6)[1]
+    # Adam + l2, every tensor regularized: one launch over the range, the betas in the momentum / rho positions
+    e = Stub()
+    e.set_regularizer(1e-6)
+    calls = _launch_list(monkeypatch, e)
+    assert [n for n, _ in calls] == ["gct2_optimizer_apply_reg"]
+    assert calls[0][1] == [0, 0x10000, 0x20000, 0x30000, 0x40000, 0x50000, BF16, 320, e.adam_alpha(), 0.9, 0, 0.999, 1e-7, 0.5, None,
+                           K.CLIP_NONE, 0.0, None, c, 0, 77]
+    assert len(calls[0][1]) == len(g._lib.SIGNATURES["gct2_optimizer_apply_reg"]) == 21
+    # plain sign-SGD: only p and g, no coefficient
+    e = Stub()
+    e.set_optimizer("sgd")
+    e.set_gradient_transform("sign")
+    (name, a), = _launch_list(monkeypatch, e, 64, 256)
+    assert name == "gct2_optimizer_apply_reg" and a[:8] == [1, 0x10000 + 256, None, None, 0x40000 + 256, 0x50000 + 128, BF16, 192]
+    assert a[8] == e.learning_rate() and a[-3:] == [0.0, 1, 77]
+    # a tensor without the regularizer splits the arena into runs of equal coefficient
+    e = Stub(unregularized=[(128, 60), (192, 8)])
+    e.set_regularizer(1e-6)
+    calls = _launch_list(monkeypatch, e)
+    assert [(a[1] - 0x10000, a[7], a[-3]) for _, a in calls] == [(0, 128, c), (4 * 128, 128, 0.0), (4 * 256, 64, c)]
+    # a sub-range meets only the runs it overlaps
+    calls = _launch_list(monkeypatch, e, 64, 192)
+    assert [(a[1] - 0x10000, a[7], a[-3]) for _, a in calls] == [(4 * 64, 64, c), (4 * 128, 64, 0.0)]
+
+
+def test_exports_header_and_signatures_agree():
+    L = g._lib
+    lib = L.load()
+    raw = ctypes.CDLL(L.LIB_PATH)
+    vp, i, f, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+    new = ("gct2_optimizer_apply_reg", "gct2_grad_sumsq_l2", "gct2_l2_penalty")
+    assert all(hasattr(raw, n) for n in new) and set(new) <= L.PLANNABLE
+    assert L.SIGNATURES["gct2_optimizer_apply_reg"] == L.SIGNATURES["gct2_optimizer_apply"][:-1] + [f, i, vp]
+    assert L.SIGNATURES["gct2_grad_sumsq_l2"] == [vp, vp, vp, vp, i, sz, f, vp, vp, vp, vp]
+    assert L.SIGNATURES["gct2_l2_penalty"] == [vp, vp, f, vp, vp, vp]
+    assert all(len(L.SIGNATURES[n]) <= 28 for n in new)                # plan.hip MAX_ARGS
+    assert lib.gct2_abi_version() == L.ABI_VERSION == 17               # additions change no signature
+    assert (L.GRAD_NONE, L.GRAD_SIGN) == (RC.GRAD_NONE, RC.GRAD_SIGN) == (0, 1) and TM.GRADIENT_TRANSFORMS == {"none": 0, "sign": 1}
+    assert (L.OPT_ADAM, L.OPT_SGD, L.OPT_RMSPROP) == (RC.ADAM, RC.SGD, RC.RMSPROP)
+    header = open(os.path.join(L._HERE, "..", "include", "gct2.h")).read()
+    for text in ("int gct2_optimizer_apply_reg(int kind, float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n,",
+                 "float l2_coeff, int transform, void* stream);",
+                 "int gct2_grad_sumsq_l2(const float* g, const float* p, const gct2_sumsq_seg* segs, const float* seg_coeff, int nseg, size_t npartials,",
+                 "int gct2_l2_penalty(const float* loss, const double* S, float l2, float* penalty_out, float* total_out, void* stream);",
+                 "#define GCT2_GRAD_NONE 0", "#define GCT2_GRAD_SIGN 1", "c = (float)(2.0 * (double)(float)l2)",
+                 "gct2_optimizer_apply_reg, gct2_grad_sumsq_l2, gct2_l2_penalty (additive)"):
+        assert text in header, text
+    for name, text in (("gct2_optimizer_apply_reg", b"optimizer_apply_reg: null pointer"), ("gct2_grad_sumsq_l2", b"grad_sumsq_l2: null pointer"),
+                       ("gct2_l2_penalty", b"l2_penalty: null pointer")):
+        nargs = len(L.SIGNATURES[name])
+        plan = L.Plan()
+        idx = ctypes.c_int(-1)
+        arr = (ctypes.c_uint64 * nargs)()
+        assert lib.gct2_plan_add_call(plan.handle, name.encode(), arr, nargs, ctypes.byref(idx)) == 0 and idx.value == 0
+        assert lib.gct2_plan_add_call(plan.handle, name.encode(), arr, nargs - 1, None) == EINVAL
+        assert b"takes %d arguments" % nargs in lib.gct2_last_error()
+        # the recorded call (all-zero arguments) is rejected by its own checks when the plan runs: nothing is launched
+        failed = ctypes.c_int(-1)
+        assert lib.gct2_plan_run(plan.handle, 0, 1, ctypes.byref(failed)) == EINVAL and failed.value == 0
+        assert text in lib.gct2_last_error()
+
+
+# ---- Trainer ------------------------------------------------------------------------------------------------------------------------
+def test_compile_passes_the_transformer_on_and_switches_it_off():
+    eng = Stub()
+    tr = g.Trainer(types.SimpleNamespace(engine=eng))
+    tr.compile(g.SGD(0.0001, gradient_transformers=[g.sign_gradient]), g.identity)
+    assert (eng.optimizer_kind, eng.grad_transform, eng.base_lr) == ("sgd", "sign", 0.0001) and "grad_transform" in vars(eng)
+    tr.compile(g.SGD(0.0001), g.identity)                              # an optimizer without one switches it off
+    assert eng.grad_transform == "none"
+    flushed = eng.flushed
+    tr.compile(g.SGD(0.0001, gradient_transformers=[]), g.identity)
+    assert eng.grad_transform == "none" and eng.flushed == flushed + 1  # (set_optimizer's flush only: no setter ran for an unchanged setting)
+
+
+def test_trainer_reads_the_regularizer_global_before_every_step():
+    keep = g.model.regularizer
+    try:
+        eng = Stub()
+        eng.device = torch.device("cpu")
+        tr = g.Trainer(types.SimpleNamespace(engine=eng, ensure_engine=lambda **kw: eng))
+        assert tr._engine() is eng and "l2" not in vars(eng)           # None: no setter is called, the engine carries nothing new
+        g.configure(regularizer=g.regularizers.l2(1e-6))
+        tr._engine()
+        assert eng.l2 == float(np.float32(1e-6))
+        g.configure(regularizer=None)
+        tr._engine()
+        assert eng.l2 == 0.0
+        for bad in (1e-6, "l2", types.SimpleNamespace(l2=1e-6)):
+            g.configure(regularizer=bad)
+            with pytest.raises(NotImplementedError, match="regularizer"):
+                tr._engine()
+    finally:
+        g.configure(regularizer=keep)
