@@ -254,6 +254,11 @@ int gct2_dense_bwd(int dtype, const void* x, int ldx, const float* w, const floa
  * x2 (may be NULL): the input channels [Cmask, Cin) come from this second view (ldx2 elements per pixel, at most 4
  * channels, 8-byte aligned rows) instead of x - the concat [UpShuffle_0 output, image] is then never assembled at all
  * (the image lives in its packed copy only).  Needs Cmask = 64, Cout <= 3 and a registered workspace.
+ * Pad channels [Cin, ldx) of x: the matrix-core version masks them, and with x2 also x's own channels [Cmask, ldx) and the slots
+ * [Cin - Cmask, 4) of x2: they may hold anything, NaN included.  It runs when Cmask = 64, Cout <= 3, the registered workspace holds
+ * min(512, ceil(ceil(M / 16) / 4)) * 288 floats, and 64 <= Cin <= 72 with ldx >= 72 (without x2) or 64 <= Cin <= 68 (with x2).
+ * Every other call without x2 falls back, silently, to the LDS-tile version (with x2: GCT2_EINVAL), which multiplies the pad
+ * channels by zero weights: they must be FINITE there, or pred, the loss and every gradient become NaN.
  * Replaces train.py:198-202 + 262-272 and their autodiff inside Keras fit (train.py:516). */
 int gct2_dense_head_train(gct2_ctx* ctx, int dtype, const void* x, int ldx, const float* w, const float* b,
                           const float* target, float* pred, void* dx, int lddx, float* dw, float* db,

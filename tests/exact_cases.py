@@ -229,6 +229,10 @@ def make_case(entry, shape, dt, special=None):
     kw = dict(allow_zero=special != "nozero", max_int=1 if special == "pm1" else None, out_dtype=c.out_dt)
     if entry in ("dense_fwd", "dense_bwd"):
         return _dense_case(c, rng)
+    if entry == "head_train":
+        return _head_case(c, rng)
+    if entry == "convT_head":
+        return _convT_head_case(c, rng)
     KS = shape[5] if len(shape) == 6 else 4
     B, H, W, Cin, Cout = shape[:5]
     s1 = entry.startswith("s1_")
@@ -399,4 +403,178 @@ def special_cases():
     out += [(e, s, dt, "nozero") for e, s in OVERFLOW_CASES for dt in (BF16, F16)]
     out += [(e, (1, 4, 12, 72, 136), F32, "nozero") for e in ("conv_dgrad", "convT_dgrad")]
     out += [(e, (4, 32, 32, 64, 128), dt, "nozero") for e in WGRAD_ENTRIES for dt in (F32, BF16, F16)]
+    return out
+
+
+# ---- the fused train-step head on exact inputs (tests/test_fused_exact_gpu.py) ----------------------------------------------------------
+#
+# gct2_dense_head_train and gct2_convT4s2_fwd_head_train chain four contractions: pred = x w + b, dx = dpred w^T, dw = x^T dpred and
+# the column sums (db, db_dx, the loss).  Every one of them is kept an exact sum:
+#   x = relu(integers / 2^HEAD_SA), w = integers / 2^sw, b on the grid lsb = 2^-(HEAD_SA + sw) of their products;
+#   target = pred_r - delta * lsb with integers delta (pred_r: the exact prediction, rounded to fp16 first in GCT2_F16), so that
+#   d = pred_r - target = delta * lsb is exact, and the loss scale is M * Cout * 2^j: gscale = scale * 2 / (M * Cout) = 2^(j + 1) for
+#   any order of the one division, dpred = d * gscale exact (one fp16 rounding in GCT2_F16);  j = sw - 1 puts dpred on the grid 2^-2
+#   and dx on 2^-(2 + sw) >= 2^-14: nothing is subnormal in fp16.
+# The budget is taken on the arrays as drawn: the sum of the MAGNITUDES of the terms of every reduction stays below BUDGET steps of its
+# grid, hence every partial sum of every order is exact in an fp32 accumulator (the sum of delta^2 below 2^24: it has one order per kernel
+# and nothing is added to it).  The matrix-core kernels carry w and d as multi-term sums of the storage type and drop the product of the
+# two LOW terms in the backward pass, so the columns are drawn such that never both have one: column 0 has wide weights and narrow
+# deltas, column 1 narrow weights and wide deltas, column 2 both within one term.
+HEAD_SHAPE = (67, 3, 72, 64)                  # Cin, Cout, ld, Cmask
+HEAD_MS = (5, 16, 1000, 32775)                # < one 16-pixel group; one group; ragged 256-pixel tile and group; > one trip per wave of 512 work-groups
+HEAD_WIDE_M = 64
+HEAD_SA = 2                                   # x = integers / 4, at most 7 / 4
+HEAD_XMAX = 7
+CONVT_HEAD_SHAPES = [(1, 16, 16, 8), (2, 16, 32, 136)]       # (B, H, W, Cin) of gct2_convT4s2_fwd_head_train; Cout = 64, head 67 -> 3
+
+
+def _head_ranges(M, dt):
+    """per output column: largest weight integer, largest delta, and (column 1 only) the share of pixels whose delta is wide.
+    The ranges shrink with M because db_dx, dw and the sum of delta^2 grow with it (tests/test_exact_cases_cpu.py decides)."""
+    if M <= 64:
+        return ((4095, 15, 63), (3, 511, 63), 1.0) if dt == BF16 else ((4095, 127, 63), (15, 511, 63), 1.0)
+    if M <= 1000:
+        return (2047, 15, 31), (3 if dt == BF16 else 7, 511, 31), 0.03
+    return (319, 7, 31), (1, 15, 7), 0.0
+
+
+def _round_to(a, dt):
+    return torch.tensor(np.asarray(a, dtype=np.float64)).to(TDT[dt]).to(torch.float64).numpy()
+
+
+def _wide_deltas(rng, n, dmax, share):
+    """deltas of column 1: |delta| <= 15 everywhere, and in `share` of the pixels one with more than 8 significant bits"""
+    d = rng.integers(-min(dmax, 15), min(dmax, 15) + 1, n).astype(np.float64)
+    if dmax <= 256:
+        return d
+    wide = rng.random(n) < share
+    big = (rng.integers(257, dmax + 1, n) | 1) * rng.choice([-1, 1], n)
+    return np.where(wide, big, d)
+
+
+def _head_tail(c, rng, xin, wmax, dmax, share, sw, tails=None):
+    """everything behind the head's input `xin` [M, Cin] (exact in the storage type): kernel, bias, target, loss scale and the fp64
+    references of every output of the fused head.  tails: {column: (lo, hi, share)} - in `share` of the pixels that column's delta
+    is an odd integer of magnitude lo .. hi instead (the few large residuals the budget of a long reduction leaves room for)"""
+    M, Cin = xin.shape
+    Cout, Cmask = 3, 64
+    c.sw, c.lsb = sw, c.x_step * 2.0 ** -sw
+    c.w = np.stack([_ints(rng, Cin, wmax[o], True) for o in range(Cout)], 1) / 2.0 ** sw
+    c.w[:, 0] = np.where(c.w[:, 0] != 0, (np.round(c.w[:, 0] * 2.0 ** sw).astype(np.int64) | 1) / 2.0 ** sw, 0.0)   # odd: the low term is there
+    c.bias = rng.integers(-wmax[0], wmax[0] + 1, Cout).astype(np.float64) * c.lsb
+    c.pred = xin @ c.w + c.bias
+    c.pred_r = _round_to(c.pred, F16) if c.dt == F16 else c.pred
+    c.delta = np.stack([rng.integers(-dmax[0], dmax[0] + 1, M).astype(np.float64), _wide_deltas(rng, M, dmax[1], share),
+                        rng.integers(-dmax[2], dmax[2] + 1, M).astype(np.float64)], 1)
+    for col, (lo, hi, part) in (tails or {}).items():
+        big = (rng.integers(lo, hi + 1, M) | 1) * rng.choice([-1, 1], M)
+        c.delta[:, col] = np.where(rng.random(M) < part, big, c.delta[:, col])
+    c.target = c.pred_r - c.delta * c.lsb
+    c.j = sw - 1 - int(round(math.log2(c.x_step * 4)))            # dpred on the grid 2^-2
+    c.gscale = 2.0 ** (c.j + 1)
+    c.loss_scale = float(M * Cout) * 2.0 ** c.j
+    c.d = c.pred_r - c.target
+    c.dpred = c.d * c.gscale
+    if c.dt == F16:
+        c.dpred = _round_to(c.dpred, F16)
+    c.g = c.dpred @ c.w[:Cmask].T                                 # the unmasked gradient rows
+    c.dx = np.where(xin[:, :Cmask] > 0, c.g, 0.0)
+    c.dw, c.db = xin.T @ c.dpred, c.dpred.sum(0)
+    c.db_dx = c.dx.sum(0)                                         # of the fp32 rows (matrix-core kernels)
+    c.db_dx_stored = _round_to(c.dx, c.dt).sum(0)                 # of the stored rows (LDS kernel)
+    c.loss = float((c.d * c.d).sum() / (M * Cout))
+    c.dp_step, c.dx_step = 0.25, 0.25 * 2.0 ** -sw
+    # what the accumulating call finds in dw / db / db_dx: on the grids, a few steps in size
+    c.prev_dw = rng.integers(-64, 65, c.dw.shape) * c.x_step * c.dp_step
+    c.prev_db = rng.integers(-64, 65, Cout) * c.dp_step
+    c.prev_db_dx = rng.integers(-64, 65, Cmask) * c.dx_step * 256
+    return c
+
+
+def head_budgets(c, xin):
+    """(name, sum of the magnitudes of the terms of the worst output, grid step) of every reduction of the head"""
+    Cmask = 64
+    dxr = _round_to(c.dx, c.dt)
+    return [("pred", float((np.abs(xin) @ np.abs(c.w) + np.abs(c.bias)).max()), c.lsb),
+            ("dx", float((np.abs(c.dpred) @ np.abs(c.w[:Cmask]).T).max()), c.dx_step),
+            ("dw", float((np.abs(xin).T @ np.abs(c.dpred) + np.abs(c.prev_dw)).max()), c.x_step * c.dp_step),
+            ("db", float((np.abs(c.dpred).sum(0) + np.abs(c.prev_db)).max()), c.dp_step),
+            ("db_dx", float((np.abs(c.dx).sum(0) + np.abs(c.prev_db_dx)).max()), c.dx_step),
+            ("db_dx_stored", float((np.abs(dxr).sum(0) + np.abs(c.prev_db_dx)).max()), c.dx_step)]
+
+
+def _head_case(c, rng):
+    """make_case("head_train", (M, Cin, Cout), dt, special): special None or "wide" (M = 64: |delta| up to 2^12 and 24-bit weights -
+    the backward pass is then a two-term approximation, tests/test_fused_exact_gpu.py bounds it)"""
+    M, Cin, Cout = c.shape
+    assert (Cin, Cout) == HEAD_SHAPE[:2]
+    c.x_step = 2.0 ** -HEAD_SA
+    c.x = np.maximum(_ints(rng, (M, Cin), HEAD_XMAX, True), 0.0) * c.x_step
+    if c.special == "wide":
+        c.sw = 24
+        c.w = _ints(rng, (Cin, Cout), (1 << 24) - 1, False) / 2.0 ** 24
+        c.lsb = c.x_step * 2.0 ** -24
+        c.bias = _ints(rng, Cout, 1 << 20, True) * 2.0 ** -20
+        c.pred = c.x @ c.w + c.bias
+        c.delta = _ints(rng, (M, Cout), 1 << 12, False)
+        c.target = _round_to(c.pred - c.delta * 2.0 ** -12, F32)          # d = delta * 2^-12 up to the fp32 rounding of the target
+        c.j = 1                                                           # d in [2^-12, 1], dpred = 4 d: both normal in fp16
+        c.gscale = 2.0 ** (c.j + 1)
+        c.loss_scale = float(M * Cout) * 2.0 ** c.j
+        return c
+    wmax, dmax, share = _head_ranges(M, c.dt)
+    # fp16 at the largest M: db_dx keeps the mean |dx| below 256 steps, the store rounds from 2048 on - a few pixels get there
+    tails = {0: (9, 15, 0.003)} if c.dt == F16 and M > 1000 else None
+    return _head_tail(c, rng, c.x, wmax, dmax, share, wmax[0].bit_length(), tails)
+
+
+# largest operand integer of the transposed convolution and the head's ranges, by (Cin, dtype): y = relu(convT(x) + bias) has a standard
+# deviation of about 200 steps in bf16 and 1500 in fp16, so that 5 % and more of the positive y lose bits at the 16-bit conversion
+# Tails: bf16 - a few column-1 residuals of 9 bits (the second term of dpred in the epilogue's two-term contractions; the column's
+# weights fit one term); fp16 - a few column-0 residuals that carry dy past 2048 steps, where the fp16 store rounds.
+_CONVT_HEAD_RANGES = {
+    (8, BF16): (10, (511, 15, 31), (15, 31, 15), {1: (257, 511, 0.02)}), (8, F16): (28, (63, 15, 31), (1, 3, 1), {0: (33, 63, 0.015)}),
+    (136, BF16): (5, (511, 15, 31), (7, 3, 7), {1: (257, 511, 0.01)}), (136, F16): (14, (63, 15, 31), (1, 1, 1), {0: (33, 63, 0.005)}),
+}
+
+
+def _convT_head_case(c, rng):
+    """make_case("convT_head", (B, H, W, Cin), dt): UpShuffle_0's forward with the head in its epilogue.  Operands of the transposed
+    convolution are small integers (grid 1), y an exact sum; the head reads y rounded once to the storage type and three image
+    channels from the packed view, and from there everything follows _head_tail."""
+    B, H, W, Cin = c.shape
+    mi, wmax, dmax, tails = _CONVT_HEAD_RANGES[(Cin, c.dt)]
+    ops = exact_operands(rng, ((B, H, W, Cin), (4, 4, 64, Cin)), c.dt, 4 * Cin, max_int=mi)
+    c.ops, c.xc, c.wc = ops, ops.a, ops.b
+    c.bc = rng.integers(-mi * mi, mi * mi + 1, 64).astype(np.float64)
+    c.y = np.maximum(O.convT4s2_fwd(c.xc, c.wc, c.bc), 0.0)
+    c.yr = _round_to(c.y, c.dt)
+    M = B * 4 * H * W
+    c.img = _ints(rng, (M, 3), HEAD_XMAX, True)
+    c.x_step = 1.0
+    c.x = np.concatenate([c.yr.reshape(M, 64), c.img], 1)         # the head's input
+    return _head_tail(c, rng, c.x, wmax, dmax, 0.0, wmax[0].bit_length(), tails)
+
+
+def fused_cases():
+    """every (entry, shape, dtype, special) of tests/test_fused_exact_gpu.py's head tests"""
+    out = [("head_train", (M, 67, 3), dt, None) for dt in (BF16, F16) for M in HEAD_MS]
+    out += [("head_train", (HEAD_WIDE_M, 67, 3), dt, "wide") for dt in (BF16, F16)]
+    out += [("convT_head", s, dt, None) for dt in (BF16, F16) for s in CONVT_HEAD_SHAPES]
+    return out
+
+
+# (entry, B): (B, 32, 32, 8, 8) leaves B slabs by wgrad_mfma()'s rule (one owner at B = 1); the fused optimizer step sums them
+ADAM_SLAB_BS = (1, 2, 8, 9, 10, 17)
+
+
+def adam_slab_shape(B):
+    return (B, 32, 32, 8, 8)
+
+
+def adam_cases():
+    """the weight-gradient cases behind which tests/test_fused_exact_gpu.py runs the fused optimizer step"""
+    out = [(e, adam_slab_shape(B), dt, None) for e in WGRAD_ENTRIES for dt in (BF16, F16) for B in ADAM_SLAB_BS]
+    out += [(e, adam_slab_shape(2), F32, None) for e in WGRAD_ENTRIES]
+    out += [(e, (2, 16, 16, 3, 8), dt, None) for e in WGRAD_ENTRIES for dt in (BF16, F16)]
     return out

@@ -205,3 +205,103 @@ def test_poisoned_view_and_guards():
     out[0, 0, 0, 0] = 1
     with pytest.raises(AssertionError):
         E.assert_outside_untouched(out, before, inside)
+
+
+# ---- the fused head and the fused optimizer step (tests/test_fused_exact_gpu.py) ----------------------------------------------------
+
+def _on_grid(a, step):
+    return bool(np.array_equal(np.round(np.asarray(a) / step) * step, a))
+
+
+def _fp16_normal(a):
+    a = np.abs(np.asarray(a))
+    a = a[a != 0]
+    return bool(((a >= 2.0 ** -14) & (a < 65504)).all())
+
+
+# 16-bit stores at which the 5 % / 0.5 % shares are out of reach under the budget, so only "some inexact, some ties" is asserted:
+#   head_train, fp16, M = 32775: db_dx sums |dx| over 32775 pixels (half of them masked), so the MEAN |dx| stays below
+#     2^22 / 16387 = 256 steps, and fp16 holds every integer up to 2048: at most 256 / 2048 = 12.5 % of the elements could reach
+#     the rounding range even if all the mass sat there, a realistic spread gets well under 5 %;
+#   convT_head, fp16: the same with head_dw = y^T dpred: y of about 1500 steps (so that its own conversion rounds) over 1024 / 4096
+#     pixels leaves a mean |delta| near 1, |dy| = |delta . w| near 100 steps.
+# A few pixels with a large residual (exact_cases' tails) take those stores into the rounding range.
+FEW_ROUNDINGS_AT_DX = {("head_train", (32775, 67, 3), F16), ("convT_head", (1, 16, 16, 8), F16), ("convT_head", (2, 16, 32, 136), F16)}
+
+
+@pytest.mark.parametrize("case", [c for c in E.fused_cases() if c[3] is None], ids=_id)
+def test_fused_head_inputs(case):
+    """conditions on the inputs of the exact head cases, met by the reference alone: storage types, the budget of every reduction on
+    the arrays as drawn, exactness of every reference in float32, both mask values, rounding and ties at the 16-bit stores, no fp16
+    overflow or subnormal, and a loss scale that makes the gradient scale a power of two"""
+    c = E.make_case(*case)
+    M = c.x.shape[0]
+    assert E.survives_storage(c.x, c.dt) and E.survives_storage(c.w, F32) and E.survives_storage(c.bias, F32) and E.survives_storage(c.target, F32)
+    for name, total, step in E.head_budgets(c, c.x):
+        assert total / step < E.BUDGET, (name, total / step)
+    for a, step in ((c.x, c.x_step), (c.w, 2.0 ** -c.sw), (c.bias, c.lsb), (c.pred, c.lsb), (c.target, c.lsb), (c.dpred, c.dp_step),
+                    (c.dx, c.dx_step), (c.prev_dw, c.x_step * c.dp_step), (c.prev_db, c.dp_step), (c.prev_db_dx, c.dx_step)):
+        assert _on_grid(a, step)
+    assert np.array_equal(c.d, c.delta * c.lsb) and float((c.delta ** 2).sum()) < 2.0 ** 24
+    for r in (c.pred, c.pred_r, c.d, c.dpred, c.dx, c.dw, c.db, c.db_dx, c.db_dx_stored, c.dw + c.prev_dw, c.db + c.prev_db,
+              c.db_dx + c.prev_db_dx, c.db_dx_stored + c.prev_db_dx):
+        E.expected(r, F32)
+    # the gradient scale as the kernels form it: fl(fl(scale * 2) / fl(M * Cout)), a power of two
+    n = np.float32(M) * np.float32(3)
+    assert float(np.float32(c.loss_scale)) == c.loss_scale and float(n) == 3.0 * M
+    assert float(np.float32(np.float32(c.loss_scale) * np.float32(2)) / n) == c.gscale == 2.0 ** (c.j + 1) and c.j >= 0
+    # the two-term operands of the matrix-core backward pass: weights within 16 bits, and never a low term in both factors
+    s = E.SIG_BITS[c.dt]
+    low = lambda a: E._round_to(a, c.dt) != a
+    assert _on_grid(c.w * 2.0 ** c.sw, 1.0) and np.abs(c.w).max() * 2.0 ** c.sw < (1 << 2 * s)
+    assert not (low(c.w[:64]).any(0) & low(c.dpred).any(0)).any()
+    if c.dt == BF16 and 16 <= M <= 4096:        # (at M = 32775 the budget leaves dpred 4 bits: no low term there; fp16 holds dpred in one)
+        assert low(c.w[:64, 0]).any() and low(c.dpred[:, 1]).any(), "no operand needs its low term"
+    mask = c.x[:, :64] > 0
+    assert 0.1 <= float(mask.mean()) <= 0.9
+    key = (c.entry, c.shape, c.dt)
+    stores = [(c.g, c.dt, key not in FEW_ROUNDINGS_AT_DX)] + ([(c.pred, F16, True)] if c.dt == F16 else [])
+    for ref, dt, rounds in stores:
+        inexact, ties = rounding_shares(ref, dt)
+        if rounds and M >= 1000:
+            assert inexact >= MIN_INEXACT and ties >= MIN_TIES, (inexact, ties)
+        else:                            # 5 and 16 pixels: at least one of each kind; FEW_ROUNDINGS_AT_DX: a hundred
+            need = 1 if rounds else 100
+            assert inexact * ref.size >= need and ties * ref.size >= need, (inexact, ties)
+    if c.dt == F16:
+        for a in (c.x, c.pred_r, c.dpred, c.dx, c.target):
+            assert _fp16_normal(a)
+    if c.entry == "convT_head":
+        E.assert_budget(c.ops)
+        assert E.survives_storage(c.xc, c.dt) and E.survives_storage(c.wc, c.dt) and E.survives_storage(c.bc, F32)
+        E.expected(c.y, F32)
+        pos = c.y > 0
+        assert float((c.yr != c.y)[pos].mean()) >= 0.05 and np.abs(c.y).max() < 65504
+        inexact, ties = rounding_shares(c.y[pos], c.dt)
+        assert ties >= MIN_TIES, ties
+
+
+@pytest.mark.parametrize("case", [c for c in E.fused_cases() if c[3] == "wide"], ids=_id)
+def test_wide_head_inputs(case):
+    """the one inexact head case: weights with 24 significant bits, a residual that needs more than one term of the storage type"""
+    c = E.make_case(*case)
+    assert E.survives_storage(c.x, c.dt) and E.survives_storage(c.w, F32) and E.survives_storage(c.target, F32)
+    bits = np.round(np.abs(c.w) * 2.0 ** 24).astype(np.int64)
+    assert float(np.mean((bits >= 1 << 23) & (bits & 1 == 1))) >= 0.2          # all 24 bits in use
+    d = c.pred - c.target
+    assert np.abs(c.delta).max() > 1 << 11 and float(np.mean(E._round_to(d, c.dt) != d)) >= 0.5
+    dp = d * c.gscale
+    assert _fp16_normal(dp) and np.abs(c.pred).max() < 65504
+    assert 0.1 <= float((c.x[:, :64] > 0).mean()) <= 0.9
+
+
+@pytest.mark.parametrize("case", E.adam_cases(), ids=_id)
+def test_fused_adam_gradient_inputs(case):
+    """the weight-gradient cases of the fused optimizer step: the usual budget - the gradient is then the same fp32 tensor whatever
+    the number of slabs - and a gradient that is not trivially zero"""
+    c = E.make_case(*case)
+    E.assert_budget(c.ops)
+    assert E.survives_storage(c.ops.a, c.dt) and E.survives_storage(c.ops.b, c.dt)
+    g = E.expected(c.dw, F32)
+    E.expected(c.db, F32)
+    assert float((g != 0).float().mean()) >= 0.9 and c.dw.size % 4 == 0
