@@ -91,6 +91,9 @@ SIGNATURES = {
     "gct2_dense_fwd": [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp],
     "gct2_dense_bwd": [_i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "gct2_dense_head_train": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "gct2_dense_steps_fwd": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "gct2_dense_steps_scratch": [_i, _i, _i, _i, C.POINTER(C.c_size_t)],
+    "gct2_dense_steps_bwd": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp],
     "gct2_rng_uniform_int": [_u64, _u64, _u64, _vp, _sz, _i, _i, _vp],
     "gct2_rng_normal": [_u64, _u64, _u64, _vp, _sz, _vp],
     "gct2_noise_image": [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
@@ -190,7 +193,7 @@ def call(name: str, *args) -> None:
 
 # the entry points a plan can hold (csrc/plan.hip ENTRIES): everything that enqueues work on a stream + the one-shot ReLU plane
 PLANNABLE = frozenset(n for n, sig in SIGNATURES.items() if n == "gct2_ctx_set_relu_bits" or (
-    not n.startswith(("gct2_ctx_", "gct2_plan_", "gct2_loss_scale_init")) and n not in ("gct2_abi_version", "gct2_build_flags", "gct2_device_check", "gct2_stream_occupy", "gct2_sumsq_layout", "gct2_loss_scratch")))
+    not n.startswith(("gct2_ctx_", "gct2_plan_", "gct2_loss_scale_init")) and n not in ("gct2_abi_version", "gct2_build_flags", "gct2_device_check", "gct2_stream_occupy", "gct2_sumsq_layout", "gct2_loss_scratch", "gct2_dense_steps_scratch")))
 _recording = None      # the Plan that is recording calls right now (one host thread drives an engine: _lib.call is not re-entrant)
 _FLOAT_STRUCT = struct.Struct("<f")
 _DOUBLE_STRUCT = struct.Struct("<d")

@@ -468,6 +468,51 @@ int gct2_dense_bwd(int dtype, const void* x, int ldx, const float* w, const floa
   return pw_dense_bwd(dtype, x, ldx, w, dy, dx, lddx, dw, db, M, Cin, Cout, Cmask, accumulate, S(stream));
 }
 
+// ---- per-timestep heads (train.py:199, 203, 211-214).  The order of the checks is part of the interface. ----
+static int check_steps_shape(const char* fn, int B, int HW, int Cin, int Cout, int steps) {
+  if (B <= 0 || HW <= 0 || Cin <= 0 || steps <= 0) return gct2_fail(GCT2_EINVAL, "%s: non-positive dimension (B=%d HW=%d Cin=%d steps=%d)", fn, B, HW, Cin, steps);
+  if (Cout < 1 || Cout > 4) return gct2_fail(GCT2_EINVAL, "%s: Cout=%d outside 1..4", fn, Cout);
+  if (B > 65535 || steps > 65535) return gct2_fail(GCT2_EINVAL, "%s: B=%d / steps=%d beyond 65535 (one grid row per image / per slice)", fn, B, steps);
+  if ((size_t)B * HW >= ((size_t)1 << 31)) return gct2_fail(GCT2_EINVAL, "%s: B*HW too large for 32-bit pixel indices", fn);
+  if ((size_t)Cin * steps * Cout >= ((size_t)1 << 31)) return gct2_fail(GCT2_EINVAL, "%s: Cin*steps*Cout too large for 32-bit weight indices", fn);
+  return GCT2_OK;
+}
+int gct2_dense_steps_fwd(gct2_ctx* ctx, int dtype, const void* x, int ldx, const float* w, const float* b, const int32_t* t_int, float* y,
+                         int B, int HW, int Cin, int Cout, int steps, void* stream) {
+  if (!dtype_ok(dtype)) return gct2_fail(GCT2_EINVAL, "dense_steps_fwd: unknown dtype %d", dtype);
+  if (!x || !w || !t_int || !y) return gct2_fail(GCT2_EINVAL, "dense_steps_fwd: null pointer (x, w, t_int, y)");
+  if (int e = check_steps_shape("dense_steps_fwd", B, HW, Cin, Cout, steps)) return e;
+  if (ldx < Cin) return gct2_fail(GCT2_EINVAL, "dense_steps_fwd: ldx=%d smaller than Cin=%d", ldx, Cin);
+  if ((size_t)Cin * 16 > 64 * 1024) return gct2_fail(GCT2_EINVAL, "dense_steps_fwd: Cin=%d too large for the LDS weight image", Cin);
+  if (ctx) gct2_log(*ctx, "dense_steps:fwd");
+  return pw_dense_steps_fwd(dtype, x, ldx, w, b, t_int, y, B, HW, Cin, Cout, steps, S(stream));
+}
+int gct2_dense_steps_scratch(int B, int HW, int Cin, int Cout, size_t* floats) {
+  if (!floats) return gct2_fail(GCT2_EINVAL, "dense_steps_scratch: null output pointer");
+  if (int e = check_steps_shape("dense_steps_scratch", B, HW, Cin, Cout, 1)) return e;
+  if ((Cin + 1) * Cout > 2048) return gct2_fail(GCT2_EINVAL, "dense_steps_scratch: (Cin+1)*Cout = %d exceeds 2048", (Cin + 1) * Cout);
+  *floats = dense_steps_scratch_floats(B, HW, Cin, Cout);
+  return GCT2_OK;
+}
+int gct2_dense_steps_bwd(gct2_ctx* ctx, int dtype, const void* x, int ldx, const float* w, const int32_t* t_int, const float* dy, void* dx,
+                         int lddx, float* dw, float* db, float* scratch, size_t scratch_floats, int B, int HW, int Cin, int Cout, int steps,
+                         int Cmask, int accumulate, void* stream) {
+  if (!dtype_ok(dtype)) return gct2_fail(GCT2_EINVAL, "dense_steps_bwd: unknown dtype %d", dtype);
+  if (!x || !w || !t_int || !dy || !dw || !scratch) return gct2_fail(GCT2_EINVAL, "dense_steps_bwd: null pointer (x, w, t_int, dy, dw, scratch)");
+  if (int e = check_steps_shape("dense_steps_bwd", B, HW, Cin, Cout, steps)) return e;
+  if (ldx < Cin) return gct2_fail(GCT2_EINVAL, "dense_steps_bwd: ldx=%d smaller than Cin=%d", ldx, Cin);
+  if (Cmask < 0 || Cmask > Cin || (dx && lddx < Cmask)) return gct2_fail(GCT2_EINVAL, "dense_steps_bwd: Cmask=%d outside 0..Cin or lddx=%d smaller than it", Cmask, lddx);
+  if ((Cin + 1) * Cout > 2048) return gct2_fail(GCT2_EINVAL, "dense_steps_bwd: (Cin+1)*Cout = %d exceeds 2048", (Cin + 1) * Cout);
+  if ((size_t)Cin * 16 + 128 * 16 + (size_t)128 * Cin * esize(dtype) > 160 * 1024)
+    return gct2_fail(GCT2_EINVAL, "dense_steps_bwd: Cin=%d too large for the LDS tile", Cin);
+  if ((uintptr_t)scratch % 16) return gct2_fail(GCT2_EINVAL, "dense_steps_bwd: scratch must be 16-byte aligned");
+  const size_t need = dense_steps_scratch_floats(B, HW, Cin, Cout);
+  if (scratch_floats < need)
+    return gct2_fail(GCT2_EINVAL, "dense_steps_bwd: %zu floats of scratch, this shape needs %zu (gct2_dense_steps_scratch)", scratch_floats, need);
+  if (ctx) gct2_log(*ctx, "dense_steps:bwd");
+  return pw_dense_steps_bwd(dtype, x, ldx, w, t_int, dy, dx, lddx, dw, db, scratch, B, HW, Cin, Cout, steps, Cmask, accumulate, S(stream));
+}
+
 int gct2_dense_head_train(gct2_ctx* ctx, int dtype, const void* x, int ldx, const float* w, const float* b, const float* target, float* pred,
                           void* dx, int lddx, float* dw, float* db, float* loss, float* partials, int M, int Cin, int Cout, int Cmask,
                           const float* loss_scale_ptr, float* db_dx, const void* x2, int ldx2, int accumulate, void* stream) {

@@ -447,6 +447,13 @@ int pw_noise_rng(int dtype, const float* x, const int32_t* t, uint64_t seed, uin
 int pw_dense_fwd(int dtype, const void* x, int ldx, const float* w, const float* b, float* y, int M, int Cin, int Cout, hipStream_t s);
 int pw_dense_bwd(int dtype, const void* x, int ldx, const float* w, const float* dy, void* dx, int lddx, float* dw, float* db, int M,
                  int Cin, int Cout, int Cmask, int accumulate, hipStream_t s);
+// per-timestep heads (gct2_dense_steps_*): the floats of scratch the backward call needs / the two launches
+size_t dense_steps_scratch_floats(int B, int HW, int Cin, int Cout);
+int pw_dense_steps_fwd(int dtype, const void* x, int ldx, const float* w, const float* b, const int32_t* t_int, float* y, int B, int HW,
+                       int Cin, int Cout, int steps, hipStream_t s);
+int pw_dense_steps_bwd(int dtype, const void* x, int ldx, const float* w, const int32_t* t_int, const float* dy, void* dx, int lddx,
+                       float* dw, float* db, float* scratch, int B, int HW, int Cin, int Cout, int steps, int Cmask, int accumulate,
+                       hipStream_t s);
 int pw_head_finish(const float* part, int rows, float* dw, float* db, float* loss, float* db_dx, int ndw, int Cout, float inv_n,
                    int accumulate, hipStream_t s);
 int pw_dense_head_train(const gct2_ctx& c, int dtype, const void* x, int ld, const float* w, const float* b, const float* target, float* pred,

@@ -284,6 +284,135 @@ __global__ __launch_bounds__(256) void dense_bwd_kernel(const T* __restrict__ x,
   }
 }
 
+// ---- per-timestep heads: Dense(Cout * steps), gathered by t (train.py:199, 203, 211-214) ----------------------------------
+// t is constant over an image, so the gathered head is the Dense(3) head above with the weight slice s = t_int[image] - 1 of the
+// (Cin, steps * Cout) kernel.  blockIdx.y = image: a work-group never sees two images.  The slice index is clamped into
+// [0, steps) before any address is formed (a t_int outside 1..steps is a caller error, not an out-of-bounds access).
+__device__ __forceinline__ int steps_slice(const int32_t* __restrict__ t_int, int img, int steps) {
+  const int s = t_int[img] - 1;
+  return s < 0 ? 0 : (s >= steps ? steps - 1 : s);
+}
+
+// dense_fwd_kernel's arithmetic (k ascending, one fmaf per term, bias last, keras_f16_point) on the image's slice: bit-identical to
+// it on the image's rows with a contiguous copy of the slice
+template <typename T>
+__global__ __launch_bounds__(256) void dense_steps_fwd_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ w,
+                                                              const float* __restrict__ b, const int32_t* __restrict__ t_int,
+                                                              float* __restrict__ y, int HW, int Cin, int Cout, int steps) {
+  extern __shared__ float wsm[];                  // [Cin][4]
+  const int img = blockIdx.y;
+  const int s = steps_slice(t_int, img, steps);
+  const int ldw = steps * Cout;                   // (Cin * steps * Cout < 2^31: checked by the entry point)
+  for (int i = threadIdx.x; i < Cin * 4; i += blockDim.x) {
+    const int o = i & 3, k = i >> 2;
+    wsm[i] = (o < Cout) ? w[k * ldw + s * Cout + o] : 0.f;
+  }
+  __syncthreads();
+  const int stride = gridDim.x * blockDim.x;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += stride) {
+    const size_t m = (size_t)img * HW + p;
+    const T* xr = x + m * ldx;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    for (int k = 0; k < Cin; k++) {
+      const float v = to_f32(xr[k]);
+      a0 = fmaf(v, wsm[4 * k + 0], a0); a1 = fmaf(v, wsm[4 * k + 1], a1);
+      a2 = fmaf(v, wsm[4 * k + 2], a2); a3 = fmaf(v, wsm[4 * k + 3], a3);
+    }
+    const float acc[4] = {a0, a1, a2, a3};
+    for (int o = 0; o < Cout; o++) y[m * Cout + o] = keras_f16_point<T>(acc[o] + (b ? b[s * Cout + o] : 0.f));
+  }
+}
+
+// work-group (chunk, image) walks the tiles chunk, chunk + gridDim.x, ... of PIX pixels of its image: dx per pixel exactly as
+// dense_bwd_kernel forms it, and the per-(i,o) sums of dw / db over its pixels, which leave as ONE partial row
+// part[image * gridDim.x + chunk][(Cin + 1) * Cout] - no atomics (dense_steps_finish_kernel adds the rows in order)
+template <typename T, int PIX>
+__global__ __launch_bounds__(256) void dense_steps_bwd_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ w,
+                                                              const int32_t* __restrict__ t_int, const float* __restrict__ dy,
+                                                              T* __restrict__ dx, int lddx, float* __restrict__ part, int HW, int Cin,
+                                                              int Cout, int steps, int Cmask) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* wsm = reinterpret_cast<float*>(smem_raw);          // [Cin][4]
+  float* dys = wsm + Cin * 4;                               // [PIX][4]
+  T* xs = reinterpret_cast<T*>(dys + PIX * 4);              // [PIX][Cin]
+  const int tid = threadIdx.x, img = blockIdx.y;
+  const int s = steps_slice(t_int, img, steps);
+  const int ldw = steps * Cout;
+  for (int i = tid; i < Cin * 4; i += 256) {
+    const int o = i & 3, k = i >> 2;
+    wsm[i] = (o < Cout) ? w[k * ldw + s * Cout + o] : 0.f;
+  }
+  const int nout = (Cin + 1) * Cout;                        // dw entries + db entries: entry e = tid + 256 k belongs to thread tid
+  constexpr int ENT = 8;                                    // (Cin + 1) * Cout <= 2048
+  float wacc[ENT];
+#pragma unroll
+  for (int k = 0; k < ENT; k++) wacc[k] = 0.f;
+  const size_t m0 = (size_t)img * HW;                       // first pixel of the image
+  const int ntiles = (HW + PIX - 1) / PIX;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int pbase = tile * PIX;
+    __syncthreads();
+    for (int i = tid; i < PIX * Cin; i += 256) {
+      const int pm = i / Cin, k = i - pm * Cin;
+      xs[i] = (pbase + pm < HW) ? x[(m0 + pbase + pm) * ldx + k] : from_f32<T>(0.f);
+    }
+    for (int i = tid; i < PIX * 4; i += 256) {
+      const int pm = i >> 2, o = i & 3;
+      dys[i] = (o < Cout && pbase + pm < HW) ? keras_f16_point<T>(dy[(m0 + pbase + pm) * Cout + o]) : 0.f;
+    }
+    __syncthreads();
+    if (dx) {
+      for (int i = tid; i < PIX * Cmask; i += 256) {
+        const int pm = i / Cmask, k = i - pm * Cmask;
+        if (pbase + pm >= HW) continue;
+        float g = dys[4 * pm] * wsm[4 * k] + dys[4 * pm + 1] * wsm[4 * k + 1] + dys[4 * pm + 2] * wsm[4 * k + 2] +
+                  dys[4 * pm + 3] * wsm[4 * k + 3];
+        if (!(to_f32(xs[pm * Cin + k]) > 0.f)) g = 0.f;
+        dx[(m0 + pbase + pm) * lddx + k] = from_f32<T>(g);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < ENT; k++) {
+      const int e = tid + 256 * k;
+      if (e >= nout) break;
+      const int my_i = e / Cout, my_o = e - my_i * Cout;
+      float a = wacc[k];
+      if (my_i < Cin) {
+        for (int pm = 0; pm < PIX; pm++) a = fmaf(to_f32(xs[pm * Cin + my_i]), dys[4 * pm + my_o], a);
+      } else {
+        for (int pm = 0; pm < PIX; pm++) a += dys[4 * pm + my_o];
+      }
+      wacc[k] = a;
+    }
+  }
+  float* row = part + ((size_t)img * gridDim.x + blockIdx.x) * nout;
+#pragma unroll
+  for (int k = 0; k < ENT; k++) {
+    const int e = tid + 256 * k;
+    if (e >= nout) break;
+    row[e] = wacc[k];
+  }
+}
+
+// blockIdx.y = slice: entry e of dw / db of that slice = the partial rows of the images that selected it, images ascending, chunks
+// ascending, one thread per entry (a fixed order: the same inputs give the same bits); a slice no image selected gets +0.0
+__global__ __launch_bounds__(256) void dense_steps_finish_kernel(const float* __restrict__ part, const int32_t* __restrict__ t_int,
+                                                                 float* __restrict__ dw, float* __restrict__ db, int B, int nchunk,
+                                                                 int Cin, int Cout, int steps, int accumulate) {
+  const int nout = (Cin + 1) * Cout, s = blockIdx.y;
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= nout) return;
+  float acc = 0.f;
+  for (int img = 0; img < B; img++) {
+    if (steps_slice(t_int, img, steps) != s) continue;
+    const float* rows = part + (size_t)img * nchunk * nout + e;
+    for (int c = 0; c < nchunk; c++) acc += rows[(size_t)c * nout];
+  }
+  const int my_i = e / Cout, my_o = e - my_i * Cout;
+  float* dst = my_i < Cin ? dw + (my_i * (steps * Cout) + s * Cout + my_o) : (db ? db + (s * Cout + my_o) : nullptr);
+  if (dst) *dst = accumulate ? *dst + acc : acc;
+}
+
 // ---- MSE -----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                   float* __restrict__ dpred, float* __restrict__ partials, size_t n,
@@ -1402,6 +1531,44 @@ int pw_dense_bwd(int dtype, const void* x, int ldx, const float* w, const float*
                        db, M, Cin, Cout, Cmask);
   });
   return gct2_check_launch("dense_bwd");
+}
+// per-timestep heads.  Pixel tile of the backward kernel and the number of work-groups (= partial rows) per image: every tile its
+// own work-group until the grid passes ~2048 work-groups (8 per CU), then a work-group walks several tiles of its image
+constexpr int STEPS_PIX = 128;
+static int dense_steps_chunks(int B, int HW) {
+  const int ntiles = (HW + STEPS_PIX - 1) / STEPS_PIX;
+  return std::min(ntiles, std::max(1, kMaxBlocks / B));
+}
+size_t dense_steps_scratch_floats(int B, int HW, int Cin, int Cout) {
+  return ((size_t)B * dense_steps_chunks(B, HW) * (size_t)((Cin + 1) * Cout) + 3) / 4 * 4;
+}
+int pw_dense_steps_fwd(int dtype, const void* x, int ldx, const float* w, const float* b, const int32_t* t_int, float* y, int B, int HW,
+                       int Cin, int Cout, int steps, hipStream_t s) {
+  const int gx = std::min((HW + 255) / 256, std::max(1, kMaxBlocks / B));
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(dense_steps_fwd_kernel<T>, dim3(gx, B), dim3(256), Cin * 4 * sizeof(float), s, reinterpret_cast<const T*>(x), ldx, w,
+                       b, t_int, y, HW, Cin, Cout, steps);
+  });
+  return gct2_check_launch("dense_steps_fwd");
+}
+int pw_dense_steps_bwd(int dtype, const void* x, int ldx, const float* w, const int32_t* t_int, const float* dy, void* dx, int lddx,
+                       float* dw, float* db, float* scratch, int B, int HW, int Cin, int Cout, int steps, int Cmask, int accumulate,
+                       hipStream_t s) {
+  constexpr int PIX = STEPS_PIX;
+  const int nchunk = dense_steps_chunks(B, HW);
+  const int nout = (Cin + 1) * Cout;
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const size_t lds = (size_t)Cin * 16 + PIX * 16 + (size_t)PIX * Cin * sizeof(T);
+    auto kern = dense_steps_bwd_kernel<T, PIX>;
+    if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kern, dim3(nchunk, B), dim3(256), lds, s, reinterpret_cast<const T*>(x), ldx, w, t_int, dy, reinterpret_cast<T*>(dx),
+                       lddx, scratch, HW, Cin, Cout, steps, Cmask);
+  });
+  hipLaunchKernelGGL(dense_steps_finish_kernel, dim3((nout + 255) / 256, steps), dim3(256), 0, s, scratch, t_int, dw, db, B, nchunk, Cin, Cout,
+                     steps, accumulate);
+  return gct2_check_launch("dense_steps_bwd");
 }
 // the ordered finish of the head's partial rows, also used by the UpShuffle_0 forward that carries the head in its epilogue
 int pw_head_finish(const float* part, int rows, float* dw, float* db, float* loss, float* db_dx, int ndw, int Cout, float inv_n,

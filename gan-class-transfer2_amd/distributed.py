@@ -165,6 +165,14 @@ def _refuse_clipping(engine, who: str) -> None:
                               "exchanged: gradient clipping (set_clipping) is not available there")
 
 
+def _refuse_timestep_heads(engine, who: str) -> None:
+    """the per-timestep heads (an engine built with timestep_heads=True: Dense(3 * steps) gathered by t) are single-GPU only: the
+    gathered head's kernels and its steps-fold gradient range have not been built into or tested with a multi-rank exchange"""
+    if getattr(engine, "timestep_heads", False):
+        raise ValueError(f"{who} has not been built or tested with the per-timestep heads: build the engine with timestep_heads=False "
+                         "(the switch is single-GPU only)")
+
+
 def _refuse_regularizer(engine, who: str) -> str:
     """the L2 weight regularizer and the gradient transformer (set_regularizer / set_gradient_transform) are single-GPU only: they run
     on the non-fused optimizer path through gct2_optimizer_apply_reg, which no multi-rank step has been run or tested with.  Refuses an
@@ -197,6 +205,7 @@ class DataParallelStep:
     UNetEngine.backward has waited for the dgrad launches of every earlier layer - the last readers of their weights."""
 
     def __init__(self, engine, bucket_elems: int = 4 << 20, group=None, force_exchange: bool = False):
+        _refuse_timestep_heads(engine, "DataParallelStep")
         adam_only = _refuse_optimizer(engine, "DataParallelStep")
         no_reg = _refuse_regularizer(engine, "DataParallelStep")
         _refuse_clipping(engine, "DataParallelStep")
@@ -298,6 +307,7 @@ class ShardedDataParallelStep:
     kernels behind the last bucket's reduce-scatter / all-gather."""
 
     def __init__(self, engine, bucket_elems: int = 4 << 20, group=None, force_exchange: bool = False, tail_layers: int = 3):
+        _refuse_timestep_heads(engine, "ShardedDataParallelStep")
         adam_only = _refuse_optimizer(engine, "ShardedDataParallelStep")
         no_reg = _refuse_regularizer(engine, "ShardedDataParallelStep")
         _refuse_clipping(engine, "ShardedDataParallelStep")

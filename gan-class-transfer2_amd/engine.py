@@ -26,6 +26,7 @@ from . import _lib
 from ._lib import BF16, F16, F32, Slot, call
 from .trainer_math import TrainerState, glorot_limit
 from .trainer_math import ema_coefficients as TM_ema_coefficients
+from .trainer_math import check_timesteps as TM_check_timesteps
 from .trainer_math import OPTIMIZER_KINDS as _OPTIMIZER_CODES
 
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
@@ -54,15 +55,16 @@ class Topology:
     def up_in(self, i: int) -> int:
         return self.fd(i) if i == self.octaves - 1 else self.fu(i + 1) + self.fd(i)
 
-    def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
+    def param_shapes(self, head_units: int = 3) -> Dict[str, Tuple[int, ...]]:
+        """head_units: 3 for Dense(3), 3 * steps for the per-timestep heads (train.py:199)"""
         s: Dict[str, Tuple[int, ...]] = {}
         for i in range(self.octaves):
             s[f"D{i}.w"] = (4, 4, self.cx(i), self.fd(i))
             s[f"D{i}.b"] = (self.fd(i),)
             s[f"U{i}.w"] = (4, 4, self.fu(i), self.up_in(i))
             s[f"U{i}.b"] = (self.fu(i),)
-        s["dense.w"] = (self.fu(0) + 3, 3)
-        s["dense.b"] = (3,)
+        s["dense.w"] = (self.fu(0) + 3, head_units)
+        s["dense.b"] = (head_units,)
         return s
 
     def backward_order(self) -> List[str]:
@@ -81,9 +83,9 @@ class Topology:
 class ParamArena:
     ALIGN = 64  # elements; keeps every tensor 16-byte aligned in the 16-bit shadow too
 
-    def __init__(self, topo: Topology, dtype: int, device: torch.device):
+    def __init__(self, topo: Topology, dtype: int, device: torch.device, head_units: int = 3):
         self.topo, self.dtype, self.device = topo, dtype, device
-        self.shapes = topo.param_shapes()
+        self.shapes = topo.param_shapes(head_units)
         self.offsets: Dict[str, int] = {}
         off = 0
         # Layout (r04): the convolution kernels first, in backward completion order (U_0 .. U_{n-1}, D_{n-1} .. D_0: a gradient bucket
@@ -301,10 +303,13 @@ class UNetEngine(TrainerState):
                  epsilon: float = 1e-7, loss_scaling: bool = False, seed: int = 1234, rng_seed: int = 0,
                  workspace_mb: int = 64, predict_x: bool = True, predict_scaled_epsilon: bool = False,
                  prediction_weighting: bool = False, ordinary_differential_equation: bool = False, f32_matrix: bool = False,
-                 use_ema: bool = False, ema_momentum: float = 0.99):
+                 use_ema: bool = False, ema_momentum: float = 0.99, timestep_heads: bool = False):
         super().__init__(dtype, device, steps, base_lr, warm_up, beta_1, beta_2, epsilon, loss_scaling, rng_seed, predict_x,
                          predict_scaled_epsilon, prediction_weighting, ordinary_differential_equation, f32_matrix)
         self.topo = topo
+        # per-timestep heads (train.py:199, 203, 211-214): dense.w is (Fu_0 + 3, 3 * steps), the head runs unfused through
+        # gct2_dense_steps_fwd / gct2_dense_steps_bwd on the slice t_int - 1 of every image.  Fixed here: it decides the arena layout
+        self.timestep_heads = bool(timestep_heads)
         self.use_fused_head = True     # False: dense_fwd + mse_fwd_bwd + dense_bwd as three kernels
         self.fuse_u0_head = True       # train step: the head runs in UpShuffle_0's forward epilogue (R_0 is never written)
         self.keep_pred = False         # train step: also store the prediction (buffers().pred); the loss does not need it
@@ -312,7 +317,7 @@ class UNetEngine(TrainerState):
         # epilogues read their masks from them instead of re-reading the activations (gct2_ctx_set_relu_bits; -16 bits per element read)
         self.relu_bits = True
         self.relu_bits_min_bytes = 32 << 20     # planes only for activation tensors of at least this size (see buffers())
-        self.arena = ParamArena(topo, dtype, self.device)
+        self.arena = ParamArena(topo, dtype, self.device, self.head_shapes(topo.fu(0) + 3)[1][0])
         self.arena.glorot_init(seed)
         self.arena.refresh_shadow(self._stream())
         # activation / gradient buffer sets by (B, H, W), least recently used first; at most `max_buffer_sets` stay allocated (the
@@ -584,7 +589,7 @@ class UNetEngine(TrainerState):
         b.t_int = z(B, dtype=torch.int32)
         b.loss = z(1, dtype=torch.float32)
         b.partials = z(1024, dtype=torch.float32)
-        b.loss_store = {}               # scratch (and the DCT basis) of the non-default training losses, allocated on first use
+        b.loss_store = {}               # scratch (and the DCT basis) of the non-default training losses and of gct2_dense_steps_bwd, allocated on first use
         self._bufs[key] = b
         return b
 
@@ -708,6 +713,10 @@ class UNetEngine(TrainerState):
         if not head:
             return b.pred
         M = b.B * b.H * b.W                                     # Dense(3)       (train.py:198-202)
+        if self.timestep_heads:                                 # Dense(3 * steps) gathered by t (train.py:199, 203, 211-214): b.t_int picks the slices
+            call("gct2_dense_steps_fwd", cx, dt, b.R[0].data_ptr(), b.ld[0], A.pptr("dense.w"), A.pptr("dense.b"), b.t_int.data_ptr(),
+                 b.pred.data_ptr(), b.B, b.H * b.W, t.fu(0) + 3, 3, self.steps, s)
+            return b.pred
         call("gct2_dense_fwd", dt, b.R[0].data_ptr(), b.ld[0], A.pptr("dense.w"), A.pptr("dense.b"), b.pred.data_ptr(),
              M, t.fu(0) + 3, 3, s)
         return b.pred
@@ -752,7 +761,7 @@ class UNetEngine(TrainerState):
         (Fu_0 = 64) in a 16-bit mode with a workspace and the MSE loss the head kernels carry; anything else runs dense_fwd + the loss
         (gct2_mse_fwd_bwd, or gct2_loss_fwd_bwd for the other training losses) + dense_bwd."""
         return (self.use_fused_head and self.dtype != F32 and self.topo.fu(0) == 64 and self.workspace is not None
-                and not self.objective_weighted() and self.training_loss == "mse")
+                and not self.objective_weighted() and self.training_loss == "mse" and not self.timestep_heads)
 
     def head_train(self, b: _Buffers, target: torch.Tensor, target_is_x: bool = False) -> torch.Tensor:
         """Dense(3) + fp32 MSE + both of their gradients in one pass over R_0 (gct2_dense_head_train)."""
@@ -836,7 +845,12 @@ class UNetEngine(TrainerState):
         side = self._side if self.overlap else main
         s, sw = main.cuda_stream, side.cuda_stream
         M = b.B * b.H * b.W
-        if not head_done:
+        if not head_done and self.timestep_heads:               # the gathered head: every slice of dw / db written, no atomics
+            scratch = self._steps_scratch(b.loss_store, b.B, b.H * b.W, t.fu(0) + 3)
+            call("gct2_dense_steps_bwd", cx, dt, b.R[0].data_ptr(), b.ld[0], A.pptr("dense.w"), b.t_int.data_ptr(), b.dpred.data_ptr(),
+                 b.dR[0].data_ptr(), b.ldd[0], A.gptr("dense.w"), A.gptr("dense.b"), scratch.data_ptr(), scratch.numel(), b.B, b.H * b.W,
+                 t.fu(0) + 3, 3, self.steps, t.fu(0), 0, s)
+        elif not head_done:
             call("gct2_dense_bwd", dt, b.R[0].data_ptr(), b.ld[0], A.pptr("dense.w"), b.dpred.data_ptr(), b.dR[0].data_ptr(),
                  b.ldd[0], A.gptr("dense.w"), A.gptr("dense.b"), M, t.fu(0) + 3, 3, t.fu(0), 0, s)
         self._ready("dense", main)                              # hooks record their events on the stream the gradients come from
@@ -1085,7 +1099,7 @@ class UNetEngine(TrainerState):
                 self.dtype, float(self.beta_1), float(self.beta_2), float(self.epsilon), float(self.base_lr), int(self.warm_up),
                 id(self.post_replay), self._side.cuda_stream, self.use_ema, float(self.ema_momentum), self.clip_mode, float(self.clip),
                 self.optimizer_kind, float(self.momentum), bool(self.nesterov), float(self.rho), self.lr_schedule, self.training_loss,
-                float(self.l2), self.grad_transform,
+                float(self.l2), self.grad_transform, self.timestep_heads,
                 self._chain_stream.cuda_stream if self._chain_stream is not None else 0)
 
     def _planned_step(self, b: _Buffers, x: torch.Tensor, apply: bool, inline: bool, cur: "torch.cuda.Stream") -> torch.Tensor:
@@ -1179,13 +1193,21 @@ class UNetEngine(TrainerState):
             self.post_replay()
         return sp.loss
 
-    def predict(self, noised: torch.Tensor, use_ema: bool = False) -> torch.Tensor:
-        """use_ema: evaluate the averaged weights (ema_weights()) instead of the raw iterate"""
+    def predict(self, noised: torch.Tensor, t=None, use_ema: bool = False) -> torch.Tensor:
+        """use_ema: evaluate the averaged weights (ema_weights()) instead of the raw iterate.  t: the timestep(s) of the batch, one int
+        or B of them in 1..steps (trainer_math.check_timesteps) - required by the per-timestep heads, which pick their weight slice
+        by it; accepted and ignored without them (train.py:207: "t is ignored")"""
+        if self.timestep_heads and t is None:
+            raise ValueError("predict: an engine built with timestep_heads=True needs the timestep(s) t of the batch (1..steps)")
         if use_ema:
             with self.ema_weights():
-                return self.predict(noised)
+                return self.predict(noised, t)
         B, H, W, _ = noised.shape
+        if self.timestep_heads:
+            vals = TM_check_timesteps(t, B, self.steps)           # (ValueError before a buffer set is allocated or anything is launched)
         b = self.buffers(B, H, W)
+        if self.timestep_heads:
+            b.t_int.copy_(torch.tensor(vals, dtype=torch.int32))
         self.load_input_into_r0(b, noised)
         return self.forward(b)
 
@@ -1208,6 +1230,8 @@ class UNetEngine(TrainerState):
         if self.optimizer_kind != "adam":       # (only then: an Adam engine's dictionary is what it always was)
             sd["optimizer"] = torch.tensor([_OPTIMIZER_CODES[self.optimizer_kind], float(self.momentum), float(bool(self.nesterov)), float(self.rho)],
                                            dtype=torch.float64)
+        if self.timestep_heads:         # (only then; load_state_dict refuses a checkpoint whose head has the other shape)
+            sd["timestep_heads"] = torch.tensor([self.steps], dtype=torch.int64)
         if self.use_ema:                # (only then: without the averages the dictionary is what it always was)
             sd["arena.ema"] = A.ema.cpu()
             sd["ema_momentum"] = torch.tensor([float(self.ema_momentum)], dtype=torch.float64)      # (restored by load_state_dict)
@@ -1267,6 +1291,11 @@ class UNetEngine(TrainerState):
                 raise ValueError(f"checkpoint topology {have[:3]} != engine {want[:3]}")
             sd = self._convert_legacy_layout(sd)
             have = [int(v) for v in sd["topology"]]
+        heads = int(sd["timestep_heads"][0]) if "timestep_heads" in sd else 0
+        if heads != (self.steps if self.timestep_heads else 0):
+            say = lambda n: f"per-timestep heads, Dense(3 * {n})" if n else "the plain Dense(3) head"
+            raise ValueError(f"the checkpoint holds {say(heads)} and this engine {say(self.steps if self.timestep_heads else 0)}: dense.w / "
+                             "dense.b have different shapes (timestep_heads is fixed when an engine is built; nothing is loaded)")
         if have != want:
             raise ValueError(f"checkpoint topology / layout {have} != engine {want}")
         if ("loss_scale_state" in sd) != (self.ls_state is not None):

@@ -51,6 +51,12 @@ training_loss = "mse"
 # Trainer reads it before every step, like training_loss
 regularizer = None
 
+# train.py:199, 203, 211-214: the commented-out per-timestep heads - `Dense(3,# * steps, ...`, `#tf.keras.layers.Reshape((size, size,
+# steps, 3))` and `#prediction = tf.gather(prediction, t - 1, batch_dims=3)`.  True: the Denoiser's head is Dense(3 * steps) and every
+# image reads the three outputs of its own timestep, so t finally reaches the network (gct2_dense_steps_fwd / gct2_dense_steps_bwd).
+# Read when a Denoiser is constructed (it decides the head's shape); single GPU, non-fused head, parity unpinned (no TensorFlow here)
+timestep_heads = False
+
 warm_up = 2_000
 
 # MI355X knob: None -> float32, or float16 when mixed_precision (train.py:38); "bfloat16" selects the
@@ -475,9 +481,10 @@ class Dense(Layer):
     """tf.keras.layers.Dense(units) on a rank-4 input: the Dense(3) head (train.py:198-202; fp32 output for the fp32 loss) and,
     with use_bias=False, the projection of Residual's residual=True mode (train.py:106; a 1 x 1 convolution in the compute dtype)."""
 
-    def __init__(self, units, use_bias=True):
+    def __init__(self, units, use_bias=True, gather_steps: int = 0):
         self.units = units
         self.use_bias = use_bias
+        self.gather_steps = gather_steps      # > 0: the per-timestep head Dense(3 * steps), evaluated by gather() on one slice per image
         self.kernel = None
         self.bias = None
         self.dtype_code = preferred_dtype_code()
@@ -499,11 +506,33 @@ class Dense(Layer):
             call("gct2_dense_fwd", self.dtype_code, x.data_ptr(), C, self.kernel.data_ptr(), self.bias.data_ptr(), y.data_ptr(),
                  M, C, self.units, _stream(x))
             return y
+        if self.gather_steps:
+            raise _lib.Gct2Error("the per-timestep head needs the timesteps of the batch: Dense.gather(input, t_int)")
         w = self.kernel if self.dtype_code == F32 else self.kernel.to(TORCH_DTYPE[self.dtype_code])
         y = torch.empty(*x.shape[:-1], self.units, dtype=x.dtype, device=x.device)
         call("gct2_conv2d_s1_fwd", None, self.dtype_code, x.data_ptr(), C, w.data_ptr(), self.bias.data_ptr() if self.bias is not None else None,
              y.data_ptr(), self.units, M, 1, 1, C, self.units, 1, 0, _stream(x))
         return y
+
+    def gather(self, input, t_int: torch.Tensor):
+        """Dense + Reshape(.., steps, units / steps) + tf.gather(.., t - 1, batch_dims=3) (train.py:199, 203, 211-214) without forming
+        the steps-fold output: image i gets the outputs of slice t_int[i] - 1 (gct2_dense_steps_fwd).  t_int: device int32[B] in
+        1..steps; fp32 [B,H,W,units / steps]"""
+        x = _as_compute(input, self.dtype_code)
+        B, C = x.shape[0], x.shape[-1]
+        cout = self.units // self.gather_steps
+        y = torch.empty(*x.shape[:-1], cout, dtype=torch.float32, device=x.device)
+        call("gct2_dense_steps_fwd", None, self.dtype_code, x.data_ptr(), C, self.kernel.data_ptr(), self.bias.data_ptr() if self.bias is not None else None,
+             t_int.data_ptr(), y.data_ptr(), B, x.numel() // (B * C), C, cout, self.gather_steps, _stream(x))
+        return y
+
+
+def _timesteps(t, batch: int, nsteps: int) -> List[int]:
+    """the t of Denoiser.call((x, t)) as `batch` checked ints: [B,1,1,1] from Trainer.call, [1] from log_sample (broadcast over the
+    batch, train.py:207-209), a plain int or a sequence"""
+    if torch.is_tensor(t):
+        t = t.reshape(-1)
+    return trainer_math.check_timesteps(t, batch, nsteps)
 
 
 # ---- the model (train.py:175-283) -------------------------------------------------------------------------
@@ -533,7 +562,9 @@ class Denoiser(Layer):
                     self.ups[i],
                 ])
             )
-        self.head = Dense(3)
+        # train.py:199, 203: Dense(3 * steps) + Reshape when the module switch is on (read here, like the reference's constructor would)
+        self.timestep_heads, self._steps = bool(timestep_heads), steps
+        self.head = Dense(3 * steps, gather_steps=steps) if self.timestep_heads else Dense(3)
         self.middle = Sequential([
             Block(pixel_size),
             self.middle,
@@ -556,6 +587,8 @@ class Denoiser(Layer):
         # no optimizer known yet (train.py:505-509 calls the model before compile): the module-level mixed_precision
         # decides about loss scaling, as it decides about the LossScaleOptimizer wrapper in train.py:82-83
         kw = dict(steps=steps, warm_up=warm_up, seed=self._seed, loss_scaling=bool(mixed_precision), **objective_switches())
+        if self.timestep_heads:                       # (the head's shape was fixed when this Denoiser was constructed)
+            kw.update(steps=self._steps, timestep_heads=True)
         if self.dtype_code == F32:
             kw["f32_matrix"] = bool(f32_matrix_cores)
         kw.update(engine_kw)
@@ -618,14 +651,21 @@ class Denoiser(Layer):
         return {k: A.param(k) for k in A.shapes}
 
     def call(self, input):
-        x, t = input            # t is ignored by the reference as well (train.py:208-210)
+        x, t = input            # t is ignored by the reference as well (train.py:208-210) - unless the per-timestep heads are on
         eng = self.ensure_engine()
+        if self.timestep_heads:                      # train.py:211-214: tf.gather(prediction, t - 1, batch_dims=3)
+            return eng.predict(x, _timesteps(t, x.shape[0], eng.steps)).clone()
         return eng.predict(x).clone()
 
     def call_eager(self, input):
         """the reference's literal layer-by-layer evaluation of self.middle (train.py:210)."""
         x, t = input
-        self.ensure_engine()
+        eng = self.ensure_engine()
+        if self.timestep_heads:                      # everything up to the head, then the head on each image's own slice
+            vals = _timesteps(t, x.shape[0], eng.steps)
+            for layer in self.middle.layers[:-1]:
+                x = layer(x)
+            return self.head.gather(x, torch.tensor(vals, dtype=torch.int32).to(x.device))
         return self.middle(x)
 
 
@@ -660,6 +700,11 @@ class Trainer(Layer):
             _supported_learning_rate(kw)
             kw["loss_scaling"] = bool(getattr(opt, "inner", opt).loss_scaling)
         l2 = regularizer_l2(regularizer)                 # anything but None / regularizers.l2: NotImplementedError, before anything is built
+        built = getattr(getattr(self.denoiser, "engine", None), "timestep_heads", getattr(self.denoiser, "timestep_heads", None))
+        if built is not None and bool(timestep_heads) != bool(built):       # (the head's shape is fixed with the Denoiser and its engine)
+            raise ValueError(f"timestep_heads = {bool(timestep_heads)} now, but the Denoiser (and the engine behind it) was built with "
+                             f"timestep_heads = {bool(built)}: the switch decides the shape of the Dense head "
+                             "(train.py:199) - construct a new Denoiser after changing it")
         clipped = kw.pop("clip_mode", None) is not None
         kw.pop("clip", None)
         transform = kw.pop("grad_transform", None)

@@ -22,6 +22,7 @@ from . import model as M
 from ._lib import SAMPLE_EPS, SAMPLE_ODE, SAMPLE_SCALED_EPS, SAMPLE_X, call
 from .engine import TORCH_DTYPE, UNetEngine
 from .trainer_math import alpha_dash            # train.py:85-93 on python floats, as in the reference
+from .trainer_math import check_timesteps
 
 
 def sample_mode(predict_x: bool, predict_scaled_epsilon: bool, ordinary_differential_equation: bool) -> int:
@@ -52,6 +53,11 @@ class _Sampler:
         if self.planned and not hasattr(eng, "_forward_graphs"):
             eng._forward_graphs = {}
         self._inputs: Dict[int, torch.Tensor] = {}
+        # per-timestep heads (train.py:199, 203, 211-214): the network reads t.  The planned engine's head takes it from the buffer
+        # set's device-resident t_int, a fixed address the captured graph reads too: set_t fills it with an ordinary launch in front
+        # of the evaluation, outside the graph.  Without the switch nothing is launched for t (train.py:207: "t is ignored")
+        self.heads = bool(getattr(eng, "timestep_heads", False))
+        self._t: Dict[int, int] = {}
 
     # ---- network evaluation ---------------------------------------------------------------------------------------------
     def _graph_for(self, b):
@@ -85,12 +91,22 @@ class _Sampler:
         cache[(id(b), version, averaged)] = (g, b)
         return None                             # this evaluation has already run (the warm-up call above)
 
+    def set_t(self, B: int, t: int) -> None:
+        """the timestep of the next evaluation at batch B (tf.constant([t]), broadcast over the batch): checked on the host against
+        1..steps of the engine (ValueError), then written where the head kernels read it"""
+        if not self.heads:
+            return
+        (t,) = check_timesteps(t, 1, self.eng.steps)
+        self._t[B] = t
+        if self.planned:
+            self.eng.buffers(B, self.H, self.W).t_int.fill_(t)
+
     def evaluate(self, B: int) -> torch.Tensor:
-        """denoiser((fake, t)) on the image gct2_diffusion_mix has just stored: t is ignored (train.py:208-210).  Returns the fp32
-        prediction [B,H,W,3] (valid until the next evaluation)."""
+        """denoiser((fake, t)) on the image gct2_diffusion_mix has just stored: t is ignored (train.py:208-210) unless the engine
+        carries the per-timestep heads (set_t).  Returns the fp32 prediction [B,H,W,3] (valid until the next evaluation)."""
         eng = self.eng
         if not self.planned:
-            return eng.predict(self._inputs[B])
+            return eng.predict(self._inputs[B], self._t[B]) if self.heads else eng.predict(self._inputs[B])
         b = eng.buffers(B, self.H, self.W)
         eng.flush_deferred()                     # optimizer launches the last train step held back: never inside a captured graph
         if not self.use_graph:
@@ -129,6 +145,7 @@ class _Sampler:
     def step(self, B: int, x, e, fake, t: int) -> None:
         a = alpha_dash(t, self.steps)
         self.mix(B, x, e, a, fake)
+        self.set_t(B, t)
         pred = self.evaluate(B)
         # ODE mode leaves epsilon_theta alone (train.py:382-392: only x_theta is assigned; `fake = ...` there is dead, the next
         # iteration recomputes it)
@@ -191,6 +208,7 @@ def _log_sample(eng, example_image, example, dictionary, steps, test_step, predi
         a_t, a_prev = factor, 0.0
     fake = torch.empty_like(image)
     S.mix(1, image, example[0, :1].contiguous(), factor, fake)
+    S.set_t(1, test_step)                       # tf.constant([test_step]) also in ODE mode, which mixes at steps / 2 (train.py:335)
     # (never through the graph: the first evaluation of a buffer set is the capture's warm-up anyway)
     pred = eng.forward(eng.buffers(1, H, W)) if S.planned else S.evaluate(1)
     denoised, scratch = torch.empty_like(image), torch.empty_like(image)

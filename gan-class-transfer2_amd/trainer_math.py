@@ -182,6 +182,37 @@ def training_loss_code(name: str) -> int:
     return _LOSS_CODES[name]
 
 
+def check_timesteps(t, batch: int, steps: int) -> list:
+    """the timesteps of a batch for the per-timestep heads (train.py:211-214: tf.gather(prediction, t - 1, batch_dims=3)) as a list
+    of `batch` Python ints in 1..steps.  t: one integer (every image), or a sequence / tensor / array of `batch` integers (a single
+    element broadcasts, like the [1] tensor of log_sample).  ValueError for anything else: a float, a bool, a wrong length, a value
+    outside 1..steps - the gather of the reference would read past the tensor there"""
+    if torch.is_tensor(t):
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+            raise ValueError(f"timesteps must be integers, got a tensor of {t.dtype}")
+        vals = t.detach().reshape(-1).cpu().tolist()
+    elif isinstance(t, np.ndarray):
+        if not np.issubdtype(t.dtype, np.integer):
+            raise ValueError(f"timesteps must be integers, got an array of {t.dtype}")
+        vals = t.reshape(-1).tolist()
+    elif isinstance(t, (list, tuple)):
+        vals = list(t)
+    else:
+        vals = [t]
+    for v in vals:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"timesteps must be integers, got {v!r}")
+    if len(vals) == 1:
+        vals = vals * batch
+    if len(vals) != batch:
+        raise ValueError(f"{len(vals)} timesteps for a batch of {batch}")
+    vals = [int(v) for v in vals]
+    for v in vals:
+        if not 1 <= v <= steps:
+            raise ValueError(f"timestep {v} outside 1..{steps}")
+    return vals
+
+
 def dct_basis(size: int) -> np.ndarray:
     """G of gct2_loss_fwd_bwd's DCT kind for the reference's dct2d (train.py:254-260): tf.signal.dct(norm='ortho') [TF] times
     frequency_weights = 1 / (k + 1), G[k, m] = 1/(k+1) * sigma_k * cos(pi (2m + 1) k / (2 size)), sigma_0 = sqrt(1/size), else
@@ -222,6 +253,11 @@ class TrainerState:
     l2, grad_transform = 0.0, "none"
     _l2_state = None
     _reg_tables = None
+    # per-timestep output heads (train.py:199, 203, 211-214: Dense(3 * steps), Reshape(.., steps, 3), tf.gather(prediction, t - 1,
+    # batch_dims=3)): off by default; an ENGINE CONSTRUCTOR argument, because it decides the shape of dense.w / dense.b and with them
+    # the arena layout.  With it on the head runs on the non-fused path through gct2_dense_steps_fwd / gct2_dense_steps_bwd, which
+    # read the device-resident t_int of the step (or the one predict / the sampler wrote); single GPU only
+    timestep_heads = False
 
     @property
     def _ema(self) -> Optional[torch.Tensor]:
@@ -313,6 +349,21 @@ class TrainerState:
         code, scratch, basis = self._loss_resources(store, B, H, W, Cc)
         call("gct2_loss_fwd_bwd", code, pred.data_ptr(), target, dpred.data_ptr() if dpred is not None else None, loss.data_ptr(),
              scratch.data_ptr(), scratch.numel(), B, H, W, Cc, basis.data_ptr() if basis is not None else None, self._ls_ptr(), stream)
+
+    # ---- per-timestep heads (train.py:199, 203, 211-214) ------------------------------------------------------------------------
+    def head_shapes(self, cin: int) -> Tuple[Tuple[int, int], Tuple[int]]:
+        """(kernel, bias) shapes of the Dense head on `cin` channels: Dense(3), or Dense(3 * steps) with timestep_heads"""
+        units = 3 * self.steps if self.timestep_heads else 3
+        return (cin, units), (units,)
+
+    def _steps_scratch(self, store: dict, B: int, HW: int, cin: int) -> torch.Tensor:
+        """scratch of gct2_dense_steps_bwd for this shape (the partial rows of dw / db), allocated on first use and kept in `store`"""
+        key = ("dense_steps", B, HW, cin)
+        if key not in store:
+            need = C.c_size_t(0)
+            _lib.check(self.lib.gct2_dense_steps_scratch(B, HW, cin, 3, C.byref(need)), "gct2_dense_steps_scratch")
+            store[key] = torch.zeros(need.value, dtype=torch.float32, device=self.device)
+        return store[key]
 
     # ---- optimizer (train.py:50-65,75) ---------------------------------------------------------------------------------------
     def learning_rate(self, k: Optional[int] = None) -> float:

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import BF16, F16, F32, call
-from .trainer_math import TrainerState, glorot_limit
+from .trainer_math import TrainerState, check_timesteps, glorot_limit
 
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 
@@ -35,6 +35,8 @@ class _Net:
         self.offsets: Dict[str, int] = {}
         self.total = 0
         self.ctx = ctx
+        self.t_int: Optional[torch.Tensor] = None      # device int32[B]: the timesteps of the batch in flight (per-timestep heads)
+        self.steps_scratch = None                      # (B, HW, cin) -> scratch tensor of gct2_dense_steps_bwd (the engine's allocator)
         self.unregularized: set = set()      # tensors built without kernel_regularizer (Residual's projection, train.py:107)
 
     def declare(self, name: str, shape: Tuple[int, ...]) -> str:
@@ -198,16 +200,27 @@ class _Residual:
 
 
 class _Head:
-    """Dense(3) (train.py:198-202): fp32 output for the fp32 loss (train.py:262-263)."""
+    """Dense(3) (train.py:198-202): fp32 output for the fp32 loss (train.py:262-263).  steps > 0: the per-timestep heads
+    (train.py:199, 203, 211-214) - Dense(3 * steps) whose slice t_int - 1 is picked per image inside gct2_dense_steps_fwd / _bwd;
+    net.t_int (device int32[B], set by the engine before the forward pass) holds the timesteps."""
 
-    def __init__(self, net: _Net, cin: int):
-        self.net, self.cin = net, cin
-        self.w, self.b = net.declare("dense.w", (cin, 3)), net.declare("dense.b", (3,))
+    def __init__(self, net: _Net, cin: int, steps: int = 0):
+        self.net, self.cin, self.steps = net, cin, steps
+        units = 3 * steps if steps else 3
+        self.w, self.b = net.declare("dense.w", (cin, units)), net.declare("dense.b", (units,))
 
     def fwd(self, x):
         n = self.net
         M = x.numel() // self.cin
         y = torch.empty(*x.shape[:-1], 3, dtype=torch.float32, device=x.device)
+        if self.steps:
+            B = x.shape[0]
+            if n.t_int is None or n.t_int.numel() != B:
+                raise _lib.Gct2Error(f"the per-timestep heads need one timestep per image: {0 if n.t_int is None else n.t_int.numel()} for a batch of {B}")
+            call("gct2_dense_steps_fwd", n.ctx.handle, n.dtype, x.data_ptr(), self.cin, n.pptr(self.w), n.pptr(self.b), n.t_int.data_ptr(),
+                 y.data_ptr(), B, M // B, self.cin, 3, self.steps, n.stream())
+            self.x = x
+            return y
         call("gct2_dense_fwd", n.dtype, x.data_ptr(), self.cin, n.pptr(self.w), n.pptr(self.b), y.data_ptr(), M, self.cin, 3, n.stream())
         self.x = x
         return y
@@ -219,6 +232,8 @@ class _Head:
         n, x = self.net, self.x
         B, H, W, C = x.shape
         M = B * H * W
+        if self.steps:
+            return self._bwd_steps(dpred)
         dummy = torch.empty(8, dtype=x.dtype, device=x.device)
         call("gct2_dense_bwd", n.dtype, x.data_ptr(), C, n.pptr(self.w), dpred.data_ptr(), dummy.data_ptr(), 0, n.gptr(self.w), n.gptr(self.b),
              M, C, 3, 0, 0, n.stream())
@@ -229,8 +244,29 @@ class _Head:
         self.x = None
         return dx
 
+    def _bwd_steps(self, dpred):
+        """the gathered head: kernel / bias gradients of every slice from gct2_dense_steps_bwd (no input gradient there: its ReLU mask
+        belongs to the planned engine's layout); the input gradient per image through the 1 x 1 convolution entry point on that
+        image's slice of the operand copy (gathered on the device, t_int clamped as the kernels clamp it: memory movement only)."""
+        n, x = self.net, self.x
+        B, H, W, C = x.shape
+        sc = n.steps_scratch(B, H * W, C)                       # (kept by the engine per shape)
+        call("gct2_dense_steps_bwd", n.ctx.handle, n.dtype, x.data_ptr(), C, n.pptr(self.w), n.t_int.data_ptr(), dpred.data_ptr(), None, 0,
+             n.gptr(self.w), n.gptr(self.b), sc.data_ptr(), sc.numel(), B, H * W, C, 3, self.steps, 0, 0, n.stream())
+        dz = dpred.to(x.dtype)
+        dx = torch.empty_like(x)
+        s_idx = (n.t_int.long() - 1).clamp_(0, self.steps - 1)
+        op = n.view(n.ema_op if n.read_ema else n.op, self.w).view(C, self.steps, 3)
+        w_img = op.index_select(1, s_idx).permute(1, 0, 2).contiguous()                # [B, C, 3]: image i's slice
+        for i in range(B):
+            call("gct2_conv2d_s1_dgrad", n.ctx.handle, n.dtype, dz[i].data_ptr(), 3, w_img[i].data_ptr(), None, 0, dx[i].data_ptr(), C, 1, H, W,
+                 C, 3, 1, 0, n.stream())
+        self.x = None
+        return dx
 
-def build_structure(net: _Net, pixel_size: int, max_size: int, octaves: int, block_depth: int, residual: bool, concat: bool):
+
+def build_structure(net: _Net, pixel_size: int, max_size: int, octaves: int, block_depth: int, residual: bool, concat: bool,
+                    head_steps: int = 0):
     """Denoiser.__init__ (train.py:175-204) with every switch honoured; returns (top sequential, channel count fed to Dense(3))."""
 
     def block(name: str, cin: int, filters: int):
@@ -262,7 +298,7 @@ def build_structure(net: _Net, pixel_size: int, max_size: int, octaves: int, blo
     else:
         mid, c = block("blkMid", c, min(pixel_size, max_size))
     b1, c = block("blkTopB", c, pixel_size)                                                   # train.py:194
-    head = _Head(net, c)
+    head = _Head(net, c, head_steps)
     return _Seq([b0, mid, b1, head]), c
 
 
@@ -275,16 +311,20 @@ class VariantEngine(TrainerState):
                  beta_2: float = 0.999, epsilon: float = 1e-7, loss_scaling: bool = False, seed: int = 1234, rng_seed: int = 0,
                  predict_x: bool = True, predict_scaled_epsilon: bool = False, prediction_weighting: bool = False,
                  ordinary_differential_equation: bool = False, f32_matrix: bool = False, use_ema: bool = False,
-                 ema_momentum: float = 0.99):
+                 ema_momentum: float = 0.99, timestep_heads: bool = False):
         super().__init__(dtype, device, steps, base_lr, warm_up, beta_1, beta_2, epsilon, loss_scaling, rng_seed, predict_x,
                          predict_scaled_epsilon, prediction_weighting, ordinary_differential_equation, f32_matrix)
         self.octaves = octaves
+        self.timestep_heads = bool(timestep_heads)      # train.py:199, 203, 211-214; fixed here: it decides the shape of dense.w / dense.b
         # one call context for the train step and for predict (the sampler): with f32_matrix every fp32 convolution runs on the
         # matrix cores, and the workspace below doubles as their split-K and weight-gradient scratch
         self.net = _Net(dtype, self.device, self._new_ctx())
         self.workspace = torch.empty(16 << 18, dtype=torch.float32, device=self.device)
         self.net.ctx.set_workspace(self.workspace)
-        self.top, self.head_cin = build_structure(self.net, pixel_size, max_size, octaves, block_depth, residual, concat)
+        self.top, self.head_cin = build_structure(self.net, pixel_size, max_size, octaves, block_depth, residual, concat,
+                                                  steps if self.timestep_heads else 0)
+        self._steps_store: dict = {}
+        self.net.steps_scratch = lambda B, HW, cin: self._steps_scratch(self._steps_store, B, HW, cin)
         self.net.allocate()
         self.glorot_init(seed)
         self.partials = torch.zeros(1024, dtype=torch.float32, device=self.device)
@@ -400,6 +440,7 @@ class VariantEngine(TrainerState):
         if regularized:
             self._penalty_begin(s)
         noised, t_int, eps = self._noised(x, t_int, eps)
+        self.net.t_int = t_int                                 # (the per-timestep heads read it inside their kernels)
         pred = self.top.fwd(noised)
         target, w = self._objective(x, t_int, eps)
         if w is not None:
@@ -437,9 +478,14 @@ class VariantEngine(TrainerState):
              0.0 if self.ls_state is not None else self.adam_alpha(), self.beta_1, self.beta_2, self.epsilon, 1.0, self._ls_ptr(), 0, s)
         self.finish_step()
 
-    def predict(self, noised: torch.Tensor, use_ema: bool = False) -> torch.Tensor:
-        """use_ema: evaluate the averaged weights (ema_weights()) instead of the raw iterate"""
+    def predict(self, noised: torch.Tensor, t=None, use_ema: bool = False) -> torch.Tensor:
+        """use_ema: evaluate the averaged weights (ema_weights()) instead of the raw iterate.  t: the timestep(s) of the batch, one int
+        or B of them in 1..steps - required by the per-timestep heads, accepted and ignored without them (as UNetEngine.predict)"""
+        if self.timestep_heads and t is None:
+            raise ValueError("predict: an engine built with timestep_heads=True needs the timestep(s) t of the batch (1..steps)")
         if use_ema:
             with self.ema_weights():
-                return self.predict(noised)
+                return self.predict(noised, t)
+        if self.timestep_heads:
+            self.net.t_int = torch.tensor(check_timesteps(t, noised.shape[0], self.steps), dtype=torch.int32).to(self.device)
         return self.top.fwd(noised.to(self.device, TORCH_DTYPE[self.dtype]).contiguous())

@@ -37,7 +37,7 @@ enum {
 };
 
 /* library / device identification ------------------------------------------------------------ */
-int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive); v17 + gct2_sumsq_layout, gct2_grad_sumsq, gct2_adam_keras_clipped (additive); v17 + gct2_optimizer_apply, gct2_loss_scale_begin_schedule (additive); v17 + gct2_loss_scratch, gct2_loss_fwd_bwd (additive); v17 + gct2_optimizer_apply_reg, gct2_grad_sumsq_l2, gct2_l2_penalty (additive)) */
+int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive); v17 + gct2_sumsq_layout, gct2_grad_sumsq, gct2_adam_keras_clipped (additive); v17 + gct2_optimizer_apply, gct2_loss_scale_begin_schedule (additive); v17 + gct2_loss_scratch, gct2_loss_fwd_bwd (additive); v17 + gct2_optimizer_apply_reg, gct2_grad_sumsq_l2, gct2_l2_penalty (additive); v17 + gct2_dense_steps_fwd, gct2_dense_steps_bwd, gct2_dense_steps_scratch (additive)) */
 /* how the library was built: 0 for the product build; bit 0 (GCT2_BUILD_STAMP) = diagnostic build with in-kernel phase stamps
  * (make EXTRA=-DGCT2_STAMP).  Product hosts (the Python binding, bench.py, the tests) refuse a library whose flags are not 0. */
 enum { GCT2_BUILD_STAMP = 1 };
@@ -266,6 +266,34 @@ int gct2_dense_head_train(gct2_ctx* ctx, int dtype, const void* x, int ldx, cons
                           const float* loss_scale_ptr, float* db_dx /* column sums of dx, or NULL */,
                           const void* x2, int ldx2, int accumulate /* dw, db, db_dx: 0 = overwrite, else add */,
                           void* stream);
+
+/* ---- per-timestep heads: Dense(Cout * steps) + Reshape(.., steps, Cout) + tf.gather(prediction, t - 1, batch_dims=3)
+ * (train.py:199, 203, 211-214) ----
+ * Because t is constant over an image, the gathered head is a Cin -> Cout head whose weight slice is picked per image; the full
+ * steps * Cout outputs are never formed.  w: fp32 (Cin, steps * Cout), the Keras Dense kernel, output index s * Cout + o; b: fp32
+ * [steps * Cout] or NULL; t_int: device int32[B]; image i uses slice s = t_int[i] - 1.  A t_int outside 1..steps is a caller error:
+ * the kernels clamp it into range before they form an address (nothing outside the tensors is read or written).
+ * x: [B * HW, Cin] view of `dtype` with ldx (pad channels [Cin, ldx) are never read); 1 <= Cout <= 4.  A work-group never mixes the
+ * pixels of two images.  ctx (may be NULL) only receives the launch-log tokens "dense_steps:fwd" / "dense_steps:bwd".
+ *
+ * forward: y[m,o] = b[s*Cout+o] + sum_k x[m,k] w[k, s*Cout+o], fp32 [B*HW, Cout] contiguous: gct2_dense_fwd's accumulation order
+ * (k ascending, one fmaf per term, bias last) and its GCT2_F16 rounding - image i's rows equal, bit for bit, gct2_dense_fwd on
+ * those rows with a contiguous copy of its slice. */
+int gct2_dense_steps_fwd(gct2_ctx* ctx, int dtype, const void* x, int ldx, const float* w, const float* b, const int32_t* t_int,
+                         float* y, int B, int HW, int Cin, int Cout, int steps, void* stream);
+/* backward: dx as gct2_dense_bwd with the image's slice (ReLU mask x > 0, channels >= Cmask untouched, GCT2_F16: dy rounded to fp16
+ * on read; dx == NULL or Cmask == 0: no input gradient).  dw (Cin, steps*Cout) and db [steps*Cout] (may be NULL) are written IN FULL:
+ * slice s receives the sum over the images with t_int - 1 == s, every other slice +0.0 (accumulate != 0: added instead).  No
+ * atomics: every work-group (one image, one chunk of its pixels) leaves one partial row in `scratch`, and a second launch adds the
+ * rows per slice over images and chunks in ascending order - the bits depend on the inputs alone.
+ * scratch: device floats, 16-byte aligned, at least what gct2_dense_steps_scratch reports (host only, no launch).
+ * GCT2_EINVAL before any launch: unknown dtype, NULL x / w / t_int / y (dy, dw, scratch), non-positive B / HW / Cin / steps, Cout
+ * outside 1..4, ldx < Cin, lddx < Cmask, Cmask outside 0..Cin, B > 65535, B*HW or Cin*steps*Cout at or beyond 2^31 (the kernels index
+ * pixels and weights with int), (Cin+1)*Cout > 2048, a Cin too large for the LDS tile, scratch_floats below the query's figure. */
+int gct2_dense_steps_scratch(int B, int HW, int Cin, int Cout, size_t* floats);
+int gct2_dense_steps_bwd(gct2_ctx* ctx, int dtype, const void* x, int ldx, const float* w, const int32_t* t_int, const float* dy,
+                         void* dx, int lddx, float* dw, float* db, float* scratch, size_t scratch_floats, int B, int HW, int Cin,
+                         int Cout, int steps, int Cmask, int accumulate, void* stream);
 
 /* UpShuffle_0's forward WITH the train-step head in its epilogue (16-bit dtypes): y = relu(convT(x) + bias) is consumed where
  * it is produced - Dense(3) + fp32 MSE + both of their gradients, exactly as gct2_dense_head_train computes them on the stored
