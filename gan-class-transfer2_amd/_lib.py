@@ -13,6 +13,10 @@ F32, BF16, F16 = 0, 1, 2
 F32_MATH_DIRECT, F32_MATH_MFMA = 0, 1      # gct2_ctx_set_f32_math
 DTYPE_NAMES = {F32: "f32", BF16: "bf16", F16: "f16"}
 ABI_VERSION = 17
+# include/gct2.h GCT2_DENSE2_*: pixels per work-group of the matrix-core kernels of gct2_dense2_fwd / _bwd (a backward launch of M pixels
+# leaves min(512, ceil(M / it)) partial rows), and the largest Cin / Chid of the plain kernels
+DENSE2_FAST_PIXELS = 64
+DENSE2_PLAIN_MAX = 256
 # gct2_diffusion_update modes (include/gct2.h; the sampler's objective switches, train.py:29-32)
 SAMPLE_X, SAMPLE_EPS, SAMPLE_SCALED_EPS, SAMPLE_ODE = 0, 1, 2, 3
 BUILD_STAMP = 1
@@ -94,6 +98,9 @@ SIGNATURES = {
     "gct2_dense_steps_fwd": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "gct2_dense_steps_scratch": [_i, _i, _i, _i, C.POINTER(C.c_size_t)],
     "gct2_dense_steps_bwd": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "gct2_dense2_fwd": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "gct2_dense2_scratch": [_i, _i, _i, _i, C.POINTER(C.c_size_t)],
+    "gct2_dense2_bwd": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp],
     "gct2_rng_uniform_int": [_u64, _u64, _u64, _vp, _sz, _i, _i, _vp],
     "gct2_rng_normal": [_u64, _u64, _u64, _vp, _sz, _vp],
     "gct2_noise_image": [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
@@ -193,7 +200,7 @@ def call(name: str, *args) -> None:
 
 # the entry points a plan can hold (csrc/plan.hip ENTRIES): everything that enqueues work on a stream + the one-shot ReLU plane
 PLANNABLE = frozenset(n for n, sig in SIGNATURES.items() if n == "gct2_ctx_set_relu_bits" or (
-    not n.startswith(("gct2_ctx_", "gct2_plan_", "gct2_loss_scale_init")) and n not in ("gct2_abi_version", "gct2_build_flags", "gct2_device_check", "gct2_stream_occupy", "gct2_sumsq_layout", "gct2_loss_scratch", "gct2_dense_steps_scratch")))
+    not n.startswith(("gct2_ctx_", "gct2_plan_", "gct2_loss_scale_init")) and n not in ("gct2_abi_version", "gct2_build_flags", "gct2_device_check", "gct2_stream_occupy", "gct2_sumsq_layout", "gct2_loss_scratch", "gct2_dense_steps_scratch", "gct2_dense2_scratch")))
 _recording = None      # the Plan that is recording calls right now (one host thread drives an engine: _lib.call is not re-entrant)
 _FLOAT_STRUCT = struct.Struct("<f")
 _DOUBLE_STRUCT = struct.Struct("<d")

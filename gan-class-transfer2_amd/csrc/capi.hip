@@ -513,6 +513,55 @@ int gct2_dense_steps_bwd(gct2_ctx* ctx, int dtype, const void* x, int ldx, const
   return pw_dense_steps_bwd(dtype, x, ldx, w, t_int, dy, dx, lddx, dw, db, scratch, B, HW, Cin, Cout, steps, Cmask, accumulate, S(stream));
 }
 
+// ---- hidden Dense(pixel_size, relu) + Dense head as one kernel per direction (train.py:195-199).  The order of the checks is part of
+// the interface (include/gct2.h): dtype, NULL pointers, non-positive dims, Cout, ldx, [Cmask / lddx], M, weight counts, plain-tile
+// limits, [scratch alignment, scratch size]. ----
+static int check_dense2_shape(const char* fn, int M, int Cin, int Chid, int Cout, int ldx) {
+  if (M <= 0 || Cin <= 0 || Chid <= 0) return gct2_fail(GCT2_EINVAL, "%s: non-positive dimension (M=%d Cin=%d Chid=%d)", fn, M, Cin, Chid);
+  if (Cout < 1 || Cout > 4) return gct2_fail(GCT2_EINVAL, "%s: Cout=%d outside 1..4", fn, Cout);
+  if (ldx < Cin) return gct2_fail(GCT2_EINVAL, "%s: ldx=%d smaller than Cin=%d", fn, ldx, Cin);
+  return GCT2_OK;
+}
+static int check_dense2_sizes(const char* fn, int M, int Cin, int Chid, int Cout) {
+  if ((size_t)M + GCT2_DENSE2_FAST_PIXELS >= ((size_t)1 << 31)) return gct2_fail(GCT2_EINVAL, "%s: M=%d too large for 32-bit pixel indices", fn, M);
+  if ((size_t)Cin * Chid >= ((size_t)1 << 31) || (size_t)Chid * Cout >= ((size_t)1 << 31))
+    return gct2_fail(GCT2_EINVAL, "%s: Cin*Chid or Chid*Cout too large for 32-bit weight indices", fn);
+  if (Cin > GCT2_DENSE2_PLAIN_MAX || Chid > GCT2_DENSE2_PLAIN_MAX)
+    return gct2_fail(GCT2_EINVAL, "%s: Cin=%d / Chid=%d beyond %d, the plain kernel's LDS tile", fn, Cin, Chid, GCT2_DENSE2_PLAIN_MAX);
+  return GCT2_OK;
+}
+int gct2_dense2_fwd(gct2_ctx* ctx, int dtype, const void* x, int ldx, const void* w1, const float* b1, const float* w2, const float* b2, float* y,
+                    int M, int Cin, int Chid, int Cout, void* stream) {
+  if (!dtype_ok(dtype)) return gct2_fail(GCT2_EINVAL, "dense2_fwd: unknown dtype %d", dtype);
+  if (!x || !w1 || !b1 || !w2 || !b2 || !y) return gct2_fail(GCT2_EINVAL, "dense2_fwd: null pointer (x, w1, b1, w2, b2, y)");
+  if (int e = check_dense2_shape("dense2_fwd", M, Cin, Chid, Cout, ldx)) return e;
+  if (int e = check_dense2_sizes("dense2_fwd", M, Cin, Chid, Cout)) return e;
+  return dense2_fwd(C(ctx), dtype, x, ldx, w1, b1, w2, b2, y, M, Cin, Chid, Cout, S(stream));
+}
+int gct2_dense2_scratch(int M, int Cin, int Chid, int Cout, size_t* floats) {
+  if (!floats) return gct2_fail(GCT2_EINVAL, "dense2_scratch: null output pointer");
+  if (int e = check_dense2_shape("dense2_scratch", M, Cin, Chid, Cout, Cin)) return e;
+  if (int e = check_dense2_sizes("dense2_scratch", M, Cin, Chid, Cout)) return e;
+  *floats = dense2_scratch_floats(M, Cin, Chid, Cout);
+  return GCT2_OK;
+}
+int gct2_dense2_bwd(gct2_ctx* ctx, int dtype, const void* x, int ldx, const void* w1, const float* b1, const float* w2, const float* dy, void* dx,
+                    int lddx, float* dw1, float* db1, float* dw2, float* db2, float* scratch, size_t scratch_floats, int M, int Cin, int Chid,
+                    int Cout, int Cmask, int accumulate, void* stream) {
+  if (!dtype_ok(dtype)) return gct2_fail(GCT2_EINVAL, "dense2_bwd: unknown dtype %d", dtype);
+  if (!x || !w1 || !b1 || !w2 || !dy || !dw1 || !db1 || !dw2 || !db2 || !scratch)
+    return gct2_fail(GCT2_EINVAL, "dense2_bwd: null pointer (x, w1, b1, w2, dy, dw1, db1, dw2, db2, scratch)");
+  if (int e = check_dense2_shape("dense2_bwd", M, Cin, Chid, Cout, ldx)) return e;
+  if (Cmask < 0 || Cmask > Cin || (dx && lddx < Cmask))
+    return gct2_fail(GCT2_EINVAL, "dense2_bwd: Cmask=%d outside 0..Cin or lddx=%d smaller than it", Cmask, lddx);
+  if (int e = check_dense2_sizes("dense2_bwd", M, Cin, Chid, Cout)) return e;
+  if ((uintptr_t)scratch % 16) return gct2_fail(GCT2_EINVAL, "dense2_bwd: scratch must be 16-byte aligned");
+  const size_t need = dense2_scratch_floats(M, Cin, Chid, Cout);
+  if (scratch_floats < need)
+    return gct2_fail(GCT2_EINVAL, "dense2_bwd: %zu floats of scratch, this shape needs %zu (gct2_dense2_scratch)", scratch_floats, need);
+  return dense2_bwd(C(ctx), dtype, x, ldx, w1, b1, w2, dy, dx, lddx, dw1, db1, dw2, db2, scratch, M, Cin, Chid, Cout, Cmask, accumulate, S(stream));
+}
+
 int gct2_dense_head_train(gct2_ctx* ctx, int dtype, const void* x, int ldx, const float* w, const float* b, const float* target, float* pred,
                           void* dx, int lddx, float* dw, float* db, float* loss, float* partials, int M, int Cin, int Cout, int Cmask,
                           const float* loss_scale_ptr, float* db_dx, const void* x2, int ldx2, int accumulate, void* stream) {

@@ -454,6 +454,14 @@ int pw_dense_steps_fwd(int dtype, const void* x, int ldx, const float* w, const 
 int pw_dense_steps_bwd(int dtype, const void* x, int ldx, const float* w, const int32_t* t_int, const float* dy, void* dx, int lddx,
                        float* dw, float* db, float* scratch, int B, int HW, int Cin, int Cout, int steps, int Cmask, int accumulate,
                        hipStream_t s);
+// dense2.hip: the hidden Dense(relu) + Dense head pair (gct2_dense2_*): floats of scratch the backward call needs / the launches
+// (they select and log the kernel)
+size_t dense2_scratch_floats(int M, int Cin, int Chid, int Cout);
+int dense2_fwd(gct2_ctx& c, int dtype, const void* x, int ldx, const void* w1, const float* b1, const float* w2, const float* b2, float* y,
+               int M, int Cin, int Chid, int Cout, hipStream_t s);
+int dense2_bwd(gct2_ctx& c, int dtype, const void* x, int ldx, const void* w1, const float* b1, const float* w2, const float* dy, void* dx,
+               int lddx, float* dw1, float* db1, float* dw2, float* db2, float* scratch, int M, int Cin, int Chid, int Cout, int Cmask,
+               int accumulate, hipStream_t s);
 int pw_head_finish(const float* part, int rows, float* dw, float* db, float* loss, float* db_dx, int ndw, int Cout, float inv_n,
                    int accumulate, hipStream_t s);
 int pw_dense_head_train(const gct2_ctx& c, int dtype, const void* x, int ld, const float* w, const float* b, const float* target, float* pred,

@@ -39,7 +39,7 @@ const Entry ENTRIES[] = {
     GCT2_ENTRY(gct2_conv2d_s1_fwd), GCT2_ENTRY(gct2_conv2d_s1_dgrad), GCT2_ENTRY(gct2_conv2d_s1_wgrad),
     GCT2_ENTRY(gct2_relu_mask), GCT2_ENTRY(gct2_add), GCT2_ENTRY(gct2_mix_per_image),
     GCT2_ENTRY(gct2_dense_fwd), GCT2_ENTRY(gct2_dense_bwd), GCT2_ENTRY(gct2_dense_head_train),
-    GCT2_ENTRY(gct2_dense_steps_fwd), GCT2_ENTRY(gct2_dense_steps_bwd),
+    GCT2_ENTRY(gct2_dense_steps_fwd), GCT2_ENTRY(gct2_dense_steps_bwd), GCT2_ENTRY(gct2_dense2_fwd), GCT2_ENTRY(gct2_dense2_bwd),
     GCT2_ENTRY(gct2_rng_uniform_int), GCT2_ENTRY(gct2_rng_normal), GCT2_ENTRY(gct2_noise_image), GCT2_ENTRY(gct2_noise_image_rng),
     GCT2_ENTRY(gct2_mse_fwd_bwd), GCT2_ENTRY(gct2_loss_fwd_bwd), GCT2_ENTRY(gct2_cast_from_f32),
     GCT2_ENTRY(gct2_loss_scale_begin), GCT2_ENTRY(gct2_scale_check_finite), GCT2_ENTRY(gct2_loss_scale_update),

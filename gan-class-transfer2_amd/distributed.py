@@ -173,6 +173,14 @@ def _refuse_timestep_heads(engine, who: str) -> None:
                          "(the switch is single-GPU only)")
 
 
+def _refuse_hidden_dense(engine, who: str) -> None:
+    """the hidden Dense(pixel_size, relu) layer in front of the head (an engine built with hidden_dense=True) is single-GPU only: the
+    two-layer head's kernels and its larger "dense" range have not been built into or tested with a multi-rank exchange"""
+    if getattr(engine, "hidden_dense", False):
+        raise ValueError(f"{who} has not been built or tested with the hidden Dense layer: build the engine with hidden_dense=False "
+                         f"({who} and hidden_dense=True do not go together; the switch is single-GPU only)")
+
+
 def _refuse_regularizer(engine, who: str) -> str:
     """the L2 weight regularizer and the gradient transformer (set_regularizer / set_gradient_transform) are single-GPU only: they run
     on the non-fused optimizer path through gct2_optimizer_apply_reg, which no multi-rank step has been run or tested with.  Refuses an
@@ -206,6 +214,7 @@ class DataParallelStep:
 
     def __init__(self, engine, bucket_elems: int = 4 << 20, group=None, force_exchange: bool = False):
         _refuse_timestep_heads(engine, "DataParallelStep")
+        _refuse_hidden_dense(engine, "DataParallelStep")
         adam_only = _refuse_optimizer(engine, "DataParallelStep")
         no_reg = _refuse_regularizer(engine, "DataParallelStep")
         _refuse_clipping(engine, "DataParallelStep")
@@ -308,6 +317,7 @@ class ShardedDataParallelStep:
 
     def __init__(self, engine, bucket_elems: int = 4 << 20, group=None, force_exchange: bool = False, tail_layers: int = 3):
         _refuse_timestep_heads(engine, "ShardedDataParallelStep")
+        _refuse_hidden_dense(engine, "ShardedDataParallelStep")
         adam_only = _refuse_optimizer(engine, "ShardedDataParallelStep")
         no_reg = _refuse_regularizer(engine, "ShardedDataParallelStep")
         _refuse_clipping(engine, "ShardedDataParallelStep")

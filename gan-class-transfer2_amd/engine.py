@@ -27,6 +27,8 @@ from ._lib import BF16, F16, F32, Slot, call
 from .trainer_math import TrainerState, glorot_limit
 from .trainer_math import ema_coefficients as TM_ema_coefficients
 from .trainer_math import check_timesteps as TM_check_timesteps
+from .trainer_math import check_head_options as TM_check_head_options
+from .trainer_math import check_hidden_marker as TM_check_hidden_marker
 from .trainer_math import OPTIMIZER_KINDS as _OPTIMIZER_CODES
 
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
@@ -55,8 +57,9 @@ class Topology:
     def up_in(self, i: int) -> int:
         return self.fd(i) if i == self.octaves - 1 else self.fu(i + 1) + self.fd(i)
 
-    def param_shapes(self, head_units: int = 3) -> Dict[str, Tuple[int, ...]]:
-        """head_units: 3 for Dense(3), 3 * steps for the per-timestep heads (train.py:199)"""
+    def param_shapes(self, head_units: int = 3, hidden_dense: bool = False) -> Dict[str, Tuple[int, ...]]:
+        """head_units: 3 for Dense(3), 3 * steps for the per-timestep heads (train.py:199); hidden_dense: the Dense(pixel_size, relu)
+        layer of train.py:195-197 sits in front of the head, which then reads pixel_size channels"""
         s: Dict[str, Tuple[int, ...]] = {}
         for i in range(self.octaves):
             s[f"D{i}.w"] = (4, 4, self.cx(i), self.fd(i))
@@ -65,6 +68,10 @@ class Topology:
             s[f"U{i}.b"] = (self.fu(i),)
         s["dense.w"] = (self.fu(0) + 3, head_units)
         s["dense.b"] = (head_units,)
+        if hidden_dense:
+            s["dense_hidden.w"] = (self.fu(0) + 3, self.pixel_size)
+            s["dense_hidden.b"] = (self.pixel_size,)
+            s["dense.w"] = (self.pixel_size, head_units)
         return s
 
     def backward_order(self) -> List[str]:
@@ -83,9 +90,9 @@ class Topology:
 class ParamArena:
     ALIGN = 64  # elements; keeps every tensor 16-byte aligned in the 16-bit shadow too
 
-    def __init__(self, topo: Topology, dtype: int, device: torch.device, head_units: int = 3):
+    def __init__(self, topo: Topology, dtype: int, device: torch.device, head_units: int = 3, hidden_dense: bool = False):
         self.topo, self.dtype, self.device = topo, dtype, device
-        self.shapes = topo.param_shapes(head_units)
+        self.shapes = topo.param_shapes(head_units, hidden_dense)
         self.offsets: Dict[str, int] = {}
         off = 0
         # Layout (r04): the convolution kernels first, in backward completion order (U_0 .. U_{n-1}, D_{n-1} .. D_0: a gradient bucket
@@ -102,7 +109,10 @@ class ParamArena:
             off = _round_up(off + int(np.prod(self.shapes[layer + ".w"])), self.ALIGN)
             self.layer_ranges[layer] = (lo, off)
         zone_lo = off
-        for name in ["dense.w", "dense.b"] + [l + ".b" for l in convs]:
+        # (the hidden Dense layer of train.py:195-197, when the engine has it, sits in front of the head inside the "dense" range; its
+        # kernel is read from the compute-dtype shadow, which every optimizer launch over the zone refreshes)
+        hidden = ["dense_hidden.w", "dense_hidden.b"] if hidden_dense else []
+        for name in hidden + ["dense.w", "dense.b"] + [l + ".b" for l in convs]:
             self.offsets[name] = off
             off = _round_up(off + int(np.prod(self.shapes[name])), self.ALIGN)
             if name == "dense.b":
@@ -198,8 +208,10 @@ class ParamArena:
         if self.shadow is not None:
             call("gct2_cast_from_f32", self.dtype, self._p.data_ptr(), self._shadow.data_ptr(), self.total, stream)
 
-    def glorot_init(self, seed: int = 1234) -> None:
-        """Keras glorot_uniform kernels, zero biases (train.py:134,149,162)."""
+    def glorot_init(self, seed: int = 1234, head_initializer: str = "glorot_uniform") -> None:
+        """Keras glorot_uniform kernels, zero biases (train.py:134,149,162).  head_initializer "zeros": the head's
+        kernel_initializer='zeros' of train.py:199 (commented out there) - dense.w starts at zero, every other tensor draws what it
+        would have drawn"""
         gen = torch.Generator(device="cpu").manual_seed(seed)
         for name in sorted(self.shapes):
             shp = self.shapes[name]
@@ -207,6 +219,8 @@ class ParamArena:
                 self.param(name).zero_()
                 continue
             w = (torch.rand(shp, generator=gen, dtype=torch.float32) * 2 - 1) * glorot_limit(shp)
+            if name == "dense.w" and head_initializer == "zeros":
+                w.zero_()
             self.param(name).copy_(w.to(self.device))
 
 
@@ -303,10 +317,17 @@ class UNetEngine(TrainerState):
                  epsilon: float = 1e-7, loss_scaling: bool = False, seed: int = 1234, rng_seed: int = 0,
                  workspace_mb: int = 64, predict_x: bool = True, predict_scaled_epsilon: bool = False,
                  prediction_weighting: bool = False, ordinary_differential_equation: bool = False, f32_matrix: bool = False,
-                 use_ema: bool = False, ema_momentum: float = 0.99, timestep_heads: bool = False):
+                 use_ema: bool = False, ema_momentum: float = 0.99, timestep_heads: bool = False,
+                 hidden_dense: bool = False, head_initializer: str = "glorot_uniform"):
+        TM_check_head_options(type(self).__name__, hidden_dense, timestep_heads, head_initializer)
         super().__init__(dtype, device, steps, base_lr, warm_up, beta_1, beta_2, epsilon, loss_scaling, rng_seed, predict_x,
                          predict_scaled_epsilon, prediction_weighting, ordinary_differential_equation, f32_matrix)
         self.topo = topo
+        # the hidden Dense(pixel_size, relu) layer between the last Block and the head (train.py:195-197, commented out in the reference):
+        # dense_hidden.w is (Fu_0 + 3, pixel_size), dense.w becomes (pixel_size, 3), and the pair runs unfused through gct2_dense2_fwd /
+        # gct2_dense2_bwd, which never store the hidden activation.  Fixed here: it decides the arena layout
+        self.hidden_dense = bool(hidden_dense)
+        self.head_initializer = head_initializer
         # per-timestep heads (train.py:199, 203, 211-214): dense.w is (Fu_0 + 3, 3 * steps), the head runs unfused through
         # gct2_dense_steps_fwd / gct2_dense_steps_bwd on the slice t_int - 1 of every image.  Fixed here: it decides the arena layout
         self.timestep_heads = bool(timestep_heads)
@@ -317,8 +338,8 @@ class UNetEngine(TrainerState):
         # epilogues read their masks from them instead of re-reading the activations (gct2_ctx_set_relu_bits; -16 bits per element read)
         self.relu_bits = True
         self.relu_bits_min_bytes = 32 << 20     # planes only for activation tensors of at least this size (see buffers())
-        self.arena = ParamArena(topo, dtype, self.device, self.head_shapes(topo.fu(0) + 3)[1][0])
-        self.arena.glorot_init(seed)
+        self.arena = ParamArena(topo, dtype, self.device, self.head_shapes(topo.fu(0) + 3)[1][0], self.hidden_dense)
+        self.arena.glorot_init(seed, head_initializer)
         self.arena.refresh_shadow(self._stream())
         # activation / gradient buffer sets by (B, H, W), least recently used first; at most `max_buffer_sets` stay allocated (the
         # train step, the sampler's batch 1 and batch 6 sets and one spare: a set at config 3 is ~0.8 GB, r02 kept every shape ever seen)
@@ -713,6 +734,10 @@ class UNetEngine(TrainerState):
         if not head:
             return b.pred
         M = b.B * b.H * b.W                                     # Dense(3)       (train.py:198-202)
+        if self.hidden_dense:                                   # Dense(pixel_size, relu) + Dense(3) in one launch (train.py:195-199)
+            call("gct2_dense2_fwd", cx, dt, b.R[0].data_ptr(), b.ld[0], A.wptr("dense_hidden.w"), A.pptr("dense_hidden.b"), A.pptr("dense.w"),
+                 A.pptr("dense.b"), b.pred.data_ptr(), M, t.fu(0) + 3, t.pixel_size, 3, s)
+            return b.pred
         if self.timestep_heads:                                 # Dense(3 * steps) gathered by t (train.py:199, 203, 211-214): b.t_int picks the slices
             call("gct2_dense_steps_fwd", cx, dt, b.R[0].data_ptr(), b.ld[0], A.pptr("dense.w"), A.pptr("dense.b"), b.t_int.data_ptr(),
                  b.pred.data_ptr(), b.B, b.H * b.W, t.fu(0) + 3, 3, self.steps, s)
@@ -761,7 +786,7 @@ class UNetEngine(TrainerState):
         (Fu_0 = 64) in a 16-bit mode with a workspace and the MSE loss the head kernels carry; anything else runs dense_fwd + the loss
         (gct2_mse_fwd_bwd, or gct2_loss_fwd_bwd for the other training losses) + dense_bwd."""
         return (self.use_fused_head and self.dtype != F32 and self.topo.fu(0) == 64 and self.workspace is not None
-                and not self.objective_weighted() and self.training_loss == "mse" and not self.timestep_heads)
+                and not self.objective_weighted() and self.training_loss == "mse" and not self.timestep_heads and not self.hidden_dense)
 
     def head_train(self, b: _Buffers, target: torch.Tensor, target_is_x: bool = False) -> torch.Tensor:
         """Dense(3) + fp32 MSE + both of their gradients in one pass over R_0 (gct2_dense_head_train)."""
@@ -845,7 +870,12 @@ class UNetEngine(TrainerState):
         side = self._side if self.overlap else main
         s, sw = main.cuda_stream, side.cuda_stream
         M = b.B * b.H * b.W
-        if not head_done and self.timestep_heads:               # the gathered head: every slice of dw / db written, no atomics
+        if not head_done and self.hidden_dense:                 # the two-layer head: the hidden activation is recomputed, no atomics
+            scratch = self._dense2_scratch(b.loss_store, M, t.fu(0) + 3, t.pixel_size)
+            call("gct2_dense2_bwd", cx, dt, b.R[0].data_ptr(), b.ld[0], A.wptr("dense_hidden.w"), A.pptr("dense_hidden.b"), A.pptr("dense.w"),
+                 b.dpred.data_ptr(), b.dR[0].data_ptr(), b.ldd[0], A.gptr("dense_hidden.w"), A.gptr("dense_hidden.b"), A.gptr("dense.w"),
+                 A.gptr("dense.b"), scratch.data_ptr(), scratch.numel(), M, t.fu(0) + 3, t.pixel_size, 3, t.fu(0), 0, s)
+        elif not head_done and self.timestep_heads:             # the gathered head: every slice of dw / db written, no atomics
             scratch = self._steps_scratch(b.loss_store, b.B, b.H * b.W, t.fu(0) + 3)
             call("gct2_dense_steps_bwd", cx, dt, b.R[0].data_ptr(), b.ld[0], A.pptr("dense.w"), b.t_int.data_ptr(), b.dpred.data_ptr(),
                  b.dR[0].data_ptr(), b.ldd[0], A.gptr("dense.w"), A.gptr("dense.b"), scratch.data_ptr(), scratch.numel(), b.B, b.H * b.W,
@@ -1099,7 +1129,7 @@ class UNetEngine(TrainerState):
                 self.dtype, float(self.beta_1), float(self.beta_2), float(self.epsilon), float(self.base_lr), int(self.warm_up),
                 id(self.post_replay), self._side.cuda_stream, self.use_ema, float(self.ema_momentum), self.clip_mode, float(self.clip),
                 self.optimizer_kind, float(self.momentum), bool(self.nesterov), float(self.rho), self.lr_schedule, self.training_loss,
-                float(self.l2), self.grad_transform, self.timestep_heads,
+                float(self.l2), self.grad_transform, self.timestep_heads, self.hidden_dense,
                 self._chain_stream.cuda_stream if self._chain_stream is not None else 0)
 
     def _planned_step(self, b: _Buffers, x: torch.Tensor, apply: bool, inline: bool, cur: "torch.cuda.Stream") -> torch.Tensor:
@@ -1232,6 +1262,8 @@ class UNetEngine(TrainerState):
                                            dtype=torch.float64)
         if self.timestep_heads:         # (only then; load_state_dict refuses a checkpoint whose head has the other shape)
             sd["timestep_heads"] = torch.tensor([self.steps], dtype=torch.int64)
+        if self.hidden_dense:           # (only then; load_state_dict refuses a checkpoint of the other head shape)
+            sd["hidden_dense"] = torch.tensor([self.topo.pixel_size], dtype=torch.int64)
         if self.use_ema:                # (only then: without the averages the dictionary is what it always was)
             sd["arena.ema"] = A.ema.cpu()
             sd["ema_momentum"] = torch.tensor([float(self.ema_momentum)], dtype=torch.float64)      # (restored by load_state_dict)
@@ -1252,6 +1284,7 @@ class UNetEngine(TrainerState):
 
     def load_named_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         A = self.arena
+        TM_check_hidden_marker(sd, self.hidden_dense)          # (before any tensor is looked up by name)
         if [int(v) for v in sd["topology"][:3]] != [self.topo.pixel_size, self.topo.max_size, self.topo.octaves]:
             raise ValueError(f"checkpoint topology {[int(v) for v in sd['topology'][:3]]} != engine")
         slots = ("p", "m", "v") + (("ema",) if any(k.startswith("ema/") for k in sd) else ())
@@ -1284,6 +1317,7 @@ class UNetEngine(TrainerState):
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         A = self.arena
+        TM_check_hidden_marker(sd, self.hidden_dense)          # (first: a legacy conversion below knows nothing of the hidden layer)
         want = [self.topo.pixel_size, self.topo.max_size, self.topo.octaves, A.total, A.LAYOUT]
         have = [int(v) for v in sd["topology"]]
         if len(have) == 4:             # r01-r03 checkpoints carry no layout tag: [kernel | bias] per layer - converted on the way in

@@ -57,6 +57,17 @@ regularizer = None
 # Read when a Denoiser is constructed (it decides the head's shape); single GPU, non-fused head, parity unpinned (no TensorFlow here)
 timestep_heads = False
 
+# train.py:195-197: the commented-out `#tf.keras.layers.Dense(pixel_size, kernel_initializer='glorot_uniform', activation='relu'),`
+# between the last Block(pixel_size) and the head.  True: every pixel's channels pass through a (Fu_0 + 3) -> pixel_size -> 3 perceptron
+# instead of the linear map (gct2_dense2_fwd / gct2_dense2_bwd: one kernel per direction, the hidden activation is never stored).
+# Read when a Denoiser is constructed (it adds dense_hidden.w / dense_hidden.b and changes dense.w's shape); single GPU, non-fused
+# head, not together with timestep_heads, parity unpinned (no TensorFlow here)
+hidden_dense = False
+
+# train.py:199: the head's `kernel_initializer='glorot_uniform', #kernel_initializer='zeros'`: "glorot_uniform" (the reference as
+# committed) or "zeros" (dense.w starts at zero: the first prediction is dense.b).  Read when a Denoiser's engine is built
+head_initializer = "glorot_uniform"
+
 warm_up = 2_000
 
 # MI355X knob: None -> float32, or float16 when mixed_precision (train.py:38); "bfloat16" selects the
@@ -78,6 +89,10 @@ def configure(**kw) -> None:
     for k, v in kw.items():
         if not hasattr(mod, k):
             raise AttributeError(f"unknown hyper-parameter {k!r}")
+        if k == "head_initializer" and v not in trainer_math.HEAD_INITIALIZERS:
+            raise ValueError(f"head_initializer must be one of {trainer_math.HEAD_INITIALIZERS}, got {v!r}")
+        if k == "hidden_dense" and not isinstance(v, (bool, int)):
+            raise ValueError(f"hidden_dense is a switch (True / False), got {v!r}")
         setattr(mod, k, v)
 
 
@@ -481,7 +496,15 @@ class Dense(Layer):
     """tf.keras.layers.Dense(units) on a rank-4 input: the Dense(3) head (train.py:198-202; fp32 output for the fp32 loss) and,
     with use_bias=False, the projection of Residual's residual=True mode (train.py:106; a 1 x 1 convolution in the compute dtype)."""
 
-    def __init__(self, units, use_bias=True, gather_steps: int = 0):
+    def __init__(self, units, use_bias=True, gather_steps: int = 0, activation=None, kernel_initializer="glorot_uniform"):
+        if activation not in (None, "relu"):
+            raise ValueError(f"Dense: activation must be None or 'relu' (train.py:195-197), got {activation!r}")
+        if activation == "relu" and not use_bias:
+            raise ValueError("Dense: activation='relu' is built for the biased hidden layer of train.py:195-197 only")
+        if kernel_initializer not in trainer_math.HEAD_INITIALIZERS:
+            raise ValueError(f"Dense: kernel_initializer must be one of {trainer_math.HEAD_INITIALIZERS}, got {kernel_initializer!r}")
+        self.activation = activation          # 'relu': the hidden Dense(pixel_size, relu) layer, a 1 x 1 convolution with ReLU in the compute dtype
+        self.kernel_initializer = kernel_initializer
         self.units = units
         self.use_bias = use_bias
         self.gather_steps = gather_steps      # > 0: the per-timestep head Dense(3 * steps), evaluated by gather() on one slice per image
@@ -495,13 +518,15 @@ class Dense(Layer):
         shp = (input_shape[-1], self.units)
         dev = torch.device("cuda", torch.cuda.current_device())
         self.kernel = ((torch.rand(shp) * 2 - 1) * trainer_math.glorot_limit(shp)).to(dev)
+        if self.kernel_initializer == "zeros":
+            self.kernel.zero_()
         self.bias = torch.zeros(self.units, device=dev) if self.use_bias else None
 
     def call(self, input):
         x = _as_compute(input, self.dtype_code)
         C = x.shape[-1]
         M = x.numel() // C
-        if self.use_bias and self.units <= 4:
+        if self.use_bias and self.units <= 4 and self.activation is None:
             y = torch.empty(*x.shape[:-1], self.units, dtype=torch.float32, device=x.device)
             call("gct2_dense_fwd", self.dtype_code, x.data_ptr(), C, self.kernel.data_ptr(), self.bias.data_ptr(), y.data_ptr(),
                  M, C, self.units, _stream(x))
@@ -511,7 +536,7 @@ class Dense(Layer):
         w = self.kernel if self.dtype_code == F32 else self.kernel.to(TORCH_DTYPE[self.dtype_code])
         y = torch.empty(*x.shape[:-1], self.units, dtype=x.dtype, device=x.device)
         call("gct2_conv2d_s1_fwd", None, self.dtype_code, x.data_ptr(), C, w.data_ptr(), self.bias.data_ptr() if self.bias is not None else None,
-             y.data_ptr(), self.units, M, 1, 1, C, self.units, 1, 0, _stream(x))
+             y.data_ptr(), self.units, M, 1, 1, C, self.units, 1, 1 if self.activation == "relu" else 0, _stream(x))
         return y
 
     def gather(self, input, t_int: torch.Tensor):
@@ -564,11 +589,17 @@ class Denoiser(Layer):
             )
         # train.py:199, 203: Dense(3 * steps) + Reshape when the module switch is on (read here, like the reference's constructor would)
         self.timestep_heads, self._steps = bool(timestep_heads), steps
-        self.head = Dense(3 * steps, gather_steps=steps) if self.timestep_heads else Dense(3)
+        self.head = Dense(3 * steps, gather_steps=steps) if self.timestep_heads else Dense(3, kernel_initializer=head_initializer)
+        # train.py:195-197: Dense(pixel_size, relu) in front of the head when the module switch is on (read here as well)
+        self.hidden_dense = bool(hidden_dense)
+        trainer_math.check_head_options("Denoiser", self.hidden_dense, self.timestep_heads, head_initializer)
+        self.head_initializer = head_initializer
+        self.hidden = Dense(pixel_size, activation="relu") if self.hidden_dense else None
         self.middle = Sequential([
             Block(pixel_size),
             self.middle,
             Block(pixel_size),
+        ] + ([self.hidden] if self.hidden_dense else []) + [
             self.head,
         ])
         self.engine: Optional[UNetEngine] = None
@@ -589,6 +620,10 @@ class Denoiser(Layer):
         kw = dict(steps=steps, warm_up=warm_up, seed=self._seed, loss_scaling=bool(mixed_precision), **objective_switches())
         if self.timestep_heads:                       # (the head's shape was fixed when this Denoiser was constructed)
             kw.update(steps=self._steps, timestep_heads=True)
+        if self.hidden_dense:                         # (... and so was the hidden layer in front of it)
+            kw.update(hidden_dense=True)
+        if self.head_initializer != "glorot_uniform":
+            kw.update(head_initializer=self.head_initializer)
         if self.dtype_code == F32:
             kw["f32_matrix"] = bool(f32_matrix_cores)
         kw.update(engine_kw)
@@ -607,6 +642,10 @@ class Denoiser(Layer):
             self.head.kernel, self.head.bias = A.param("dense.w"), A.param("dense.b")
             self.head.dtype_code = self.dtype_code
             self.head._built = True
+            if self.hidden_dense:
+                self.hidden.kernel, self.hidden.bias = A.param("dense_hidden.w"), A.param("dense_hidden.b")
+                self.hidden.dtype_code = self.dtype_code
+                self.hidden._built = True
         return self.engine
 
     def _bind_variant_parameters(self) -> None:
@@ -705,6 +744,11 @@ class Trainer(Layer):
             raise ValueError(f"timestep_heads = {bool(timestep_heads)} now, but the Denoiser (and the engine behind it) was built with "
                              f"timestep_heads = {bool(built)}: the switch decides the shape of the Dense head "
                              "(train.py:199) - construct a new Denoiser after changing it")
+        built = getattr(getattr(self.denoiser, "engine", None), "hidden_dense", getattr(self.denoiser, "hidden_dense", None))
+        if built is not None and bool(hidden_dense) != bool(built):         # (... and so is the hidden layer in front of it)
+            raise ValueError(f"hidden_dense = {bool(hidden_dense)} now, but the Denoiser (and the engine behind it) was built with "
+                             f"hidden_dense = {bool(built)}: the switch adds the Dense(pixel_size, relu) layer of train.py:195-197 and "
+                             "changes the head's shape - construct a new Denoiser after changing it")
         clipped = kw.pop("clip_mode", None) is not None
         kw.pop("clip", None)
         transform = kw.pop("grad_transform", None)

@@ -223,6 +223,27 @@ def dct_basis(size: int) -> np.ndarray:
     return (sigma / (k + 1.0) * np.cos(np.pi * (2.0 * m + 1.0) * k / (2.0 * size))).astype(np.float32)
 
 
+HEAD_INITIALIZERS = ("glorot_uniform", "zeros")       # train.py:199: the head's kernel_initializer (the default) / '#kernel_initializer='zeros''
+
+
+def check_head_options(who: str, hidden_dense, timestep_heads, head_initializer) -> None:
+    """the constructor arguments that shape the head, checked before anything is allocated"""
+    if head_initializer not in HEAD_INITIALIZERS:
+        raise ValueError(f"{who}: head_initializer must be one of {HEAD_INITIALIZERS}, got {head_initializer!r}")
+    if hidden_dense and timestep_heads:
+        raise ValueError(f"{who}: hidden_dense=True (the Dense(pixel_size, relu) layer of train.py:195-197) together with timestep_heads=True "
+                         "(Dense(3 * steps) gathered by t, train.py:199-214) is not built: switch one of the two off")
+
+
+def check_hidden_marker(sd: dict, hidden_dense: bool) -> None:
+    """a checkpoint written with / without the hidden Dense layer against an engine of the other shape: refused, nothing is loaded"""
+    have = "hidden_dense" in sd
+    if have != bool(hidden_dense):
+        say = lambda on: "the hidden Dense(pixel_size, relu) layer in front of the head" if on else "the plain head (no hidden Dense layer)"
+        raise ValueError(f"the checkpoint holds {say(have)} and this engine {say(bool(hidden_dense))}: dense_hidden.w / dense_hidden.b exist "
+                         "only with the layer and dense.w has another shape (hidden_dense is fixed when an engine is built; nothing is loaded)")
+
+
 class TrainerState:
     """what a train-step engine holds besides its network: constructor arguments checked, then plain attributes that
     `Trainer.compile()` may rewrite between steps (base_lr, warm_up, beta_1, beta_2, epsilon) and `Trainer` sets before every
@@ -258,6 +279,11 @@ class TrainerState:
     # the arena layout.  With it on the head runs on the non-fused path through gct2_dense_steps_fwd / gct2_dense_steps_bwd, which
     # read the device-resident t_int of the step (or the one predict / the sampler wrote); single GPU only
     timestep_heads = False
+    # the hidden Dense(pixel_size, relu) layer in front of the head (train.py:195-197, commented out in the reference): off by default;
+    # an ENGINE CONSTRUCTOR argument like timestep_heads (it adds dense_hidden.w / dense_hidden.b and changes dense.w's shape).  With
+    # it on the head pair runs through gct2_dense2_fwd / gct2_dense2_bwd on the non-fused head path; single GPU only, and not
+    # together with timestep_heads
+    hidden_dense = False
 
     @property
     def _ema(self) -> Optional[torch.Tensor]:
@@ -362,6 +388,15 @@ class TrainerState:
         if key not in store:
             need = C.c_size_t(0)
             _lib.check(self.lib.gct2_dense_steps_scratch(B, HW, cin, 3, C.byref(need)), "gct2_dense_steps_scratch")
+            store[key] = torch.zeros(need.value, dtype=torch.float32, device=self.device)
+        return store[key]
+
+    def _dense2_scratch(self, store: dict, M: int, cin: int, chid: int) -> torch.Tensor:
+        """scratch of gct2_dense2_bwd for this shape (the partial rows of the four head gradients), allocated on first use and kept in `store`"""
+        key = ("dense2", M, cin, chid)
+        if key not in store:
+            need = C.c_size_t(0)
+            _lib.check(self.lib.gct2_dense2_scratch(M, cin, chid, 3, C.byref(need)), "gct2_dense2_scratch")
             store[key] = torch.zeros(need.value, dtype=torch.float32, device=self.device)
         return store[key]
 

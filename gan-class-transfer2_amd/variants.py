@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import BF16, F16, F32, call
-from .trainer_math import TrainerState, check_timesteps, glorot_limit
+from .trainer_math import TrainerState, check_head_options, check_timesteps, glorot_limit
 
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 
@@ -74,17 +74,19 @@ class _Net:
 
 
 class _Conv:
-    """y = relu(conv(x) + b) for the three convolution kinds; reverse pass: ReLU mask, weight / bias gradient, input gradient."""
+    """y = relu(conv(x) + b) for the three convolution kinds; reverse pass: ReLU mask, weight / bias gradient, input gradient.
+    Kind "d1" is Dense(cout, relu) on a rank-4 tensor - the hidden layer of train.py:195-197 - as a 1 x 1 convolution: kernel (cin, cout)."""
 
     def __init__(self, net: _Net, name: str, kind: str, cin: int, cout: int):
         self.net, self.kind, self.cin, self.cout = net, kind, cin, cout
-        shape = {"down": (4, 4, cin, cout), "up": (4, 4, cout, cin), "c3": (3, 3, cin, cout)}[kind]
+        shape = {"down": (4, 4, cin, cout), "up": (4, 4, cout, cin), "c3": (3, 3, cin, cout), "d1": (cin, cout)}[kind]
+        self.ks = 1 if kind == "d1" else 3
         self.w, self.b = net.declare(name + ".w", shape), net.declare(name + ".b", (cout,))
 
     def fwd(self, x: torch.Tensor) -> torch.Tensor:
         n, (B, H, W, C) = self.net, x.shape
         assert C == self.cin, (C, self.cin)
-        Ho, Wo = {"down": (H // 2, W // 2), "up": (2 * H, 2 * W), "c3": (H, W)}[self.kind]
+        Ho, Wo = {"down": (H // 2, W // 2), "up": (2 * H, 2 * W), "c3": (H, W), "d1": (H, W)}[self.kind]
         y = torch.empty(B, Ho, Wo, self.cout, dtype=x.dtype, device=x.device)
         cx, dt, s = n.ctx.handle, n.dtype, n.stream()
         if self.kind == "down":
@@ -94,7 +96,7 @@ class _Conv:
         elif self.kind == "up":
             call("gct2_convT4s2_fwd", cx, dt, x.data_ptr(), C, n.optr(self.w), n.pptr(self.b), y.data_ptr(), self.cout, B, H, W, C, self.cout, 1, s)
         else:
-            call("gct2_conv2d_s1_fwd", cx, dt, x.data_ptr(), C, n.optr(self.w), n.pptr(self.b), y.data_ptr(), self.cout, B, H, W, C, self.cout, 3, 1, s)
+            call("gct2_conv2d_s1_fwd", cx, dt, x.data_ptr(), C, n.optr(self.w), n.pptr(self.b), y.data_ptr(), self.cout, B, H, W, C, self.cout, self.ks, 1, s)
         self.x, self.y = x, y
         return y
 
@@ -114,8 +116,8 @@ class _Conv:
             call("gct2_convT4s2_dgrad", cx, dt, dz.data_ptr(), self.cout, n.optr(self.w), None, 0, dx.data_ptr(), C, B, H, W, C, self.cout, 0,
                  None, 0, None, 0, s)
         else:
-            call("gct2_conv2d_s1_wgrad", cx, dt, x.data_ptr(), C, dz.data_ptr(), self.cout, n.gptr(self.w), n.gptr(self.b), B, H, W, C, self.cout, 3, 0, s)
-            call("gct2_conv2d_s1_dgrad", cx, dt, dz.data_ptr(), self.cout, n.optr(self.w), None, 0, dx.data_ptr(), C, B, H, W, C, self.cout, 3, 0, s)
+            call("gct2_conv2d_s1_wgrad", cx, dt, x.data_ptr(), C, dz.data_ptr(), self.cout, n.gptr(self.w), n.gptr(self.b), B, H, W, C, self.cout, self.ks, 0, s)
+            call("gct2_conv2d_s1_dgrad", cx, dt, dz.data_ptr(), self.cout, n.optr(self.w), None, 0, dx.data_ptr(), C, B, H, W, C, self.cout, self.ks, 0, s)
         self.x = self.y = None
         return dx
 
@@ -266,8 +268,11 @@ class _Head:
 
 
 def build_structure(net: _Net, pixel_size: int, max_size: int, octaves: int, block_depth: int, residual: bool, concat: bool,
-                    head_steps: int = 0):
-    """Denoiser.__init__ (train.py:175-204) with every switch honoured; returns (top sequential, channel count fed to Dense(3))."""
+                    head_steps: int = 0, hidden_dense: bool = False):
+    """Denoiser.__init__ (train.py:175-204) with every switch honoured; returns (top sequential, channel count fed to Dense(3)).
+    hidden_dense: Dense(pixel_size, relu) in front of the head (train.py:195-197) - here the composition the fused pair
+    gct2_dense2_* is defined by (a 1 x 1 convolution with ReLU, then the head): the head's input is not a ReLU output in every
+    variant, so the masked input gradient of the fused backward kernel does not apply."""
 
     def block(name: str, cin: int, filters: int):
         """Block(filters) (train.py:123-143): block_depth x [Conv2D(filters, 3, 1, 'same', relu)]; identity at depth 0."""
@@ -298,8 +303,11 @@ def build_structure(net: _Net, pixel_size: int, max_size: int, octaves: int, blo
     else:
         mid, c = block("blkMid", c, min(pixel_size, max_size))
     b1, c = block("blkTopB", c, pixel_size)                                                   # train.py:194
+    hid = None
+    if hidden_dense:
+        hid, c = _Conv(net, "dense_hidden", "d1", c, pixel_size), pixel_size
     head = _Head(net, c, head_steps)
-    return _Seq([b0, mid, b1, head]), c
+    return _Seq([b0, mid, b1, hid, head]), c
 
 
 class VariantEngine(TrainerState):
@@ -311,18 +319,22 @@ class VariantEngine(TrainerState):
                  beta_2: float = 0.999, epsilon: float = 1e-7, loss_scaling: bool = False, seed: int = 1234, rng_seed: int = 0,
                  predict_x: bool = True, predict_scaled_epsilon: bool = False, prediction_weighting: bool = False,
                  ordinary_differential_equation: bool = False, f32_matrix: bool = False, use_ema: bool = False,
-                 ema_momentum: float = 0.99, timestep_heads: bool = False):
+                 ema_momentum: float = 0.99, timestep_heads: bool = False, hidden_dense: bool = False,
+                 head_initializer: str = "glorot_uniform"):
+        check_head_options(type(self).__name__, hidden_dense, timestep_heads, head_initializer)
         super().__init__(dtype, device, steps, base_lr, warm_up, beta_1, beta_2, epsilon, loss_scaling, rng_seed, predict_x,
                          predict_scaled_epsilon, prediction_weighting, ordinary_differential_equation, f32_matrix)
         self.octaves = octaves
         self.timestep_heads = bool(timestep_heads)      # train.py:199, 203, 211-214; fixed here: it decides the shape of dense.w / dense.b
+        self.hidden_dense = bool(hidden_dense)          # train.py:195-197; fixed here: it adds dense_hidden.w / .b and changes dense.w's shape
+        self.head_initializer = head_initializer        # train.py:199
         # one call context for the train step and for predict (the sampler): with f32_matrix every fp32 convolution runs on the
         # matrix cores, and the workspace below doubles as their split-K and weight-gradient scratch
         self.net = _Net(dtype, self.device, self._new_ctx())
         self.workspace = torch.empty(16 << 18, dtype=torch.float32, device=self.device)
         self.net.ctx.set_workspace(self.workspace)
         self.top, self.head_cin = build_structure(self.net, pixel_size, max_size, octaves, block_depth, residual, concat,
-                                                  steps if self.timestep_heads else 0)
+                                                  steps if self.timestep_heads else 0, self.hidden_dense)
         self._steps_store: dict = {}
         self.net.steps_scratch = lambda B, HW, cin: self._steps_scratch(self._steps_store, B, HW, cin)
         self.net.allocate()
@@ -372,7 +384,10 @@ class VariantEngine(TrainerState):
         for name, shp in self.net.specs:
             if name.endswith(".b"):
                 continue
-            self.net.view(self.net.p, name).copy_(((torch.rand(shp, generator=gen) * 2 - 1) * glorot_limit(shp)).to(self.device))
+            w = (torch.rand(shp, generator=gen) * 2 - 1) * glorot_limit(shp)
+            if name == "dense.w" and self.head_initializer == "zeros":      # train.py:199 '#kernel_initializer='zeros'' (the draw is still made)
+                w.zero_()
+            self.net.view(self.net.p, name).copy_(w.to(self.device))
         self.refresh_operands()
 
     def refresh_operands(self) -> None:

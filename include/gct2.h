@@ -37,7 +37,7 @@ enum {
 };
 
 /* library / device identification ------------------------------------------------------------ */
-int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive); v17 + gct2_sumsq_layout, gct2_grad_sumsq, gct2_adam_keras_clipped (additive); v17 + gct2_optimizer_apply, gct2_loss_scale_begin_schedule (additive); v17 + gct2_loss_scratch, gct2_loss_fwd_bwd (additive); v17 + gct2_optimizer_apply_reg, gct2_grad_sumsq_l2, gct2_l2_penalty (additive); v17 + gct2_dense_steps_fwd, gct2_dense_steps_bwd, gct2_dense_steps_scratch (additive)) */
+int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive); v17 + gct2_sumsq_layout, gct2_grad_sumsq, gct2_adam_keras_clipped (additive); v17 + gct2_optimizer_apply, gct2_loss_scale_begin_schedule (additive); v17 + gct2_loss_scratch, gct2_loss_fwd_bwd (additive); v17 + gct2_optimizer_apply_reg, gct2_grad_sumsq_l2, gct2_l2_penalty (additive); v17 + gct2_dense_steps_fwd, gct2_dense_steps_bwd, gct2_dense_steps_scratch (additive); v17 + gct2_dense2_fwd, gct2_dense2_bwd, gct2_dense2_scratch (additive)) */
 /* how the library was built: 0 for the product build; bit 0 (GCT2_BUILD_STAMP) = diagnostic build with in-kernel phase stamps
  * (make EXTRA=-DGCT2_STAMP).  Product hosts (the Python binding, bench.py, the tests) refuse a library whose flags are not 0. */
 enum { GCT2_BUILD_STAMP = 1 };
@@ -294,6 +294,43 @@ int gct2_dense_steps_scratch(int B, int HW, int Cin, int Cout, size_t* floats);
 int gct2_dense_steps_bwd(gct2_ctx* ctx, int dtype, const void* x, int ldx, const float* w, const int32_t* t_int, const float* dy,
                          void* dx, int lddx, float* dw, float* db, float* scratch, size_t scratch_floats, int B, int HW, int Cin,
                          int Cout, int steps, int Cmask, int accumulate, void* stream);
+
+/* ---- the hidden Dense(Chid, relu) layer in front of the Dense(Cout) head (train.py:195-199; the first one is commented out in the
+ * reference) as ONE kernel per direction: the [M, Chid] hidden activation - the largest tensor the network would have - is never
+ * stored; the backward call recomputes it from x.  Per pixel m
+ *   h[j]   = round_T(relu(b1[j] + sum_i x[m,i] w1[i,j]))        y[m,o] = b2[o] + sum_j h[j] w2[j,o]
+ * x: [M, Cin] view of `dtype`, row pitch ldx; the pad channels [Cin, ldx) are never multiplied (the plain kernels do not read them, the
+ * matrix-core ones zero them in registers): they may hold anything, NaN included.  w1: (Cin, Chid) in `dtype` - the compute-dtype operand
+ * copy, as the convolutions read their kernels; b1: fp32 [Chid]; w2: fp32 (Chid, Cout); b2: fp32 [Cout]; y: fp32 [M, Cout] contiguous.
+ * fp32 accumulation (the plain kernels form the two sums behind h and dh in fp64 when `dtype` is GCT2_F32, so that both are correctly
+ * rounded fp32 values); round_T is ONE rounding to `dtype` (the identity for GCT2_F32) - the value a stored activation would have had,
+ * so the pair means "gct2_conv2d_s1_fwd(KS = 1, relu) followed by gct2_dense_fwd".  GCT2_F16 follows their rounding points: y is rounded
+ * to fp16 (stored as fp32), dy is rounded to fp16 on read.
+ * backward (h recomputed):
+ *   dh[j] = round_T((h[j] > 0) * sum_o dy[m,o] w2[j,o])         dw2 (+)= h^T dy     db2 (+)= sum_m dy
+ *   dw1 (+)= x^T dh      db1 (+)= sum_m dh      dx[m,i] = (x[m,i] > 0) * sum_j dh[j] w1[i,j] for i < Cmask
+ * (x is a ReLU output: dx is the gradient at its pre-activation, as in gct2_dense_bwd).  Channels >= Cmask of dx are left untouched;
+ * dx == NULL or Cmask == 0: no input gradient.  accumulate != 0 adds to dw1 / db1 / dw2 / db2, else they are overwritten.  No atomics:
+ * every work-group leaves ONE partial row [dw1 | db1 | dw2 | db2] in `scratch` and a second launch adds the rows in ascending work-group
+ * order - the bits depend on the inputs alone.  scratch: device floats, 16-byte aligned, at least what gct2_dense2_scratch reports
+ * (host only, no launch; monotone in M).
+ * Kernels: 16-bit dtypes with Chid in {32, 64, 128}, Cin <= 80, ldx % 8 == 0 and x 16-byte aligned run layer 1, dh w1^T and x^T dh on
+ * v_mfma_f32_16x16x32 (GCT2_DENSE2_FAST_PIXELS pixels per work-group; Cin is padded to a multiple of 32 with zeros inside the kernel);
+ * everything else - fp32, other shapes, a ctx with gct2_ctx_force_direct - runs the plain kernels (Cin, Chid <= GCT2_DENSE2_PLAIN_MAX).
+ * The launch log of ctx (may be NULL) receives "dense2:fwd:mfma" / "dense2:fwd:plain" / "dense2:bwd:mfma" / "dense2:bwd:plain".
+ * GCT2_EINVAL before any launch, checked in THIS order (the first failing check names itself in gct2_last_error):
+ *   1 unknown dtype; 2 NULL x / w1 / b1 / w2 / b2 / y (backward: x / w1 / b1 / w2 / dy / dw1 / db1 / dw2 / db2 / scratch); 3 non-positive
+ *   M / Cin / Chid; 4 Cout outside 1..4; 5 ldx < Cin; 6 (backward) Cmask outside 0..Cin, or dx given and lddx < Cmask; 7 M at or beyond
+ *   2^31 - GCT2_DENSE2_FAST_PIXELS; 8 Cin*Chid or Chid*Cout at or beyond 2^31; 9 Cin or Chid above GCT2_DENSE2_PLAIN_MAX; 10 (backward)
+ *   scratch not 16-byte aligned; 11 (backward) scratch_floats below the query's figure.  gct2_dense2_scratch: NULL floats, then 3, 4, 7-9. */
+#define GCT2_DENSE2_FAST_PIXELS 64
+#define GCT2_DENSE2_PLAIN_MAX 256
+int gct2_dense2_fwd(gct2_ctx* ctx, int dtype, const void* x, int ldx, const void* w1, const float* b1, const float* w2, const float* b2,
+                    float* y, int M, int Cin, int Chid, int Cout, void* stream);
+int gct2_dense2_scratch(int M, int Cin, int Chid, int Cout, size_t* floats);
+int gct2_dense2_bwd(gct2_ctx* ctx, int dtype, const void* x, int ldx, const void* w1, const float* b1, const float* w2, const float* dy,
+                    void* dx, int lddx, float* dw1, float* db1, float* dw2, float* db2, float* scratch, size_t scratch_floats,
+                    int M, int Cin, int Chid, int Cout, int Cmask, int accumulate, void* stream);
 
 /* UpShuffle_0's forward WITH the train-step head in its epilogue (16-bit dtypes): y = relu(convT(x) + bias) is consumed where
  * it is produced - Dense(3) + fp32 MSE + both of their gradients, exactly as gct2_dense_head_train computes them on the stored
