@@ -754,74 +754,70 @@ int gct2_grad_sumsq(const float* g, const gct2_sumsq_seg* segs, int nseg, size_t
   return pw_grad_sumsq(g, segs, nseg, npartials, grad_mul, ls, partials, sumsq, S(stream));
 }
 
+// the three entry points of the non-fused update share one list of rejections and one launcher; what differs between them is named here:
+// whether the caller chooses the kind and may choose Adam, the kernels launched (reg), and three pieces of error text
+struct UpdateEntry {
+  const char* name;
+  bool reg, adam;
+  const char* kinds;              // what the unknown-kind message lists
+  const char* aligned16;          // how the alignment message names the fp32 arenas
+  const char* sumsq_from;         // where the sumsq message says the sums come from
+};
+static const UpdateEntry ADAM_KERAS_CLIPPED = {"adam_keras_clipped", false, true, "", "p, m, v and g", "gct2_grad_sumsq"};
+static const UpdateEntry OPTIMIZER_APPLY = {"optimizer_apply", false, false, "GCT2_OPT_SGD / GCT2_OPT_RMSPROP; Adam is gct2_adam_keras_clipped",
+                                            "p, g and the slots in use", "gct2_grad_sumsq"};
+static const UpdateEntry OPTIMIZER_APPLY_REG = {"optimizer_apply_reg", true, true, "GCT2_OPT_ADAM / GCT2_OPT_SGD / GCT2_OPT_RMSPROP",
+                                                "p, g and the slots in use", "gct2_grad_sumsq / gct2_grad_sumsq_l2"};
+
+// Adam: momentum = beta1, rho = beta2, unchecked.  An entry point without a transformer or a regularizer passes GCT2_GRAD_NONE and 0
+static int run_update(const UpdateEntry& e, int kind, float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n, float lr,
+                      float momentum, int nesterov, float rho, float epsilon, float grad_mul, const gct2_loss_scale_state* ls, int clip_mode,
+                      float clip, const double* sumsq, float l2_coeff, int transform, void* stream) {
+  const bool adam = kind == GCT2_OPT_ADAM;
+  if (!(adam && e.adam) && kind != GCT2_OPT_SGD && kind != GCT2_OPT_RMSPROP)
+    return gct2_fail(GCT2_EINVAL, "%s: unknown kind %d (%s)", e.name, kind, e.kinds);
+  if (!adam && !(momentum >= 0.f && momentum <= 1.f)) return gct2_fail(GCT2_EINVAL, "%s: momentum %g outside [0, 1]", e.name, (double)momentum);
+  if (kind == GCT2_OPT_RMSPROP && !(rho >= 0.f && rho <= 1.f)) return gct2_fail(GCT2_EINVAL, "%s: rho %g outside [0, 1]", e.name, (double)rho);
+  if (kind == GCT2_OPT_RMSPROP && !(epsilon >= 0.f)) return gct2_fail(GCT2_EINVAL, "%s: epsilon %g < 0", e.name, (double)epsilon);
+  const bool use_m = adam || momentum > 0.f, use_v = kind != GCT2_OPT_SGD;
+  if (!p || !g || (use_m && !m) || (use_v && !v)) return gct2_fail(GCT2_EINVAL, "%s: null pointer", e.name);
+  if (n == 0) return gct2_fail(GCT2_EINVAL, "%s: n == 0", e.name);
+  if (shadow && shadow_dtype != GCT2_BF16 && shadow_dtype != GCT2_F16)
+    return gct2_fail(GCT2_EINVAL, "%s: a shadow needs a 16-bit dtype (GCT2_BF16 / GCT2_F16), got %d", e.name, shadow_dtype);
+  if (((uintptr_t)p | (uintptr_t)g | (use_m ? (uintptr_t)m : 0) | (use_v ? (uintptr_t)v : 0)) % 16 || (shadow && (uintptr_t)shadow % 8) ||
+      (uintptr_t)sumsq % 8)
+    return gct2_fail(GCT2_EINVAL, "%s: %s must be 16-byte aligned, the shadow and sumsq 8-byte aligned", e.name, e.aligned16);
+  if (clip_mode < GCT2_CLIP_NONE || clip_mode > GCT2_CLIP_GLOBAL_NORM) return gct2_fail(GCT2_EINVAL, "%s: unknown clip_mode %d", e.name, clip_mode);
+  if (clip_mode != GCT2_CLIP_NONE && !(clip > 0.f && clip <= 3.402823466e38f))
+    return gct2_fail(GCT2_EINVAL, "%s: clip = %g must be finite and > 0", e.name, (double)clip);
+  if ((clip_mode == GCT2_CLIP_NORM || clip_mode == GCT2_CLIP_GLOBAL_NORM) && !sumsq)
+    return gct2_fail(GCT2_EINVAL, "%s: clip_mode %d needs sumsq (%s)", e.name, clip_mode, e.sumsq_from);
+  if (transform != GCT2_GRAD_NONE && transform != GCT2_GRAD_SIGN) return gct2_fail(GCT2_EINVAL, "%s: unknown transform %d", e.name, transform);
+  if (!(l2_coeff >= 0.f && l2_coeff <= 3.402823466e38f))
+    return gct2_fail(GCT2_EINVAL, "%s: l2_coeff = %g must be finite and >= 0", e.name, (double)l2_coeff);
+  return pw_update(e.name, e.reg, kind, p, m, v, g, shadow, shadow_dtype, n, lr, momentum, nesterov, rho, epsilon, grad_mul, ls, clip_mode, clip,
+                   sumsq, l2_coeff, transform, S(stream));
+}
+
 int gct2_adam_keras_clipped(float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n, float alpha, float beta1,
                             float beta2, float eps, float grad_mul, const gct2_loss_scale_state* ls, int clip_mode, float clip,
                             const double* sumsq, void* stream) {
-  if (!p || !m || !v || !g) return gct2_fail(GCT2_EINVAL, "adam_keras_clipped: null pointer");
-  if (n == 0) return gct2_fail(GCT2_EINVAL, "adam_keras_clipped: n == 0");
-  if (shadow && shadow_dtype != GCT2_BF16 && shadow_dtype != GCT2_F16)
-    return gct2_fail(GCT2_EINVAL, "adam_keras_clipped: a shadow needs a 16-bit dtype (GCT2_BF16 / GCT2_F16), got %d", shadow_dtype);
-  if (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g) % 16 || (shadow && (uintptr_t)shadow % 8) || (uintptr_t)sumsq % 8)
-    return gct2_fail(GCT2_EINVAL, "adam_keras_clipped: p, m, v and g must be 16-byte aligned, the shadow and sumsq 8-byte aligned");
-  if (clip_mode < GCT2_CLIP_NONE || clip_mode > GCT2_CLIP_GLOBAL_NORM) return gct2_fail(GCT2_EINVAL, "adam_keras_clipped: unknown clip_mode %d", clip_mode);
-  if (clip_mode != GCT2_CLIP_NONE && !(clip > 0.f && clip <= 3.402823466e38f))
-    return gct2_fail(GCT2_EINVAL, "adam_keras_clipped: clip = %g must be finite and > 0", (double)clip);
-  if ((clip_mode == GCT2_CLIP_NORM || clip_mode == GCT2_CLIP_GLOBAL_NORM) && !sumsq)
-    return gct2_fail(GCT2_EINVAL, "adam_keras_clipped: clip_mode %d needs sumsq (gct2_grad_sumsq)", clip_mode);
-  return pw_adam_clipped(p, m, v, g, shadow, shadow_dtype, n, alpha, beta1, beta2, eps, grad_mul, ls, clip_mode, clip, sumsq, S(stream));
+  return run_update(ADAM_KERAS_CLIPPED, GCT2_OPT_ADAM, p, m, v, g, shadow, shadow_dtype, n, alpha, beta1, 0, beta2, eps, grad_mul, ls, clip_mode,
+                    clip, sumsq, 0.f, GCT2_GRAD_NONE, stream);
 }
 
 int gct2_optimizer_apply(int kind, float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,
                          int nesterov, float rho, float epsilon, float grad_mul, const gct2_loss_scale_state* ls, int clip_mode, float clip,
                          const double* sumsq, void* stream) {
-  if (kind != GCT2_OPT_SGD && kind != GCT2_OPT_RMSPROP)
-    return gct2_fail(GCT2_EINVAL, "optimizer_apply: unknown kind %d (GCT2_OPT_SGD / GCT2_OPT_RMSPROP; Adam is gct2_adam_keras_clipped)", kind);
-  if (!(momentum >= 0.f && momentum <= 1.f)) return gct2_fail(GCT2_EINVAL, "optimizer_apply: momentum %g outside [0, 1]", (double)momentum);
-  if (kind == GCT2_OPT_RMSPROP && !(rho >= 0.f && rho <= 1.f)) return gct2_fail(GCT2_EINVAL, "optimizer_apply: rho %g outside [0, 1]", (double)rho);
-  if (kind == GCT2_OPT_RMSPROP && !(epsilon >= 0.f)) return gct2_fail(GCT2_EINVAL, "optimizer_apply: epsilon %g < 0", (double)epsilon);
-  const bool use_m = momentum > 0.f, use_v = kind == GCT2_OPT_RMSPROP;
-  if (!p || !g || (use_m && !m) || (use_v && !v)) return gct2_fail(GCT2_EINVAL, "optimizer_apply: null pointer");
-  if (n == 0) return gct2_fail(GCT2_EINVAL, "optimizer_apply: n == 0");
-  if (shadow && shadow_dtype != GCT2_BF16 && shadow_dtype != GCT2_F16)
-    return gct2_fail(GCT2_EINVAL, "optimizer_apply: a shadow needs a 16-bit dtype (GCT2_BF16 / GCT2_F16), got %d", shadow_dtype);
-  if (((uintptr_t)p | (uintptr_t)g | (use_m ? (uintptr_t)m : 0) | (use_v ? (uintptr_t)v : 0)) % 16 || (shadow && (uintptr_t)shadow % 8) ||
-      (uintptr_t)sumsq % 8)
-    return gct2_fail(GCT2_EINVAL, "optimizer_apply: p, g and the slots in use must be 16-byte aligned, the shadow and sumsq 8-byte aligned");
-  if (clip_mode < GCT2_CLIP_NONE || clip_mode > GCT2_CLIP_GLOBAL_NORM) return gct2_fail(GCT2_EINVAL, "optimizer_apply: unknown clip_mode %d", clip_mode);
-  if (clip_mode != GCT2_CLIP_NONE && !(clip > 0.f && clip <= 3.402823466e38f))
-    return gct2_fail(GCT2_EINVAL, "optimizer_apply: clip = %g must be finite and > 0", (double)clip);
-  if ((clip_mode == GCT2_CLIP_NORM || clip_mode == GCT2_CLIP_GLOBAL_NORM) && !sumsq)
-    return gct2_fail(GCT2_EINVAL, "optimizer_apply: clip_mode %d needs sumsq (gct2_grad_sumsq)", clip_mode);
-  return pw_optimizer(kind, p, m, v, g, shadow, shadow_dtype, n, lr, momentum, nesterov, rho, epsilon, grad_mul, ls, clip_mode, clip, sumsq, S(stream));
+  return run_update(OPTIMIZER_APPLY, kind, p, m, v, g, shadow, shadow_dtype, n, lr, momentum, nesterov, rho, epsilon, grad_mul, ls, clip_mode,
+                    clip, sumsq, 0.f, GCT2_GRAD_NONE, stream);
 }
 
 int gct2_optimizer_apply_reg(int kind, float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,
                              int nesterov, float rho, float epsilon, float grad_mul, const gct2_loss_scale_state* ls, int clip_mode, float clip,
                              const double* sumsq, float l2_coeff, int transform, void* stream) {
-  if (kind != GCT2_OPT_ADAM && kind != GCT2_OPT_SGD && kind != GCT2_OPT_RMSPROP)
-    return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: unknown kind %d (GCT2_OPT_ADAM / GCT2_OPT_SGD / GCT2_OPT_RMSPROP)", kind);
-  const bool adam = kind == GCT2_OPT_ADAM;         // (momentum = beta1, rho = beta2: unchecked, as gct2_adam_keras_clipped leaves them)
-  if (!adam && !(momentum >= 0.f && momentum <= 1.f)) return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: momentum %g outside [0, 1]", (double)momentum);
-  if (kind == GCT2_OPT_RMSPROP && !(rho >= 0.f && rho <= 1.f)) return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: rho %g outside [0, 1]", (double)rho);
-  if (kind == GCT2_OPT_RMSPROP && !(epsilon >= 0.f)) return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: epsilon %g < 0", (double)epsilon);
-  const bool use_m = adam || momentum > 0.f, use_v = kind != GCT2_OPT_SGD;
-  if (!p || !g || (use_m && !m) || (use_v && !v)) return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: null pointer");
-  if (n == 0) return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: n == 0");
-  if (shadow && shadow_dtype != GCT2_BF16 && shadow_dtype != GCT2_F16)
-    return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: a shadow needs a 16-bit dtype (GCT2_BF16 / GCT2_F16), got %d", shadow_dtype);
-  if (((uintptr_t)p | (uintptr_t)g | (use_m ? (uintptr_t)m : 0) | (use_v ? (uintptr_t)v : 0)) % 16 || (shadow && (uintptr_t)shadow % 8) ||
-      (uintptr_t)sumsq % 8)
-    return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: p, g and the slots in use must be 16-byte aligned, the shadow and sumsq 8-byte aligned");
-  if (clip_mode < GCT2_CLIP_NONE || clip_mode > GCT2_CLIP_GLOBAL_NORM) return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: unknown clip_mode %d", clip_mode);
-  if (clip_mode != GCT2_CLIP_NONE && !(clip > 0.f && clip <= 3.402823466e38f))
-    return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: clip = %g must be finite and > 0", (double)clip);
-  if ((clip_mode == GCT2_CLIP_NORM || clip_mode == GCT2_CLIP_GLOBAL_NORM) && !sumsq)
-    return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: clip_mode %d needs sumsq (gct2_grad_sumsq / gct2_grad_sumsq_l2)", clip_mode);
-  if (transform != GCT2_GRAD_NONE && transform != GCT2_GRAD_SIGN) return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: unknown transform %d", transform);
-  if (!(l2_coeff >= 0.f && l2_coeff <= 3.402823466e38f))
-    return gct2_fail(GCT2_EINVAL, "optimizer_apply_reg: l2_coeff = %g must be finite and >= 0", (double)l2_coeff);
-  return pw_optimizer_reg(kind, p, m, v, g, shadow, shadow_dtype, n, lr, momentum, nesterov, rho, epsilon, grad_mul, ls, clip_mode, clip, sumsq,
-                          l2_coeff, transform, S(stream));
+  return run_update(OPTIMIZER_APPLY_REG, kind, p, m, v, g, shadow, shadow_dtype, n, lr, momentum, nesterov, rho, epsilon, grad_mul, ls, clip_mode,
+                    clip, sumsq, l2_coeff, transform, stream);
 }
 
 int gct2_grad_sumsq_l2(const float* g, const float* p, const gct2_sumsq_seg* segs, const float* seg_coeff, int nseg, size_t npartials,

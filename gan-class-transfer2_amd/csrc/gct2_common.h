@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/gct2.h"
 
@@ -379,6 +380,12 @@ template <typename F> inline auto with_dtype(int dtype, F&& f) {
   if (dtype == GCT2_F32) return f(DTypeTag<float>{});
   return with_dtype16(dtype, f);
 }
+// with_shadow16(shadow, dtype, f): the three cases of an optional 16-bit copy - f(DTypeTag<float>{}, std::false_type{}) without one,
+// else f(DTypeTag<T>{}, std::true_type{}) with with_dtype16's T
+template <typename F> inline auto with_shadow16(const void* shadow, int dtype, F&& f) {
+  if (!shadow) return f(DTypeTag<float>{}, std::false_type{});
+  return with_dtype16(dtype, [&](auto tag) { return f(tag, std::true_type{}); });
+}
 
 // ---- host side: every function one translation unit defines and another one calls, declared HERE and nowhere else (each defining
 // file includes this header, so a definition that drifts from its declaration does not compile) ---------------------------------------
@@ -485,20 +492,16 @@ int pw_adam(float* p, float* m, float* v, float* g, void* shadow, int shadow_dty
 int pw_ema(float* ema, const float* p, void* shadow, int shadow_dtype, size_t n, float momentum, float one_minus,
            const gct2_loss_scale_state* ls, hipStream_t s);
 // gradient clipping: per-segment and total sum of squares of the scaled gradient in fp64 (two launches, fixed summation order; sets
-// ls->found_inf like pw_ls_check) / pw_adam from the arena with the clipping step of `mode` between g' and the update
+// ls->found_inf like pw_ls_check); pw_grad_sumsq_l2 the same over the regularized gradient
 int pw_grad_sumsq(const float* g, const gct2_sumsq_seg* segs, int nseg, size_t npartials, float grad_mul, gct2_loss_scale_state* ls,
                   double* partials, double* sumsq, hipStream_t s);
-int pw_adam_clipped(float* p, float* m, float* v, const float* g, void* shadow, int shadow_dtype, size_t n, float alpha, float b1, float b2,
-                    float eps, float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip, const double* sumsq, hipStream_t s);
-// Keras SGD / RMSprop over a flat range (kind: GCT2_OPT_SGD / GCT2_OPT_RMSPROP): pw_adam_clipped's geometry over the slots the kind uses
-int pw_optimizer(int kind, float* p, float* m, float* v, const float* g, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,
-                 int nesterov, float rho, float eps, float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip, const double* sumsq,
-                 hipStream_t s);
-// pw_optimizer for all three kinds (GCT2_OPT_ADAM: lr = alpha, momentum = beta1, rho = beta2) with the penalty gradient l2c * p in front of
-// the clipping step and the gradient transformer behind it; pw_grad_sumsq over the regularized gradient; the reported penalty
-int pw_optimizer_reg(int kind, float* p, float* m, float* v, const float* g, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,
-                     int nesterov, float rho, float eps, float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip, const double* sumsq,
-                     float l2c, int transform, hipStream_t s);
+// the update of every non-fused step over a flat range, launched under the entry point's name `what`: Keras Adam / SGD / RMSprop (kind;
+// GCT2_OPT_ADAM: lr = alpha, momentum = beta1, rho = beta2) over the slots the kind uses, with the clipping step of `mode` between g'
+// and the update; reg selects the kernels that also read l2c (the penalty gradient l2c * p in front of the clipping step) and
+// transform (the gradient transformer behind it) - without reg neither is read
+int pw_update(const char* what, bool reg, int kind, float* p, float* m, float* v, const float* g, void* shadow, int shadow_dtype, size_t n,
+              float lr, float momentum, int nesterov, float rho, float eps, float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip,
+              const double* sumsq, float l2c, int transform, hipStream_t s);
 int pw_grad_sumsq_l2(const float* g, const float* p, const gct2_sumsq_seg* segs, const float* seg_coeff, int nseg, size_t npartials,
                      float grad_mul, gct2_loss_scale_state* ls, double* partials, double* sumsq, hipStream_t s);
 int pw_l2_penalty(const float* loss, const double* S, float l2, float* penalty, float* total, hipStream_t s);

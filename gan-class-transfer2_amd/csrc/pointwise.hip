@@ -1223,49 +1223,6 @@ __device__ __forceinline__ float clip_grad(float g, int mode, float clip, float 
     default: return g;
   }
 }
-// adam_kernel (same geometry, streaming accesses, shadow write, ls skip and ls->alpha; the gradient comes from g only and is never
-// zeroed) with clip_grad between g' and the update
-template <typename S, bool HAS_SHADOW>
-__global__ __launch_bounds__(256) void clipped_adam_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
-                                                           const float* __restrict__ g, S* __restrict__ shadow, size_t n, float alpha,
-                                                           float b1, float b2, float eps, float grad_mul,
-                                                           const gct2_loss_scale_state* __restrict__ ls, int mode, float clip,
-                                                           const double* __restrict__ sumsq) {
-#pragma clang fp contract(off)
-  if (ls && ls->found_inf != 0) return;            // a skipped step writes nothing
-  const float inv_scale = (ls ? ls->inv_scale : 1.f) * grad_mul;
-  if (ls) alpha = ls->alpha;
-  const float a = clip_operand(mode, clip, sumsq);
-  const size_t n4 = n >> 2;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const float ob1 = 1.f - b1, ob2 = 1.f - b2;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    const f32x4_t gv = reinterpret_cast<const f32x4_t*>(g)[i];
-    f32x4_t pv = __builtin_nontemporal_load(reinterpret_cast<f32x4_t*>(p) + i), mv = __builtin_nontemporal_load(reinterpret_cast<f32x4_t*>(m) + i),
-            vv = __builtin_nontemporal_load(reinterpret_cast<f32x4_t*>(v) + i);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      float pp = pv[k], mm = mv[k], v1 = vv[k];
-      adam_keras_update(pp, mm, v1, clip_grad(gv[k] * inv_scale, mode, clip, a), alpha, b1, ob1, b2, ob2, eps);
-      pv[k] = pp; mv[k] = mm; vv[k] = v1;
-    }
-    __builtin_nontemporal_store(pv, reinterpret_cast<f32x4_t*>(p) + i);
-    __builtin_nontemporal_store(mv, reinterpret_cast<f32x4_t*>(m) + i);
-    __builtin_nontemporal_store(vv, reinterpret_cast<f32x4_t*>(v) + i);
-    if constexpr (HAS_SHADOW) {
-      const u32x2_t o = {pack2<S>(pv[0], pv[1]), pack2<S>(pv[2], pv[3])};
-      reinterpret_cast<u32x2_t*>(shadow)[i] = o;
-    }
-  }
-  // tail (n % 4 elements)
-  const size_t i = (n4 << 2) + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    float mm = m[i], vv = v[i], pp = p[i];
-    adam_keras_update(pp, mm, vv, clip_grad(g[i] * inv_scale, mode, clip, a), alpha, b1, ob1, b2, ob2, eps);
-    m[i] = mm; v[i] = vv; p[i] = pp;
-    if constexpr (HAS_SHADOW) shadow[i] = from_f32<S>(pp);
-  }
-}
 
 // ---- Keras SGD / RMSprop over a flat arena [TF] (include/gct2.h gct2_optimizer_apply) ---------------------------------------------
 // one element of the kind's update; m / v are touched only where USE_M / KIND say so.  Every product, sum, quotient and root is
@@ -1302,58 +1259,6 @@ __device__ __forceinline__ void optimizer_update(float& p, float& m, float& v, f
     }
   }
 }
-// clipped_adam_kernel's geometry (256 threads, f32x4 main loop and a scalar tail, streaming accesses on what is touched once per step,
-// the shadow packed two per dword, ls skip and ls->alpha, clip_grad between g' and the update) over the slots the kind uses: m only
-// with momentum, v only for RMSprop - the other pointers are never dereferenced (they may be null)
-template <int KIND, bool USE_M, typename S, bool HAS_SHADOW>
-__global__ __launch_bounds__(256) void optimizer_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
-                                                        const float* __restrict__ g, S* __restrict__ shadow, size_t n, float lr,
-                                                        float momentum, int nesterov, float rho, float eps, float grad_mul,
-                                                        const gct2_loss_scale_state* __restrict__ ls, int mode, float clip,
-                                                        const double* __restrict__ sumsq) {
-#pragma clang fp contract(off)
-  constexpr bool USE_V = KIND == GCT2_OPT_RMSPROP;
-  if (ls && ls->found_inf != 0) return;            // a skipped step writes nothing
-  const float inv_scale = (ls ? ls->inv_scale : 1.f) * grad_mul;
-  if (ls) lr = ls->alpha;
-  const float a = clip_operand(mode, clip, sumsq);
-  const bool nes = nesterov != 0;
-  const float orho = 1.f - rho;
-  const size_t n4 = n >> 2;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    const f32x4_t gv = reinterpret_cast<const f32x4_t*>(g)[i];
-    f32x4_t pv = __builtin_nontemporal_load(reinterpret_cast<f32x4_t*>(p) + i);
-    f32x4_t mv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (USE_M) mv = __builtin_nontemporal_load(reinterpret_cast<f32x4_t*>(m) + i);
-    if constexpr (USE_V) vv = __builtin_nontemporal_load(reinterpret_cast<f32x4_t*>(v) + i);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      float pp = pv[k], mm = mv[k], v1 = vv[k];
-      optimizer_update<KIND, USE_M>(pp, mm, v1, clip_grad(gv[k] * inv_scale, mode, clip, a), lr, momentum, nes, rho, orho, eps);
-      pv[k] = pp; mv[k] = mm; vv[k] = v1;
-    }
-    __builtin_nontemporal_store(pv, reinterpret_cast<f32x4_t*>(p) + i);
-    if constexpr (USE_M) __builtin_nontemporal_store(mv, reinterpret_cast<f32x4_t*>(m) + i);
-    if constexpr (USE_V) __builtin_nontemporal_store(vv, reinterpret_cast<f32x4_t*>(v) + i);
-    if constexpr (HAS_SHADOW) {
-      const u32x2_t o = {pack2<S>(pv[0], pv[1]), pack2<S>(pv[2], pv[3])};
-      reinterpret_cast<u32x2_t*>(shadow)[i] = o;
-    }
-  }
-  // tail (n % 4 elements)
-  const size_t i = (n4 << 2) + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    float pp = p[i], mm = 0.f, vv = 0.f;
-    if constexpr (USE_M) mm = m[i];
-    if constexpr (USE_V) vv = v[i];
-    optimizer_update<KIND, USE_M>(pp, mm, vv, clip_grad(g[i] * inv_scale, mode, clip, a), lr, momentum, nes, rho, orho, eps);
-    p[i] = pp;
-    if constexpr (USE_M) m[i] = mm;
-    if constexpr (USE_V) v[i] = vv;
-    if constexpr (HAS_SHADOW) shadow[i] = from_f32<S>(pp);
-  }
-}
 
 // ---- L2 weight regularizer and sign transformer in front of any kind's update (include/gct2.h gct2_optimizer_apply_reg) -----------
 // Keras' gradient_transformers=[sign_gradient] (train.py:47-48): tf.sign - a NaN stays NaN, -0 gives +0
@@ -1369,15 +1274,21 @@ __device__ __forceinline__ float reg_grad(float g1, float p, float l2c, int tran
   g1 = clip_grad(g1, mode, clip, a);
   return transform == GCT2_GRAD_SIGN ? sign_grad(g1) : g1;
 }
-// optimizer_kernel over all three kinds (GCT2_OPT_ADAM: lr = alpha, momentum = beta1, rho = beta2, both slots in use) with reg_grad
-// where the siblings have clip_grad; adam_keras_update and optimizer_update are the siblings' own
-template <int KIND, bool USE_M, typename S, bool HAS_SHADOW>
-__global__ __launch_bounds__(256) void reg_optimizer_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
-                                                            const float* __restrict__ g, S* __restrict__ shadow, size_t n, float lr,
-                                                            float momentum, int nesterov, float rho, float eps, float grad_mul,
-                                                            const gct2_loss_scale_state* __restrict__ ls, int mode, float clip,
-                                                            const double* __restrict__ sumsq, float l2c, int transform) {
+
+// ---- the update of every non-fused step: gct2_adam_keras_clipped, gct2_optimizer_apply and gct2_optimizer_apply_reg -------------
+// adam_kernel's geometry (256 threads, f32x4 main loop and a scalar tail, streaming accesses on what is touched once per step, the
+// shadow packed two per dword, ls skip and ls->alpha; the gradient comes from g only and is never zeroed) for all three kinds, over
+// the slots the kind uses: m only with momentum, v not for SGD - the other pointers are never dereferenced (they may be null).
+// GCT2_OPT_ADAM: lr = alpha, momentum = beta1, rho = beta2, both slots in use.  Between g' and the kind's update stands clip_grad, or
+// with REG reg_grad (l2c and transform stay launch-uniform run-time switches; without REG neither is read)
+template <int KIND, bool USE_M, bool REG, typename S, bool HAS_SHADOW>
+__global__ __launch_bounds__(256) void arena_update_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                                           const float* __restrict__ g, S* __restrict__ shadow, size_t n, float lr, float momentum,
+                                                           int nesterov, float rho, float eps, float grad_mul,
+                                                           const gct2_loss_scale_state* __restrict__ ls, int mode, float clip,
+                                                           const double* __restrict__ sumsq, float l2c, int transform) {
 #pragma clang fp contract(off)
+  static_assert(USE_M || KIND != GCT2_OPT_ADAM, "Adam always uses both slots");
   constexpr bool USE_V = KIND != GCT2_OPT_SGD;
   if (ls && ls->found_inf != 0) return;            // a skipped step writes nothing
   const float inv_scale = (ls ? ls->inv_scale : 1.f) * grad_mul;
@@ -1385,6 +1296,10 @@ __global__ __launch_bounds__(256) void reg_optimizer_kernel(float* __restrict__ 
   const float a = clip_operand(mode, clip, sumsq);
   const bool nes = nesterov != 0;
   const float omom = 1.f - momentum, orho = 1.f - rho;       // (Adam: 1 - beta1, 1 - beta2)
+  auto grad = [&](float g1, float pp) {
+    if constexpr (REG) return reg_grad(g1, pp, l2c, transform, mode, clip, a);
+    else return clip_grad(g1, mode, clip, a);
+  };
   auto update = [&](float& pp, float& mm, float& vv, float gg) {
     if constexpr (KIND == GCT2_OPT_ADAM) adam_keras_update(pp, mm, vv, gg, lr, momentum, omom, rho, orho, eps);
     else optimizer_update<KIND, USE_M>(pp, mm, vv, gg, lr, momentum, nes, rho, orho, eps);
@@ -1400,7 +1315,7 @@ __global__ __launch_bounds__(256) void reg_optimizer_kernel(float* __restrict__ 
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       float pp = pv[k], mm = mv[k], v1 = vv[k];
-      update(pp, mm, v1, reg_grad(gv[k] * inv_scale, pp, l2c, transform, mode, clip, a));
+      update(pp, mm, v1, grad(gv[k] * inv_scale, pp));
       pv[k] = pp; mv[k] = mm; vv[k] = v1;
     }
     __builtin_nontemporal_store(pv, reinterpret_cast<f32x4_t*>(p) + i);
@@ -1417,7 +1332,7 @@ __global__ __launch_bounds__(256) void reg_optimizer_kernel(float* __restrict__ 
     float pp = p[i], mm = 0.f, vv = 0.f;
     if constexpr (USE_M) mm = m[i];
     if constexpr (USE_V) vv = v[i];
-    update(pp, mm, vv, reg_grad(g[i] * inv_scale, pp, l2c, transform, mode, clip, a));
+    update(pp, mm, vv, grad(g[i] * inv_scale, pp));
     p[i] = pp;
     if constexpr (USE_M) m[i] = mm;
     if constexpr (USE_V) v[i] = vv;
@@ -1715,11 +1630,11 @@ int pw_ema(float* ema, const float* p, void* shadow, int sdt, size_t n, float mo
            hipStream_t s) {
   if (n == 0) return GCT2_OK;
   const int nb = blocks_for(n / 4 + 4, 256);
-#define GCT2_EMA(S, HS) hipLaunchKernelGGL((ema_kernel<S, HS>), dim3(nb), dim3(256), 0, s, ema, p, reinterpret_cast<S*>(shadow), n, momentum, one_minus, ls)
-  if (!shadow) GCT2_EMA(float, false);
-  else if (sdt == GCT2_BF16) GCT2_EMA(__bf16, true);
-  else GCT2_EMA(_Float16, true);
-#undef GCT2_EMA
+  with_shadow16(shadow, sdt, [&](auto tag, auto has_shadow) {
+    using S = typename decltype(tag)::type;
+    hipLaunchKernelGGL((ema_kernel<S, decltype(has_shadow)::value>), dim3(nb), dim3(256), 0, s, ema, p, reinterpret_cast<S*>(shadow), n, momentum,
+                       one_minus, ls);
+  });
   return gct2_check_launch("ema_update");
 }
 int pw_grad_sumsq(const float* g, const gct2_sumsq_seg* segs, int nseg, size_t npartials, float grad_mul, gct2_loss_scale_state* ls,
@@ -1741,41 +1656,28 @@ int pw_l2_penalty(const float* loss, const double* S, float l2, float* penalty, 
   hipLaunchKernelGGL(l2_penalty_kernel, dim3(1), dim3(1), 0, s, loss, S, l2, penalty, total);
   return gct2_check_launch("l2_penalty");
 }
-int pw_adam_clipped(float* p, float* m, float* v, const float* g, void* shadow, int sdt, size_t n, float alpha, float b1, float b2, float eps,
-                    float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip, const double* sumsq, hipStream_t s) {
+int pw_update(const char* what, bool reg, int kind, float* p, float* m, float* v, const float* g, void* shadow, int sdt, size_t n, float lr,
+              float momentum, int nesterov, float rho, float eps, float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip,
+              const double* sumsq, float l2c, int transform, hipStream_t s) {
   const int nb = blocks_for(n / 4 + 4, 256);
-#define GCT2_ADAM(S, HS) hipLaunchKernelGGL((clipped_adam_kernel<S, HS>), dim3(nb), dim3(256), 0, s, p, m, v, g, reinterpret_cast<S*>(shadow), n, alpha, b1, b2, eps, grad_mul, ls, mode, clip, sumsq)
-  if (!shadow) GCT2_ADAM(float, false);
-  else if (sdt == GCT2_BF16) GCT2_ADAM(__bf16, true);
-  else GCT2_ADAM(_Float16, true);
-#undef GCT2_ADAM
-  return gct2_check_launch("adam_keras_clipped");
-}
-int pw_optimizer(int kind, float* p, float* m, float* v, const float* g, void* shadow, int sdt, size_t n, float lr, float momentum, int nesterov,
-                 float rho, float eps, float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip, const double* sumsq, hipStream_t s) {
-  const int nb = blocks_for(n / 4 + 4, 256);
-  const bool use_m = momentum > 0.f;
-#define GCT2_OPT(K, M, S, HS) hipLaunchKernelGGL((optimizer_kernel<K, M, S, HS>), dim3(nb), dim3(256), 0, s, p, m, v, g, reinterpret_cast<S*>(shadow), n, lr, momentum, nesterov, rho, eps, grad_mul, ls, mode, clip, sumsq)
-#define GCT2_OPT_SHADOW(K, M) do { if (!shadow) GCT2_OPT(K, M, float, false); else if (sdt == GCT2_BF16) GCT2_OPT(K, M, __bf16, true); else GCT2_OPT(K, M, _Float16, true); } while (0)
-  if (kind == GCT2_OPT_SGD) { if (use_m) GCT2_OPT_SHADOW(GCT2_OPT_SGD, true); else GCT2_OPT_SHADOW(GCT2_OPT_SGD, false); }
-  else { if (use_m) GCT2_OPT_SHADOW(GCT2_OPT_RMSPROP, true); else GCT2_OPT_SHADOW(GCT2_OPT_RMSPROP, false); }
-#undef GCT2_OPT_SHADOW
-#undef GCT2_OPT
-  return gct2_check_launch("optimizer_apply");
-}
-int pw_optimizer_reg(int kind, float* p, float* m, float* v, const float* g, void* shadow, int sdt, size_t n, float lr, float momentum,
-                     int nesterov, float rho, float eps, float grad_mul, const gct2_loss_scale_state* ls, int mode, float clip, const double* sumsq,
-                     float l2c, int transform, hipStream_t s) {
-  const int nb = blocks_for(n / 4 + 4, 256);
-  const bool use_m = momentum > 0.f;
-#define GCT2_REG(K, M, S, HS) hipLaunchKernelGGL((reg_optimizer_kernel<K, M, S, HS>), dim3(nb), dim3(256), 0, s, p, m, v, g, reinterpret_cast<S*>(shadow), n, lr, momentum, nesterov, rho, eps, grad_mul, ls, mode, clip, sumsq, l2c, transform)
-#define GCT2_REG_SHADOW(K, M) do { if (!shadow) GCT2_REG(K, M, float, false); else if (sdt == GCT2_BF16) GCT2_REG(K, M, __bf16, true); else GCT2_REG(K, M, _Float16, true); } while (0)
-  if (kind == GCT2_OPT_ADAM) GCT2_REG_SHADOW(GCT2_OPT_ADAM, true);
-  else if (kind == GCT2_OPT_SGD) { if (use_m) GCT2_REG_SHADOW(GCT2_OPT_SGD, true); else GCT2_REG_SHADOW(GCT2_OPT_SGD, false); }
-  else { if (use_m) GCT2_REG_SHADOW(GCT2_OPT_RMSPROP, true); else GCT2_REG_SHADOW(GCT2_OPT_RMSPROP, false); }
-#undef GCT2_REG_SHADOW
-#undef GCT2_REG
-  return gct2_check_launch("optimizer_apply_reg");
+  auto launch = [&](auto kind_c, auto use_m, auto reg_c) {
+    with_shadow16(shadow, sdt, [&](auto tag, auto has_shadow) {
+      using S = typename decltype(tag)::type;
+      hipLaunchKernelGGL((arena_update_kernel<decltype(kind_c)::value, decltype(use_m)::value, decltype(reg_c)::value, S, decltype(has_shadow)::value>),
+                         dim3(nb), dim3(256), 0, s, p, m, v, g, reinterpret_cast<S*>(shadow), n, lr, momentum, nesterov, rho, eps, grad_mul, ls,
+                         mode, clip, sumsq, l2c, transform);
+    });
+  };
+  auto with_reg = [&](auto kind_c, auto use_m) {
+    if (reg) launch(kind_c, use_m, std::true_type{}); else launch(kind_c, use_m, std::false_type{});
+  };
+  auto with_momentum = [&](auto kind_c) {
+    if (momentum > 0.f) with_reg(kind_c, std::true_type{}); else with_reg(kind_c, std::false_type{});
+  };
+  if (kind == GCT2_OPT_ADAM) with_reg(std::integral_constant<int, GCT2_OPT_ADAM>{}, std::true_type{});      // (momentum carries beta1)
+  else if (kind == GCT2_OPT_SGD) with_momentum(std::integral_constant<int, GCT2_OPT_SGD>{});
+  else with_momentum(std::integral_constant<int, GCT2_OPT_RMSPROP>{});
+  return gct2_check_launch(what);
 }
 int pw_cast(int dtype, const float* src, void* dst, size_t n, hipStream_t s) {
   if (n == 0) return GCT2_OK;

@@ -1015,10 +1015,7 @@ class UNetEngine(TrainerState):
             if self._clip_by_norm() and (lo, hi) != (0, A.total):
                 raise ValueError(f"apply_adam({lo}, {hi}) with clipnorm / global_clipnorm: a norm needs every gradient of the arena "
                                  f"[0, {A.total}) reduced before the first update; clipping under a bucketed exchange is not built")
-            launches = self._adam_clipped if self.optimizer_kind == "adam" else self._optimizer_launches       # (SGD / RMSprop, clipped or not)
-            if self._regularized():                             # (an L2 regularizer or a gradient transformer: every kind, one entry point)
-                launches = self._reg_launches
-            launches(A._p, A._m, A._v, A.g, A._shadow, lo, hi, 1.0 / grad_div, s)
+            self._update_launches(A._p, A._m, A._v, A.g, A._shadow, lo, hi, 1.0 / grad_div, s)
             return
         # with loss scaling the kernel takes inv_scale / found_inf / alpha from the device-resident state (the step counter that
         # alpha depends on only advances on applied steps); otherwise alpha comes from the host's counter

@@ -523,58 +523,6 @@ class TrainerState:
         return (table, n, int(npartials.value), torch.zeros(npartials.value, dtype=torch.float64, device=dev),
                 torch.zeros(n + 1, dtype=torch.float64, device=dev), segs)
 
-    def _adam_clipped(self, p: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tensor, shadow: Optional[torch.Tensor], lo: int, hi: int,
-                      grad_mul: float, stream: int) -> None:
-        """the optimizer launches of a clipped step over arenas (tensors; shadow None in fp32 mode): clipvalue = one
-        gct2_adam_keras_clipped over [lo, hi).  The norm modes take the whole arena, [lo, hi) = [0, total): global_clipnorm =
-        gct2_grad_sumsq, then one launch over [0, total) reading the total; clipnorm = gct2_grad_sumsq, then one launch per tensor
-        over exactly its elements, reading its own sum"""
-        ls_ptr = self._ls_ptr()
-        alpha = 0.0 if self.ls_state is not None else self.adam_alpha()
-
-        def launch(lo: int, n: int, sumsq_ptr: Optional[int]) -> None:
-            call("gct2_adam_keras_clipped", p.data_ptr() + 4 * lo, m.data_ptr() + 4 * lo, v.data_ptr() + 4 * lo, g.data_ptr() + 4 * lo,
-                 None if shadow is None else shadow.data_ptr() + 2 * lo, self.dtype, n, Slot("alpha", alpha), self.beta_1, self.beta_2,
-                 self.epsilon, grad_mul, ls_ptr, self.clip_mode, float(self.clip), sumsq_ptr, stream)
-
-        if not self._clip_by_norm():
-            launch(lo, hi - lo, None)
-            return
-        table, nseg, npartials, partials, sumsq, segs = self._clip_reduction()
-        call("gct2_grad_sumsq", g.data_ptr(), table.data_ptr(), nseg, npartials, grad_mul, ls_ptr, partials.data_ptr(), sumsq.data_ptr(), stream)
-        if self.clip_mode == _lib.CLIP_GLOBAL_NORM:
-            launch(lo, hi - lo, sumsq.data_ptr() + 8 * nseg)
-        else:
-            for s, (begin, n) in enumerate(segs):
-                launch(begin, n, sumsq.data_ptr() + 8 * s)
-
-    def _optimizer_launches(self, p: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tensor, shadow: Optional[torch.Tensor], lo: int,
-                            hi: int, grad_mul: float, stream: int) -> None:
-        """_adam_clipped for the kinds of gct2_optimizer_apply (SGD, RMSprop), clipped or not: the same sequence - gct2_grad_sumsq
-        first for the two norm modes, then the update once over [lo, hi) or, for clipnorm, once per tensor - with only the slots the
-        kind uses handed to the kernel"""
-        ls_ptr = self._ls_ptr()
-        lr = 0.0 if self.ls_state is not None else self.step_size()
-        kind = OPTIMIZER_KINDS[self.optimizer_kind]
-        use_m, use_v = float(self.momentum) > 0.0, kind == _lib.OPT_RMSPROP
-
-        def launch(lo: int, n: int, sumsq_ptr: Optional[int]) -> None:
-            call("gct2_optimizer_apply", kind, p.data_ptr() + 4 * lo, m.data_ptr() + 4 * lo if use_m else None,
-                 v.data_ptr() + 4 * lo if use_v else None, g.data_ptr() + 4 * lo, None if shadow is None else shadow.data_ptr() + 2 * lo,
-                 self.dtype, n, Slot("alpha", lr), float(self.momentum), int(bool(self.nesterov)), float(self.rho), float(self.epsilon),
-                 grad_mul, ls_ptr, self.clip_mode, float(self.clip), sumsq_ptr, stream)
-
-        if not self._clip_by_norm():
-            launch(lo, hi - lo, None)
-            return
-        table, nseg, npartials, partials, sumsq, segs = self._clip_reduction()
-        call("gct2_grad_sumsq", g.data_ptr(), table.data_ptr(), nseg, npartials, grad_mul, ls_ptr, partials.data_ptr(), sumsq.data_ptr(), stream)
-        if self.clip_mode == _lib.CLIP_GLOBAL_NORM:
-            launch(lo, hi - lo, sumsq.data_ptr() + 8 * nseg)
-        else:
-            for s, (begin, n) in enumerate(segs):
-                launch(begin, n, sumsq.data_ptr() + 8 * s)
-
     # ---- L2 weight regularizer and gradient transformer (train.py:47-48, 71-74, 80) [TF] ------------------------------------------------
     # what an engine provides besides the clipping hooks: _l2_segments() -> the (begin, count) of the tensors that carry the
     # regularizer (default: every tensor; VariantEngine leaves Residual's bias-free projection out, train.py:107)
@@ -627,30 +575,42 @@ class TrainerState:
                                    torch.tensor(coeffs, dtype=torch.float32).to(self._clip_device()))
         return self._reg_tables[c]
 
-    def _reg_launches(self, p: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tensor, shadow: Optional[torch.Tensor], lo: int,
-                      hi: int, grad_mul: float, stream: int) -> None:
-        """_adam_clipped / _optimizer_launches of a step with a regularizer or a transformer, for every kind: the same sequence through
-        gct2_optimizer_apply_reg - the reduction first for the two norm modes (gct2_grad_sumsq_l2 over the regularized gradient as soon
-        as a coefficient is non-zero), then the update once per run of neighbouring tensors with the same coefficient inside [lo, hi)
-        (ONE launch where every tensor carries the regularizer) or, for clipnorm, once per tensor"""
+    # ---- the launches of a non-fused optimizer step: every kind, clipped or not, regularized or not ---------------------------------------
+    def _update_launches(self, p: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tensor, shadow: Optional[torch.Tensor], lo: int,
+                         hi: int, grad_mul: float, stream: int) -> None:
+        """the optimizer launches of every step that is not the plain fused Adam one, over arenas (tensors; shadow None in fp32 mode).
+        The entry point: gct2_optimizer_apply_reg for every kind as soon as a regularizer or a transformer is on (Adam's betas ride in
+        the momentum / rho positions), else gct2_adam_keras_clipped for Adam and gct2_optimizer_apply for SGD / RMSprop; only the slots
+        the kind uses are handed over.  The sequence: for the two norm modes, which take the whole arena ([lo, hi) = [0, total)), the
+        reduction first (gct2_grad_sumsq; gct2_grad_sumsq_l2 over the regularized gradient as soon as a coefficient is non-zero), then
+        for clipnorm one update per tensor over exactly its elements, reading its own sum; otherwise one update per run of neighbouring
+        tensors with the same coefficient inside [lo, hi) - ONE launch where every tensor carries the regularizer, or none does -
+        reading the total under global_clipnorm"""
         ls_ptr = self._ls_ptr()
         lr = 0.0 if self.ls_state is not None else self.step_size()
         kind = OPTIMIZER_KINDS[self.optimizer_kind]
-        adam = kind == _lib.OPT_ADAM
+        adam, reg = kind == _lib.OPT_ADAM, self._regularized()
         use_m, use_v = adam or float(self.momentum) > 0.0, kind != _lib.OPT_SGD
-        first, second = (self.beta_1, self.beta_2) if adam else (self.momentum, self.rho)      # (Adam's betas ride in these positions)
-        transform = GRADIENT_TRANSFORMS[self.grad_transform]
-        segs, coeffs, runs, dev_coeffs = self._reg_table(p.numel())
+        if reg:
+            name, transform = "gct2_optimizer_apply_reg", GRADIENT_TRANSFORMS[self.grad_transform]
+            _, coeffs, runs, dev_coeffs = self._reg_table(p.numel())         # (per tensor of _clip_segments(), the reduction's segments)
+        else:
+            name, coeffs, runs = "gct2_adam_keras_clipped" if adam else "gct2_optimizer_apply", None, [(lo, hi, 0.0)]
+        if adam and not reg:
+            head, hyper = (), (float(self.beta_1), float(self.beta_2))
+        else:
+            first, second = (self.beta_1, self.beta_2) if adam else (self.momentum, self.rho)
+            head, hyper = (kind,), (float(first), int(bool(self.nesterov)), float(second))
 
         def launch(lo: int, n: int, sumsq_ptr: Optional[int], coeff: float) -> None:
-            call("gct2_optimizer_apply_reg", kind, p.data_ptr() + 4 * lo, m.data_ptr() + 4 * lo if use_m else None,
-                 v.data_ptr() + 4 * lo if use_v else None, g.data_ptr() + 4 * lo, None if shadow is None else shadow.data_ptr() + 2 * lo,
-                 self.dtype, n, Slot("alpha", lr), float(first), int(bool(self.nesterov)), float(second), float(self.epsilon),
-                 grad_mul, ls_ptr, self.clip_mode, float(self.clip), sumsq_ptr, coeff, transform, stream)
+            call(name, *head, p.data_ptr() + 4 * lo, m.data_ptr() + 4 * lo if use_m else None, v.data_ptr() + 4 * lo if use_v else None,
+                 g.data_ptr() + 4 * lo, None if shadow is None else shadow.data_ptr() + 2 * lo, self.dtype, n, Slot("alpha", lr), *hyper,
+                 float(self.epsilon), grad_mul, ls_ptr, self.clip_mode, float(self.clip), sumsq_ptr, *((coeff, transform) if reg else ()), stream)
 
         total_ptr = None
         if self._clip_by_norm():
-            table, nseg, npartials, partials, sumsq, _ = self._clip_reduction()
+            table, nseg, npartials, partials, sumsq, segs = self._clip_reduction()
+            coeffs = coeffs or [0.0] * nseg
             if any(coeffs):
                 call("gct2_grad_sumsq_l2", g.data_ptr(), p.data_ptr(), table.data_ptr(), dev_coeffs.data_ptr(), nseg, npartials, grad_mul,
                      ls_ptr, partials.data_ptr(), sumsq.data_ptr(), stream)

@@ -481,10 +481,7 @@ class VariantEngine(TrainerState):
         if self.clip_mode != _lib.CLIP_NONE or self.optimizer_kind != "adam" or self._regularized():
             if not self._clip_by_norm():                       # (a norm-clipped step: gct2_grad_sumsq sets found_inf in its one pass)
                 self._check_finite(N.g.data_ptr(), N.g.numel(), s)
-            launches = self._adam_clipped if self.optimizer_kind == "adam" else self._optimizer_launches       # (SGD / RMSprop, clipped or not)
-            if self._regularized():                             # (an L2 regularizer or a gradient transformer: every kind, one entry point)
-                launches = self._reg_launches
-            launches(N.p, N.m, N.v, N.g, N.op if self.dtype != F32 else None, 0, N.p.numel(), 1.0, s)
+            self._update_launches(N.p, N.m, N.v, N.g, N.op if self.dtype != F32 else None, 0, N.p.numel(), 1.0, s)
             self.finish_step()
             return
         self._check_finite(N.g.data_ptr(), N.g.numel(), s)

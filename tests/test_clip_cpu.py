@@ -180,6 +180,54 @@ def test_adam_keras_clipped_rejects_bad_arguments_without_a_device(args, text):
     assert msg.startswith("adam_keras_clipped: ") and text in msg, msg
 
 
+def _update(entry, **o):
+    """the argument list of one of the three update entry points (RMSprop with momentum where the caller chooses the kind: both slots
+    in use, like Adam), valid except for what `o` replaces"""
+    a = dict(p=P, g=P + 12288, shadow=None, dtype=g.BF16, n=1024, mode=NONE, clip=0.0, sumsq=None)
+    assert not set(o) - set(a)
+    a.update(o)
+    arenas = [a["p"], P + 4096, P + 8192, a["g"], a["shadow"], a["dtype"], a["n"]]
+    clipping = [1.0, None, a["mode"], a["clip"], a["sumsq"]]
+    if entry == "gct2_adam_keras_clipped":
+        return arenas + [1e-3, 0.9, 0.999, 1e-7] + clipping + [None]
+    args = [2] + arenas + [1e-3, 0.9, 0, 0.9, 1e-7] + clipping
+    return args + ([1e-6, 0, None] if entry == "gct2_optimizer_apply_reg" else [None])
+
+
+UPDATE_ENTRIES = ("gct2_adam_keras_clipped", "gct2_optimizer_apply", "gct2_optimizer_apply_reg")
+# one bad argument of each class and the full message of each entry point, in UPDATE_ENTRIES' order
+UPDATE_REJECTIONS = {
+    "null_p": (dict(p=None), ("adam_keras_clipped: null pointer", "optimizer_apply: null pointer", "optimizer_apply_reg: null pointer")),
+    "n_zero": (dict(n=0), ("adam_keras_clipped: n == 0", "optimizer_apply: n == 0", "optimizer_apply_reg: n == 0")),
+    "misaligned_g": (dict(g=P + 12288 + 4),
+                     ("adam_keras_clipped: p, m, v and g must be 16-byte aligned, the shadow and sumsq 8-byte aligned",
+                      "optimizer_apply: p, g and the slots in use must be 16-byte aligned, the shadow and sumsq 8-byte aligned",
+                      "optimizer_apply_reg: p, g and the slots in use must be 16-byte aligned, the shadow and sumsq 8-byte aligned")),
+    "shadow_dtype": (dict(shadow=P + 16384, dtype=7),
+                     ("adam_keras_clipped: a shadow needs a 16-bit dtype (GCT2_BF16 / GCT2_F16), got 7",
+                      "optimizer_apply: a shadow needs a 16-bit dtype (GCT2_BF16 / GCT2_F16), got 7",
+                      "optimizer_apply_reg: a shadow needs a 16-bit dtype (GCT2_BF16 / GCT2_F16), got 7")),
+    "clip_mode": (dict(mode=4, clip=1.0),
+                  ("adam_keras_clipped: unknown clip_mode 4", "optimizer_apply: unknown clip_mode 4", "optimizer_apply_reg: unknown clip_mode 4")),
+    "clip_not_finite": (dict(mode=VALUE, clip=float("inf")),
+                        ("adam_keras_clipped: clip = inf must be finite and > 0", "optimizer_apply: clip = inf must be finite and > 0",
+                         "optimizer_apply_reg: clip = inf must be finite and > 0")),
+    "norm_without_sumsq": (dict(mode=NORM, clip=1.0),
+                           ("adam_keras_clipped: clip_mode 2 needs sumsq (gct2_grad_sumsq)", "optimizer_apply: clip_mode 2 needs sumsq (gct2_grad_sumsq)",
+                            "optimizer_apply_reg: clip_mode 2 needs sumsq (gct2_grad_sumsq / gct2_grad_sumsq_l2)")),
+}
+
+
+@pytest.mark.parametrize("entry", UPDATE_ENTRIES)
+@pytest.mark.parametrize("bad", UPDATE_REJECTIONS)
+def test_the_three_update_entry_points_reject_alike_without_a_device(bad, entry):
+    """the same bad argument to all three: GCT2_EINVAL before any launch, and the whole message of that entry point"""
+    lib = g._lib.load()
+    change, messages = UPDATE_REJECTIONS[bad]
+    assert getattr(lib, entry)(*_update(entry, **change)) == EINVAL
+    assert lib.gct2_last_error().decode() == messages[UPDATE_ENTRIES.index(entry)]
+
+
 # ---- the public surface ------------------------------------------------------------------------------------------------------------
 def test_adam_validates_the_clipping_arguments():
     for kw in (dict(clipnorm=1.0, clipvalue=0.5), dict(clipnorm=1.0, global_clipnorm=1.0), dict(global_clipnorm=2.0, clipvalue=0.5),

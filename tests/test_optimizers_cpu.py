@@ -328,8 +328,8 @@ def test_loss_scale_begin_schedule_rejects_bad_arguments_without_a_device(args, 
 # ---- the call lists ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("loss_scaled", [False, True], ids=["host_counter", "loss_scaled"])
 def test_launch_helper_and_begin_step_call_lists(monkeypatch, loss_scaled):
-    """_optimizer_launches in the four clipping modes (the sequence of _adam_clipped: gct2_grad_sumsq first for the two norm modes,
-    then the update once or per tensor; only the slots in use are handed over) and which begin entry point begin_step calls"""
+    """_update_launches for SGD / RMSprop in the four clipping modes (gct2_grad_sumsq first for the two norm modes, then the update
+    once or per tensor; only the slots in use are handed over) and which begin entry point begin_step calls"""
     calls = []
     monkeypatch.setattr(TM, "call", lambda name, *a: calls.append((name, [x.value if type(x) is TM.Slot else x for x in a])))
 
@@ -365,7 +365,7 @@ def test_launch_helper_and_begin_step_call_lists(monkeypatch, loss_scaled):
                          (K.CLIP_NORM, dict(clipnorm=0.5))):
             e.set_clipping(**kw)
             del calls[:]
-            e._optimizer_launches(p, m, v, gr, sh, 64, 256, 0.5, 9)
+            e._update_launches(p, m, v, gr, sh, 64, 256, 0.5, 9)
             thr = 0.5 if kw else 0.0
 
             def update(lo, n, ss):

@@ -409,7 +409,7 @@ def _launch_list(monkeypatch, e, lo=0, hi=320):
     calls = []
     monkeypatch.setattr(TM, "call", lambda name, *a: calls.append((name, [x.value if type(x) is g._lib.Slot else x for x in a])))
     p, m, v, gr, sh = Ptr(0x10000), Ptr(0x20000), Ptr(0x30000), Ptr(0x40000), Ptr(0x50000)
-    e._reg_launches(p, m, v, gr, sh, lo, hi, 0.5, 77)
+    e._update_launches(p, m, v, gr, sh, lo, hi, 0.5, 77)
     return calls
 
 
