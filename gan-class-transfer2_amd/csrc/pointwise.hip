@@ -29,18 +29,20 @@ __device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t stream_id,
 }
 
 __global__ void rng_uniform_int_kernel(uint64_t seed, uint64_t stream_id, uint64_t offset, int32_t* out, size_t n,
-                                       int lo, uint32_t range) {
+                                       int lo, uint64_t range) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint64_t e = offset + i;
   uint32_t r[4];
   philox4x32_10(seed, stream_id, e >> 2, r);
-  out[i] = lo + (int32_t)__umulhi(r[e & 3], range);
+  // range = hi - lo + 1 <= 2^32 (all of int32: the result is lo + r); the sum wraps in 32 bits, and lands inside [lo, hi]
+  out[i] = (int32_t)((uint32_t)lo + (uint32_t)(((uint64_t)r[e & 3] * range) >> 32));
 }
 
 // Box-Muller on the hardware transcendental units: v_log_f32 (log2), v_sin_f32 / v_cos_f32 (argument in revolutions, so
-// u2 goes in as is).  Absolute error ~1e-6 on a unit normal - a noise source, not a parity quantity (TF's own stream
-// cannot be reproduced) - and ~5x fewer instructions than libm's logf / sinf / cosf.
+// u2 goes in as is).  Absolute error 5.3e-7 at most against a float64 Box-Muller of the same uniforms (measured on an MI355X over
+// 5e5 draws, profiles/rng_parity.json; tests/test_pointwise_exact_gpu.py bounds it) - a noise source, not a parity quantity (TF's
+// own stream cannot be reproduced) - and ~5x fewer instructions than libm's logf / sinf / cosf.
 __device__ __forceinline__ void box_muller(uint32_t r0, uint32_t r1, float& zc, float& zs) {
   const float u1 = ((float)(r0 >> 8) + 0.5f) * (1.0f / 16777216.0f);
   const float u2 = ((float)(r1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
@@ -76,7 +78,12 @@ template <typename T> struct NoiseCoef {
       sa = (float)(_Float16)sqrtf((float)a);
       sb = (float)(_Float16)sqrtf((float)(_Float16)((_Float16)1.0f - a));
     } else {
-      const float t = (float)t_int * (1.0f / (float)steps1);
+      // fp32: a division, like train.py:87 (t_int times the rounded reciprocal gives another sqrt(a) at 36 of 200 timesteps, which
+      // an fp32 output shows in its last bit).  bf16 keeps the product: there the two differ only where the fp32 sum is a tie of
+      // the bf16 store (one element in ~2^16), and the 16-bit train step stays bit-identical from commit to commit.
+      float t;
+      if constexpr (__is_same(T, float)) t = (float)t_int / (float)steps1;
+      else t = (float)t_int * (1.0f / (float)steps1);
       const float a = (1.f - t) * (1.f - t) * 0.25f;
       sa = sqrtf(a); sb = sqrtf(1.f - a);
     }
@@ -915,9 +922,11 @@ __global__ void add_kernel(T* __restrict__ dst, int lddst, const T* __restrict__
     dst[pix * lddst + c] = from_f32<T>(to_f32(dst[pix * lddst + c]) + to_f32(src[pix * ldsrc + c]));
   }
 }
-// out = a[b] * x + c[b] * eps (eps may be null: out = a[b] * x), fp32, per-image coefficients
+// out = a[b] * x + c[b] * eps (eps may be null: out = a[b] * x), fp32, per-image coefficients; both products and the sum rounded
+// once each (no FMA contraction), like the unfused op chain of train.py:238-252 and every other pointwise kernel of the step
 __global__ void mix_per_image_kernel(const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ a,
                                      const float* __restrict__ c, float* __restrict__ out, size_t n, size_t per_image) {
+#pragma clang fp contract(off)
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const size_t b = i / per_image;
@@ -1382,8 +1391,9 @@ inline int blocks_for(size_t n, int per_block) {
 // ---- host launchers (called from capi.hip) ------------------------------------------------------------------
 int pw_rng_uniform_int(uint64_t seed, uint64_t stream_id, uint64_t offset, int32_t* out, size_t n, int lo, int hi, hipStream_t s) {
   if (n == 0) return GCT2_OK;
+  const uint64_t range = (uint64_t)((int64_t)hi - (int64_t)lo + 1);      // in 64 bits: lo = INT32_MIN, hi = INT32_MAX is 2^32
   hipLaunchKernelGGL(rng_uniform_int_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, seed, stream_id, offset, out, n, lo,
-                     (uint32_t)(hi - lo + 1));
+                     range);
   return gct2_check_launch("rng_uniform_int");
 }
 int pw_rng_normal(uint64_t seed, uint64_t stream_id, uint64_t offset, float* out, size_t n, hipStream_t s) {

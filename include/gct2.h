@@ -226,7 +226,8 @@ int gct2_relu_mask(int dtype, const void* act, int ldact, void* d, int ldd, size
 /* dst[pix,c] += src[pix,c] (train.py:112 `input + ...` and the gradient joins of the variants) */
 int gct2_add(int dtype, void* dst, int lddst, const void* src, int ldsrc, size_t npix, int C, void* stream);
 /* out = a[b] * x + c[b] * eps, fp32, per-image coefficients (eps = NULL: out = a[b] * x): the targets and prediction weights of
- * train.py:238-252 (ODE target, epsilon / scaled-epsilon prediction, prediction_weighting) */
+ * train.py:238-252 (ODE target, epsilon / scaled-epsilon prediction, prediction_weighting).  Every operation is rounded once, as in
+ * the reference's unfused op chain: fl(fl(a[b] * x) + fl(c[b] * eps)), never a fused multiply-add.  out may be x (in place). */
 int gct2_mix_per_image(const float* x, const float* eps, const float* a, const float* c, float* out, int B, size_t per_image,
                        void* stream);
 
@@ -348,7 +349,20 @@ int gct2_convT4s2_fwd_head_train(gct2_ctx* ctx, int dtype, const void* x, int ld
 
 /* ---- Trainer.call pieces   train.py:223-272 -------------------------------------------------- */
 /* t_int[b] ~ U{1..steps} (train.py:224-226) and eps ~ N(0,1) (train.py:227) from a counter-based
- * Philox4x32-10 stream keyed by (seed, stream_id); `offset` = elements already drawn. */
+ * Philox4x32-10 stream keyed by (seed, stream_id); `offset` = elements already drawn.
+ * The stream (tests/pointwise_cases.py restates it on the host; tests/test_pointwise_exact_gpu.py pins it per element):
+ *   Philox4x32-10 of Salmon et al. (SC'11), every one of the 64 bits of seed, stream_id and the counter index in use:
+ *     counter = (idx & 0xffffffff, idx >> 32, stream_id & 0xffffffff, stream_id >> 32),  key = (seed & 0xffffffff, seed >> 32);
+ *   element e (= offset + position in the output) uses the four output words r[0..3] of counter idx = e >> 2, so a draw may
+ *   start and end inside a counter, and a draw split into several calls at any offsets equals the single call.
+ *   gct2_rng_uniform_int: out = lo + ((r[e & 3] * range) >> 32) with range = hi_inclusive - lo + 1 formed in 64 bits.  Every
+ *     lo <= hi_inclusive is valid, range up to 2^32 (lo = INT32_MIN, hi_inclusive = INT32_MAX: out = lo + r); hi_inclusive < lo is
+ *     GCT2_EINVAL.  Integer arithmetic: the values are exact.
+ *   gct2_rng_normal: Box-Muller.  Words (r[0], r[1]) make elements 4 idx (cosine) and 4 idx + 1 (sine), words (r[2], r[3]) elements
+ *     4 idx + 2 and 4 idx + 3: with u = ((float)(r >> 8) + 0.5f) * 2^-24 (float32, each operation rounded; u in (0, 1], u = 1 at
+ *     r >> 8 = 2^24 - 1 where 16777215.5 rounds to even), rad = sqrt(-2 ln u1), z = rad cos(2 pi u2) or rad sin(2 pi u2).
+ *     Always finite (|z| < 5.9).  log2 / sin / cos run on the hardware transcendental units: within 5.3e-7 absolute of that formula
+ *     evaluated in double (measured on an MI355X, profiles/rng_parity.json; the test asserts 2^-18). */
 int gct2_rng_uniform_int(uint64_t seed, uint64_t stream_id, uint64_t offset, int32_t* out, size_t n,
                          int lo, int hi_inclusive, void* stream);
 int gct2_rng_normal(uint64_t seed, uint64_t stream_id, uint64_t offset, float* out, size_t n,
@@ -356,7 +370,12 @@ int gct2_rng_normal(uint64_t seed, uint64_t stream_id, uint64_t offset, float* o
 
 /* noised = x*sqrt(a_b) + eps*sqrt(1-a_b), a_b = 0.25*(1 - t_b/(steps+1))^2  (train.py:85-93,229-234)
  * x, eps: fp32 [B, HW, C] contiguous; t_int: int32[B]; out: view [B*HW, C] of `dtype` with ldout.
- * GCT2_F32 / GCT2_BF16: fp32 arithmetic, one rounding at the store.  GCT2_F16: every operation is rounded to fp16 as under
+ * GCT2_F32 / GCT2_BF16: fp32 arithmetic in the reference's order, every operation rounded once (no fused multiply-add):
+ * t, om = 1 - t, a = (om * om) * 0.25, sqrt(a), sqrt(1 - a), fl(fl(x * sqrt(a)) + fl(eps * sqrt(1 - a))), and one more rounding at
+ * a bf16 store.  GCT2_F32: t = (float)t_b / (float)(steps + 1), a division like train.py:87.  GCT2_BF16: t = (float)t_b *
+ * (1.0f / (float)(steps + 1)); the last-bit difference this makes in sqrt(a) at some timesteps (36 of 200 at steps = 200) reaches a
+ * bf16 output only where the fp32 sum is a tie of the store, about one element in 2^16 (tests/test_pointwise_exact_gpu.py pins
+ * that form on images made of such ties).  GCT2_F16: every operation is rounded to fp16 as under
  * Keras' mixed_float16 policy, where x, eps and t are fp16 tensors (train.py:38, 227-234, 292).
  * out2 (may be NULL): a second view [B*HW, C] with ldout2 that receives the same values - the engine keeps a packed
  * copy of the image (ld 4) for DownShuffle_0 beside the slice of the concat buffer that Dense(3) reads. */

@@ -297,6 +297,26 @@ def noise_image_f16(x, t_int, eps, steps=200):
     return (x16 * sa).astype(h) + (e16 * sb).astype(h)
 
 
+def noise_image_f32(x, t_int, eps, steps=200, out_dtype="f32"):
+    """train.py:229-234 at the reference's default precision: x, epsilon and t = cast(t_int, x.dtype) are float32 tensors, so
+    alpha_dash (train.py:85-93) and the mix run in float32, every operation rounded on its own, in the reference's order:
+    t = t_int / (steps + 1) (a DIVISION, train.py:87); om = 1 - t; a = (om * om) * 0.25; sa = sqrt(a); sb = sqrt(1 - a);
+    fl(fl(x * sa) + fl(eps * sb)).  out_dtype "bf16": that sum rounded once more to bfloat16 (gct2_noise_image's GCT2_BF16: fp32
+    arithmetic, one rounding at the store).  x, eps: [B, ...]; returns a float32 array holding the values."""
+    f = np.float32
+    t = np.asarray(t_int).astype(f) / f(steps + 1)
+    om = f(1.0) - t
+    a = (om * om) * f(0.25)
+    shape = (-1,) + (1,) * (np.ndim(x) - 1)
+    sa, sb = np.sqrt(a).reshape(shape), np.sqrt(f(1.0) - a).reshape(shape)
+    out = np.asarray(x, dtype=f) * sa + np.asarray(eps, dtype=f) * sb
+    assert out.dtype == f
+    if out_dtype == "bf16":
+        return round_bf16(out)
+    assert out_dtype == "f32", out_dtype
+    return out
+
+
 def unet_forward(params, x0, cfg: OracleConfig, operand_round: Optional[str] = None, keras_strict: bool = False):
     """Denoiser.call (train.py:206-215): `t` is ignored; returns (prediction, cache).
 

@@ -24,7 +24,7 @@ DTYPE_NAMES = {F32: "f32", BF16: "bf16", F16: "f16"}
 SIG_BITS = {F32: 24, BF16: 8, F16: 11}        # significand widths (with the hidden bit) of the storage types
 BUDGET = 1 << 22                              # two bits of slack under fp32's 24
 GUARD = 64                                    # NaN / sentinel elements in front of and behind weight and bias arrays
-SENTINEL = -1234.0                            # exactly representable in bf16, f16 and fp32
+SENTINEL = -1234.0                            # exact in f16 and fp32; bf16 stores it as -1232 (compare against the stored value)
 
 
 # ---- operands -------------------------------------------------------------------------------------------------------------------
@@ -104,7 +104,8 @@ def expected(ref64, out_dtype):
     return t32.to(TDT[out_dtype])
 
 
-_INT_VIEW = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float64: torch.int64}
+_INT_VIEW = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float64: torch.int64,
+             torch.int32: torch.int32}
 
 
 def _shared_coordinates(idx, shape, names):
