@@ -11,3 +11,4 @@ from .engine import Topology, UNetEngine          # noqa: F401
 from .model import (Adam, Block, Dense, Denoiser, DownShuffle, InverseTimeDecay, LambdaCallback, LossScaleOptimizer,  # noqa: F401
                     RMSprop, Residual, SGD, Sequential, Trainer, UpShuffle, WarmUp, alpha_dash, configure, identity, regularizers,
                     sign_gradient)
+from .trainer_math import NOISE_SCHEDULES, alpha_table, noise_table  # noqa: F401

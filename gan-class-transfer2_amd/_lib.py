@@ -105,6 +105,8 @@ SIGNATURES = {
     "gct2_rng_normal": [_u64, _u64, _u64, _vp, _sz, _vp],
     "gct2_noise_image": [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "gct2_noise_image_rng": [_i, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
+    "gct2_noise_image_table": [_i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
+    "gct2_noise_image_rng_table": [_i, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "gct2_mse_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp],
     "gct2_loss_scratch": [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)],
     "gct2_loss_fwd_bwd": [_i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp],

@@ -605,6 +605,31 @@ int gct2_noise_image_rng(int dtype, const float* x, const int32_t* t_int, uint64
   return pw_noise_rng(dtype, x, t_int, seed, stream_id, offset, eps_out, out, ldout, out2, ldout2, B, HW, C, steps, S(stream));
 }
 
+// the table forms: coef = float[steps][2], entry t - 1 = (sa, sb), read as one 8-byte load per thread
+static int noise_table_ok(const char* who, const float* coef, int steps) {
+  if (!coef || (uintptr_t)coef % 8) return gct2_fail(GCT2_EINVAL, "%s: coef is NULL or not 8-byte aligned", who);
+  if (steps < 1) return gct2_fail(GCT2_EINVAL, "%s: steps must be >= 1", who);
+  return GCT2_OK;
+}
+
+int gct2_noise_image_table(int dtype, const float* x, const int32_t* t_int, const float* eps, const float* coef, void* out, int ldout,
+                           void* out2, int ldout2, int B, int HW, int C, int steps, void* stream) {
+  if (!dtype_ok(dtype) || !x || !t_int || !eps || !out) return gct2_fail(GCT2_EINVAL, "noise_image_table: bad dtype or null pointer");
+  if (int rc = noise_table_ok("noise_image_table", coef, steps)) return rc;
+  if (B <= 0 || HW <= 0 || C <= 0 || ldout < C || (out2 && ldout2 < C)) return gct2_fail(GCT2_EINVAL, "noise_image_table: bad shape");
+  return pw_noise_table(dtype, x, t_int, eps, coef, out, ldout, out2, ldout2, B, HW, C, steps, S(stream));
+}
+
+int gct2_noise_image_rng_table(int dtype, const float* x, const int32_t* t_int, uint64_t seed, uint64_t stream_id, uint64_t offset,
+                               float* eps_out, const float* coef, void* out, int ldout, void* out2, int ldout2, int B, int HW, int C,
+                               int steps, void* stream) {
+  if (!dtype_ok(dtype) || !x || !t_int || !out) return gct2_fail(GCT2_EINVAL, "noise_image_rng_table: bad dtype or null pointer");
+  if (int rc = noise_table_ok("noise_image_rng_table", coef, steps)) return rc;
+  if (B <= 0 || HW <= 0 || C <= 0 || ldout < C || (out2 && ldout2 < C) || (size_t)B * HW * C >= ((size_t)1 << 31))
+    return gct2_fail(GCT2_EINVAL, "noise_image_rng_table: bad shape");
+  return pw_noise_rng_table(dtype, x, t_int, seed, stream_id, offset, eps_out, coef, out, ldout, out2, ldout2, B, HW, C, steps, S(stream));
+}
+
 int gct2_diffusion_mix(int dtype, const float* x_theta, const float* eps_theta, float alpha, float* fake, void* out, int ldout, void* out2,
                        int ldout2, size_t npix, int C, void* stream) {
   if (!dtype_ok(dtype) || !x_theta || !eps_theta || !fake || !out) return gct2_fail(GCT2_EINVAL, "diffusion_mix: bad dtype or null pointer");

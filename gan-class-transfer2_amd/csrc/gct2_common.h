@@ -451,6 +451,10 @@ int pw_noise(int dtype, const float* x, const int32_t* t, const float* eps, void
              int C, int steps, hipStream_t s);
 int pw_noise_rng(int dtype, const float* x, const int32_t* t, uint64_t seed, uint64_t stream_id, uint64_t offset, float* eps_out, void* out,
                  int ldout, void* out2, int ldout2, int B, int HW, int C, int steps, hipStream_t s);
+int pw_noise_table(int dtype, const float* x, const int32_t* t, const float* eps, const float* coef, void* out, int ldout, void* out2,
+                   int ldout2, int B, int HW, int C, int steps, hipStream_t s);
+int pw_noise_rng_table(int dtype, const float* x, const int32_t* t, uint64_t seed, uint64_t stream_id, uint64_t offset, float* eps_out,
+                       const float* coef, void* out, int ldout, void* out2, int ldout2, int B, int HW, int C, int steps, hipStream_t s);
 int pw_dense_fwd(int dtype, const void* x, int ldx, const float* w, const float* b, float* y, int M, int Cin, int Cout, hipStream_t s);
 int pw_dense_bwd(int dtype, const void* x, int ldx, const float* w, const float* dy, void* dx, int lddx, float* dw, float* db, int M,
                  int Cin, int Cout, int Cmask, int accumulate, hipStream_t s);

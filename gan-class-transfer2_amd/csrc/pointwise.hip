@@ -67,10 +67,23 @@ __global__ void rng_normal_kernel(uint64_t seed, uint64_t stream_id, uint64_t of
 // noised = x sqrt(a) + eps sqrt(1 - a), a = alpha_dash(t) (train.py:85-93, 229-234).  fp32 / bf16: fp32 arithmetic, one rounding at
 // the store.  fp16 = Keras' mixed_float16 policy, where x, eps and t are fp16 tensors (train.py:38, 227, 292): every operation
 // rounds to fp16 (t/(steps+1), 1-t, the square, *0.25, both square roots, both products, the sum).
+//
+// Where the pair (sa, sb) comes from: NoiseFormula evaluates the reference's live line (train.py:93) per thread; NoiseTable reads
+// what the host put down for the schedule in force (trainer_math.noise_table: any of train.py:88-93, or the user's own body) from
+// float[steps][2], entry t - 1 = (sa, sb), as ONE 8-byte load - sb is never derived from sa.  t_int is clamped to 1..steps before the
+// address is formed (the rule of gct2_dense_steps_fwd).  Both kernel arguments are wave-uniform; the mix is the same.
+struct NoiseFormula { int steps1; };
+struct NoiseTable { const float* coef; int steps; };
 template <typename T> struct NoiseCoef {
   float sa, sb;
-  __device__ __forceinline__ NoiseCoef(int t_int, int steps1) {
+  __device__ __forceinline__ NoiseCoef(int t_int, NoiseTable tab) {
+    const int t = t_int < 1 ? 1 : (t_int > tab.steps ? tab.steps : t_int);
+    const f32x2_t p = reinterpret_cast<const f32x2_t*>(tab.coef)[t - 1];
+    sa = p[0]; sb = p[1];
+  }
+  __device__ __forceinline__ NoiseCoef(int t_int, NoiseFormula formula) {
 #pragma clang fp contract(off)      // every fp16 operation rounds on its own (no fused multiply-add): that IS the model
+    const int steps1 = formula.steps1;
     if constexpr (sizeof(T) == 2 && !__is_same(T, __bf16)) {
       const _Float16 t = (_Float16)((_Float16)(float)t_int / (_Float16)(float)steps1);
       const _Float16 om = (_Float16)1.0f - t;
@@ -102,10 +115,10 @@ template <typename T> struct NoiseCoef {
 // noising with eps drawn on the fly from the same stream positions rng_normal_kernel would use.  One thread per Philox
 // counter = 4 consecutive elements of the flattened [pixel][channel] image: one Philox call, two logs and two sin/cos pairs
 // make four normals (philox_normal spends a whole call per element); values are bit-identical to it.
-template <typename T>
+template <typename T, typename Src>
 __global__ void noise_rng_kernel(const float* __restrict__ x, const int32_t* __restrict__ t_int, uint64_t seed, uint64_t stream_id,
                                  uint64_t offset, float* __restrict__ eps_out, T* __restrict__ out, int ldout,
-                                 T* __restrict__ out2, int ldout2, size_t n, int HW, int C, int steps1) {
+                                 T* __restrict__ out2, int ldout2, size_t n, int HW, int C, Src src) {
   const uint64_t c0 = offset >> 2;
   const size_t ncounters = (size_t)(((offset + n + 3) >> 2) - c0);
   const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -123,14 +136,14 @@ __global__ void noise_rng_kernel(const float* __restrict__ x, const int32_t* __r
     const uint32_t i0 = (uint32_t)(first - offset);
     uint32_t pix = i0 / (uint32_t)C, c = i0 - pix * (uint32_t)C;
     uint32_t b = pix / (uint32_t)HW, rem = pix - b * (uint32_t)HW;
-    NoiseCoef<T> nc(1, steps1);
+    NoiseCoef<T> nc(1, src);
     bool have = false;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       const uint64_t e = e0 + k;
       if (e < first || e >= offset + n) continue;
       if (!have) {
-        nc = NoiseCoef<T>(t_int[b], steps1);
+        nc = NoiseCoef<T>(t_int[b], src);
         have = true;
       }
       const size_t i = (size_t)(e - offset);
@@ -150,15 +163,15 @@ __global__ void noise_rng_kernel(const float* __restrict__ x, const int32_t* __r
 // position a multiple of 12.  A thread owns 12 consecutive elements = THREE Philox counters = FOUR whole pixels: three 16-byte loads of x,
 // the same counters / normals / mix as noise_rng_kernel (bit-identical), and the four pixels leave as two 16-byte stores (slot 3 = 0,
 // which is what the packed image holds there) instead of twelve 2-byte ones.  11 -> 5 us at config 3, on the step's critical path.
-template <typename T>
+template <typename T, typename Src>
 __global__ __launch_bounds__(256) void noise_rng_px4_kernel(const float* __restrict__ x, const int32_t* __restrict__ t_int, uint64_t seed,
                                                             uint64_t stream_id, uint64_t ctr0, T* __restrict__ out, size_t ngroups, int HW,
-                                                            int steps1) {
+                                                            Src src) {
   static_assert(sizeof(T) == 2, "16-bit storage types only");
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < ngroups; t += stride) {
     const uint32_t b = (uint32_t)((4 * t) / (size_t)HW);          // HW % 4 == 0: the four pixels belong to one image
-    const NoiseCoef<T> nc(t_int[b], steps1);
+    const NoiseCoef<T> nc(t_int[b], src);
     const f32x4_t* xs = reinterpret_cast<const f32x4_t*>(x) + 3 * t;
     const f32x4_t x0 = xs[0], x1 = xs[1], x2 = xs[2];
     const float xv[12] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3], x2[0], x2[1], x2[2], x2[3]};
@@ -184,17 +197,17 @@ __global__ __launch_bounds__(256) void noise_rng_px4_kernel(const float* __restr
   }
 }
 
-template <typename T>
+template <typename T, typename Src>
 __global__ void noise_kernel(const float* __restrict__ x, const int32_t* __restrict__ t_int, const float* __restrict__ eps,
                              T* __restrict__ out, int ldout, T* __restrict__ out2, int ldout2, size_t npix, int HW, int C,
-                             int steps1) {
+                             Src src) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const size_t total = npix * C;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
     const size_t pix = i / C;
     const int c = (int)(i - pix * C);
     const int b = (int)(pix / HW);
-    const NoiseCoef<T> nc(t_int[b], steps1);                   // alpha_dash, train.py:87-93
+    const NoiseCoef<T> nc(t_int[b], src);                      // alpha_dash, train.py:87-93
     const T v = nc.mix(x[i], eps[i]);                          // train.py:231-234
     out[pix * ldout + c] = v;
     if (out2) out2[pix * ldout2 + c] = v;
@@ -1401,18 +1414,20 @@ int pw_rng_normal(uint64_t seed, uint64_t stream_id, uint64_t offset, float* out
   hipLaunchKernelGGL(rng_normal_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, seed, stream_id, offset, out, n);
   return gct2_check_launch("rng_normal");
 }
-int pw_noise(int dtype, const float* x, const int32_t* t, const float* eps, void* out, int ldout, void* out2, int ldout2, int B, int HW,
-             int C, int steps, hipStream_t s) {
+// one launcher per kernel family for both coefficient sources (NoiseFormula: gct2_noise_image / _rng; NoiseTable: the _table forms)
+template <typename Src>
+static void launch_noise(int dtype, const float* x, const int32_t* t, const float* eps, void* out, int ldout, void* out2, int ldout2, int B,
+                         int HW, int C, Src src, hipStream_t s) {
   const size_t npix = (size_t)B * HW;
   with_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    hipLaunchKernelGGL(noise_kernel<T>, dim3(blocks_for(npix * C, 256)), dim3(256), 0, s, x, t, eps, reinterpret_cast<T*>(out), ldout,
-                       reinterpret_cast<T*>(out2), ldout2, npix, HW, C, steps + 1);
+    hipLaunchKernelGGL((noise_kernel<T, Src>), dim3(blocks_for(npix * C, 256)), dim3(256), 0, s, x, t, eps, reinterpret_cast<T*>(out), ldout,
+                       reinterpret_cast<T*>(out2), ldout2, npix, HW, C, src);
   });
-  return gct2_check_launch("noise_image");
 }
-int pw_noise_rng(int dtype, const float* x, const int32_t* t, uint64_t seed, uint64_t sid, uint64_t off, float* eps_out, void* out,
-                 int ldout, void* out2, int ldout2, int B, int HW, int C, int steps, hipStream_t s) {
+template <typename Src>
+static void launch_noise_rng(int dtype, const float* x, const int32_t* t, uint64_t seed, uint64_t sid, uint64_t off, float* eps_out,
+                             void* out, int ldout, void* out2, int ldout2, int B, int HW, int C, Src src, hipStream_t s) {
   const size_t npix = (size_t)B * HW;
   with_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
@@ -1420,15 +1435,34 @@ int pw_noise_rng(int dtype, const float* x, const int32_t* t, uint64_t seed, uin
       // the train step's call: 3 channels into the packed 4-slot image and nothing else, whole groups of four pixels / three counters
       if (C == 3 && ldout == 4 && !out2 && !eps_out && off % 12 == 0 && npix % 4 == 0 && HW % 4 == 0 && (uintptr_t)x % 16 == 0 &&
           (uintptr_t)out % 16 == 0) {
-        hipLaunchKernelGGL(noise_rng_px4_kernel<T>, dim3(blocks_for(npix / 4, 256)), dim3(256), 0, s, x, t, seed, sid, off >> 2,
-                           reinterpret_cast<T*>(out), npix / 4, HW, steps + 1);
+        hipLaunchKernelGGL((noise_rng_px4_kernel<T, Src>), dim3(blocks_for(npix / 4, 256)), dim3(256), 0, s, x, t, seed, sid, off >> 2,
+                           reinterpret_cast<T*>(out), npix / 4, HW, src);
         return;
       }
     }
-    hipLaunchKernelGGL(noise_rng_kernel<T>, dim3(blocks_for(npix * C / 4 + 2, 256)), dim3(256), 0, s, x, t, seed, sid, off, eps_out,
-                       reinterpret_cast<T*>(out), ldout, reinterpret_cast<T*>(out2), ldout2, npix * C, HW, C, steps + 1);
+    hipLaunchKernelGGL((noise_rng_kernel<T, Src>), dim3(blocks_for(npix * C / 4 + 2, 256)), dim3(256), 0, s, x, t, seed, sid, off, eps_out,
+                       reinterpret_cast<T*>(out), ldout, reinterpret_cast<T*>(out2), ldout2, npix * C, HW, C, src);
   });
+}
+int pw_noise(int dtype, const float* x, const int32_t* t, const float* eps, void* out, int ldout, void* out2, int ldout2, int B, int HW,
+             int C, int steps, hipStream_t s) {
+  launch_noise(dtype, x, t, eps, out, ldout, out2, ldout2, B, HW, C, NoiseFormula{steps + 1}, s);
+  return gct2_check_launch("noise_image");
+}
+int pw_noise_rng(int dtype, const float* x, const int32_t* t, uint64_t seed, uint64_t sid, uint64_t off, float* eps_out, void* out,
+                 int ldout, void* out2, int ldout2, int B, int HW, int C, int steps, hipStream_t s) {
+  launch_noise_rng(dtype, x, t, seed, sid, off, eps_out, out, ldout, out2, ldout2, B, HW, C, NoiseFormula{steps + 1}, s);
   return gct2_check_launch("noise_image_rng");
+}
+int pw_noise_table(int dtype, const float* x, const int32_t* t, const float* eps, const float* coef, void* out, int ldout, void* out2,
+                   int ldout2, int B, int HW, int C, int steps, hipStream_t s) {
+  launch_noise(dtype, x, t, eps, out, ldout, out2, ldout2, B, HW, C, NoiseTable{coef, steps}, s);
+  return gct2_check_launch("noise_image_table");
+}
+int pw_noise_rng_table(int dtype, const float* x, const int32_t* t, uint64_t seed, uint64_t sid, uint64_t off, float* eps_out,
+                       const float* coef, void* out, int ldout, void* out2, int ldout2, int B, int HW, int C, int steps, hipStream_t s) {
+  launch_noise_rng(dtype, x, t, seed, sid, off, eps_out, out, ldout, out2, ldout2, B, HW, C, NoiseTable{coef, steps}, s);
+  return gct2_check_launch("noise_image_rng_table");
 }
 int pw_dense_fwd(int dtype, const void* x, int ldx, const float* w, const float* b, float* y, int M, int Cin, int Cout, hipStream_t s) {
   with_dtype(dtype, [&](auto tag) {

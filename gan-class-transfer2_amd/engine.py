@@ -29,6 +29,8 @@ from .trainer_math import ema_coefficients as TM_ema_coefficients
 from .trainer_math import check_timesteps as TM_check_timesteps
 from .trainer_math import check_head_options as TM_check_head_options
 from .trainer_math import check_hidden_marker as TM_check_hidden_marker
+from .trainer_math import check_schedule_marker as TM_check_schedule_marker
+from .trainer_math import schedule_marker as TM_schedule_marker
 from .trainer_math import OPTIMIZER_KINDS as _OPTIMIZER_CODES
 
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
@@ -654,8 +656,13 @@ class UNetEngine(TrainerState):
         s = self._stream()
         out, ldout, out2, ldout2 = self._noise_targets(b)
         call("gct2_rng_uniform_int", self.rng_seed, 1, Slot("off_t", self.rng_offset_t), b.t_int.data_ptr(), b.B, 1, self.steps, s)
-        call("gct2_noise_image_rng", self.dtype, Slot("x", x.data_ptr()), b.t_int.data_ptr(), self.rng_seed, 2, Slot("off_eps", self.rng_offset_eps),
-             b.eps.data_ptr() if keep_eps else None, out, ldout, out2, ldout2, b.B, b.H * b.W, 3, self.steps, s)
+        if self._default_schedule():
+            call("gct2_noise_image_rng", self.dtype, Slot("x", x.data_ptr()), b.t_int.data_ptr(), self.rng_seed, 2, Slot("off_eps", self.rng_offset_eps),
+                 b.eps.data_ptr() if keep_eps else None, out, ldout, out2, ldout2, b.B, b.H * b.W, 3, self.steps, s)
+        else:                                                  # another schedule (set_noise_schedule): the pair comes from the host's table
+            call("gct2_noise_image_rng_table", self.dtype, Slot("x", x.data_ptr()), b.t_int.data_ptr(), self.rng_seed, 2,
+                 Slot("off_eps", self.rng_offset_eps), b.eps.data_ptr() if keep_eps else None, self._noise_coef_ptr(), out, ldout, out2, ldout2,
+                 b.B, b.H * b.W, 3, self.steps, s)
         self.rng_offset_t += b.B
         self.rng_offset_eps += b.eps.numel()
 
@@ -670,8 +677,12 @@ class UNetEngine(TrainerState):
 
     def noise_into_r0(self, b: _Buffers, x: torch.Tensor, unfused_head: bool = False) -> None:
         out, ldout, out2, ldout2 = self._noise_targets(b, unfused_head)
-        call("gct2_noise_image", self.dtype, x.data_ptr(), b.t_int.data_ptr(), b.eps.data_ptr(), out, ldout, out2, ldout2,
-             b.B, b.H * b.W, 3, self.steps, self._stream())
+        if self._default_schedule():
+            call("gct2_noise_image", self.dtype, x.data_ptr(), b.t_int.data_ptr(), b.eps.data_ptr(), out, ldout, out2, ldout2,
+                 b.B, b.H * b.W, 3, self.steps, self._stream())
+        else:
+            call("gct2_noise_image_table", self.dtype, x.data_ptr(), b.t_int.data_ptr(), b.eps.data_ptr(), self._noise_coef_ptr(), out, ldout,
+                 out2, ldout2, b.B, b.H * b.W, 3, self.steps, self._stream())
 
     def load_input_into_r0(self, b: _Buffers, noised: torch.Tensor) -> None:
         """Denoiser.call on an externally prepared image (sampler / inference path)."""
@@ -1127,6 +1138,7 @@ class UNetEngine(TrainerState):
                 id(self.post_replay), self._side.cuda_stream, self.use_ema, float(self.ema_momentum), self.clip_mode, float(self.clip),
                 self.optimizer_kind, float(self.momentum), bool(self.nesterov), float(self.rho), self.lr_schedule, self.training_loss,
                 float(self.l2), self.grad_transform, self.timestep_heads, self.hidden_dense,
+                self.noise_schedule if isinstance(self.noise_schedule, str) else id(self.noise_schedule), float(self.alpha_dash_offset),
                 self._chain_stream.cuda_stream if self._chain_stream is not None else 0)
 
     def _planned_step(self, b: _Buffers, x: torch.Tensor, apply: bool, inline: bool, cur: "torch.cuda.Stream") -> torch.Tensor:
@@ -1261,6 +1273,8 @@ class UNetEngine(TrainerState):
             sd["timestep_heads"] = torch.tensor([self.steps], dtype=torch.int64)
         if self.hidden_dense:           # (only then; load_state_dict refuses a checkpoint of the other head shape)
             sd["hidden_dense"] = torch.tensor([self.topo.pixel_size], dtype=torch.int64)
+        if not self._default_schedule():    # (only then; load_state_dict refuses a named schedule that disagrees with the engine's)
+            sd["noise_schedule"] = TM_schedule_marker(self.noise_schedule, self.alpha_dash_offset)
         if self.use_ema:                # (only then: without the averages the dictionary is what it always was)
             sd["arena.ema"] = A.ema.cpu()
             sd["ema_momentum"] = torch.tensor([float(self.ema_momentum)], dtype=torch.float64)      # (restored by load_state_dict)
@@ -1315,6 +1329,7 @@ class UNetEngine(TrainerState):
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         A = self.arena
         TM_check_hidden_marker(sd, self.hidden_dense)          # (first: a legacy conversion below knows nothing of the hidden layer)
+        TM_check_schedule_marker(sd, self.noise_schedule, self.alpha_dash_offset)
         want = [self.topo.pixel_size, self.topo.max_size, self.topo.octaves, A.total, A.LAYOUT]
         have = [int(v) for v in sd["topology"]]
         if len(have) == 4:             # r01-r03 checkpoints carry no layout tag: [kernel | bias] per layer - converted on the way in

@@ -68,6 +68,13 @@ hidden_dense = False
 # committed) or "zeros" (dense.w starts at zero: the first prediction is dense.b).  Read when a Denoiser's engine is built
 head_initializer = "glorot_uniform"
 
+# train.py:85-93: which `return` of alpha_dash is live - "quadratic" (train.py:93, the reference as committed), "exp2" (:88), "rational"
+# (:89), "exp16" (:90), "cosine" (:91) or "quartic" (:92) (trainer_math.NOISE_SCHEDULES), or a callable f(t01) -> alpha, the user's own
+# body on t01 = t / (steps + 1) - and the offset added behind it (1e-4 is the commented-out tail of train.py:93).  Trainer reads both
+# before every step, like training_loss; a Denoiser's engine starts under them; alpha_dash(t) below and log_sample follow them
+noise_schedule = "quadratic"
+alpha_dash_offset = 0.0
+
 warm_up = 2_000
 
 # MI355X knob: None -> float32, or float16 when mixed_precision (train.py:38); "bfloat16" selects the
@@ -93,6 +100,10 @@ def configure(**kw) -> None:
             raise ValueError(f"head_initializer must be one of {trainer_math.HEAD_INITIALIZERS}, got {v!r}")
         if k == "hidden_dense" and not isinstance(v, (bool, int)):
             raise ValueError(f"hidden_dense is a switch (True / False), got {v!r}")
+        if k == "noise_schedule":
+            v = trainer_math.check_noise_schedule(v, 0.0)[0]
+        if k == "alpha_dash_offset":
+            v = trainer_math.check_noise_schedule(None, v)[1]
         setattr(mod, k, v)
 
 
@@ -326,8 +337,8 @@ def clipping_arguments(optimizer) -> Dict[str, object]:
 
 
 def alpha_dash(t):
-    """train.py:85-93 (reads the module-level `steps` when called, like the reference)"""
-    return trainer_math.alpha_dash(t, steps)
+    """train.py:85-93 (reads the module-level `steps`, `noise_schedule` and `alpha_dash_offset` when called, like the reference)"""
+    return trainer_math.alpha_dash(t, steps, noise_schedule, alpha_dash_offset)
 
 
 test_step = 25  # train.py:95
@@ -615,6 +626,7 @@ class Denoiser(Layer):
         engine built by anything else silently trained the default objective)."""
         if self.engine is not None:
             return self.engine
+        schedule = trainer_math.check_noise_schedule(noise_schedule, alpha_dash_offset)      # (ValueError before anything is built)
         # no optimizer known yet (train.py:505-509 calls the model before compile): the module-level mixed_precision
         # decides about loss scaling, as it decides about the LossScaleOptimizer wrapper in train.py:82-83
         kw = dict(steps=steps, warm_up=warm_up, seed=self._seed, loss_scaling=bool(mixed_precision), **objective_switches())
@@ -646,6 +658,8 @@ class Denoiser(Layer):
                 self.hidden.kernel, self.hidden.bias = A.param("dense_hidden.w"), A.param("dense_hidden.b")
                 self.hidden.dtype_code = self.dtype_code
                 self.hidden._built = True
+        if not trainer_math.default_noise_schedule(*schedule):     # alpha_dash's live line (train.py:85-93), like the objective switches
+            self.engine.set_noise_schedule(*schedule)
         return self.engine
 
     def _bind_variant_parameters(self) -> None:
@@ -739,6 +753,7 @@ class Trainer(Layer):
             _supported_learning_rate(kw)
             kw["loss_scaling"] = bool(getattr(opt, "inner", opt).loss_scaling)
         l2 = regularizer_l2(regularizer)                 # anything but None / regularizers.l2: NotImplementedError, before anything is built
+        schedule = trainer_math.check_noise_schedule(noise_schedule, alpha_dash_offset)      # an unknown name, a non-finite offset: ValueError
         built = getattr(getattr(self.denoiser, "engine", None), "timestep_heads", getattr(self.denoiser, "timestep_heads", None))
         if built is not None and bool(timestep_heads) != bool(built):       # (the head's shape is fixed with the Denoiser and its engine)
             raise ValueError(f"timestep_heads = {bool(timestep_heads)} now, but the Denoiser (and the engine behind it) was built with "
@@ -767,6 +782,8 @@ class Trainer(Layer):
         eng.training_loss = loss_kind                    # (... and the `return` of train.py:265-280 that is live now)
         if trainer_math.l2_coefficients(l2)[0] != getattr(eng, "l2", 0.0):     # (... and the regularizer of train.py:80)
             eng.set_regularizer(l2)
+        if schedule != (getattr(eng, "noise_schedule", "quadratic"), getattr(eng, "alpha_dash_offset", 0.0)):     # (... and alpha_dash's live line)
+            eng.set_noise_schedule(*schedule)
         return eng
 
     def call(self, x):

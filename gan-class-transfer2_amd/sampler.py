@@ -22,7 +22,7 @@ from . import model as M
 from ._lib import SAMPLE_EPS, SAMPLE_ODE, SAMPLE_SCALED_EPS, SAMPLE_X, call
 from .engine import TORCH_DTYPE, UNetEngine
 from .trainer_math import alpha_dash            # train.py:85-93 on python floats, as in the reference
-from .trainer_math import check_timesteps
+from .trainer_math import check_noise_schedule, check_timesteps, noise_schedule_name
 
 
 def sample_mode(predict_x: bool, predict_scaled_epsilon: bool, ordinary_differential_equation: bool) -> int:
@@ -38,8 +38,9 @@ class _Sampler:
     """one network + the pointwise steps around it.  `net(B)` hands out the evaluation of a batch size: (input views for
     gct2_diffusion_mix, a function that runs the network and returns the fp32 prediction tensor)."""
 
-    def __init__(self, eng, steps: int, mode: int, H: int, W: int, use_graph: bool = True):
+    def __init__(self, eng, steps: int, mode: int, H: int, W: int, use_graph: bool = True, schedule=None, offset: float = 0.0):
         self.eng, self.steps, self.mode, self.H, self.W = eng, steps, mode, H, W
+        self.schedule, self.offset = schedule, offset            # alpha_dash's live line (train.py:85-93); None / 0.0 = the reference's
         self.planned = isinstance(eng, UNetEngine)
         # a network evaluation at batch 1 / 6 is ~20 short launches, and log_sample runs 401 of them back to back: launch-bound.
         # The planned forward pass of a buffer set is captured ONCE into a HIP graph (every pointer and shape is fixed per buffer
@@ -143,13 +144,13 @@ class _Sampler:
              e.data_ptr() if e is not None else None, pred.numel(), self._stream())
 
     def step(self, B: int, x, e, fake, t: int) -> None:
-        a = alpha_dash(t, self.steps)
+        a = alpha_dash(t, self.steps, self.schedule, self.offset)
         self.mix(B, x, e, a, fake)
         self.set_t(B, t)
         pred = self.evaluate(B)
         # ODE mode leaves epsilon_theta alone (train.py:382-392: only x_theta is assigned; `fake = ...` there is dead, the next
         # iteration recomputes it)
-        self.update(pred, fake, a, alpha_dash(t - 1, self.steps), x, None if self.mode == SAMPLE_ODE else e)
+        self.update(pred, fake, a, alpha_dash(t - 1, self.steps, self.schedule, self.offset), x, None if self.mode == SAMPLE_ODE else e)
 
 
 def _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_differential_equation) -> int:
@@ -171,40 +172,60 @@ def _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_different
     return mode
 
 
+def _resolve_schedule(eng, noise_schedule, alpha_dash_offset):
+    """the sampler's noise schedule: an explicit noise_schedule= / alpha_dash_offset= pair, else the engine's own.  Like
+    _resolve_switches: a network trained under another schedule samples garbage without any error, so an explicit pair that
+    disagrees with the engine's is refused (callables compare by identity)."""
+    have = (getattr(eng, "noise_schedule", "quadratic"), float(getattr(eng, "alpha_dash_offset", 0.0)))
+    if noise_schedule is None and alpha_dash_offset is None:
+        return have
+    want = check_noise_schedule(have[0] if noise_schedule is None else noise_schedule, have[1] if alpha_dash_offset is None else alpha_dash_offset)
+    if want != have:
+        raise ValueError(f"log_sample: noise schedule {noise_schedule_name(want[0])!r} with offset {want[1]!r} was asked for, but the engine "
+                         f"was set up for {noise_schedule_name(have[0])!r} with offset {have[1]!r} (set_noise_schedule / the module globals "
+                         "noise_schedule and alpha_dash_offset; train.py:85-93 is read by Trainer.call and log_sample alike)")
+    return want
+
+
 def log_sample(denoiser: "M.Denoiser", example_image: torch.Tensor, example: torch.Tensor, dictionary: torch.Tensor,
                steps: Optional[int] = None, test_step: Optional[int] = None, predict_x: Optional[bool] = None,
                predict_scaled_epsilon: Optional[bool] = None, ordinary_differential_equation: Optional[bool] = None,
-               use_graph: bool = True, use_ema: bool = False) -> Dict[str, torch.Tensor]:
+               use_graph: bool = True, use_ema: bool = False, noise_schedule=None, alpha_dash_offset: Optional[float] = None,
+               ) -> Dict[str, torch.Tensor]:
     """example_image [1,H,W,3] fp32 in [-1,1) (train.py:305); example [1,2,H,W,3] ~ N(0,1) (train.py:306);
     dictionary [H,W,2**bits_per_pixel,3] ~ N(0,1) (train.py:308-311); all on the HIP device.
-    use_ema: every network evaluation reads the engine's parameter averages (Adam(use_ema=True)) instead of the raw iterate."""
+    use_ema: every network evaluation reads the engine's parameter averages (Adam(use_ema=True)) instead of the raw iterate.
+    noise_schedule / alpha_dash_offset: alpha_dash's live line (train.py:85-93); by default the engine's (set_noise_schedule), an
+    explicit pair must agree with it (ValueError)."""
     eng = denoiser.ensure_engine()
     with (eng.ema_weights() if use_ema else contextlib.nullcontext()):
         return _log_sample(eng, example_image, example, dictionary, steps, test_step, predict_x, predict_scaled_epsilon,
-                           ordinary_differential_equation, use_graph)
+                           ordinary_differential_equation, use_graph, noise_schedule, alpha_dash_offset)
 
 
 def _log_sample(eng, example_image, example, dictionary, steps, test_step, predict_x, predict_scaled_epsilon,
-                ordinary_differential_equation, use_graph) -> Dict[str, torch.Tensor]:
+                ordinary_differential_equation, use_graph, noise_schedule=None, alpha_dash_offset=None) -> Dict[str, torch.Tensor]:
     steps = M.steps if steps is None else steps
     test_step = M.test_step if test_step is None else test_step
     mode = _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_differential_equation)
+    schedule, offset = _resolve_schedule(eng, noise_schedule, alpha_dash_offset)
+    alpha = lambda t: alpha_dash(t, steps, schedule, offset)
     dev = eng.device
     f32 = lambda t: t.to(dev, torch.float32).contiguous()
     example_image, example, dictionary = f32(example_image), f32(example), f32(dictionary)
     _, H, W, _ = example_image.shape
     if example.shape != (1, 2, H, W, 3) or dictionary.shape[:2] != (H, W) or dictionary.shape[3] != 3:
         raise ValueError("log_sample: example must be [1,2,H,W,3] and dictionary [H,W,K,3] for an example image [1,H,W,3]")
-    S = _Sampler(eng, steps, mode, H, W, use_graph)
+    S = _Sampler(eng, steps, mode, H, W, use_graph, schedule, offset)
     out: Dict[str, torch.Tensor] = {}
     image = example_image[0][None].contiguous()
 
     # ---- single-shot denoising (train.py:325-361): at test_step; ODE mode mixes with alpha_dash(steps / 2) ** 0.5
     if mode == SAMPLE_ODE:
-        factor = alpha_dash(steps / 2, steps) ** 0.5                  # train.py:326-328
-        a_t, a_prev = alpha_dash(steps / 2, steps), alpha_dash(steps / 2 - 1, steps)
+        factor = alpha(steps / 2) ** 0.5                              # train.py:326-328
+        a_t, a_prev = alpha(steps / 2), alpha(steps / 2 - 1)
     else:
-        factor = alpha_dash(test_step, steps)
+        factor = alpha(test_step)
         a_t, a_prev = factor, 0.0
     fake = torch.empty_like(image)
     S.mix(1, image, example[0, :1].contiguous(), factor, fake)

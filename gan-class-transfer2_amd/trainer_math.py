@@ -22,9 +22,117 @@ from ._lib import F32, Slot, call
 LOSS_SCALE_GROWTH_INTERVAL = 2000   # tf.keras.mixed_precision.LossScaleOptimizer's dynamic_growth_steps default [TF]
 
 
-def alpha_dash(t, steps: int):
-    """train.py:85-93; `t` a python float (the sampler) or a tensor (float32: the train step's t_int)."""
-    return (1 - t / (steps + 1)) ** 2 * 0.25
+# train.py:85-93: the body of alpha_dash holds six formulas, five of them commented out (the author moves the `return`), and a
+# commented-out offset behind the live one.  In the order quadratic = :93 (live), exp2 = :88, rational = :89, exp16 = :90,
+# cosine = :91, quartic = :92.  A schedule is one of these names or a callable f(t01) -> alpha (the user's own body, called on
+# t01 = t / (steps + 1)), plus a float offset added behind the formula (0.0; 1e-4 is the tail of train.py:93)
+NOISE_SCHEDULES = ("quadratic", "exp2", "rational", "exp16", "cosine", "quartic")
+
+# the bodies on t01, written once for Python floats, torch tensors and numpy arrays: c(v) types a literal (the identity for Python
+# floats and tensors, the array's dtype D for numpy, so that EVERY operation rounds in D) and cos is the cosine of that arithmetic.
+# Python's ** is right-associative: 2**8**t is 2**(8**t); 256*256 is formed in D (it overflows float16, as the reference's would)
+_SCHEDULE_BODIES = {
+    "quadratic": lambda t, c, cos: (c(1) - t) ** 2 * c(0.25),                                          # train.py:93
+    "exp2": lambda t, c, cos: c(1) - c(2) ** (t - c(1)),                                               # train.py:88
+    "rational": lambda t, c, cos: ((c(2 ** 8) - c(2) ** (c(8) ** t))
+                                   / (c(256) * c(2) ** (c(8) ** t) - c(2) ** (c(8) ** t) + c(2 ** 8))),   # train.py:89
+    "exp16": lambda t, c, cos: (c(256) * c(256)) ** (c(-1) * t),                                       # train.py:90
+    "cosine": lambda t, c, cos: cos(c(math.pi / 2) * t) ** 2,                                          # train.py:91
+    "quartic": lambda t, c, cos: (c(1) - t) ** 4,                                                      # train.py:92
+}
+
+
+def check_noise_schedule(schedule=None, offset=0.0):
+    """(schedule, offset) checked: a NOISE_SCHEDULES name (None is "quadratic") or a callable, and a finite float (ValueError)"""
+    schedule = "quadratic" if schedule is None else schedule
+    if isinstance(schedule, str):
+        if schedule not in NOISE_SCHEDULES:
+            raise ValueError(f"unknown noise_schedule {schedule!r} (one of {', '.join(NOISE_SCHEDULES)}, or a callable f(t01) -> alpha)")
+    elif not callable(schedule):
+        raise ValueError(f"noise_schedule must be one of {NOISE_SCHEDULES} or a callable f(t01) -> alpha, got {schedule!r}")
+    try:
+        off = float(offset)
+    except (TypeError, ValueError):
+        raise ValueError(f"alpha_dash_offset must be a finite float, got {offset!r}") from None
+    if not math.isfinite(off):
+        raise ValueError(f"alpha_dash_offset must be a finite float, got {offset!r}")
+    return schedule, off
+
+
+def default_noise_schedule(schedule=None, offset=0.0) -> bool:
+    """the reference as committed (train.py:93 without its tail): the formula kernels and the torch formulas serve it"""
+    return (schedule is None or (isinstance(schedule, str) and schedule == "quadratic")) and float(offset) == 0.0
+
+
+def noise_schedule_name(schedule) -> str:
+    """what a checkpoint and a message call a schedule: its name, or "custom" for a callable"""
+    return schedule if isinstance(schedule, str) else "custom"
+
+
+def alpha_dash(t, steps: int, schedule=None, offset=0.0):
+    """train.py:85-93; `t` a python float (the sampler) or a tensor (float32: the train step's t_int).  The two-argument call is the
+    reference as committed.  schedule / offset: another body (NOISE_SCHEDULES or a callable) evaluated in the arithmetic of `t` -
+    Python floats for a Python float, which is how the sampler calls it (t = steps / 2 and t - 1 = 0 included).  "cosine" on a Python
+    float is math.cos in double; TensorFlow would evaluate tf.cos of a Python float as a float32 tensor [TF]: a deviation, parity
+    unpinned (there is no TensorFlow here)."""
+    if default_noise_schedule(schedule, offset):
+        return (1 - t / (steps + 1)) ** 2 * 0.25
+    t01 = t / (steps + 1)
+    if callable(schedule):
+        a = schedule(t01)
+    else:
+        a = _SCHEDULE_BODIES[check_noise_schedule(schedule)[0]](t01, lambda v: v, torch.cos if torch.is_tensor(t01) else math.cos)
+    return a + offset if offset else a
+
+
+def _alpha_array(schedule, offset, t: np.ndarray, what: str) -> np.ndarray:
+    """alpha on the array t of t01 values, every numpy operation rounded in t's dtype D; a callable is called once on the array and
+    its result cast to D.  ValueError when the evaluation overflows or is invalid in D, or when an entry is non-finite or outside
+    [0, 1] (an underflow to 0 is legal)."""
+    schedule, offset = check_noise_schedule(schedule, offset)
+    D, name = t.dtype.type, noise_schedule_name(schedule)
+    try:
+        with np.errstate(over="raise", invalid="raise", divide="raise", under="ignore"):
+            if callable(schedule):
+                a = np.asarray(schedule(t)).astype(D)
+                if a.shape != t.shape:
+                    raise ValueError(f"the noise schedule returned shape {a.shape} for {t.shape} timesteps")
+            else:
+                a = np.asarray(_SCHEDULE_BODIES[schedule](t, D, np.cos), dtype=D)
+            if offset:
+                a = a + D(offset)
+    except (FloatingPointError, OverflowError, ZeroDivisionError) as e:
+        raise ValueError(f"noise schedule {name!r} cannot be evaluated in {np.dtype(D).name} ({what}): {e}") from None
+    if not (np.isfinite(a).all() and (a >= 0).all() and (a <= 1).all()):
+        bad = int(np.flatnonzero(~(np.isfinite(a) & (a >= 0) & (a <= 1)))[0])
+        raise ValueError(f"noise schedule {name!r} (offset {offset!r}) in {np.dtype(D).name} ({what}): alpha = {a[bad]!r} at table "
+                         f"entry {bad} is not a finite value in [0, 1]")
+    return a
+
+
+def noise_table(schedule, offset, steps: int, dtype: int) -> np.ndarray:
+    """float32 [steps, 2], entry t - 1 = (sqrt(alpha_dash(t)), sqrt(1 - alpha_dash(t))): what gct2_noise_image_table reads.  Formed
+    in the reference's operation order in D = float32 (F32 and BF16) or float16 (F16: Keras' mixed_float16, where t is an fp16
+    tensor): t = arange(1..steps).astype(D) / D(steps + 1), a division like train.py:87, the body, the offset, then sa = sqrt(a)
+    and sb = sqrt(D(1) - a) in D, widened to float32 (exactly).  ValueError as _alpha_array says."""
+    D = np.float16 if dtype == _lib.F16 else np.float32
+    if int(steps) < 1:
+        raise ValueError(f"steps must be >= 1, got {steps!r}")
+    with np.errstate(over="ignore"):
+        t = np.arange(1, int(steps) + 1).astype(D) / D(int(steps) + 1)
+    if not np.isfinite(t).all():
+        raise ValueError(f"{steps} timesteps cannot be held in {np.dtype(D).name}")
+    a = _alpha_array(schedule, offset, t, f"noise_table, steps {steps}")
+    out = np.stack([np.sqrt(a), np.sqrt(D(1) - a)], axis=1)
+    assert out.dtype == D
+    return np.ascontiguousarray(out, dtype=np.float32)
+
+
+def alpha_table(schedule, offset, steps: int) -> np.ndarray:
+    """float32 [steps + 1]: alpha_dash(t) for t = 0 .. steps in float32 arithmetic (the arithmetic of the train step's torch formula):
+    objective_coefficients gathers alpha(t) and alpha(t - 1) from it under a non-default schedule"""
+    t = np.arange(0, int(steps) + 1).astype(np.float32) / np.float32(int(steps) + 1)
+    return _alpha_array(schedule, offset, t, f"alpha_table, steps {steps}")
 
 
 def warmup_lr(k: int, base_lr: float, warm_up: int) -> float:
@@ -71,21 +179,58 @@ def objective_weighted(predict_x: bool, prediction_weighting: bool, ordinary_dif
 
 def objective_coefficients(t_int: torch.Tensor, steps: int, predict_x: bool = True, predict_scaled_epsilon: bool = False,
                            prediction_weighting: bool = False, ordinary_differential_equation: bool = False,
+                           schedule=None, offset: float = 0.0, roots: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                            ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """per-image (a, c, w) of train.py:238-252: target = a x + c eps, prediction weight w (ones unless objective_weighted) -
-    contiguous float32 vectors on t_int's device."""
+    contiguous float32 vectors on t_int's device.  The default schedule keeps its torch formula; any other gathers sqrt(alpha) and
+    sqrt(1 - alpha), formed on the host in float32 from alpha_table, at t or t - 1 (roots: those two [steps + 1] vectors already on
+    the device - an engine keeps them)."""
     t = t_int.to(torch.float32)
     one, zero = torch.ones_like(t), torch.zeros_like(t)
+    tabled = not default_noise_schedule(schedule, offset)
+    if tabled:
+        if roots is None:
+            roots = tuple(torch.from_numpy(r).to(t_int.device) for r in alpha_roots(schedule, offset, steps))
+        at = lambda r, shift: r.index_select(0, (t_int.to(torch.int64) - shift).clamp(0, steps)).contiguous()
     if ordinary_differential_equation:                                # train.py:238-242
+        if tabled:
+            return at(roots[0], 1), at(roots[1], 1), one
         a1 = alpha_dash(t - 1, steps)
         return a1.sqrt().contiguous(), (1 - a1).sqrt().contiguous(), one
     if predict_x:                                                     # train.py:243-244
         return one, zero, one
-    s = (1 - alpha_dash(t, steps)).sqrt()
+    s = at(roots[1], 0) if tabled else (1 - alpha_dash(t, steps)).sqrt()
     c = s if predict_scaled_epsilon else one                          # train.py:245-248
     if prediction_weighting:                                          # train.py:250-252
         return zero, (c * s).contiguous(), s.contiguous()
     return zero, c.contiguous(), one
+
+
+def alpha_roots(schedule, offset, steps: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(sqrt(alpha), sqrt(1 - alpha)) of alpha_table, float32 [steps + 1] each, every operation rounded in float32"""
+    a = alpha_table(schedule, offset, steps)
+    return np.sqrt(a), np.sqrt(np.float32(1.0) - a)
+
+
+def check_schedule_marker(sd: dict, schedule, offset: float) -> None:
+    """a checkpoint's "noise_schedule" entry ([index into NOISE_SCHEDULES or -1 for a callable, offset]; absent = the default)
+    against an engine's schedule: two NAMED schedules that disagree are refused, nothing is loaded - a network trained under another
+    schedule would continue (and sample) wrongly without any error.  A callable on either side cannot be compared and passes."""
+    if "noise_schedule" in sd:
+        code, have_off = int(sd["noise_schedule"][0]), float(sd["noise_schedule"][1])
+        have = NOISE_SCHEDULES[code] if 0 <= code < len(NOISE_SCHEDULES) else "custom"
+    else:
+        have, have_off = "quadratic", 0.0
+    want = noise_schedule_name(schedule)
+    if "custom" not in (have, want) and (have, have_off) != (want, float(offset)):
+        raise ValueError(f"the checkpoint was trained under noise schedule {have!r} with offset {have_off!r} and this engine runs "
+                         f"{want!r} with offset {float(offset)!r} (set_noise_schedule before loading; nothing is loaded)")
+
+
+def schedule_marker(schedule, offset: float) -> torch.Tensor:
+    """the "noise_schedule" entry of a checkpoint (written only for a non-default schedule)"""
+    code = NOISE_SCHEDULES.index(schedule) if isinstance(schedule, str) else -1
+    return torch.tensor([float(code), float(offset)], dtype=torch.float64)
 
 
 def ema_coefficients(momentum: float) -> Tuple[float, float]:
@@ -284,6 +429,12 @@ class TrainerState:
     # it on the head pair runs through gct2_dense2_fwd / gct2_dense2_bwd on the non-fused head path; single GPU only, and not
     # together with timestep_heads
     hidden_dense = False
+    # the noise schedule (train.py:85-93: which `return` of alpha_dash is live, and its offset): a NOISE_SCHEDULES name or a callable,
+    # set_noise_schedule() writes the pair.  The default keeps the formula kernels (gct2_noise_image / _rng) and the torch formula of
+    # the objective; any other goes through gct2_noise_image_table / _rng_table and host-built tables, which exist only after the
+    # first use of such a schedule
+    noise_schedule, alpha_dash_offset = "quadratic", 0.0
+    _noise_tables = None
 
     @property
     def _ema(self) -> Optional[torch.Tensor]:
@@ -351,7 +502,47 @@ class TrainerState:
         return objective_weighted(self.predict_x, self.prediction_weighting, self.ordinary_differential_equation)
 
     def objective_coefficients(self, t_int: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        return objective_coefficients(t_int, self.steps, *(getattr(self, k) for k in OBJECTIVE_SWITCHES))
+        if self._default_schedule():
+            return objective_coefficients(t_int, self.steps, *(getattr(self, k) for k in OBJECTIVE_SWITCHES))
+        return objective_coefficients(t_int, self.steps, *(getattr(self, k) for k in OBJECTIVE_SWITCHES), schedule=self.noise_schedule,
+                                      offset=self.alpha_dash_offset, roots=self._schedule_tables()[1:])
+
+    # ---- the noise schedule (train.py:85-93) ------------------------------------------------------------------------------------
+    def set_noise_schedule(self, schedule="quadratic", offset: float = 0.0) -> None:
+        """which body of alpha_dash is live: a NOISE_SCHEDULES name or a callable f(t01) -> alpha, and the offset added behind it.
+        Both tables are formed here on the host, so an unknown name, a non-finite offset, an alpha outside [0, 1] or a formula that
+        overflows in this engine's arithmetic (float16 for F16) is a ValueError before anything changes or is launched.  A setting like
+        set_regularizer: it holds from the next step on.  Optimizer launches the engine holds back are flushed first."""
+        schedule, offset = check_noise_schedule(schedule, offset)
+        if not default_noise_schedule(schedule, offset):
+            self._schedule_host(schedule, offset)
+        self.flush_deferred()
+        self.noise_schedule, self.alpha_dash_offset = schedule, offset
+
+    def _default_schedule(self) -> bool:
+        return default_noise_schedule(self.noise_schedule, self.alpha_dash_offset)
+
+    def _schedule_host(self, schedule, offset: float) -> dict:
+        """the host tables of (schedule identity, offset, steps, dtype), formed once per engine (a callable is held by the key, so
+        its identity cannot be recycled)"""
+        if self._noise_tables is None:
+            self._noise_tables = {}
+        key = (schedule, float(offset), int(self.steps), int(self.dtype))
+        if key not in self._noise_tables:
+            self._noise_tables[key] = dict(host=(noise_table(schedule, offset, self.steps, self.dtype),) + alpha_roots(schedule, offset, self.steps))
+        return self._noise_tables[key]
+
+    def _schedule_tables(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(coef [steps, 2], sqrt(alpha) [steps + 1], sqrt(1 - alpha) [steps + 1]) of the current schedule on the device: uploaded on
+        first use and kept for the engine's lifetime (step plans hold the address of coef)"""
+        entry = self._schedule_host(self.noise_schedule, self.alpha_dash_offset)
+        if "device" not in entry:
+            entry["device"] = tuple(torch.from_numpy(h).to(self.device) for h in entry["host"])
+        return entry["device"]
+
+    def _noise_coef_ptr(self) -> int:
+        """the coef argument of gct2_noise_image_table / _rng_table"""
+        return self._schedule_tables()[0].data_ptr()
 
     # ---- the training losses besides the plain MSE (train.py:254-280) -------------------------------------------------------------
     def _loss_resources(self, store: dict, B: int, H: int, W: int, Cc: int = 3) -> Tuple[int, torch.Tensor, Optional[torch.Tensor]]:

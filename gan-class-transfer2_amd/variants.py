@@ -422,8 +422,12 @@ class VariantEngine(TrainerState):
         else:
             eps = eps.to(self.device, torch.float32).contiguous()
         out = torch.empty(B, H, W, 3, dtype=TORCH_DTYPE[self.dtype], device=self.device)
-        call("gct2_noise_image", self.dtype, x.data_ptr(), t_int.data_ptr(), eps.data_ptr(), out.data_ptr(), 3, None, 0, B, H * W, 3,
-             self.steps, s)
+        if self._default_schedule():
+            call("gct2_noise_image", self.dtype, x.data_ptr(), t_int.data_ptr(), eps.data_ptr(), out.data_ptr(), 3, None, 0, B, H * W, 3,
+                 self.steps, s)
+        else:                                                  # another schedule (set_noise_schedule): the pair comes from the host's table
+            call("gct2_noise_image_table", self.dtype, x.data_ptr(), t_int.data_ptr(), eps.data_ptr(), self._noise_coef_ptr(), out.data_ptr(), 3,
+                 None, 0, B, H * W, 3, self.steps, s)
         return out, t_int, eps
 
     def _objective(self, x, t_int, eps):

@@ -37,7 +37,7 @@ enum {
 };
 
 /* library / device identification ------------------------------------------------------------ */
-int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive); v17 + gct2_sumsq_layout, gct2_grad_sumsq, gct2_adam_keras_clipped (additive); v17 + gct2_optimizer_apply, gct2_loss_scale_begin_schedule (additive); v17 + gct2_loss_scratch, gct2_loss_fwd_bwd (additive); v17 + gct2_optimizer_apply_reg, gct2_grad_sumsq_l2, gct2_l2_penalty (additive); v17 + gct2_dense_steps_fwd, gct2_dense_steps_bwd, gct2_dense_steps_scratch (additive); v17 + gct2_dense2_fwd, gct2_dense2_bwd, gct2_dense2_scratch (additive)) */
+int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive); v17 + gct2_sumsq_layout, gct2_grad_sumsq, gct2_adam_keras_clipped (additive); v17 + gct2_optimizer_apply, gct2_loss_scale_begin_schedule (additive); v17 + gct2_loss_scratch, gct2_loss_fwd_bwd (additive); v17 + gct2_optimizer_apply_reg, gct2_grad_sumsq_l2, gct2_l2_penalty (additive); v17 + gct2_dense_steps_fwd, gct2_dense_steps_bwd, gct2_dense_steps_scratch (additive); v17 + gct2_dense2_fwd, gct2_dense2_bwd, gct2_dense2_scratch (additive); v17 + gct2_noise_image_table, gct2_noise_image_rng_table (additive)) */
 /* how the library was built: 0 for the product build; bit 0 (GCT2_BUILD_STAMP) = diagnostic build with in-kernel phase stamps
  * (make EXTRA=-DGCT2_STAMP).  Product hosts (the Python binding, bench.py, the tests) refuse a library whose flags are not 0. */
 enum { GCT2_BUILD_STAMP = 1 };
@@ -388,6 +388,28 @@ int gct2_noise_image(int dtype, const float* x, const int32_t* t_int, const floa
 int gct2_noise_image_rng(int dtype, const float* x, const int32_t* t_int, uint64_t seed, uint64_t stream_id,
                          uint64_t offset, float* eps_out, void* out, int ldout, void* out2, int ldout2, int B, int HW,
                          int C, int steps, void* stream);
+
+/* the two calls above for ANY noise schedule (train.py:88-93: the author moves the `return` of alpha_dash): the kernels evaluate no
+ * formula, they read the per-timestep pair from a device table the host filled in the reference's operation order
+ * (trainer_math.noise_table).
+ * coef: float[steps][2], 8-byte aligned; entry t - 1 = (sa, sb) = (sqrt(alpha_dash(t)), sqrt(1 - alpha_dash(t))) as the host formed
+ * them - sb is never derived from sa.  Every thread reads its pair as one 8-byte load.  t_int[b] is clamped to 1..steps before the
+ * address is formed (the rule of gct2_dense_steps_fwd: a value outside the range reads entry 1 or entry steps, never past the table).
+ * GCT2_EINVAL for a NULL or misaligned coef and for steps < 1.
+ * The mix, every operation rounded once (no fused multiply-add):
+ *   GCT2_F32:  fl(fl(x * sa) + fl(eps * sb)).
+ *   GCT2_BF16: the same, and one more rounding at the bf16 store.
+ *   GCT2_F16:  (fp16)x * (fp16)sa and (fp16)eps * (fp16)sb, each rounded to fp16, then their fp16 sum; the host stores
+ *              fp16-representable pairs for this dtype, so their conversion is exact.
+ * Everything else as in the formula forms: out2, eps_out, the stream positions (gct2_noise_image_rng_table is bit-identical to
+ * gct2_rng_normal followed by gct2_noise_image_table), and the train step's 16-bit fast path under the same conditions.  With the
+ * table of the quadratic schedule both calls give the bits of gct2_noise_image / gct2_noise_image_rng (GCT2_BF16: with the product
+ * form of t described above). */
+int gct2_noise_image_table(int dtype, const float* x, const int32_t* t_int, const float* eps, const float* coef,
+                           void* out, int ldout, void* out2, int ldout2, int B, int HW, int C, int steps, void* stream);
+int gct2_noise_image_rng_table(int dtype, const float* x, const int32_t* t_int, uint64_t seed, uint64_t stream_id,
+                               uint64_t offset, float* eps_out, const float* coef, void* out, int ldout, void* out2,
+                               int ldout2, int B, int HW, int C, int steps, void* stream);
 
 /* ---- log_sample, the reference's sampler (train.py:323-496, every objective switch of train.py:29-32): pointwise steps, fp32 state ---- */
 /* fake = sqrt(alpha) x_theta + sqrt(1-alpha) eps_theta  (train.py:372-375, 441-444), alpha = alpha_dash(t) from the caller.
