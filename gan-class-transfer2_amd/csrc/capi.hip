@@ -711,6 +711,37 @@ int gct2_loss_fwd_bwd(int kind, const float* pred, const float* target, float* d
   }
 }
 
+// shape rules of the per-image losses: those of the kind, plus the limits of a (chunk, image) grid and of int element indices
+static int check_eval_shape(const char* fn, int kind, int B, int H, int W, int C) {
+  if (int e = check_loss_shape(fn, kind, B, H, W, C)) return e;
+  if (B > 65535) return gct2_fail(GCT2_EINVAL, "%s: B=%d above 65535 (one grid row per image)", fn, B);
+  if ((size_t)B * H * W * C >= ((size_t)1 << 31)) return gct2_fail(GCT2_EINVAL, "%s: B*H*W*C at or beyond 2^31", fn);
+  return GCT2_OK;
+}
+
+int gct2_eval_loss_scratch(int kind, int B, int H, int W, int C, size_t* floats) {
+  if (!floats) return gct2_fail(GCT2_EINVAL, "eval_loss_scratch: null output pointer");
+  if (int e = check_eval_shape("eval_loss_scratch", kind, B, H, W, C)) return e;
+  *floats = eval_scratch_floats(kind, B, H, W, C);
+  return GCT2_OK;
+}
+
+int gct2_eval_loss_rows(int kind, const float* pred, const float* x, const float* eps, const float* a, const float* c, const float* w,
+                        float* rows, float* scratch, size_t scratch_floats, int B, int H, int W, int C, const float* basis, void* stream) {
+  if (int e = check_eval_shape("eval_loss_rows", kind, B, H, W, C)) return e;
+  if (!pred || !x || !rows || !scratch) return gct2_fail(GCT2_EINVAL, "eval_loss_rows: null pointer");
+  if (c && !eps) return gct2_fail(GCT2_EINVAL, "eval_loss_rows: c without eps");
+  if (a && eps && !c) return gct2_fail(GCT2_EINVAL, "eval_loss_rows: a and eps without c");
+  if (kind == GCT2_LOSS_DCT && !basis) return gct2_fail(GCT2_EINVAL, "eval_loss_rows: the DCT loss needs a basis");
+  if (((uintptr_t)pred | (uintptr_t)x | (uintptr_t)eps | (uintptr_t)a | (uintptr_t)c | (uintptr_t)w | (uintptr_t)rows) % 4 ||
+      (uintptr_t)scratch % 16 || (kind == GCT2_LOSS_DCT && (uintptr_t)basis % 16))
+    return gct2_fail(GCT2_EINVAL, "eval_loss_rows: scratch and basis must be 16-byte aligned, the other pointers 4-byte aligned");
+  const size_t need = eval_scratch_floats(kind, B, H, W, C);
+  if (scratch_floats < need)
+    return gct2_fail(GCT2_EINVAL, "eval_loss_rows: %zu floats of scratch, this kind and shape need %zu (gct2_eval_loss_scratch)", scratch_floats, need);
+  return eval_loss_rows(kind, pred, x, eps, a, c, w, rows, scratch, B, H, W, C, basis, S(stream));
+}
+
 int gct2_adam_keras_multi(float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n, float alpha, float beta1,
                           float beta2, float eps, float grad_mul, const gct2_loss_scale_state* ls, int zero_grad, void* stream) {
   if (!p || !m || !v || !g) return gct2_fail(GCT2_EINVAL, "adam_keras_multi: null pointer");

@@ -434,6 +434,10 @@ int loss_pooled(const float* pred, const float* target, float* dpred, float* los
                 hipStream_t s);
 int loss_dct(const float* pred, const float* target, float* dpred, float* loss, float* scratch, int B, int S, int C, const float* basis,
              const float* ls, hipStream_t s);
+// the per-image losses of gct2_eval_loss_rows: the floats of scratch a kind and shape need / the launches
+size_t eval_scratch_floats(int kind, int B, int H, int W, int C);
+int eval_loss_rows(int kind, const float* pred, const float* x, const float* eps, const float* a, const float* c, const float* w, float* rows,
+                   float* scratch, int B, int H, int W, int C, const float* basis, hipStream_t s);
 
 // direct_kernels.hip: one thread per output, every dtype
 int tapgemm_direct(int dtype, int form, int epi, const TapGemmParams& p, hipStream_t s);

@@ -12,6 +12,9 @@
 // stage s.  A pass is out[img][m][n] = sum_k A[m][k] X[img][k][n] with A = G or G^T and n running over (line, channel) pairs of the
 // image: the column pass reduces over h (X rows are W*C contiguous floats), the row pass over w (a stride-C gather on the reduction
 // index).  Rows, columns and reduction elements beyond `size` are staged as zeros and add exact zeros.
+//
+// gct2_eval_loss_rows (evaluation: the same four losses PER IMAGE, without gradients) lives here too: it forms the residual from the
+// prediction, the clean image and the noise on load, keeps every partial sum inside one image, and reuses the two forward DCT passes.
 #include "gct2_common.h"
 #include <algorithm>
 
@@ -298,6 +301,158 @@ inline int dct_tiles(int S, int C, int* mt, int* nt) {
   return *mt * *nt;
 }
 
+// ---- the per-image losses of gct2_eval_loss_rows (Trainer.evaluate) ---------------------------------------------------------------
+// The residual is formed on load from the prediction, the clean image and the noise: target = x | a[b] x | a[b] x + c[b] eps (the
+// rule of mix_per_image_kernel), p = pred | w[b] pred, d = target - p, every operation rounded on its own.  Neither target nor p is
+// stored.  blockIdx.y (or the cell / tile index) fixes the image of a work-group: no partial sum mixes two images.
+struct EvalSrc {
+  const float* pred; const float* x; const float* eps;      // eps: null when the target has no noise term
+  const float* a; const float* c; const float* w;           // per-image coefficients, each may be null
+};
+struct EvalCoef { float a, c, w; bool has_a, has_eps, has_w; };
+
+__device__ __forceinline__ EvalCoef eval_coef(const EvalSrc& s, int b) {
+  EvalCoef k;
+  k.has_a = s.a != nullptr; k.has_eps = k.has_a && s.eps != nullptr; k.has_w = s.w != nullptr;
+  k.a = k.has_a ? s.a[b] : 1.f; k.c = k.has_eps ? s.c[b] : 0.f; k.w = k.has_w ? s.w[b] : 1.f;
+  return k;
+}
+__device__ __forceinline__ float eval_d(const EvalCoef& k, float p, float x, float e) {
+#pragma clang fp contract(off)
+  float t = x;
+  if (k.has_a) {
+    t = k.a * x;
+    if (k.has_eps) { const float ce = k.c * e; t = t + ce; }
+  }
+  const float pp = k.has_w ? k.w * p : p;
+  return t - pp;
+}
+
+constexpr int EVAL_MAX_CHUNKS = 64;        // work-groups per image at most (MSE, L1, the DCT's residual plane)
+constexpr int EVAL_GROUPS = 4;             // 16-byte groups per thread a chunk is sized for
+inline int eval_chunks(size_t n_img) {
+  const size_t per = (size_t)256 * EVAL_GROUPS * 4;
+  return (int)std::min<size_t>(EVAL_MAX_CHUNKS, std::max<size_t>(1, (n_img + per - 1) / per));
+}
+
+// KIND 0: sum d^2; 1: sum max(d, -d); 2: d is stored to dout ([B, n_img], the DCT's input plane) and nothing is summed.
+// grid = (chunks, B).  An image starts at element b * n_img, 16-byte aligned or not: with `vec` (every base pointer is 16-byte aligned)
+// the first (4 - b n_img % 4) % 4 elements and the last few are read one by one by the first threads of chunk 0 and everything between
+// them in aligned groups of four; without it the groups start at the image's first element and are read element by element.
+template <int KIND>
+__global__ __launch_bounds__(256) void eval_rows_kernel(EvalSrc s, float* __restrict__ dout, double* __restrict__ partials, int n_img, int vec) {
+#pragma clang fp contract(off)
+  __shared__ double ws4[4];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const size_t base = (size_t)b * n_img;
+  const EvalCoef k = eval_coef(s, b);
+  const float* __restrict__ pp = s.pred + base;
+  const float* __restrict__ xp = s.x + base;
+  const float* __restrict__ ep = k.has_eps ? s.eps + base : nullptr;
+  float* __restrict__ op = KIND == 2 ? dout + base : nullptr;
+  const int head = vec ? min(n_img, (int)((4 - (base & 3)) & 3)) : 0;
+  const int n4 = (n_img - head) >> 2, rest = n_img - head - 4 * n4;
+  const int per = (n4 + gridDim.x - 1) / gridDim.x;
+  const int q1 = min(n4, ((int)blockIdx.x + 1) * per);
+  double acc = 0.0;
+  auto term = [&](float d) {
+    if (KIND == 0) acc += (double)d * (double)d;
+    if (KIND == 1) { const float nd = -d; acc += (double)(d >= nd ? d : nd); }
+  };
+  for (int q = blockIdx.x * per + tid; q < q1; q += 256) {
+    const int i = head + 4 * q;
+    const f32x4_t p = ld4(pp + i, vec), x = ld4(xp + i, vec);
+    const f32x4_t e = ep ? ld4(ep + i, vec) : f32x4_t{0.f, 0.f, 0.f, 0.f};
+    f32x4_t d;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      d[j] = eval_d(k, p[j], x[j], e[j]);
+      term(d[j]);
+    }
+    if (KIND == 2) st4(op + i, d, vec);
+  }
+  if (blockIdx.x == 0 && tid < head + rest) {        // at most 6 elements: the unaligned head and the last n % 4
+    const int i = tid < head ? tid : 4 * n4 + tid;
+    const float d = eval_d(k, pp[i], xp[i], ep ? ep[i] : 0.f);
+    term(d);
+    if (KIND == 2) op[i] = d;
+  }
+  if (KIND != 2) {
+    const double sum = block_sum(acc, ws4);
+    if (tid == 0) partials[(size_t)b * gridDim.x + blockIdx.x] = sum;
+  }
+}
+
+// pooled MSE per image: pooled_kernel's cell layout (one work-group per 16 x 16 cell, thread = (row, group of four)), loss only, the
+// cell sums kept in fp64.  partials[cell] = sum d^2, partials[ncells + cell] = sum over channels of (qsum / 256)^2
+__global__ __launch_bounds__(256) void eval_pooled_kernel(EvalSrc s, double* __restrict__ partials, int H, int W, int C, int ncells, int vec) {
+#pragma clang fp contract(off)
+  __shared__ float ds[16][64];
+  __shared__ double col[64];
+  __shared__ double qs[4];
+  __shared__ double ws4[4];
+  const int tid = threadIdx.x, cell = blockIdx.x;
+  const int cw = W >> 4, chh = H >> 4;
+  const int cx = cell % cw, cy = (cell / cw) % chh, b = cell / (cw * chh);
+  const EvalCoef k = eval_coef(s, b);
+  const int groups = 4 * C;
+  const bool active = tid < 16 * groups;
+  const int r = tid / groups, q = tid - r * groups;
+  const size_t base = (((size_t)b * H + (size_t)cy * 16 + r) * W + (size_t)cx * 16) * C + 4 * q;
+  double acc = 0.0;
+  if (active) {
+    const f32x4_t p = ld4(s.pred + base, vec), x = ld4(s.x + base, vec);
+    const f32x4_t e = k.has_eps ? ld4(s.eps + base, vec) : f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const float d = eval_d(k, p[j], x[j], e[j]);
+      ds[r][4 * q + j] = d;
+      acc += (double)d * (double)d;
+    }
+  }
+  __syncthreads();
+  if (tid < 16 * C) {                                // rows first ...
+    double sum = 0.0;
+    for (int rr = 0; rr < 16; rr++) sum += (double)ds[rr][tid];
+    col[tid] = sum;
+  }
+  __syncthreads();
+  if (tid < C) {                                     // ... then the 16 pixels of the row, ascending
+    double sum = 0.0;
+    for (int x = 0; x < 16; x++) sum += col[x * C + tid];
+    qs[tid] = sum;
+  }
+  const double s1 = block_sum(acc, ws4);             // (its barriers also publish qs)
+  if (tid == 0) {
+    double s2 = 0.0;
+    for (int c = 0; c < C; c++) {
+      const double m = qs[c] / 256.0;
+      s2 += m * m;
+    }
+    partials[cell] = s1;
+    partials[ncells + cell] = s2;
+  }
+}
+
+// rows[b] = (float)(S1 / dn [+ S2 / dn2]) with S1 = part[b n1, (b + 1) n1) and S2 = part[off2 + b n2, off2 + (b + 1) n2), each added
+// in index order per thread and then over the threads (loss_finish_kernel per image): one work-group per image
+__global__ __launch_bounds__(256) void eval_finish_kernel(const double* __restrict__ part, int n1, int n2, size_t off2, double dn, double dn2,
+                                                          float* __restrict__ rows) {
+#pragma clang fp contract(off)
+  __shared__ double ws4[4];
+  const double* __restrict__ p1 = part + (size_t)blockIdx.x * n1;
+  const double* __restrict__ p2 = part + off2 + (size_t)blockIdx.x * n2;
+  double a1 = 0.0, a2 = 0.0;
+  for (int i = threadIdx.x; i < n1; i += 256) a1 += p1[i];
+  for (int i = threadIdx.x; i < n2; i += 256) a2 += p2[i];
+  const double s1 = block_sum(a1, ws4);
+  const double s2 = block_sum(a2, ws4);
+  if (threadIdx.x == 0) {
+    const double q1 = s1 / dn;
+    rows[blockIdx.x] = n2 ? (float)(q1 + s2 / dn2) : (float)q1;
+  }
+}
+
 }  // namespace
 
 // floats of scratch a kind needs: the partial sums (fp64, two floats each) and, for the DCT, one [B,H,W,C] plane set behind them
@@ -368,4 +523,56 @@ int loss_dct(const float* pred, const float* target, float* dpred, float* loss, 
   }
   hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, s, part, nblocks, 0, (double)n, 0.0, loss);
   return gct2_check_launch("loss_fwd_bwd (dct)");
+}
+
+// ---- gct2_eval_loss_rows --------------------------------------------------------------------------------------------------------
+// scratch: the fp64 partial sums (two floats each) and, for the DCT, the residual plane and the plane of the first pass behind them
+static size_t eval_partial_floats(int kind, int B, int H, int W, int C) {
+  if (kind == GCT2_LOSS_MSE_POOLED) return round4(4 * (size_t)B * (H / 16) * (W / 16));
+  if (kind == GCT2_LOSS_DCT) {
+    int mt, nt;
+    return round4(2 * (size_t)B * dct_tiles(H, C, &mt, &nt));
+  }
+  return round4(2 * (size_t)B * eval_chunks((size_t)H * W * C));
+}
+size_t eval_scratch_floats(int kind, int B, int H, int W, int C) {
+  const size_t part = eval_partial_floats(kind, B, H, W, C);
+  return kind == GCT2_LOSS_DCT ? part + 2 * round4((size_t)B * H * W * C) : part;
+}
+
+int eval_loss_rows(int kind, const float* pred, const float* x, const float* eps, const float* a, const float* c, const float* w, float* rows,
+                   float* scratch, int B, int H, int W, int C, const float* basis, hipStream_t s) {
+  const int n_img = H * W * C;
+  const EvalSrc src{pred, x, a ? eps : nullptr, a, c, w};
+  const int vec = !(((uintptr_t)pred | (uintptr_t)x | (uintptr_t)src.eps) % 16);
+  double* part = reinterpret_cast<double*>(scratch);
+  const int chunks = eval_chunks((size_t)n_img);
+  if (kind == GCT2_LOSS_MSE || kind == GCT2_LOSS_L1) {
+    if (kind == GCT2_LOSS_MSE) hipLaunchKernelGGL(eval_rows_kernel<0>, dim3(chunks, B), dim3(256), 0, s, src, nullptr, part, n_img, vec);
+    else hipLaunchKernelGGL(eval_rows_kernel<1>, dim3(chunks, B), dim3(256), 0, s, src, nullptr, part, n_img, vec);
+    hipLaunchKernelGGL(eval_finish_kernel, dim3(B), dim3(256), 0, s, part, chunks, 0, (size_t)0, (double)n_img, 0.0, rows);
+    return gct2_check_launch(kind == GCT2_LOSS_MSE ? "eval_loss_rows (mse)" : "eval_loss_rows (l1)");
+  }
+  if (kind == GCT2_LOSS_MSE_POOLED) {
+    const int cpi = (H / 16) * (W / 16), cells = B * cpi;
+    hipLaunchKernelGGL(eval_pooled_kernel, dim3((unsigned)cells), dim3(256), 0, s, src, part, H, W, C, cells, vec);
+    hipLaunchKernelGGL(eval_finish_kernel, dim3(B), dim3(256), 0, s, part, cpi, cpi, (size_t)cells, (double)n_img, (double)cpi * C, rows);
+    return gct2_check_launch("eval_loss_rows (mse_pooled)");
+  }
+  // DCT: d -> scratch, T = G d (over h) -> scratch, E = T G^T (over w) summed per tile; loss_dct's first two passes
+  const int S = H;
+  const size_t n = (size_t)B * n_img;
+  float* dplane = scratch + eval_partial_floats(kind, B, H, W, C);
+  float* tplane = dplane + round4(n);
+  hipLaunchKernelGGL(eval_rows_kernel<2>, dim3(chunks, B), dim3(256), 0, s, src, dplane, nullptr, n_img, vec);
+  DctPass p{};
+  p.G = basis; p.S = S; p.C = C; p.N = S * C; p.at = 0; p.xsub = nullptr; p.scale = 0; p.c1 = 0.f; p.ls = nullptr;
+  const int tiles = dct_tiles(S, C, &p.m_tiles, &p.n_tiles);
+  DctPass col = p, row = p;
+  col.x = dplane; col.out = tplane; col.partials = nullptr; col.sk = S * C; col.rs = C; col.xvec = 1;
+  row.x = tplane; row.out = nullptr; row.partials = part; row.sk = C; row.rs = S * C; row.xvec = 0;
+  hipLaunchKernelGGL(dct_pass_kernel, dim3(B * tiles), dim3(256), 0, s, col);
+  hipLaunchKernelGGL(dct_pass_kernel, dim3(B * tiles), dim3(256), 0, s, row);
+  hipLaunchKernelGGL(eval_finish_kernel, dim3(B), dim3(256), 0, s, part, tiles, 0, (size_t)0, (double)n_img, 0.0, rows);
+  return gct2_check_launch("eval_loss_rows (dct)");
 }

@@ -60,9 +60,40 @@ class ImageDataset:
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.rng = np.random.default_rng(seed)
         self.shuffle_buffer, self.prefetch = shuffle_buffer, prefetch
+        self.finite = False             # training mode: an endless shuffled stream (ImageDataset.validation builds the finite form)
+
+    @classmethod
+    def validation(cls, source, size: int, batch_size: int, device: Optional[torch.device] = None,
+                   decoder: Callable[[str], np.ndarray] = decode_rgb, prefetch: int = 2) -> "ImageDataset":
+        """the held-out folder (the reference's test/ beside train/) for Trainer.evaluate and fit(validation_data=...): ONE pass over
+        the items in sorted order (a list keeps its order), the centre size x size crop with origin ((H0 - size) // 2, (W0 - size) // 2),
+        no flip, the last partial batch kept - nothing is drawn, so iterating it again gives the same batches.  The device side is the
+        training one (gct2_image_prepare)."""
+        ds = cls(source, size, batch_size, device=device, shuffle_buffer=1, prefetch=prefetch, crop=True, decoder=decoder)
+        ds.finite = True
+        return ds
 
     # ---- host side: pick, decode, draw the augmentation --------------------------------------------------------------------
+    def _decoded(self, it) -> np.ndarray:
+        im = self.decoder(it) if isinstance(it, str) else np.ascontiguousarray(it, dtype=np.uint8)
+        if im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < self.size or im.shape[1] < self.size:
+            raise ValueError(f"image of shape {im.shape} cannot be cropped to {self.size}x{self.size}x3 (tf.image.random_crop "
+                             "raises here, train.py:289)")
+        return im
+
+    def _validation_batches(self) -> Iterator[Tuple[List[np.ndarray], np.ndarray]]:
+        for first in range(0, len(self.items), self.batch_size):
+            imgs = [self._decoded(it) for it in self.items[first:first + self.batch_size]]
+            dims = np.zeros((len(imgs), 5), dtype=np.int32)
+            for b, im in enumerate(imgs):
+                H0, W0 = im.shape[:2]
+                dims[b] = (H0, W0, (H0 - self.size) // 2, (W0 - self.size) // 2, 0)
+            yield imgs, dims
+
     def host_batches(self) -> Iterator[Tuple[List[np.ndarray], np.ndarray]]:
+        if self.finite:
+            yield from self._validation_batches()
+            return
         stream = shuffle_repeat(self.items, self.shuffle_buffer, self.rng)
         while True:
             imgs, dims = [], np.zeros((self.batch_size, 5), dtype=np.int32)
@@ -116,6 +147,7 @@ class ImageDataset:
                     ev = torch.cuda.Event()
                     ev.record(side)
                     q.put((x, ev))
+                q.put(None)                     # a finite (validation) pass is over
             except BaseException as e:          # surface decoder / shape errors in the consumer
                 q.put(e)
 
@@ -126,6 +158,8 @@ class ImageDataset:
                 item = q.get()
                 if isinstance(item, BaseException):
                     raise item
+                if item is None:
+                    return
                 x, ev = item
                 torch.cuda.current_stream(self.device).wait_event(ev)
                 x.record_stream(torch.cuda.current_stream(self.device))

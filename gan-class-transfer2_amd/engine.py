@@ -32,6 +32,7 @@ from .trainer_math import check_hidden_marker as TM_check_hidden_marker
 from .trainer_math import check_schedule_marker as TM_check_schedule_marker
 from .trainer_math import schedule_marker as TM_schedule_marker
 from .trainer_math import OPTIMIZER_KINDS as _OPTIMIZER_CODES
+from .trainer_math import EVAL_STREAM_EPS
 
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 
@@ -1249,6 +1250,26 @@ class UNetEngine(TrainerState):
             b.t_int.copy_(torch.tensor(vals, dtype=torch.int32))
         self.load_input_into_r0(b, noised)
         return self.forward(b)
+
+    # ---- evaluation (TrainerState.evaluate_batch): where the input goes and how the forward pass runs ------------------------------
+    def _eval_buffers(self, B: int, H: int, W: int) -> Tuple[torch.Tensor, torch.Tensor, dict]:
+        """the buffer set of this shape (a train step of the same shape overwrites everything evaluation leaves in it)"""
+        b = self._eval_b = self.buffers(B, H, W)
+        return b.t_int, b.eps, b.loss_store
+
+    def _eval_noise(self, x: torch.Tensor, t_int: torch.Tensor, eps: torch.Tensor, draw) -> torch.Tensor:
+        """forward(head=True) reads the image channels from R_0 itself, so the noised image goes to R_0's strided slice and to the
+        packed copy.  On that pair of views gct2_rng_normal + gct2_noise_image (the same bits, by the contract of the fused call) take
+        35.7 us at config 3 where gct2_noise_image_rng takes 47.8 us (a kernel trace on one MI355X): the noise is drawn first"""
+        b = self._eval_b
+        if draw is not None:
+            seed, offset, _ = draw
+            call("gct2_rng_normal", seed, EVAL_STREAM_EPS, offset, eps.data_ptr(), eps.numel(), self._stream())
+        self.noise_into_r0(b, x, unfused_head=True)
+        return b.img
+
+    def _eval_forward(self, noised: torch.Tensor, t_int: torch.Tensor) -> torch.Tensor:
+        return self.forward(self._eval_b)                      # (flush_deferred() first, as predict)
 
     # ---- state serialisation (SURVEY.md 8f rank 4; the reference has none, train.py:499-503 only logs) ----------------
     def state_dict(self) -> Dict[str, torch.Tensor]:

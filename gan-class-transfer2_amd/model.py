@@ -13,6 +13,7 @@ from __future__ import annotations
 import sys
 from typing import Callable, Dict, Iterable, List, Optional, Sequence as Seq
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -841,12 +842,90 @@ class Trainer(Layer):
             inner._engine = eng
         return {"loss": loss}
 
-    def fit(self, dataset: Iterable, steps_per_epoch: int = 1000, epochs: int = 1, callbacks: Seq = (), verbose: int = 1):
-        """train.py:516-523.  `dataset` yields (image, image) batches, NHWC in [-1, 1)."""
+    def evaluate(self, dataset: Iterable, steps: Optional[int] = None, return_dict: bool = False, use_ema: bool = False, t=None,
+                 seed: Optional[int] = None):
+        """Keras' Model.evaluate on held-out data: the training loss as it stands now (objective, training_loss, noise schedule),
+        averaged over every IMAGE `dataset` yields - (x, x) pairs or bare x batches, a partial last batch included.  steps: at most
+        that many batches (None: until the dataset ends; an endless dataset then is a ValueError where it can be known).  Each image
+        gets its timestep and noise from evaluation's own streams by its running index (TrainerState.evaluate_batch), so the figure
+        does not depend on the batch size and no training state moves; t: one timestep (or one per image of a batch) instead;
+        seed: instead of the engine's rng_seed.  use_ema: the averaged weights.  With an L2 regularizer the penalty of the weights
+        read is added, as in the train step's loss.  One host synchronisation, at the end.
+        return_dict: {"loss": float, "per_image": float32 [N] (the data term of every image), "t": int32 [N]} instead of the float."""
+        if steps is not None and (isinstance(steps, bool) or not isinstance(steps, int) or steps < 1):
+            raise ValueError(f"evaluate: steps must be a positive int or None, got {steps!r}")
+        if steps is None and getattr(dataset, "finite", True) is False:
+            raise ValueError("evaluate: the dataset never ends (an ImageDataset in training mode): pass steps, or build it with "
+                             "ImageDataset.validation")
+        eng = self._engine()
+        rows, ts, index = [], [], 0
+
+        def run():
+            nonlocal index
+            for k, data in enumerate(dataset):
+                x = data[0] if isinstance(data, (tuple, list)) else data
+                r, tt = eng.evaluate_batch(x, index0=index, t=t, seed=seed)
+                rows.append(r)
+                ts.append(tt)
+                index += int(x.shape[0])
+                if steps is not None and k + 1 >= steps:       # (an endless dataset is not asked for a batch nobody reads)
+                    break
+
+        if use_ema:
+            with eng.ema_weights():
+                run()
+                penalty = self._evaluation_penalty(eng)
+        else:
+            run()
+            penalty = self._evaluation_penalty(eng)
+        if not rows:
+            raise ValueError("evaluate: the dataset yielded no batch")
+        per_image = torch.cat(rows).cpu().numpy()              # the one host synchronisation
+        t_all = torch.cat(ts).cpu().numpy()
+        loss = float(np.mean(per_image, dtype=np.float64))
+        if penalty is not None:
+            loss += float(penalty.cpu()[0])
+        if return_dict:
+            return {"loss": loss, "per_image": per_image, "t": t_all}
+        return loss
+
+    @staticmethod
+    def _evaluation_penalty(eng) -> Optional[torch.Tensor]:
+        """l2 * sum(w^2) over the regularized tensors of the weights evaluation just read (the averages inside ema_weights()), fp32 [1]
+        on the device; None without a regularizer.  Scalars of its own: the train step's reported penalty stays what it was."""
+        if not getattr(eng, "l2", 0.0) > 0.0:
+            return None
+        eng.flush_deferred()
+        if getattr(eng, "_eval_l2_state", None) is None:       # (built once: the segment table, the partial sums, three scalars)
+            eng._eval_l2_state = (eng._sumsq_tables(eng._l2_segments()), torch.zeros(3, dtype=torch.float32, device=eng._clip_device()))
+        (table, nseg, npartials, partials, sumsq, _), scalars = eng._eval_l2_state
+        p = eng._ema if eng._ema_reading else eng._fp32_parameters()
+        zero, penalty, total = scalars[0:1].zero_(), scalars[1:2], scalars[2:3]
+        s = eng._stream()
+        _lib.call("gct2_grad_sumsq", p.data_ptr(), table.data_ptr(), nseg, npartials, 1.0, None, partials.data_ptr(), sumsq.data_ptr(), s)
+        _lib.call("gct2_l2_penalty", zero.data_ptr(), sumsq.data_ptr() + 8 * nseg, float(eng.l2), penalty.data_ptr(), total.data_ptr(), s)
+        return penalty
+
+    def fit(self, dataset: Iterable, steps_per_epoch: int = 1000, epochs: int = 1, callbacks: Seq = (), verbose: int = 1,
+            validation_data: Optional[Iterable] = None, validation_steps: Optional[int] = None, validation_freq: int = 1,
+            validation_use_ema: bool = False):
+        """train.py:516-523.  `dataset` yields (image, image) batches, NHWC in [-1, 1).
+        validation_data (Keras' argument; None: nothing about fit changes): after every validation_freq-th epoch,
+        evaluate(iter(validation_data), validation_steps, use_ema=validation_use_ema) goes into logs["val_loss"] and
+        history["val_loss"] before on_epoch_end runs - pass something that can be iterated once per validation (a list of batches,
+        an ImageDataset.validation)."""
         if self.optimizer is None:
             raise RuntimeError("call compile(optimizer, loss) before fit (train.py:511)")
+        if validation_data is not None:
+            if isinstance(validation_freq, bool) or not isinstance(validation_freq, int) or validation_freq < 1:
+                raise ValueError(f"fit: validation_freq must be a positive int, got {validation_freq!r}")
+            if validation_steps is None and getattr(validation_data, "finite", True) is False:
+                raise ValueError("fit: validation_data never ends (an ImageDataset in training mode): pass validation_steps, or build "
+                                 "it with ImageDataset.validation")
         it = iter(dataset)
         history = {"loss": []}
+        if validation_data is not None:
+            history["val_loss"] = []
         for epoch in range(epochs):
             logs: Dict[str, float] = {}
             for cb in callbacks:
@@ -858,8 +937,13 @@ class Trainer(Layer):
                 running = out["loss"] if running is None else running + out["loss"]
             logs["loss"] = float(running[0]) / steps_per_epoch     # one host sync per epoch
             history["loss"].append(logs["loss"])
+            line = f"Epoch {epoch + 1}/{epochs} - loss: {logs['loss']:.6f}"
+            if validation_data is not None and (epoch + 1) % validation_freq == 0:
+                logs["val_loss"] = self.evaluate(iter(validation_data), validation_steps, use_ema=validation_use_ema)
+                history["val_loss"].append(logs["val_loss"])
+                line += f" - val_loss: {logs['val_loss']:.6f}"
             if verbose:
-                print(f"Epoch {epoch + 1}/{epochs} - loss: {logs['loss']:.6f}", flush=True)
+                print(line, flush=True)
             for cb in callbacks:
                 if getattr(cb, "on_epoch_end", None):
                     cb.on_epoch_end(epoch, logs)

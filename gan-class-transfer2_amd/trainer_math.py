@@ -327,6 +327,35 @@ def training_loss_code(name: str) -> int:
     return _LOSS_CODES[name]
 
 
+# the Philox stream ids of evaluation (TrainerState.evaluate_batch): the train step draws t from stream 1 and eps from stream 2
+EVAL_STREAM_T, EVAL_STREAM_EPS = 3, 4
+
+
+def loss_by_timestep(per_image, t, steps: int, bins: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """(counts int64 [bins], means float64 [bins]) of per-image losses grouped by timestep: which timesteps are hard.  per_image and
+    t: N values each (arrays or tensors; t integers in 1..steps).  bins=None: one bin per timestep (bin k holds t = k + 1); else
+    `bins` equal-width groups, timestep t in bin (t - 1) * bins // steps.  Host only, numpy float64; an empty bin's mean is NaN."""
+    as_np = lambda v: v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+    loss, tt = as_np(per_image).astype(np.float64).reshape(-1), as_np(t).reshape(-1)
+    steps = int(steps)
+    nb = steps if bins is None else int(bins)
+    if steps < 1 or not 1 <= nb <= steps:
+        raise ValueError(f"loss_by_timestep: bins = {bins!r} must lie in 1..steps = {steps}")
+    if tt.shape != loss.shape:
+        raise ValueError(f"loss_by_timestep: {loss.size} losses for {tt.size} timesteps")
+    if tt.size and not np.issubdtype(tt.dtype, np.integer):
+        raise ValueError(f"loss_by_timestep: timesteps must be integers, got {tt.dtype}")
+    tt = tt.astype(np.int64)
+    if tt.size and (tt.min() < 1 or tt.max() > steps):
+        raise ValueError(f"loss_by_timestep: timesteps outside 1..{steps}")
+    which = (tt - 1) * nb // steps
+    counts = np.bincount(which, minlength=nb).astype(np.int64)
+    sums = np.bincount(which, weights=loss, minlength=nb).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        means = np.where(counts > 0, sums / np.maximum(counts, 1), np.nan)
+    return counts, means
+
+
 def check_timesteps(t, batch: int, steps: int) -> list:
     """the timesteps of a batch for the per-timestep heads (train.py:211-214: tf.gather(prediction, t - 1, batch_dims=3)) as a list
     of `batch` Python ints in 1..steps.  t: one integer (every image), or a sequence / tensor / array of `batch` integers (a single
@@ -566,6 +595,78 @@ class TrainerState:
         code, scratch, basis = self._loss_resources(store, B, H, W, Cc)
         call("gct2_loss_fwd_bwd", code, pred.data_ptr(), target, dpred.data_ptr() if dpred is not None else None, loss.data_ptr(),
              scratch.data_ptr(), scratch.numel(), B, H, W, Cc, basis.data_ptr() if basis is not None else None, self._ls_ptr(), stream)
+
+    # ---- evaluation: the training loss per held-out image (Keras Model.evaluate / fit(validation_data=...)) ----------------------------
+    # what an engine provides: _eval_buffers(B, H, W) -> (t_int int32 [B], eps fp32 [B,H,W,3], store dict), device tensors the engine
+    # keeps per shape; _eval_noise(x, t_int, eps, draw) -> the noised network input, stored where its forward pass reads it (draw None:
+    # eps holds the noise; else (seed, offset, keep): drawn inside the noising kernel from stream EVAL_STREAM_EPS, written to eps only
+    # when keep); _eval_forward(noised, t_int) -> the fp32 [B,H,W,3] prediction, optimizer launches held back flushed first
+    def _eval_resources(self, store: dict, B: int, H: int, W: int, Cc: int = 3) -> Tuple[int, torch.Tensor, Optional[torch.Tensor], torch.Tensor]:
+        """(kind code, scratch, basis or None, rows [B]) of gct2_eval_loss_rows for the current training_loss and this shape: allocated
+        on first use and kept in `store`; a shape the kind refuses raises here, before anything is launched"""
+        code = training_loss_code(self.training_loss)
+        key = ("eval", code, B, H, W, Cc)
+        if key not in store:
+            need = C.c_size_t(0)
+            _lib.check(self.lib.gct2_eval_loss_scratch(code, B, H, W, Cc, C.byref(need)), "gct2_eval_loss_scratch")
+            scratch = torch.zeros(max(4, need.value), dtype=torch.float32, device=self.device)
+            basis = torch.from_numpy(dct_basis(H)).to(self.device) if code == _lib.LOSS_DCT else None
+            store[key] = (scratch, basis)
+        return (code,) + store[key]
+
+    def evaluate_batch(self, x: torch.Tensor, index0: int = 0, t=None, eps: Optional[torch.Tensor] = None,
+                       seed: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """the training loss of every image of a held-out batch on its own: (rows fp32 [B], t_int int32 [B]), device tensors, no host
+        synchronisation.  In exact arithmetic rows.mean() is what Trainer.call computes for the same t and eps.
+
+        The draws belong to evaluation alone and depend on the image, not on the batch: with seed (None: rng_seed), the image of
+        global index i = index0 + k takes position i of Philox stream EVAL_STREAM_T for its timestep and positions
+        [i*H*W*3, (i+1)*H*W*3) of stream EVAL_STREAM_EPS for its noise, however the validation set is cut into batches.  t: an int or B
+        ints in 1..steps instead of the draw (check_timesteps); eps: injected noise, fp32 [B,H,W,3].
+
+        A pure function of the weights: the training streams' offsets, iterations, the optimizer slots, the averages, the loss-scale
+        state and the recorded step plans are left alone, nothing is scaled in place and the loss is never multiplied by a loss scale.
+        Refused inside a plan recording."""
+        if _lib._recording is not None:
+            raise _lib.Gct2Error("evaluate_batch inside a plan recording: evaluation is not part of a train step")
+        if x.dim() != 4 or x.shape[-1] != 3:
+            raise ValueError(f"expected an NHWC batch [B,H,W,3], got {tuple(x.shape)}")
+        index0 = int(index0)
+        if index0 < 0:
+            raise ValueError(f"index0 must be >= 0, got {index0}")
+        B, H, W, _ = x.shape
+        vals = None if t is None else check_timesteps(t, B, self.steps)
+        if eps is not None and tuple(eps.shape) != tuple(x.shape):
+            raise ValueError(f"eps of shape {tuple(eps.shape)} for a batch of shape {tuple(x.shape)}")
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.device != self.device:
+            x = x.to(self.device, torch.float32).contiguous()
+        seed = int(self.rng_seed if seed is None else seed)
+        t_int, eps_buf, store = self._eval_buffers(B, H, W)
+        code, scratch, basis = self._eval_resources(store, B, H, W)
+        rows = torch.empty(B, dtype=torch.float32, device=self.device)
+        s = self._stream()
+        if vals is None:
+            call("gct2_rng_uniform_int", seed, EVAL_STREAM_T, index0, t_int.data_ptr(), B, 1, self.steps, s)
+        else:
+            t_int.copy_(torch.tensor(vals, dtype=torch.int32))
+        default = self.default_objective()
+        if eps is not None:
+            eps_buf.copy_(eps.to(self.device, torch.float32))
+            noised = self._eval_noise(x, t_int, eps_buf, None)
+        else:
+            noised = self._eval_noise(x, t_int, eps_buf, (seed, index0 * H * W * 3, not default))
+        pred = self._eval_forward(noised, t_int)
+        a = c = w = None
+        if not default:                                        # train.py:238-252; the target is formed inside the loss kernel
+            a, c, w = self.objective_coefficients(t_int)
+            if not self.objective_weighted():
+                w = None
+        call("gct2_eval_loss_rows", code, pred.data_ptr(), x.data_ptr(), None if default else eps_buf.data_ptr(),
+             None if a is None else a.data_ptr(), None if c is None else c.data_ptr(), None if w is None else w.data_ptr(), rows.data_ptr(),
+             scratch.data_ptr(), scratch.numel(), B, H, W, 3, basis.data_ptr() if basis is not None else None, s)
+        # what the launches read stays alive with the engine until the next evaluation (and is what the tests restate the rows from)
+        self.last_eval = dict(x=x, pred=pred, eps=None if default and eps is None else eps_buf, t_int=t_int, coef=(a, c, w), noised=noised)
+        return rows, t_int.clone()
 
     # ---- per-timestep heads (train.py:199, 203, 211-214) ------------------------------------------------------------------------
     def head_shapes(self, cin: int) -> Tuple[Tuple[int, int], Tuple[int]]:

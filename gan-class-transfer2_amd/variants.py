@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import BF16, F16, F32, call
-from .trainer_math import TrainerState, check_head_options, check_timesteps, glorot_limit
+from .trainer_math import EVAL_STREAM_EPS, TrainerState, check_head_options, check_timesteps, glorot_limit
 
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 
@@ -479,6 +479,37 @@ class VariantEngine(TrainerState):
         if apply:
             self.apply_adam()
         return loss
+
+    # ---- evaluation (TrainerState.evaluate_batch): where the input goes and how the forward pass runs ------------------------------
+    def _eval_buffers(self, B: int, H: int, W: int):
+        if H % (2 ** self.octaves) or W % (2 ** self.octaves):
+            raise ValueError(f"spatial size {H}x{W} is not divisible by 2**octaves (train.py:114-119)")
+        sets = self.__dict__.setdefault("_eval_sets", {})
+        if (B, H, W) not in sets:
+            sets[(B, H, W)] = (torch.zeros(B, dtype=torch.int32, device=self.device),
+                               torch.zeros(B, H, W, 3, dtype=torch.float32, device=self.device), {})
+        return sets[(B, H, W)]
+
+    def _eval_noise(self, x, t_int, eps, draw):
+        B, H, W, _ = x.shape
+        out = torch.empty(B, H, W, 3, dtype=TORCH_DTYPE[self.dtype], device=self.device)
+        tail = (out.data_ptr(), 3, None, 0, B, H * W, 3, self.steps, self.net.stream())
+        if draw is None:
+            head, name = (self.dtype, x.data_ptr(), t_int.data_ptr(), eps.data_ptr()), "gct2_noise_image"
+        else:
+            seed, offset, keep = draw
+            head = (self.dtype, x.data_ptr(), t_int.data_ptr(), seed, EVAL_STREAM_EPS, offset, eps.data_ptr() if keep else None)
+            name = "gct2_noise_image_rng"
+        if self._default_schedule():
+            call(name, *head, *tail)
+        else:
+            call(name + "_table", *head, self._noise_coef_ptr(), *tail)
+        return out
+
+    def _eval_forward(self, noised, t_int):
+        self.flush_deferred()
+        self.net.t_int = t_int                                 # (the per-timestep heads read it inside their kernels)
+        return self.top.fwd(noised)
 
     def apply_adam(self) -> None:
         N, s = self.net, self.net.stream()

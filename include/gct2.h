@@ -37,7 +37,7 @@ enum {
 };
 
 /* library / device identification ------------------------------------------------------------ */
-int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive); v17 + gct2_sumsq_layout, gct2_grad_sumsq, gct2_adam_keras_clipped (additive); v17 + gct2_optimizer_apply, gct2_loss_scale_begin_schedule (additive); v17 + gct2_loss_scratch, gct2_loss_fwd_bwd (additive); v17 + gct2_optimizer_apply_reg, gct2_grad_sumsq_l2, gct2_l2_penalty (additive); v17 + gct2_dense_steps_fwd, gct2_dense_steps_bwd, gct2_dense_steps_scratch (additive); v17 + gct2_dense2_fwd, gct2_dense2_bwd, gct2_dense2_scratch (additive); v17 + gct2_noise_image_table, gct2_noise_image_rng_table (additive)) */
+int gct2_abi_version(void);                 /* bumps when a signature below changes (v13: ReLU bit planes; v14: pruned tuning word, launch log, no deferred row sums; v15: launch-log read reports the size it needs, step plans; v16: bias queue; v17: plan event kinds - system-scope and timed records, gct2_plan_elapsed; v17 + gct2_ema_update (additive); v17 + gct2_sumsq_layout, gct2_grad_sumsq, gct2_adam_keras_clipped (additive); v17 + gct2_optimizer_apply, gct2_loss_scale_begin_schedule (additive); v17 + gct2_loss_scratch, gct2_loss_fwd_bwd (additive); v17 + gct2_optimizer_apply_reg, gct2_grad_sumsq_l2, gct2_l2_penalty (additive); v17 + gct2_dense_steps_fwd, gct2_dense_steps_bwd, gct2_dense_steps_scratch (additive); v17 + gct2_dense2_fwd, gct2_dense2_bwd, gct2_dense2_scratch (additive); v17 + gct2_noise_image_table, gct2_noise_image_rng_table (additive); v17 + gct2_eval_loss_scratch, gct2_eval_loss_rows (additive)) */
 /* how the library was built: 0 for the product build; bit 0 (GCT2_BUILD_STAMP) = diagnostic build with in-kernel phase stamps
  * (make EXTRA=-DGCT2_STAMP).  Product hosts (the Python binding, bench.py, the tests) refuse a library whose flags are not 0. */
 enum { GCT2_BUILD_STAMP = 1 };
@@ -489,6 +489,33 @@ int gct2_loss_scratch(int kind, int B, int H, int W, int C, size_t* floats);
 int gct2_loss_fwd_bwd(int kind, const float* pred, const float* target, float* dpred, float* loss,
                       float* scratch, size_t scratch_floats, int B, int H, int W, int C,
                       const float* basis, const float* loss_scale_ptr, void* stream);
+
+/* ---- evaluation (Keras Model.evaluate / fit(validation_data=...) on the reference's test/ folder): the training loss PER IMAGE ----
+ * rows[b] = the loss of `kind` (the GCT2_LOSS_* codes above) over image b alone; in exact arithmetic the mean of rows over the batch
+ * is gct2_loss_fwd_bwd's loss on the same batch.  The objective's target and the prediction weight are formed on load and never
+ * stored.  pred, x, eps: fp32 [B,H,W,C] contiguous, C in 1..4, all three read only; a, c, w: device float[B] or NULL; rows: float[B].
+ * Per element, every operation rounded once (no fused multiply-add), by the rule of gct2_mix_per_image:
+ *   target = x                                 (a == NULL)
+ *          = fl(a[b] * x)                      (a given, eps == NULL)
+ *          = fl(fl(a[b] * x) + fl(c[b] * eps)) (a and eps given; c is then required, and c without eps is GCT2_EINVAL)
+ *   p = w ? fl(w[b] * pred) : pred;   d = fl(target - p).
+ * With n_img = H*W*C and S the sum over image b in fp64:
+ *   GCT2_LOSS_MSE         rows[b] = (float)(S((double)d * (double)d) / n_img)
+ *   GCT2_LOSS_L1          rows[b] = (float)(S(max(d, -d)) / n_img)
+ *   GCT2_LOSS_MSE_POOLED  rows[b] = (float)(S(d^2) / n_img + S((qsum / 256)^2) / n2_img), qsum = the fp64 sum of d over a 16 x 16 cell
+ *                         and channel, n2_img = (H/16)(W/16)C; H and W multiples of 16
+ *   GCT2_LOSS_DCT         E = G D G^T per plane by the two fp32 matrix-core passes gct2_loss_fwd_bwd runs first (d is written to
+ *                         scratch for them), rows[b] = (float)(S((double)E * (double)E) / n_img); shape and basis rules as there
+ * No atomics; a work-group never mixes two images; work-groups leave fp64 partial sums in scratch and one finishing launch adds them
+ * per image in index order: the bits depend on the inputs alone.  Images need not start at 16-byte boundaries (n_img = 105).
+ * scratch: device floats, 16-byte aligned, at least what gct2_eval_loss_scratch reports (host only, no launch).
+ * GCT2_EINVAL before any launch: unknown kind; NULL pred / x / rows / scratch; non-positive dims or C outside 1..4; the per-kind shape
+ * rules; c without eps, or a and eps without c; a NULL or misaligned basis for the DCT; pointers not 4-byte aligned, scratch not 16-byte
+ * aligned; scratch_floats below the query's figure; B > 65535; B*n_img at or beyond 2^31. */
+int gct2_eval_loss_scratch(int kind, int B, int H, int W, int C, size_t* floats);
+int gct2_eval_loss_rows(int kind, const float* pred, const float* x, const float* eps, const float* a, const float* c,
+                        const float* w, float* rows, float* scratch, size_t scratch_floats, int B, int H, int W, int C,
+                        const float* basis, void* stream);
 
 /* ---- mixed precision (train.py:34,43-45,82-83) ------------------------------------------------ */
 /* device-resident state of Keras' LossScaleOptimizer [TF] plus the optimizer step counter it gates: a skipped step (inf/nan
