@@ -387,8 +387,9 @@ int gct2_convT4s2_fwd_head_train(gct2_ctx* ctx, int dtype, const void* x, int ld
   p.head = HeadFuse{head_w, head_b, target, pred, x2, ldx2, nullptr, loss_scale_ptr, head_Cin, head_Cout,
                     (float)((double)B * 2 * H * 2 * W * head_Cout)};
   if (c.force_direct || !halo_head_supported(c, dtype, p))
-    return gct2_fail(GCT2_EINVAL, "convT4s2_fwd_head_train: needs a 16-bit dtype, Cout = 64, H and W multiples of 16, 16-byte aligned views "
-                                  "and a ctx workspace of B*(H/16)*(W/16)*288 floats");
+    return gct2_fail(GCT2_EINVAL, "convT4s2_fwd_head_train: needs a 16-bit dtype, Cout = 64, H and W multiples of 16, 16-byte aligned views, "
+                                  "a ctx workspace of B*(H/16)*(W/16)*288 floats, and 31-bit source offsets: B*H*W*ldx*2 + 2*Cin + 128 and "
+                                  "the kernel's 16*Cin*Cout*2 bytes below 0x7ff00000");
   return halo_head(c, dtype, p, head_dw, head_db, loss, db, accumulate, S(stream));
 }
 

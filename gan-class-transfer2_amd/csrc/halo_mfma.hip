@@ -638,6 +638,12 @@ bool halo_head_supported(const gct2_ctx& c, int dtype, const TapGemmParams& p) {
   if (dtype != GCT2_BF16 && dtype != GCT2_F16) return false;
   if (p.N != 64 || (p.Hs & 15) || (p.Ws & 15) || p.K % 8 || p.ldx % 8) return false;
   if ((uintptr_t)p.y % 16 || p.ldy % 8 || (uintptr_t)p.x % 16 || (uintptr_t)p.w % 16) return false;
+  // 31-bit buffer offsets, as in tapgemm_mfma_supported (which the plain halo launch is reached through): the kernel forms a lane's
+  // source offset ((b Hs + y) Ws + x) ldx 2 + chunk 16 in 32 bits with bit 31 as its "outside the image" flag and adds the k-chunk
+  // (below 2 K bytes) as a scalar offset; the weight offsets ((n K + chunk 8) 2, tap and k-chunk scalar) stay inside the 16-tap tensor
+  const size_t src_bytes = (size_t)p.B * p.Hs * p.Ws * p.ldx * 2, lane_max = 7 * 16 + 16, scalar_max = (size_t)p.K * 2;
+  const size_t w_bytes = (size_t)16 * p.K * p.N * 2;
+  if (src_bytes + lane_max + scalar_max >= 0x7ff00000u || w_bytes >= 0x7ff00000u) return false;
   const size_t rows = (size_t)p.B * (p.Hs >> 4) * (p.Ws >> 4);
   return c.ws && c.ws_bytes >= rows * HEAD_ROW * sizeof(float);
 }

@@ -41,6 +41,16 @@ def _round_up(a: int, b: int) -> int:
     return (a + b - 1) // b * b
 
 
+# gct2_convT4s2_fwd_head_train loads its source and its kernel through 2-GiB buffer descriptors with 31-bit lane offsets
+# (halo_head_supported, csrc/halo_mfma.hip; include/gct2.h states the bound): both must stay below this many bytes
+U0_HEAD_MAX_BYTES = 0x7ff00000
+
+
+def u0_head_sizes_ok(B: int, Hs: int, Ws: int, ldx: int, Cin: int, Cout: int) -> bool:
+    """the size bound of the fused UpShuffle_0 + head call on a [B, Hs, Ws, Cin] source with pixel stride ldx (16-bit elements)"""
+    return B * Hs * Ws * ldx * 2 + 2 * Cin + 128 < U0_HEAD_MAX_BYTES and 16 * Cin * Cout * 2 < U0_HEAD_MAX_BYTES
+
+
 @dataclass
 class Topology:
     """channel rule of Denoiser.__init__ (train.py:179-190)."""
@@ -812,20 +822,28 @@ class UNetEngine(TrainerState):
 
     def fused_u0_head_ok(self, b: _Buffers) -> bool:
         """UpShuffle_0's forward with the head in its epilogue (gct2_convT4s2_fwd_head_train): the fused head's conditions plus
-        UpShuffle_0's source grid tiling into 16 x 16 patches and one partial row per patch in the workspace."""
+        UpShuffle_0's source grid tiling into 16 x 16 patches, one partial row per patch in the workspace, and a source view and
+        kernel inside the 31-bit offsets of the kernel's loads (U0_HEAD_MAX_BYTES; include/gct2.h).  That entry point has no
+        fall-back of its own: a step that fails one of these runs gct2_convT4s2_fwd + gct2_dense_head_train."""
         if not (self.fuse_u0_head and self.fused_head_ok() and self.topo.octaves >= 1):
             return False
         Hs, Ws = b.hw[1]
-        return Hs % 16 == 0 and Ws % 16 == 0 and self.workspace.numel() >= b.B * (Hs // 16) * (Ws // 16) * 288
+        if not (Hs % 16 == 0 and Ws % 16 == 0 and self.workspace.numel() >= b.B * (Hs // 16) * (Ws // 16) * 288):
+            return False
+        return u0_head_sizes_ok(b.B, Hs, Ws, self.u0_source(b)[1], self.topo.up_in(0), self.topo.fu(0))
+
+    def u0_source(self, b: _Buffers) -> Tuple[torch.Tensor, int]:
+        """UpShuffle_0's input view and its pixel stride: R_1, or the last DownShuffle output of a one-octave network"""
+        return (b.R[1], b.ld[1]) if self.topo.octaves > 1 else (b.Dlast, self.topo.fd(0))
 
     def u0_head_train(self, b: _Buffers, target: torch.Tensor, target_is_x: bool = False) -> torch.Tensor:
         """UpShuffle_0 forward + Dense(3) + fp32 MSE + both gradients in one launch: R_0 is never written, dR_0 receives the
         gradient w.r.t. UpShuffle_0's pre-activation (train.py:188, 198-202, 262-272)."""
         t, A, n = self.topo, self.arena, self.topo.octaves
         Hi, Wi = b.hw[1]
-        x, ldx = (b.R[1].data_ptr(), b.ld[1]) if n > 1 else (b.Dlast.data_ptr(), t.fd(0))
+        x, ldx = self.u0_source(b)
         ls_ptr = self._ls_ptr()
-        call("gct2_convT4s2_fwd_head_train", self.ctx.handle, self.dtype, x, ldx, A.wptr("U0.w"), A.pptr("U0.b"),
+        call("gct2_convT4s2_fwd_head_train", self.ctx.handle, self.dtype, x.data_ptr(), ldx, A.wptr("U0.w"), A.pptr("U0.b"),
              A.pptr("dense.w"), A.pptr("dense.b"), Slot("x", target.data_ptr()) if target_is_x else target.data_ptr(),
              b.pred.data_ptr() if self.keep_pred else None, b.dR[0].data_ptr(), b.ldd[0],
              A.gptr("dense.w"), A.gptr("dense.b"), b.loss.data_ptr(), b.B, Hi, Wi, t.up_in(0), t.fu(0), t.fu(0) + 3, 3, ls_ptr,

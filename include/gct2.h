@@ -17,6 +17,18 @@
  *  - kernels are enqueued on `stream` (a hipStream_t passed as void*; NULL = default stream).
  *    No allocation, no host synchronisation, no ownership transfer; re-entrant across streams.
  *  - return value: GCT2_OK or an error code; nothing is launched when arguments are rejected.
+ *  - operand sizes ("Operand size limits"; tests/test_large_views_gpu.py): the layer entry points bound the PIXEL count
+ *    (B*H*W*4 < 2^31 on the larger grid, GCT2_EINVAL beyond); `ld` is any int >= the channel count, so a view may span many GiB.
+ *    Every kernel forms the addresses of its views in 64 bits, except the loads of the 16-bit matrix-core kernels (2-GiB buffer
+ *    descriptors, 31-bit lane offsets).  With Hs x Ws the smaller of a layer's two grids, a 16-bit call runs on the matrix cores only while
+ *      forward / input gradient: 4*B*Hs*Ws*ld*2 + (8*Ws + 4)*ld*2 + 2*K < 0x7ff00000  (ld, K: stride and channels of the tensor the
+ *                                call reads: x, or dz) and the kernel's 16*Cin*Cout*2 bytes likewise;
+ *      weight gradient:          4*B*Hs*Ws*ld*2 < 0x7ff00000 for the tensor on the larger grid (stride-1: B*H*W*ld*2) and
+ *                                B*Hs*Ws*ld*2 < 0x7ff00000 for the other one;
+ *    beyond that it runs on the direct kernels - same results, slower, never an error.  gct2_convT4s2_fwd_head_train, which has no
+ *    direct form, returns GCT2_EINVAL past its own bound (stated there).  Output, mask (act), bit-plane and fp32 views have no limit
+ *    beyond the pixel count.  The pointwise entry points take size_t pixel counts, or int M / B*HW that they check against 2^31 where
+ *    they index with int; gct2_dense_head_train bounds ldx by its LDS tile (its message names it).
  */
 #ifndef GCT2_H
 #define GCT2_H
@@ -339,8 +351,11 @@ int gct2_dense2_bwd(gct2_ctx* ctx, int dtype, const void* x, int ldx, const void
  * ([B,2H,2W,Cout] view) receives the gradient w.r.t. the layer's pre-activation, db its column sums (this layer's bias
  * gradient), head_dw / head_db the Dense gradients, loss the scalar.  Saves one write and one read of the largest activation
  * of the network plus the head launch (train.py:188, 198-202, 262-272 and their autodiff).
- * Needs Cout = 64, H and W multiples of 16, head_Cin - Cout <= 3 image channels in x2 (packed, ldx2 multiple of 4), head_Cout <= 3
- * and a ctx workspace of B*(H/16)*(W/16)*288 floats; GCT2_EINVAL otherwise (use convT4s2_fwd + dense_head_train). */
+ * Needs Cout = 64, H and W multiples of 16, head_Cin - Cout <= 3 image channels in x2 (packed, ldx2 multiple of 4), head_Cout <= 3,
+ * a ctx workspace of B*(H/16)*(W/16)*288 floats, and a source view and kernel within the 31-bit offsets of the kernel's loads:
+ * B*H*W*ldx*2 + 2*Cin + 128 < 0x7ff00000 bytes (the span of x plus the largest lane and k-chunk offset added to it) and
+ * 16*Cin*Cout*2 < 0x7ff00000; GCT2_EINVAL otherwise (use convT4s2_fwd + dense_head_train: this entry point has no fall-back of its
+ * own).  dy, x2, target and pred are addressed with 64-bit offsets: their views may span any number of bytes. */
 int gct2_convT4s2_fwd_head_train(gct2_ctx* ctx, int dtype, const void* x, int ldx, const void* w, const float* bias,
                                  const float* head_w, const float* head_b, const float* target, float* pred, void* dy,
                                  int lddy, float* head_dw, float* head_db, float* loss, int B, int H, int W, int Cin,

@@ -186,6 +186,49 @@ def assert_outside_untouched(after, before, inside, what=""):
         raise AssertionError(f"{what}: {idx.shape[0]} elements outside the view changed, first at {tuple(int(v) for v in idx[0])} of {tuple(a.shape)}")
 
 
+def wide_view(t, ld, fill=float("nan"), guard_pixels=None):
+    """a [..., C] tensor (leading dimensions are pixels, row-major) as a view with pixel stride `ld` inside a FLAT buffer filled with
+    `fill`, for strides of millions of elements (tests/test_large_views_gpu.py): `guard_pixels` pixels (default: one row, t.shape[-2])
+    in front of and behind the view instead of poisoned_view's two guard images.  Returns the buffer, the strided view of it that
+    holds t (a torch view: reading it gathers, writing it scatters) and the device pointer to channel 0 of pixel 0."""
+    C = t.shape[-1]
+    npix = t.numel() // C
+    guard = (t.shape[-2] if guard_pixels is None else guard_pixels) * ld
+    assert ld >= C
+    buf = torch.full((guard + (npix - 1) * ld + C + guard,), fill, dtype=t.dtype, device=t.device)
+    strides, s = [], ld
+    for n in reversed(t.shape[:-1]):
+        strides.insert(0, s)
+        s *= n
+    view = buf.as_strided(tuple(t.shape), (*strides, 1), guard)
+    view.copy_(t)
+    return buf, view, buf.data_ptr() + guard * buf.element_size()
+
+
+UNTOUCHED_PIECE = 1 << 26                     # elements compared at a time by assert_outside_untouched_device
+
+
+def assert_outside_untouched_device(buf, view, fill, what=""):
+    """the device-side sibling of assert_outside_untouched for buffers of many GiB: everything of `buf` (filled with `fill` when it
+    was made) outside `view` (a torch view of buf, e.g. wide_view's) still holds the fill value, bit for bit.  The view is MASKED -
+    overwritten with the fill value: gather it first - and the whole buffer is compared in pieces of UNTOUCHED_PIECE elements (a bool
+    and an int64 of temporaries each); only the count of changed elements and, on failure, the first index come to the host."""
+    iv = _INT_VIEW[buf.dtype]
+    view.fill_(fill)
+    want = torch.full((1,), fill, dtype=buf.dtype, device=buf.device).view(iv)
+    flat = buf.view(iv)
+    bad = torch.zeros((), dtype=torch.int64, device=buf.device)
+    for piece in flat.split(UNTOUCHED_PIECE):
+        bad += torch.count_nonzero(piece != want)
+    if int(bad):
+        at = 0
+        for piece in flat.split(UNTOUCHED_PIECE):
+            hit = (piece != want).nonzero()
+            if hit.numel():
+                raise AssertionError(f"{what}: {int(bad)} elements outside the view changed, first at element {at + int(hit[0])} of {flat.numel()}")
+            at += piece.numel()
+
+
 # ---- cases: inputs and fp64 references, shared by the CPU quality checks and the GPU tests ------------------------------------------
 
 # (B, H, W, Cin, Cout) as in tests/test_kernels_gpu.py: H, W the big grid of the Conv2D form and the small one of the transposed form
@@ -536,6 +579,9 @@ def _head_case(c, rng):
 _CONVT_HEAD_RANGES = {
     (8, BF16): (10, (511, 15, 31), (15, 31, 15), {1: (257, 511, 0.02)}), (8, F16): (28, (63, 15, 31), (1, 3, 1), {0: (33, 63, 0.015)}),
     (136, BF16): (5, (511, 15, 31), (7, 3, 7), {1: (257, 511, 0.01)}), (136, F16): (14, (63, 15, 31), (1, 1, 1), {0: (33, 63, 0.005)}),
+    # Cin = 16: the B = 4 and B = 5 cases of tests/large_view_cases.py (4096 / 5120 output pixels; tests/test_large_view_cases_cpu.py
+    # checks their budgets)
+    (16, BF16): (9, (511, 15, 31), (4, 3, 4), {1: (257, 511, 0.004)}), (16, F16): (22, (63, 15, 31), (1, 1, 1), {0: (33, 63, 0.003)}),
 }
 
 

@@ -70,6 +70,15 @@ PLANE = "a ReLU bit plane was registered (gct2_ctx_set_relu_bits), but this call
 PLANE_SHAPE = "ReLU bit plane needs channels % 8 == 0 and ld_bytes >= channels / 8 (got 12, 1)"
 KSIZE = "(odd, 1..7: 'same' padding is symmetric then)"
 HEAD = "convT4s2_fwd_head_train"
+HEAD_NEEDS = (f"{HEAD}: needs a 16-bit dtype, Cout = 64, H and W multiples of 16, 16-byte aligned views, a ctx workspace of "
+              "B*(H/16)*(W/16)*288 floats, and 31-bit source offsets: B*H*W*ldx*2 + 2*Cin + 128 and the kernel's 16*Cin*Cout*2 bytes "
+              "below 0x7ff00000")
+# the fused head's size bound (halo_head_supported, csrc/halo_mfma.hip) at the builder's B = 1, H = W = 16, Cin = 8: the first ldx,
+# a multiple of 8, with 256 * ldx * 2 + 2 * 8 + 128 >= 0x7ff00000; and a workspace (fake, like every pointer here) that holds its one
+# partial row, so that the size is the ONLY thing the predicate can object to
+HEAD_LDX_REFUSED = 0x7ff00000 // 512
+HEAD_WS = (P, 288 * 4)
+assert 512 * (HEAD_LDX_REFUSED - 8) + 144 < 0x7ff00000 <= 512 * HEAD_LDX_REFUSED + 144 and HEAD_LDX_REFUSED % 8 == 0
 
 
 def _common(name, build, null, extra=None):
@@ -97,7 +106,8 @@ def _adam_rows(name):
             (fn, wgrad(adam=ADAM, accumulate=1, lddz=7), {"adam": adam(p=None)}, EINVAL, f"{name}: ld smaller than channel count")]
 
 
-# (entry point, arguments, {"plane": (pointer, ld_bytes) registered on the ctx first, "adam": fields of the struct behind ADAM}, code, text)
+# (entry point, arguments, {"plane": (pointer, ld_bytes) registered on the ctx first, "adam": fields of the struct behind ADAM,
+#  "ws": (pointer, bytes) the ctx's workspace during this row}, code, text)
 CASES = (
     # ---- gct2_conv4s2_fwd
     _common("conv4s2_fwd", fwd, "w") + [
@@ -154,14 +164,20 @@ CASES = (
          f"{HEAD}: head needs <= 3 outputs and <= 3 image channels in a packed x2 (8-byte rows)"),
         # shape and dtype are fine, the ctx has no workspace for the partial rows / the dtype is fp32 / H is no multiple of 16
         ("gct2_" + HEAD, head(), {}, EINVAL,
-         f"{HEAD}: needs a 16-bit dtype, Cout = 64, H and W multiples of 16, 16-byte aligned views and a ctx workspace of "
-         "B*(H/16)*(W/16)*288 floats"),
+         HEAD_NEEDS),
         ("gct2_" + HEAD, head(dtype=F32), {}, EINVAL,
-         f"{HEAD}: needs a 16-bit dtype, Cout = 64, H and W multiples of 16, 16-byte aligned views and a ctx workspace of "
-         "B*(H/16)*(W/16)*288 floats"),
+         HEAD_NEEDS),
         ("gct2_" + HEAD, head(H=8), {}, EINVAL,
-         f"{HEAD}: needs a 16-bit dtype, Cout = 64, H and W multiples of 16, 16-byte aligned views and a ctx workspace of "
-         "B*(H/16)*(W/16)*288 floats")]
+         HEAD_NEEDS),
+        # the size bound, with the workspace in place: the source view at the first refused ldx, the kernel at the first refused Cin
+        # (16 * Cin * 64 * 2 >= 0x7ff00000), and a source just past 4 GiB, where the kernel's int pixel-times-ldx product would wrap
+        ("gct2_" + HEAD, head(ldx=HEAD_LDX_REFUSED), {"ws": HEAD_WS}, EINVAL, HEAD_NEEDS),
+        ("gct2_" + HEAD, head(Cin=0x7ff00000 // 2048, ldx=0x7ff00000 // 2048), {"ws": HEAD_WS}, EINVAL, HEAD_NEEDS),
+        ("gct2_" + HEAD, head(ldx=(1 << 23) + 8), {"ws": HEAD_WS}, EINVAL, HEAD_NEEDS),
+        # its place in the order: behind the ld and the head-shape checks, together with the other needs of the kernel
+        ("gct2_" + HEAD, head(ldx=HEAD_LDX_REFUSED, lddy=63), {"ws": HEAD_WS}, EINVAL, f"{HEAD}: ld smaller than channel count"),
+        ("gct2_" + HEAD, head(ldx=HEAD_LDX_REFUSED, head_Cout=4), {"ws": HEAD_WS}, EINVAL,
+         f"{HEAD}: head needs <= 3 outputs and <= 3 image channels in a packed x2 (8-byte rows)")]
     # ---- gct2_convT4s2_dgrad
     + _common("convT4s2_dgrad", dgrad, "dz") + [
         ("gct2_convT4s2_dgrad", dgrad(H=5, lddz=7), {}, EINVAL, "convT4s2_dgrad: ld smaller than channel count"),
@@ -230,6 +246,7 @@ def _child():
         for fn, args, pre, _code, _text in CASES:
             if "plane" in pre:
                 assert lib.gct2_ctx_set_relu_bits(handle.value, *pre["plane"]) == 0
+            assert lib.gct2_ctx_set_workspace(handle.value, *pre.get("ws", (None, 0))) == 0      # (a row's workspace is its own)
             a = L.AdamArgs(**pre["adam"]) if "adam" in pre else None
             real = [handle.value if v == CTX else ctypes.addressof(a) if v == ADAM else v for v in args]
             code = getattr(lib, fn)(*real)

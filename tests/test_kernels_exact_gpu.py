@@ -92,6 +92,25 @@ def nan_like(shape, dt, gpu):
     return torch.full(shape, NAN, dtype=E.TDT[dt], device=gpu)
 
 
+class Place:
+    """where the runners below put the views of a case.  This one: every view in a poisoned buffer of its own at lay()'s stride and
+    channel offset.  tests/test_large_views_gpu.py overrides it per role ("x", "dz", "act", "y", "dx") to give one view a stride of
+    millions of elements."""
+
+    def inp(self, role, t, mode, kind):
+        """an input view (kind: "in" or "act", lay()'s roles) -> (buffer, device pointer, ld)"""
+        buf, ptr = E.poisoned_view(t, *lay(mode, t.shape[-1], kind))
+        return buf, ptr, buf.shape[-1]
+
+    def out(self, role, init, mode):
+        """an output view holding `init` -> (an object with .ptr and .check(want, what, names), ld)"""
+        ld, off = lay(mode, init.shape[-1], "out")
+        return Out(init, ld, off), ld
+
+
+PLACE = Place()
+
+
 def tap_family(entry, shape, mode, halo=False):
     """the launch-log prefix the case must show"""
     Cin, Cout = shape[3], shape[4]
@@ -120,40 +139,40 @@ def check_log(c, prefix, contains=(), split=None):
 
 # ---- a. forward and input-gradient calls of the 4x4 / stride-2 layers --------------------------------------------------------------------
 
-def run_fwd(gpu, entry, shape, mode, ws=False, tuning=0, halo=False, contains=(), split=None):
-    """bias, relu 0 and 1"""
+def run_fwd(gpu, entry, shape, mode, ws=False, tuning=0, halo=False, contains=(), split=None, place=PLACE, variants=(0, 1), family=None):
+    """bias, relu 0 and 1 (variants); family: the launch-log prefix when it is not tap_family()'s"""
     dt = MODE_DT[mode]
     cs = E.make_case(entry, shape, dt)
     B, H, W, Cin, Cout = shape
     c = make_ctx(gpu, mode, ws, tuning)
-    xb, xp = E.poisoned_view(dev(cs.x, dt, gpu), *lay(mode, Cin, "in"))
+    xb, xp, ldx = place.inp("x", dev(cs.x, dt, gpu), mode, "in")
     wb, wp = E.guarded(dev(cs.w, dt, gpu))
     bb, bp = E.guarded(dev(cs.bias, F32, gpu))
-    ldy, offy = lay(mode, Cout, "out")
-    for relu in (0, 1):
-        y = Out(nan_like(cs.ref.shape, dt, gpu), ldy, offy)
-        lib().call(FN[entry], c.handle, dt, xp, xb.shape[-1], wp, bp, y.ptr, ldy, B, H, W, Cin, Cout, relu, stream())
+    for relu in variants:
+        y, ldy = place.out("y", nan_like(cs.ref.shape, dt, gpu), mode)
+        lib().call(FN[entry], c.handle, dt, xp, ldx, wp, bp, y.ptr, ldy, B, H, W, Cin, Cout, relu, stream())
         y.check(E.expected(np.maximum(cs.ref, 0) if relu else cs.ref, dt), f"{entry} {shape} {mode} relu={relu}")
-    check_log(c, tap_family(entry, shape, mode, halo), contains, split)
+        del y                                               # (a view of several GiB leaves before the next one is made)
+    return check_log(c, family or tap_family(entry, shape, mode, halo), contains, split)
 
 
-def run_dgrad(gpu, entry, shape, mode, ws=False, tuning=0, halo=False, contains=(), split=None):
-    """mask on and off, accumulate 0 and 1"""
+def run_dgrad(gpu, entry, shape, mode, ws=False, tuning=0, halo=False, contains=(), split=None, place=PLACE,
+              variants=((1, 0), (1, 1), (0, 0), (0, 1)), family=None):
+    """mask on and off, accumulate 0 and 1 (variants: (masked, accumulate) pairs)"""
     dt = MODE_DT[mode]
     cs = E.make_case(entry, shape, dt)
     B, H, W, Cin, Cout = shape
     c = make_ctx(gpu, mode, ws, tuning)
-    dzb, dzp = E.poisoned_view(dev(cs.dz, dt, gpu), *lay(mode, Cout, "in"))
+    dzb, dzp, lddz = place.inp("dz", dev(cs.dz, dt, gpu), mode, "in")
     wb, wp = E.guarded(dev(cs.w, dt, gpu))
-    ab, ap = E.poisoned_view(dev(cs.act, dt, gpu), *lay(mode, Cin, "act"))
-    lddx, offdx = lay(mode, Cin, "out")
-    for masked in (1, 0):
-        for accumulate in (0, 1):
-            dx = Out(dev(cs.prev, dt, gpu) if accumulate else nan_like(cs.prev.shape, dt, gpu), lddx, offdx)
-            lib().call(FN[entry], c.handle, dt, dzp, dzb.shape[-1], wp, ap if masked else None, ab.shape[-1], dx.ptr, lddx,
-                       B, H, W, Cin, Cout, accumulate, None, 0, None, 0, stream())
-            dx.check(E.expected(E.dgrad_ref(cs, masked, accumulate), dt), f"{entry} {shape} {mode} mask={masked} accumulate={accumulate}")
-    check_log(c, tap_family(entry, shape, mode, halo), contains, split)
+    ab, ap, ldact = place.inp("act", dev(cs.act, dt, gpu), mode, "act")
+    for masked, accumulate in variants:
+        dx, lddx = place.out("dx", dev(cs.prev, dt, gpu) if accumulate else nan_like(cs.prev.shape, dt, gpu), mode)
+        lib().call(FN[entry], c.handle, dt, dzp, lddz, wp, ap if masked else None, ldact, dx.ptr, lddx,
+                   B, H, W, Cin, Cout, accumulate, None, 0, None, 0, stream())
+        dx.check(E.expected(E.dgrad_ref(cs, masked, accumulate), dt), f"{entry} {shape} {mode} mask={masked} accumulate={accumulate}")
+        del dx
+    return check_log(c, family or tap_family(entry, shape, mode, halo), contains, split)
 
 
 def run_tap(gpu, entry, *a, **kw):
@@ -218,20 +237,21 @@ def wgrad_views(gpu, cs, mode, x=None, dz=None):
     return xb, xp, dzb, dzp
 
 
-def run_wgrad(gpu, entry, shape, mode, ws, tuning=0, contains=()):
+def run_wgrad(gpu, entry, shape, mode, ws, tuning=0, contains=(), place=PLACE):
     """dw and db, overwrite (over NaN), then accumulate (twice the gradient: still inside the budget)"""
     dt = MODE_DT[mode]
     cs = E.make_case(entry, shape, dt)
     B, Cin, Cout = shape[0], shape[3], shape[4]
     h, w_ = E.wgrad_hw(entry, shape)
     c = make_ctx(gpu, mode, ws, tuning)
-    xb, xp, dzb, dzp = wgrad_views(gpu, cs, mode)
+    xb, xp, ldx = place.inp("x", dev(cs.x, dt, gpu), mode, "in")
+    dzb, dzp, lddz = place.inp("dz", dev(cs.dz, dt, gpu), mode, "in")
     dw = Out(nan_like(cs.dw.shape, F32, gpu), 0, 0, guard=True)
     db = Out(nan_like(cs.db.shape, F32, gpu), 0, 0, guard=True)
     tail = (shape[5],) if entry == "s1_wgrad" else ()
     extra = () if entry == "s1_wgrad" else (None,)          # gct2_adam_args of the 4x4 entries
     for accumulate in (0, 1):
-        lib().call(FN[entry], c.handle, dt, xp, xb.shape[-1], dzp, dzb.shape[-1], dw.ptr, db.ptr, B, h, w_, Cin, Cout, *tail, accumulate,
+        lib().call(FN[entry], c.handle, dt, xp, ldx, dzp, lddz, dw.ptr, db.ptr, B, h, w_, Cin, Cout, *tail, accumulate,
                    *extra, stream())
         k = 1 + accumulate
         what = f"{entry} {shape} {mode} ws={ws} accumulate={accumulate}"
@@ -289,39 +309,45 @@ S1_CASES = [pytest.param(e, s, m, w, id=f"{e}-{'x'.join(map(str, s))}-{m}-{'ws' 
             for m in ("bf16", "f16", "f32", "f32m") for w in (False, True) if not (w and s1_prefix(e, s, m) is None)]
 
 
-@pytest.mark.parametrize("entry,shape,mode,ws", S1_CASES)
-def test_conv2d_s1_exact(gpu, entry, shape, mode, ws):
-    prefix = s1_prefix(entry, shape, mode)
+def run_s1(gpu, entry, shape, mode, ws, place=PLACE, variants=None, prefix="default"):
+    """the three stride-1 entries; variants as in run_fwd / run_dgrad; prefix: the launch-log family (None: nothing is logged) when it
+    is not s1_prefix()'s.  Returns the log."""
+    prefix = s1_prefix(entry, shape, mode) if prefix == "default" else prefix
     dt = MODE_DT[mode]
     B, H, W, Cin, Cout, KS = shape
     if entry == "s1_wgrad":
-        c = run_wgrad(gpu, entry, shape, mode, ws)
+        c = run_wgrad(gpu, entry, shape, mode, ws, place=place)
     else:
         cs = E.make_case(entry, shape, dt)
         c = make_ctx(gpu, mode, ws)
         wb, wp = E.guarded(dev(cs.w, dt, gpu))
         if entry == "s1_fwd":
-            xb, xp = E.poisoned_view(dev(cs.x, dt, gpu), *lay(mode, Cin, "in"))
+            xb, xp, ldx = place.inp("x", dev(cs.x, dt, gpu), mode, "in")
             bb, bp = E.guarded(dev(cs.bias, F32, gpu))
-            ldy, offy = lay(mode, Cout, "out")
-            for relu in (0, 1):
-                y = Out(nan_like(cs.ref.shape, dt, gpu), ldy, offy)
-                lib().call(FN[entry], c.handle, dt, xp, xb.shape[-1], wp, bp, y.ptr, ldy, B, H, W, Cin, Cout, KS, relu, stream())
+            for relu in variants or (0, 1):
+                y, ldy = place.out("y", nan_like(cs.ref.shape, dt, gpu), mode)
+                lib().call(FN[entry], c.handle, dt, xp, ldx, wp, bp, y.ptr, ldy, B, H, W, Cin, Cout, KS, relu, stream())
                 y.check(E.expected(np.maximum(cs.ref, 0) if relu else cs.ref, dt), f"{entry} {shape} {mode} relu={relu}")
+                del y
         else:
-            dzb, dzp = E.poisoned_view(dev(cs.dz, dt, gpu), *lay(mode, Cout, "in"))
-            ab, ap = E.poisoned_view(dev(cs.act, dt, gpu), *lay(mode, Cin, "act"))
-            lddx, offdx = lay(mode, Cin, "out")
-            for masked in (1, 0):
-                for accumulate in (0, 1):
-                    dx = Out(dev(cs.prev, dt, gpu) if accumulate else nan_like(cs.prev.shape, dt, gpu), lddx, offdx)
-                    lib().call(FN[entry], c.handle, dt, dzp, dzb.shape[-1], wp, ap if masked else None, ab.shape[-1], dx.ptr, lddx,
-                               B, H, W, Cin, Cout, KS, accumulate, stream())
-                    dx.check(E.expected(E.dgrad_ref(cs, masked, accumulate), dt), f"{entry} {shape} {mode} mask={masked} accumulate={accumulate}")
+            dzb, dzp, lddz = place.inp("dz", dev(cs.dz, dt, gpu), mode, "in")
+            ab, ap, ldact = place.inp("act", dev(cs.act, dt, gpu), mode, "act")
+            for masked, accumulate in variants or ((1, 0), (1, 1), (0, 0), (0, 1)):
+                dx, lddx = place.out("dx", dev(cs.prev, dt, gpu) if accumulate else nan_like(cs.prev.shape, dt, gpu), mode)
+                lib().call(FN[entry], c.handle, dt, dzp, lddz, wp, ap if masked else None, ldact, dx.ptr, lddx,
+                           B, H, W, Cin, Cout, KS, accumulate, stream())
+                dx.check(E.expected(E.dgrad_ref(cs, masked, accumulate), dt), f"{entry} {shape} {mode} mask={masked} accumulate={accumulate}")
+                del dx
     if prefix is None:
-        assert c.read_launch_log() == []
-    else:
-        check_log(c, prefix)
+        log = c.read_launch_log()
+        assert log == []
+        return log
+    return check_log(c, prefix)
+
+
+@pytest.mark.parametrize("entry,shape,mode,ws", S1_CASES)
+def test_conv2d_s1_exact(gpu, entry, shape, mode, ws):
+    run_s1(gpu, entry, shape, mode, ws)
 
 
 # ---- Dense(3) head ----------------------------------------------------------------------------------------------------------------------
