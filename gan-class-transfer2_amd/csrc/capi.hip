@@ -1,5 +1,6 @@
 // extern "C" boundary (include/gct2.h): argument validation, path selection (MFMA vs direct), launches.
 #include "gct2_common.h"
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -741,6 +742,48 @@ int gct2_eval_loss_rows(int kind, const float* pred, const float* x, const float
   if (scratch_floats < need)
     return gct2_fail(GCT2_EINVAL, "eval_loss_rows: %zu floats of scratch, this kind and shape need %zu (gct2_eval_loss_scratch)", scratch_floats, need);
   return eval_loss_rows(kind, pred, x, eps, a, c, w, rows, scratch, B, H, W, C, basis, S(stream));
+}
+
+// shape rules of the image metrics: the limits of a (tile, image) grid and of int element indices
+static int check_metrics_shape(const char* fn, int B, int H, int W, int C, int K) {
+  if (B <= 0 || H <= 0 || W <= 0) return gct2_fail(GCT2_EINVAL, "%s: non-positive dims B=%d H=%d W=%d", fn, B, H, W);
+  if (C < 1 || C > 4) return gct2_fail(GCT2_EINVAL, "%s: C=%d outside 1..4", fn, C);
+  if (K < 1 || K > 16) return gct2_fail(GCT2_EINVAL, "%s: K=%d outside 1..16", fn, K);
+  return GCT2_OK;
+}
+static int check_metrics_size(const char* fn, int B, int H, int W, int C) {
+  if (B > 65535) return gct2_fail(GCT2_EINVAL, "%s: B=%d above 65535 (one grid row per image)", fn, B);
+  if ((size_t)B * H * W * C >= ((size_t)1 << 31)) return gct2_fail(GCT2_EINVAL, "%s: B*H*W*C at or beyond 2^31", fn);
+  return GCT2_OK;
+}
+
+int gct2_image_metrics_scratch(int B, int H, int W, int C, int K, size_t* floats) {
+  if (!floats) return gct2_fail(GCT2_EINVAL, "image_metrics_scratch: null output pointer");
+  if (int e = check_metrics_shape("image_metrics_scratch", B, H, W, C, K)) return e;
+  if (int e = check_metrics_size("image_metrics_scratch", B, H, W, C)) return e;
+  *floats = image_metrics_scratch_floats(B, H, W, C);
+  return GCT2_OK;
+}
+
+int gct2_image_metrics(const float* pred, const float* noised, const float* u, const float* v, const float* x, const float* window, int K,
+                       float max_val, float k1, float k2, float* mse, float* psnr, float* ssim, float* scratch, size_t scratch_floats, int B,
+                       int H, int W, int C, void* stream) {
+  if (!pred || !x || !mse || !scratch) return gct2_fail(GCT2_EINVAL, "image_metrics: null pointer");
+  if (u && (!noised || !v)) return gct2_fail(GCT2_EINVAL, "image_metrics: u without noised or v");
+  if (!u && (noised || v)) return gct2_fail(GCT2_EINVAL, "image_metrics: noised or v without u");
+  if (ssim && !window) return gct2_fail(GCT2_EINVAL, "image_metrics: ssim without window");
+  if (int e = check_metrics_shape("image_metrics", B, H, W, C, K)) return e;
+  if (ssim && (H < K || W < K)) return gct2_fail(GCT2_EINVAL, "image_metrics: a %d x %d image is smaller than the %d x %d window", H, W, K, K);
+  if (!std::isfinite(max_val) || !(max_val > 0.f)) return gct2_fail(GCT2_EINVAL, "image_metrics: max_val must be finite and > 0");
+  if (!std::isfinite(k1) || !std::isfinite(k2) || k1 < 0.f || k2 < 0.f) return gct2_fail(GCT2_EINVAL, "image_metrics: k1 and k2 must be finite and >= 0");
+  if (((uintptr_t)pred | (uintptr_t)noised | (uintptr_t)u | (uintptr_t)v | (uintptr_t)x | (uintptr_t)window | (uintptr_t)mse | (uintptr_t)psnr |
+       (uintptr_t)ssim) % 4 || (uintptr_t)scratch % 16)
+    return gct2_fail(GCT2_EINVAL, "image_metrics: scratch must be 16-byte aligned, the other pointers 4-byte aligned");
+  if (int e = check_metrics_size("image_metrics", B, H, W, C)) return e;
+  const size_t need = image_metrics_scratch_floats(B, H, W, C);
+  if (scratch_floats < need)
+    return gct2_fail(GCT2_EINVAL, "image_metrics: %zu floats of scratch, this shape needs %zu (gct2_image_metrics_scratch)", scratch_floats, need);
+  return image_metrics(pred, noised, u, v, x, window, K, max_val, k1, k2, mse, psnr, ssim, scratch, B, H, W, C, S(stream));
 }
 
 int gct2_adam_keras_multi(float* p, float* m, float* v, float* g, void* shadow, int shadow_dtype, size_t n, float alpha, float beta1,

@@ -439,6 +439,11 @@ size_t eval_scratch_floats(int kind, int B, int H, int W, int C);
 int eval_loss_rows(int kind, const float* pred, const float* x, const float* eps, const float* a, const float* c, const float* w, float* rows,
                    float* scratch, int B, int H, int W, int C, const float* basis, hipStream_t s);
 
+// metrics.hip: the image metrics of gct2_image_metrics: the floats of scratch a shape needs / the launches
+size_t image_metrics_scratch_floats(int B, int H, int W, int C);
+int image_metrics(const float* pred, const float* noised, const float* u, const float* v, const float* x, const float* window, int K, float max_val,
+                  float k1, float k2, float* mse, float* psnr, float* ssim, float* scratch, int B, int H, int W, int C, hipStream_t s);
+
 // direct_kernels.hip: one thread per output, every dtype
 int tapgemm_direct(int dtype, int form, int epi, const TapGemmParams& p, hipStream_t s);
 int wgrad_direct(int dtype, WgradParams p, hipStream_t s);

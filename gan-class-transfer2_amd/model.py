@@ -10,6 +10,7 @@ several at once.  `compute_dtype` is the one MI355X-specific knob.
 """
 from __future__ import annotations
 
+import ctypes
 import sys
 from typing import Callable, Dict, Iterable, List, Optional, Sequence as Seq
 
@@ -743,6 +744,7 @@ class Trainer(Layer):
         self.denoiser = denoiser
         self.optimizer = None
         self.loss_fn = None
+        self.metrics = ()                                # compile(metrics=[...]): what evaluate and fit's validation report besides the loss
 
     def _engine(self) -> UNetEngine:
         trainer_math.training_loss_code(training_loss)   # an unknown name: ValueError, before anything is built or changed
@@ -804,8 +806,10 @@ class Trainer(Layer):
             return eng.weighted_loss_and_dpred(b, target, w, grad=False).clone()[0]
         return eng.loss_and_dpred(b, target, grad=False).clone()[0]
 
-    def compile(self, optimizer, loss):
-        """train.py:511-514"""
+    def compile(self, optimizer, loss, metrics=None):
+        """train.py:511-514.  metrics (Keras' argument; None: none): names out of trainer_math.METRICS - "mse_x0", "psnr", "ssim" -
+        that evaluate() and fit(validation_data=...) report by default; an unknown or repeated name is a ValueError and nothing changes."""
+        metrics = trainer_math.check_metrics(metrics)
         if self.denoiser.engine is not None and optimizer is not None:
             eng, inner = self.denoiser.engine, getattr(optimizer, "inner", optimizer)
             hp = engine_hyper_parameters(optimizer)
@@ -827,7 +831,7 @@ class Trainer(Layer):
                 if eng.iterations != 0:
                     raise _lib.Gct2Error("the engine has already stepped with dynamic loss scaling; it cannot be dropped now")
                 eng.ls_state, eng.loss_scaling = None, False
-        self.optimizer, self.loss_fn = optimizer, loss
+        self.optimizer, self.loss_fn, self.metrics = optimizer, loss, metrics
         inner = getattr(optimizer, "inner", optimizer)
         if inner is not None:
             inner._engine = self.denoiser.engine
@@ -843,7 +847,7 @@ class Trainer(Layer):
         return {"loss": loss}
 
     def evaluate(self, dataset: Iterable, steps: Optional[int] = None, return_dict: bool = False, use_ema: bool = False, t=None,
-                 seed: Optional[int] = None):
+                 seed: Optional[int] = None, metrics=None):
         """Keras' Model.evaluate on held-out data: the training loss as it stands now (objective, training_loss, noise schedule),
         averaged over every IMAGE `dataset` yields - (x, x) pairs or bare x batches, a partial last batch included.  steps: at most
         that many batches (None: until the dataset ends; an endless dataset then is a ValueError where it can be known).  Each image
@@ -851,7 +855,13 @@ class Trainer(Layer):
         does not depend on the batch size and no training state moves; t: one timestep (or one per image of a batch) instead;
         seed: instead of the engine's rng_seed.  use_ema: the averaged weights.  With an L2 regularizer the penalty of the weights
         read is added, as in the train step's loss.  One host synchronisation, at the end.
-        return_dict: {"loss": float, "per_image": float32 [N] (the data term of every image), "t": int32 [N]} instead of the float."""
+        return_dict: {"loss": float, "per_image": float32 [N] (the data term of every image), "t": int32 [N]} instead of the float.
+        metrics: names out of trainer_math.METRICS (None: those of compile(); (): none) - the image-space metrics of every image's x0
+        estimate against the clean image (gct2_image_metrics), whatever the objective predicts.  With any, the return value is
+        [loss, m1, m2, ...] in the order asked, as Keras returns it, each the float64 mean over the images (inf for "psnr" when an
+        image is reproduced exactly); return_dict adds each mean under its name and "per_image_<name>" float32 [N].  With none the
+        return value is exactly the one above.  Still one host synchronisation."""
+        metrics = self.metrics if metrics is None else trainer_math.check_metrics(metrics)
         if steps is not None and (isinstance(steps, bool) or not isinstance(steps, int) or steps < 1):
             raise ValueError(f"evaluate: steps must be a positive int or None, got {steps!r}")
         if steps is None and getattr(dataset, "finite", True) is False:
@@ -859,12 +869,18 @@ class Trainer(Layer):
                              "ImageDataset.validation")
         eng = self._engine()
         rows, ts, index = [], [], 0
+        mrows = {n: [] for n in metrics}
 
         def run():
             nonlocal index
             for k, data in enumerate(dataset):
                 x = data[0] if isinstance(data, (tuple, list)) else data
-                r, tt = eng.evaluate_batch(x, index0=index, t=t, seed=seed)
+                if metrics:
+                    r, tt, mm = eng.evaluate_batch(x, index0=index, t=t, seed=seed, metrics=metrics)
+                    for n in metrics:
+                        mrows[n].append(mm[n])
+                else:
+                    r, tt = eng.evaluate_batch(x, index0=index, t=t, seed=seed)
                 rows.append(r)
                 ts.append(tt)
                 index += int(x.shape[0])
@@ -880,14 +896,30 @@ class Trainer(Layer):
             penalty = self._evaluation_penalty(eng)
         if not rows:
             raise ValueError("evaluate: the dataset yielded no batch")
-        per_image = torch.cat(rows).cpu().numpy()              # the one host synchronisation
+        N = index
+        if metrics:                                            # (one tensor, so that one copy brings everything to the host)
+            everything = torch.cat(rows + [m for n in metrics for m in mrows[n]]).cpu().numpy()      # the one host synchronisation
+            per_image = everything[:N]
+            per_metric = {n: everything[(k + 1) * N:(k + 2) * N] for k, n in enumerate(metrics)}
+        else:
+            per_image = torch.cat(rows).cpu().numpy()          # the one host synchronisation
         t_all = torch.cat(ts).cpu().numpy()
         loss = float(np.mean(per_image, dtype=np.float64))
         if penalty is not None:
             loss += float(penalty.cpu()[0])
+        if not metrics:
+            if return_dict:
+                return {"loss": loss, "per_image": per_image, "t": t_all}
+            return loss
+        with np.errstate(invalid="ignore"):
+            means = {n: float(np.mean(per_metric[n], dtype=np.float64)) for n in metrics}
         if return_dict:
-            return {"loss": loss, "per_image": per_image, "t": t_all}
-        return loss
+            out = {"loss": loss, "per_image": per_image, "t": t_all}
+            for n in metrics:
+                out[n] = means[n]
+                out["per_image_" + n] = per_metric[n]
+            return out
+        return [loss] + [means[n] for n in metrics]
 
     @staticmethod
     def _evaluation_penalty(eng) -> Optional[torch.Tensor]:
@@ -913,7 +945,7 @@ class Trainer(Layer):
         validation_data (Keras' argument; None: nothing about fit changes): after every validation_freq-th epoch,
         evaluate(iter(validation_data), validation_steps, use_ema=validation_use_ema) goes into logs["val_loss"] and
         history["val_loss"] before on_epoch_end runs - pass something that can be iterated once per validation (a list of batches,
-        an ImageDataset.validation)."""
+        an ImageDataset.validation).  The metrics of compile(metrics=[...]) go into logs["val_<name>"] and history["val_<name>"]."""
         if self.optimizer is None:
             raise RuntimeError("call compile(optimizer, loss) before fit (train.py:511)")
         if validation_data is not None:
@@ -926,6 +958,8 @@ class Trainer(Layer):
         history = {"loss": []}
         if validation_data is not None:
             history["val_loss"] = []
+            for n in self.metrics:
+                history["val_" + n] = []
         for epoch in range(epochs):
             logs: Dict[str, float] = {}
             for cb in callbacks:
@@ -939,12 +973,40 @@ class Trainer(Layer):
             history["loss"].append(logs["loss"])
             line = f"Epoch {epoch + 1}/{epochs} - loss: {logs['loss']:.6f}"
             if validation_data is not None and (epoch + 1) % validation_freq == 0:
-                logs["val_loss"] = self.evaluate(iter(validation_data), validation_steps, use_ema=validation_use_ema)
-                history["val_loss"].append(logs["val_loss"])
-                line += f" - val_loss: {logs['val_loss']:.6f}"
+                val = self.evaluate(iter(validation_data), validation_steps, use_ema=validation_use_ema)
+                val = val if self.metrics else [val]
+                for n, value in zip(("loss",) + self.metrics, val):
+                    logs["val_" + n] = value
+                    history["val_" + n].append(value)
+                    line += f" - val_{n}: {value:.6f}"
             if verbose:
                 print(line, flush=True)
             for cb in callbacks:
                 if getattr(cb, "on_epoch_end", None):
                     cb.on_epoch_end(epoch, logs)
         return history
+
+
+def image_metrics(a: torch.Tensor, b: torch.Tensor, max_val: float = 2.0, filter_size: int = 11, filter_sigma: float = 1.5,
+                  k1: float = 0.01, k2: float = 0.03) -> Dict[str, torch.Tensor]:
+    """tf.image.psnr / tf.image.ssim [TF] of two device image batches [B,H,W,C] (C in 1..4), e.g. samples against references:
+    {"mse_x0", "psnr", "ssim"}, fp32 [B] device tensors, by one gct2_image_metrics launch on the current stream of a's device; no
+    host synchronisation.  max_val: the dynamic range (2 for images in [-1, 1)); the window is trainer_math.ssim_window(filter_size,
+    filter_sigma), both sides of the image at least filter_size."""
+    if a.dim() != 4 or tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"image_metrics: two NHWC batches of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.device.type != "cuda" or b.device != a.device:
+        raise _lib.Gct2Error("image_metrics needs both batches on one HIP device (torch device 'cuda'); there is no CPU path")
+    window = torch.from_numpy(trainer_math.ssim_window(filter_size, filter_sigma)).to(a.device)
+    a, b = a.to(torch.float32).contiguous(), b.to(torch.float32).contiguous()
+    B, H, W, Cc = a.shape
+    need = ctypes.c_size_t(0)
+    _lib.check(_lib.load().gct2_image_metrics_scratch(B, H, W, Cc, window.numel(), ctypes.byref(need)), "gct2_image_metrics_scratch")
+    scratch = torch.zeros(max(4, need.value), dtype=torch.float32, device=a.device)
+    out = torch.empty(3, B, dtype=torch.float32, device=a.device)
+    _lib.call("gct2_image_metrics", a.data_ptr(), None, None, None, b.data_ptr(), window.data_ptr(), window.numel(), float(max_val), float(k1),
+              float(k2), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), scratch.data_ptr(), scratch.numel(), B, H, W, Cc,
+              torch.cuda.current_stream(a.device).cuda_stream)
+    for keep in (a, b, window, scratch):                   # (the launch is asynchronous: its operands live until the stream has passed it)
+        keep.record_stream(torch.cuda.current_stream(a.device))
+    return {n: out[k] for k, n in enumerate(trainer_math.METRICS)}

@@ -331,8 +331,105 @@ def training_loss_code(name: str) -> int:
 EVAL_STREAM_T, EVAL_STREAM_EPS = 3, 4
 
 
+# ---- image metrics of evaluation (Keras compile(metrics=[...]); gct2_image_metrics) ---------------------------------------------------
+# "mse_x0": the mean squared error of the x0 estimate against the clean image; "psnr", "ssim": tf.image.psnr / tf.image.ssim [TF] of
+# the same pair.  Images live in [-1, 1): max_val = 2
+METRICS = ("mse_x0", "psnr", "ssim")
+METRICS_MAX_VAL, METRICS_K1, METRICS_K2 = 2.0, 0.01, 0.03
+
+
+def check_metrics(names) -> Tuple[str, ...]:
+    """metric names as a tuple (None and () are no metrics; one string is one name); an unknown or repeated name is a ValueError"""
+    if names is None:
+        return ()
+    names = (names,) if isinstance(names, str) else tuple(names)
+    for k, n in enumerate(names):
+        if not isinstance(n, str) or n not in METRICS:
+            raise ValueError(f"unknown metric {n!r} (one of {', '.join(METRICS)})")
+        if n in names[:k]:
+            raise ValueError(f"metric {n!r} is named twice")
+    return names
+
+
+def ssim_window(K: int = 11, sigma: float = 1.5) -> np.ndarray:
+    """the 1-D taps of tf.image.ssim's Gaussian window [TF], float32 [K]: exp(-((i - (K - 1) / 2)^2) / (2 sigma^2)), normalised in
+    float64 and then rounded once"""
+    K = int(K)
+    if not 1 <= K <= 16:
+        raise ValueError(f"ssim_window: filter_size must lie in 1..16, got {K!r}")
+    if not (float(sigma) > 0.0 and math.isfinite(float(sigma))):
+        raise ValueError(f"ssim_window: filter_sigma must be a finite float > 0, got {sigma!r}")
+    i = np.arange(K, dtype=np.float64) - (K - 1) / 2.0
+    g = np.exp(-(i * i) / (2.0 * float(sigma) ** 2))
+    return (g / g.sum()).astype(np.float32)
+
+
+def x0_mode(predict_x: bool, predict_scaled_epsilon: bool, ordinary_differential_equation: bool) -> int:
+    """the gct2_diffusion_update mode of the objective switches (sampler.sample_mode: ODE first, then predict_x, then the epsilon forms)"""
+    if ordinary_differential_equation:
+        return _lib.SAMPLE_ODE
+    if predict_x:
+        return _lib.SAMPLE_X
+    return _lib.SAMPLE_SCALED_EPS if predict_scaled_epsilon else _lib.SAMPLE_EPS
+
+
+def x0_tables(steps: int, mode: int, schedule=None, offset: float = 0.0) -> Optional[Tuple[np.ndarray, np.ndarray]]:
+    """float32 (u, v), [steps + 1] each: entry t holds the coefficients of x0 = u noised + v pred at timestep t (x0_coefficients);
+    entry 0 is never gathered and holds zeros.  None for SAMPLE_X.  Every coefficient is formed from Python floats and rounded once."""
+    if mode == _lib.SAMPLE_X:
+        return None
+    if mode not in (_lib.SAMPLE_EPS, _lib.SAMPLE_SCALED_EPS, _lib.SAMPLE_ODE):
+        raise ValueError(f"x0_tables: unknown mode {mode!r}")
+    steps = int(steps)
+    u, v = np.zeros(steps + 1, dtype=np.float32), np.zeros(steps + 1, dtype=np.float32)
+    name = noise_schedule_name(check_noise_schedule(schedule, offset)[0])
+    for t in range(1, steps + 1):
+        a = float(alpha_dash(float(t), steps, schedule, offset))
+        a1 = float(alpha_dash(float(t) - 1, steps, schedule, offset)) if mode == _lib.SAMPLE_ODE else a
+        if not (0.0 <= a <= 1.0 and 0.0 <= a1 <= 1.0):
+            raise ValueError(f"x0_tables: noise schedule {name!r} leaves [0, 1] at timestep {t} (alpha = {a!r})")
+        try:
+            if mode == _lib.SAMPLE_ODE:
+                den = a1 ** 0.5 * (1 - a) ** 0.5 - a ** 0.5 * (1 - a1) ** 0.5
+                uu, vv = -((1 - a1) ** 0.5) / den, (1 - a) ** 0.5 / den
+            elif mode == _lib.SAMPLE_EPS:
+                uu, vv = 1.0 / a ** 0.5, -((1 - a) ** 0.5) / a ** 0.5
+            else:
+                uu, vv = 1.0 / a ** 0.5, -1.0 / a ** 0.5
+        except ZeroDivisionError:
+            raise ValueError(f"x0_tables: the x0 estimate divides by zero at timestep {t} under noise schedule {name!r} (alpha = {a!r})") from None
+        with np.errstate(over="ignore"):
+            u[t], v[t] = uu, vv
+    if not (np.isfinite(u).all() and np.isfinite(v).all()):
+        raise ValueError(f"x0_tables: the x0 estimate has a coefficient beyond float32 under noise schedule {name!r}")
+    return u, v
+
+
+def x0_coefficients(t_int, steps: int, mode: int, schedule=None, offset: float = 0.0, tables=None):
+    """per-image float32 (u, v) with x0 = u noised + v pred, the x_theta of gct2_diffusion_update (train.py:382-413) at each image's own
+    timestep; (None, None) for SAMPLE_X (x0 = pred).  With a = alpha_dash(t) and a1 = alpha_dash(t - 1):
+        SAMPLE_EPS         u = 1 / sqrt(a),  v = -sqrt(1 - a) / sqrt(a)
+        SAMPLE_SCALED_EPS  u = 1 / sqrt(a),  v = -1 / sqrt(a)
+        SAMPLE_ODE         D = sqrt(a1) sqrt(1 - a) - sqrt(a) sqrt(1 - a1),  u = -sqrt(1 - a1) / D,  v = sqrt(1 - a) / D
+    each formed per timestep from Python floats (alpha_dash(t, steps, schedule, offset)), the way the sampler forms its coefficients,
+    rounded to float32 once and gathered by t.  t_int: a tensor (the result stays on its device) or an array of integers in 1..steps;
+    tables: the two [steps + 1] vectors of x0_tables already where t_int lives (an engine keeps them)."""
+    if mode == _lib.SAMPLE_X:
+        return None, None
+    if torch.is_tensor(t_int):
+        if tables is None:
+            tables = tuple(torch.from_numpy(h).to(t_int.device) for h in x0_tables(steps, mode, schedule, offset))
+        idx = t_int.to(torch.int64).clamp(0, int(steps))
+        return tables[0].index_select(0, idx).contiguous(), tables[1].index_select(0, idx).contiguous()
+    if tables is None:
+        tables = x0_tables(steps, mode, schedule, offset)
+    idx = np.asarray(t_int).astype(np.int64)
+    return tables[0][idx], tables[1][idx]
+
+
 def loss_by_timestep(per_image, t, steps: int, bins: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
-    """(counts int64 [bins], means float64 [bins]) of per-image losses grouped by timestep: which timesteps are hard.  per_image and
+    """(counts int64 [bins], means float64 [bins]) of per-image losses grouped by timestep: which timesteps are hard.  Any per-image
+    vector bins the same way: the per_image_psnr or per_image_ssim of Trainer.evaluate(metrics=...) give PSNR / SSIM by timestep.  per_image and
     t: N values each (arrays or tensors; t integers in 1..steps).  bins=None: one bin per timestep (bin k holds t = k + 1); else
     `bins` equal-width groups, timestep t in bin (t - 1) * bins // steps.  Host only, numpy float64; an empty bin's mean is NaN."""
     as_np = lambda v: v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
@@ -464,6 +561,9 @@ class TrainerState:
     # first use of such a schedule
     noise_schedule, alpha_dash_offset = "quadratic", 0.0
     _noise_tables = None
+    # the image metrics of evaluation (evaluate_batch(metrics=...)): the [steps + 1] coefficient tables of the x0 estimate per (mode,
+    # schedule, offset) and the SSIM window, on the device; they exist only after the first evaluation that asks for a metric
+    _x0_tables = None
 
     @property
     def _ema(self) -> Optional[torch.Tensor]:
@@ -614,10 +714,72 @@ class TrainerState:
             store[key] = (scratch, basis)
         return (code,) + store[key]
 
+    def _metrics_resources(self, store: dict, B: int, H: int, W: int, Cc: int = 3) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(scratch, window) of gct2_image_metrics for this shape: allocated on first use and kept in `store`"""
+        key = ("metrics", B, H, W, Cc)
+        if key not in store:
+            window = ssim_window()
+            need = C.c_size_t(0)
+            _lib.check(self.lib.gct2_image_metrics_scratch(B, H, W, Cc, len(window), C.byref(need)), "gct2_image_metrics_scratch")
+            store[key] = (torch.zeros(max(4, need.value), dtype=torch.float32, device=self.device), torch.from_numpy(window).to(self.device))
+        return store[key]
+
+    def _x0_coefficients(self, t_int: torch.Tensor) -> Tuple[int, Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """(mode, u, v) of x0_coefficients for the objective switches and the noise schedule as they stand"""
+        mode = x0_mode(self.predict_x, self.predict_scaled_epsilon, self.ordinary_differential_equation)
+        if mode == _lib.SAMPLE_X:
+            return mode, None, None
+        if self._x0_tables is None:
+            self._x0_tables = {}
+        key = (mode, self.noise_schedule, float(self.alpha_dash_offset), int(self.steps))
+        if key not in self._x0_tables:
+            host = x0_tables(self.steps, mode, self.noise_schedule, self.alpha_dash_offset)
+            self._x0_tables[key] = tuple(torch.from_numpy(h).to(self.device) for h in host)
+        return (mode,) + x0_coefficients(t_int, self.steps, mode, tables=self._x0_tables[key])
+
+    def _noise_roots(self, t_int: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """per-image float32 (sqrt(alpha_dash(t)), sqrt(1 - alpha_dash(t))): the default schedule's torch formula, or the host tables"""
+        if self._default_schedule():
+            a = alpha_dash(t_int.to(torch.float32), self.steps)
+            return a.sqrt().contiguous(), (1 - a).sqrt().contiguous()
+        _, sa, sb = self._schedule_tables()
+        idx = t_int.to(torch.int64).clamp(0, self.steps)
+        return sa.index_select(0, idx).contiguous(), sb.index_select(0, idx).contiguous()
+
+    def _eval_metrics(self, names: Tuple[str, ...], store: dict, x: torch.Tensor, pred: torch.Tensor, eps_buf: torch.Tensor,
+                      t_int: torch.Tensor) -> dict:
+        """gct2_image_metrics of the x0 estimate against the clean batch: {name: fp32 [B] device tensor} for `names`.  Under a
+        non-default objective the fp32 noised image sqrt(a) x + sqrt(1 - a) eps is formed first (gct2_mix_per_image; eps is kept
+        there) and x0 = u noised + v pred inside the metrics kernel; under the default one x0 is the prediction itself."""
+        B, H, W, Cc = x.shape
+        scratch, window = self._metrics_resources(store, B, H, W, Cc)
+        s = self._stream()
+        mode, u, v = self._x0_coefficients(t_int)
+        noised32 = None
+        if u is not None:
+            sa, sb = self._noise_roots(t_int)
+            key = ("metrics_noised", B, H, W, Cc)
+            if key not in store:
+                store[key] = torch.empty(B, H, W, Cc, dtype=torch.float32, device=self.device)
+            noised32 = store[key]
+            call("gct2_mix_per_image", x.data_ptr(), eps_buf.data_ptr(), sa.data_ptr(), sb.data_ptr(), noised32.data_ptr(), B, H * W * Cc, s)
+        out = torch.empty(3, B, dtype=torch.float32, device=self.device)
+        want_ssim = "ssim" in names
+        call("gct2_image_metrics", pred.data_ptr(), None if u is None else noised32.data_ptr(), None if u is None else u.data_ptr(),
+             None if u is None else v.data_ptr(), x.data_ptr(), window.data_ptr(), window.numel(), METRICS_MAX_VAL, METRICS_K1, METRICS_K2,
+             out[0].data_ptr(), out[1].data_ptr() if "psnr" in names else None, out[2].data_ptr() if want_ssim else None,
+             scratch.data_ptr(), scratch.numel(), B, H, W, Cc, s)
+        self.last_eval["metrics"] = dict(mode=mode, u=u, v=v, noised=noised32, window=window)
+        return {n: out[METRICS.index(n)] for n in names}
+
     def evaluate_batch(self, x: torch.Tensor, index0: int = 0, t=None, eps: Optional[torch.Tensor] = None,
-                       seed: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                       seed: Optional[int] = None, metrics=()):
         """the training loss of every image of a held-out batch on its own: (rows fp32 [B], t_int int32 [B]), device tensors, no host
         synchronisation.  In exact arithmetic rows.mean() is what Trainer.call computes for the same t and eps.
+
+        metrics: names out of METRICS (check_metrics); with any, the return value is (rows, t_int, {name: fp32 [B]}) - the image-space
+        metrics of every image's x0 estimate (x0_coefficients) against the clean image, by one gct2_image_metrics launch on what the
+        loss launch read.  With none, nothing changes: the same launches, the same return value, the same last_eval keys.
 
         The draws belong to evaluation alone and depend on the image, not on the batch: with seed (None: rng_seed), the image of
         global index i = index0 + k takes position i of Philox stream EVAL_STREAM_T for its timestep and positions
@@ -629,6 +791,7 @@ class TrainerState:
         Refused inside a plan recording."""
         if _lib._recording is not None:
             raise _lib.Gct2Error("evaluate_batch inside a plan recording: evaluation is not part of a train step")
+        metrics = check_metrics(metrics)
         if x.dim() != 4 or x.shape[-1] != 3:
             raise ValueError(f"expected an NHWC batch [B,H,W,3], got {tuple(x.shape)}")
         index0 = int(index0)
@@ -666,6 +829,8 @@ class TrainerState:
              scratch.data_ptr(), scratch.numel(), B, H, W, 3, basis.data_ptr() if basis is not None else None, s)
         # what the launches read stays alive with the engine until the next evaluation (and is what the tests restate the rows from)
         self.last_eval = dict(x=x, pred=pred, eps=None if default and eps is None else eps_buf, t_int=t_int, coef=(a, c, w), noised=noised)
+        if metrics:
+            return rows, t_int.clone(), self._eval_metrics(metrics, store, x, pred, eps_buf, t_int)
         return rows, t_int.clone()
 
     # ---- per-timestep heads (train.py:199, 203, 211-214) ------------------------------------------------------------------------

@@ -532,6 +532,46 @@ int gct2_eval_loss_rows(int kind, const float* pred, const float* x, const float
                         const float* w, float* rows, float* scratch, size_t scratch_floats, int B, int H, int W, int C,
                         const float* basis, void* stream);
 
+/* ---- image metrics of evaluation (Keras compile(metrics=[...]); tf.image.psnr / tf.image.ssim [TF]): PER IMAGE, in image space ----
+ * The x0 estimate e of image b against the clean image x: mse[b], psnr[b] and ssim[b] (Wang et al. 2004 with the defaults of
+ * tf.image.ssim; parity unpinned, there is no TensorFlow here).  pred, noised, x: fp32 [B,H,W,C] contiguous, C in 1..4, all three
+ * read only; u, v: device float[B] or NULL; window: device float[K], K in 1..16, the 1-D filter taps (the host passes the table:
+ * trainer_math.ssim_window; nothing evaluates a Gaussian on the device); mse, psnr, ssim: float[B]; psnr and / or ssim may be NULL,
+ * and a NULL ssim skips the windowed pass entirely (window may then be NULL too).
+ * Per element, every operation rounded once (no fused multiply-add), by the rule of gct2_mix_per_image:
+ *   e = pred                                    (u == NULL; noised and v must then be NULL too)
+ *     = fl(fl(u[b] * noised) + fl(v[b] * pred)) (u given; noised and v are then required)
+ *   d = fl(x - e).
+ * With n_img = H*W*C and S the sum over image b in fp64:
+ *   m = S((double)d * (double)d) / n_img,  mse[b] = (float)m   (the MSE row of gct2_eval_loss_rows)
+ *   psnr[b] = (float)(10 * log10((double)max_val * max_val / m)) in fp64, +inf when m == 0
+ * SSIM, everything in fp64: a = (double)e, b = (double)x, w = (double)window[.],
+ *   F(q)[i,j,c] = sum_r sum_s w[r] w[s] q[i+r, j+s, c]   for i in [0, H-K], j in [0, W-K]   (VALID: nothing outside the image is read;
+ *   evaluated separably, rows then columns),
+ *   mu_a = F(a), mu_b = F(b), A = F(a a), Bq = F(b b), AB = F(a b)  (a product of two floats is exact in fp64: only the sums round),
+ *   C1 = (k1 max_val)^2, C2 = (k2 max_val)^2,
+ *   lum = (2 mu_a mu_b + C1) / (mu_a^2 + mu_b^2 + C1),
+ *   cs  = (2 AB - 2 mu_a mu_b + C2) / (A + Bq - (mu_a^2 + mu_b^2) + C2),
+ *   ssim[b] = (float)(the mean of lum * cs over all (H-K+1)(W-K+1)C positions and channels).
+ * Identical images give mse 0, psnr +inf and ssim exactly 1.
+ * One work-group per image, GCT2_METRICS_TILE x GCT2_METRICS_TILE tile of pixels and channel.  The tiles cut the image, so d^2 counts
+ * every element once although the staged regions overlap, and the cut depends on neither K nor ssim: mse and psnr have the same bits
+ * with and without SSIM.  No atomics; a work-group never mixes two images; work-groups leave fp64 partial sums in scratch and one
+ * finishing launch adds them per image in index order: the bits depend on the inputs alone.  Images need not start at 16-byte
+ * boundaries (n_img = 121).
+ * scratch: device floats, 16-byte aligned, at least what gct2_image_metrics_scratch reports (host only, no launch; K is checked,
+ * the figure does not depend on it).
+ * GCT2_EINVAL before any launch, in this order: NULL pred / x / mse / scratch; u without noised or v, or either of those without u;
+ * ssim without window; non-positive dims, C outside 1..4, K outside 1..16; H < K or W < K when ssim is given; max_val not finite
+ * or <= 0, k1 or k2 negative or not finite; pointers not 4-byte aligned, scratch not 16-byte aligned; B > 65535; B*n_img at or
+ * beyond 2^31; scratch_floats below the query's figure. */
+#define GCT2_METRICS_TILE 32
+int gct2_image_metrics_scratch(int B, int H, int W, int C, int K, size_t* floats);
+int gct2_image_metrics(const float* pred, const float* noised, const float* u, const float* v, const float* x,
+                       const float* window, int K, float max_val, float k1, float k2,
+                       float* mse, float* psnr, float* ssim,
+                       float* scratch, size_t scratch_floats, int B, int H, int W, int C, void* stream);
+
 /* ---- mixed precision (train.py:34,43-45,82-83) ------------------------------------------------ */
 /* device-resident state of Keras' LossScaleOptimizer [TF] plus the optimizer step counter it gates: a skipped step (inf/nan
  * gradients) does not run the inner apply_gradients, so optimizer.iterations - and with it the WarmUp step and Adam's bias
