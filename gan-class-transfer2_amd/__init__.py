@@ -5,10 +5,11 @@ The directory name carries a hyphen (project convention); import it as `gan_clas
 """
 from . import _lib, build, data, engine, model, sampler, trainer_math # noqa: F401
 from .data import ImageDataset                    # noqa: F401
-from .sampler import log_sample, make_log_sample  # noqa: F401
+from .sampler import generate, log_sample, make_log_sample  # noqa: F401
 from ._lib import BF16, F16, F32, Gct2Error       # noqa: F401
 from .engine import Topology, UNetEngine          # noqa: F401
 from .model import (Adam, Block, Dense, Denoiser, DownShuffle, InverseTimeDecay, LambdaCallback, LossScaleOptimizer,  # noqa: F401
                     RMSprop, Residual, SGD, Sequential, Trainer, UpShuffle, WarmUp, alpha_dash, configure, identity, image_metrics,
                     regularizers, sign_gradient)
 from .trainer_math import METRICS, NOISE_SCHEDULES, alpha_table, noise_table, ssim_window  # noqa: F401
+from .trainer_math import GENERATE_STREAM, ddim_sigma2, sampling_timesteps                 # noqa: F401

@@ -655,6 +655,38 @@ int gct2_diffusion_update(int mode, const float* pred, const float* fake, double
   return pw_diffusion_update(mode, pred, fake, alpha, alpha_prev, x_theta, eps_theta, n, S(stream));
 }
 
+// the image views of gct2_diffusion_step / _start: B images of per_image = H*W*C elements, flat indices below 2^31
+static int step_views_ok(const char* who, int dtype, const float* fake_out, const void* out, int ldout, const void* out2, int ldout2, int B,
+                         size_t per_image, int C) {
+  if (!dtype_ok(dtype) || !fake_out || !out) return gct2_fail(GCT2_EINVAL, "%s: bad dtype or null pointer", who);
+  if (B <= 0 || per_image == 0 || C <= 0 || per_image % (size_t)C || ldout < C || (out2 && ldout2 < C) ||
+      per_image >= ((size_t)1 << 31) || (size_t)B * per_image >= ((size_t)1 << 31))
+    return gct2_fail(GCT2_EINVAL, "%s: bad shape (per_image a multiple of C, ldout >= C, B * per_image < 2^31)", who);
+  return GCT2_OK;
+}
+
+int gct2_diffusion_step(int mode, int dtype, const float* pred, const float* fake_in, double a_t, double a_prev, double sigma2, double clip,
+                        uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t image_stride, float* fake_out, float* x0_out, void* out,
+                        int ldout, void* out2, int ldout2, int B, size_t per_image, int C, void* stream) {
+  if (mode < GCT2_SAMPLE_X || mode > GCT2_SAMPLE_SCALED_EPS)
+    return gct2_fail(GCT2_EINVAL, "diffusion_step: mode %d (the ODE objective predicts one step back only: gct2_diffusion_update)", mode);
+  if (!pred || !fake_in) return gct2_fail(GCT2_EINVAL, "diffusion_step: null pointer");
+  if (int rc = step_views_ok("diffusion_step", dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
+  if (!(a_t >= 0. && a_t < 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step: a_t must be in [0, 1)");
+  if (mode != GCT2_SAMPLE_X && !(a_t > 0.)) return gct2_fail(GCT2_EINVAL, "diffusion_step: this mode divides by sqrt(a_t): a_t must be > 0");
+  if (!(a_prev >= 0. && a_prev <= 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step: a_prev must be in [0, 1]");
+  if (!(sigma2 >= 0.) || !((1.f - (float)a_prev) - (float)sigma2 >= 0.f))
+    return gct2_fail(GCT2_EINVAL, "diffusion_step: sigma2 must be in [0, 1 - a_prev]");
+  return pw_diffusion_step(mode, dtype, pred, fake_in, a_t, a_prev, sigma2, clip, seed, stream_id, offset, image_stride, fake_out, x0_out, out,
+                           ldout, out2, ldout2, B, per_image, C, S(stream));
+}
+
+int gct2_diffusion_start(int dtype, uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t image_stride, float* fake_out, void* out,
+                         int ldout, void* out2, int ldout2, int B, size_t per_image, int C, void* stream) {
+  if (int rc = step_views_ok("diffusion_start", dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
+  return pw_diffusion_start(dtype, seed, stream_id, offset, image_stride, fake_out, out, ldout, out2, ldout2, B, per_image, C, S(stream));
+}
+
 int gct2_noise_edits(const float* eps, const float* dictionary, int K, float* out, int H, int W, int C, void* stream) {
   if (!eps || !dictionary || !out) return gct2_fail(GCT2_EINVAL, "noise_edits: null pointer");
   if (H <= 0 || W <= 0 || C <= 0 || K <= 0 || (H & 3) || (W & 3))

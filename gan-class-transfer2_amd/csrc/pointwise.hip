@@ -865,6 +865,142 @@ __global__ void diffusion_update_kernel(const float* __restrict__ pred, const fl
     }
   }
 }
+
+// ---- Denoiser.generate: one strided DDIM / DDPM step in ONE launch (include/gct2.h: gct2_diffusion_step, gct2_diffusion_start) ----
+// diffusion_update_kernel's x / e, the clip of x (and e re-derived from the clipped x), then the re-noising to a_prev with
+// diffusion_mix_kernel's arithmetic and stores - x_theta and eps_theta never reach memory.  Every operation rounds once.
+// STEP_START: no update at all, the value is the draw itself (gct2_diffusion_start).
+constexpr int STEP_START = -1;
+struct StepCoef { float sa, sb, clip, cx, ce, cz; };
+
+template <int MODE>
+__device__ __forceinline__ float step_update(float p, float f, const StepCoef& k, float& x) {
+#pragma clang fp contract(off)
+  float e;
+  if (MODE == GCT2_SAMPLE_X) {
+    x = p;
+    e = (f - k.sa * p) / k.sb;
+  } else if (MODE == GCT2_SAMPLE_EPS) {
+    e = p;
+    x = (f - p * k.sb) / k.sa;
+  } else {
+    e = p / k.sb;
+    x = (f - p) / k.sa;
+  }
+  if (k.clip > 0.f) {                       // (wave-uniform)  a NaN fails both comparisons and stays
+    const float c = k.clip;
+    x = x < -c ? -c : (x > c ? c : x);
+    e = (f - k.sa * x) / k.sb;
+  }
+  return k.cx * x + k.ce * e;
+}
+template <typename T>
+__device__ __forceinline__ void step_store(float v, size_t i, size_t pix, int c, float* fake_out, T* __restrict__ out, int ldout,
+                                           T* __restrict__ out2, int ldout2) {
+  fake_out[i] = v;
+  out[pix * ldout + c] = from_f32<T>(v);
+  if (out2) out2[pix * ldout2 + c] = from_f32<T>(v);
+}
+
+// one whole Philox counter: four consecutive elements from a flat index that is a multiple of 4, all planes 16-byte aligned - the fp32
+// planes move as 16-byte accesses, the compute-dtype copies element by element (a row holds C of them).  z: the four normals
+template <typename T, int MODE>
+__device__ __forceinline__ void step_quad(const float* __restrict__ pred, const float* fake_in, const StepCoef& k, const float (&z)[4], size_t i,
+                                          float* fake_out, float* __restrict__ x0_out, T* __restrict__ out, int ldout, T* __restrict__ out2,
+                                          int ldout2, int C) {
+#pragma clang fp contract(off)
+  f32x4_t v, x4;
+  if constexpr (MODE == STEP_START) {
+    v = f32x4_t{z[0], z[1], z[2], z[3]};
+  } else {
+    const f32x4_t p = *reinterpret_cast<const f32x4_t*>(pred + i), f = *reinterpret_cast<const f32x4_t*>(fake_in + i);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      float x;
+      const float m = step_update<MODE>(p[j], f[j], k, x);
+      v[j] = m + k.cz * z[j];
+      x4[j] = x;
+    }
+    if (x0_out) *reinterpret_cast<f32x4_t*>(x0_out + i) = x4;
+  }
+  *reinterpret_cast<f32x4_t*>(fake_out + i) = v;
+  uint32_t pix = (uint32_t)i / (uint32_t)C;                       // B * per_image < 2^31 (checked by the entry point)
+  int c = (int)((uint32_t)i - pix * (uint32_t)C);
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    out[(size_t)pix * ldout + c] = from_f32<T>(v[j]);
+    if (out2) out2[(size_t)pix * ldout2 + c] = from_f32<T>(v[j]);
+    if (++c == C) { c = 0; ++pix; }
+  }
+}
+
+// sigma^2 == 0: nothing is drawn, the images are one flat range, one element per thread (fake_in may be fake_out: a thread reads its
+// element, then writes it).  Four elements per thread with 16-byte accesses measured SLOWER here (25.6 against 20.5 us at 64x128x128x3,
+// profiles/generate_bench.json): consecutive lanes then store their copies 4 elements apart
+template <typename T, int MODE>
+__global__ void diffusion_step_kernel(const float* __restrict__ pred, const float* fake_in, StepCoef k, float* fake_out,
+                                      float* __restrict__ x0_out, T* __restrict__ out, int ldout, T* __restrict__ out2, int ldout2, size_t n,
+                                      int C) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    float x;
+    const float v = step_update<MODE>(pred[i], fake_in[i], k, x);
+    if (x0_out) x0_out[i] = x;
+    const uint32_t pix = (uint32_t)i / (uint32_t)C;               // B * per_image < 2^31 (checked by the entry point)
+    step_store<T>(v, i, pix, (int)((uint32_t)i - pix * (uint32_t)C), fake_out, out, ldout, out2, ldout2);
+  }
+}
+
+// with noise: element i of image b adds cz * (the normal of stream element offset + b image_stride + i).  noise_rng_kernel's scheme per
+// image (blockIdx.y walks the images): one thread per Philox counter = up to four consecutive elements, one Philox call and two
+// Box-Muller pairs; an image may start and end inside a counter, whatever offset, image_stride and per_image are.  The counter index
+// is 64 bits wide, so a range across a wrap of its low word needs nothing special.  VEC (the launcher: offset, image_stride and
+// per_image multiples of 4, 16-byte aligned planes - what generate passes): every counter lies inside its image and moves as 16-byte
+// accesses, 25.0 us where the general form takes 57.3 us (profiles/generate_bench.json)
+template <typename T, int MODE, bool VEC>
+__global__ void diffusion_step_rng_kernel(const float* __restrict__ pred, const float* fake_in, StepCoef k, uint64_t seed, uint64_t stream_id,
+                                          uint64_t offset, uint64_t image_stride, float* fake_out, float* __restrict__ x0_out,
+                                          T* __restrict__ out, int ldout, T* __restrict__ out2, int ldout2, int B, uint32_t per_image, int C) {
+#pragma clang fp contract(off)
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const uint64_t base = offset + (uint64_t)b * image_stride, end = base + per_image;
+    const uint64_t c0 = base >> 2;
+    const size_t ncounters = (size_t)(((end + 3) >> 2) - c0);
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < ncounters; t += stride) {
+      const uint64_t ctr = c0 + t;
+      uint32_t r[4];
+      philox4x32_10(seed, stream_id, ctr, r);
+      float nrm[4];
+      box_muller(r[0], r[1], nrm[0], nrm[1]);
+      box_muller(r[2], r[3], nrm[2], nrm[3]);
+      if constexpr (VEC) {
+        step_quad<T, MODE>(pred, fake_in, k, nrm, (size_t)b * per_image + 4 * t, fake_out, x0_out, out, ldout, out2, ldout2, C);
+      } else {
+        const uint64_t e0 = 4 * ctr;
+        const uint64_t first = e0 < base ? base : e0;               // (< end: the counter range was cut to the image)
+        const uint32_t i0 = (uint32_t)b * per_image + (uint32_t)(first - base);   // B * per_image < 2^31 (checked by the entry point)
+        uint32_t pix = i0 / (uint32_t)C, c = i0 - pix * (uint32_t)C;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const uint64_t e = e0 + j;
+          if (e < first || e >= end) continue;
+          const size_t i = (size_t)b * per_image + (size_t)(e - base);
+          float v;
+          if constexpr (MODE == STEP_START) {
+            v = nrm[j];
+          } else {
+            float x;
+            v = step_update<MODE>(pred[i], fake_in[i], k, x) + k.cz * nrm[j];
+            if (x0_out) x0_out[i] = x;
+          }
+          step_store<T>(v, i, pix, (int)c, fake_out, out, ldout, out2, ldout2);
+          if (++c == (uint32_t)C) { c = 0; ++pix; }
+        }
+      }
+    }
+  }
+}
 // the four noise variants of train.py:416-431 from one eps image [H,W,C]: out[0] = eps, out[1] = nearest-upsample x4 of the
 // 4x4 average pool, out[2] = rolled by one pixel along H and W, out[3] = per-pixel nearest entry of dictionary [H,W,K,C]
 __global__ void noise_edits_kernel(const float* __restrict__ eps, const float* __restrict__ dict, int K, float* __restrict__ out,
@@ -1600,6 +1736,59 @@ int pw_diffusion_update(int mode, const float* pred, const float* fake, double a
     hipLaunchKernelGGL(diffusion_update_kernel<GCT2_SAMPLE_SCALED_EPS>, grid, block, 0, s, pred, fake, sa, sb, sb1, den, x, e, n);
   else hipLaunchKernelGGL(diffusion_update_kernel<GCT2_SAMPLE_ODE>, grid, block, 0, s, pred, fake, sa, sb, sb1, den, x, e, n);
   return gct2_check_launch("diffusion_update");
+}
+// the grid of the per-image kernels: x over the Philox counters of one image, y over the images, kMaxBlocks work-groups at the most
+static dim3 step_rng_grid(int B, size_t per_image) {
+  const int gx = blocks_for(per_image / 4 + 2, 256);
+  const int gy = std::max(1, std::min(B, kMaxBlocks / gx));
+  return dim3(gx, gy);
+}
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+int pw_diffusion_step(int mode, int dtype, const float* pred, const float* fake_in, double a, double a_prev, double sigma2, double clip,
+                      uint64_t seed, uint64_t sid, uint64_t off, uint64_t image_stride, float* fake_out, float* x0_out, void* out, int ldout,
+                      void* out2, int ldout2, int B, size_t per_image, int C, hipStream_t s) {
+  // sa, sb as pw_diffusion_update forms them; the re-noising coefficients from the fp32 a_prev like pw_diffusion_mix's
+  const float A = (float)a_prev, S = (float)sigma2;
+  const StepCoef k = {(float)sqrt(a), (float)sqrt(1. - a), clip > 0. ? (float)clip : 0.f, sqrtf(A), sqrtf((1.f - A) - S), sqrtf(S)};
+  const size_t n = (size_t)B * per_image;
+  // the four-element form of the with-noise kernel: every image starts on a Philox counter and on a 16-byte boundary
+  const bool vec = aligned16(pred) && aligned16(fake_in) && aligned16(fake_out) && aligned16(x0_out) && off % 4 == 0 && image_stride % 4 == 0 &&
+                   per_image % 4 == 0;
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    T *o = reinterpret_cast<T*>(out), *o2 = reinterpret_cast<T*>(out2);
+    auto launch = [&](auto m) {
+      constexpr int MODE = decltype(m)::value;
+      auto noisy = [&](auto v) {
+        hipLaunchKernelGGL((diffusion_step_rng_kernel<T, MODE, decltype(v)::value>), step_rng_grid(B, per_image), dim3(256), 0, s, pred, fake_in,
+                           k, seed, sid, off, image_stride, fake_out, x0_out, o, ldout, o2, ldout2, B, (uint32_t)per_image, C);
+      };
+      if (S == 0.f)
+        hipLaunchKernelGGL((diffusion_step_kernel<T, MODE>), dim3(blocks_for(n, 256)), dim3(256), 0, s, pred, fake_in, k, fake_out, x0_out, o,
+                           ldout, o2, ldout2, n, C);
+      else if (vec) noisy(std::true_type{});
+      else noisy(std::false_type{});
+    };
+    if (mode == GCT2_SAMPLE_X) launch(std::integral_constant<int, GCT2_SAMPLE_X>{});
+    else if (mode == GCT2_SAMPLE_EPS) launch(std::integral_constant<int, GCT2_SAMPLE_EPS>{});
+    else launch(std::integral_constant<int, GCT2_SAMPLE_SCALED_EPS>{});
+  });
+  return gct2_check_launch("diffusion_step");
+}
+int pw_diffusion_start(int dtype, uint64_t seed, uint64_t sid, uint64_t off, uint64_t image_stride, float* fake_out, void* out, int ldout,
+                       void* out2, int ldout2, int B, size_t per_image, int C, hipStream_t s) {
+  const bool vec = aligned16(fake_out) && off % 4 == 0 && image_stride % 4 == 0 && per_image % 4 == 0;
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    auto launch = [&](auto v) {
+      hipLaunchKernelGGL((diffusion_step_rng_kernel<T, STEP_START, decltype(v)::value>), step_rng_grid(B, per_image), dim3(256), 0, s,
+                         (const float*)nullptr, (const float*)nullptr, StepCoef{}, seed, sid, off, image_stride, fake_out, (float*)nullptr,
+                         reinterpret_cast<T*>(out), ldout, reinterpret_cast<T*>(out2), ldout2, B, (uint32_t)per_image, C);
+    };
+    if (vec) launch(std::true_type{});
+    else launch(std::false_type{});
+  });
+  return gct2_check_launch("diffusion_start");
 }
 int pw_noise_edits(const float* eps, const float* dict, int K, float* out, int H, int W, int C, hipStream_t s) {
   hipLaunchKernelGGL(noise_edits_kernel, dim3((H * W + 255) / 256), dim3(256), 0, s, eps, dict, K, out, H, W, C);

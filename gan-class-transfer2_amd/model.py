@@ -664,6 +664,12 @@ class Denoiser(Layer):
             self.engine.set_noise_schedule(*schedule)
         return self.engine
 
+    def generate(self, n: int, **kw):
+        """n new images from noise, fp32 [n,H,W,3] on the device: sampler.generate(self, n, ...) - strided DDIM sampling with
+        num_steps, eta, clip_denoised, seed, first_index, batch_size, timesteps, noise, use_ema, use_graph, return_steps, size"""
+        from .sampler import generate
+        return generate(self, n, **kw)
+
     def _bind_variant_parameters(self) -> None:
         """the nested eager layers of self.middle share the variant engine's parameters: both enumerate the layers in forward
         order (train.py:183-204), so the k-th layer with a kernel is the k-th (kernel[, bias]) group of the engine."""

@@ -7,7 +7,11 @@ codebook), and `steps` evaluations of reverse sampling on a batch of six.
 Everything stays on the device: the state (x_theta, epsilon_theta, fake) is fp32 like the reference's, the pointwise steps
 are library kernels (gct2_diffusion_mix / _update / gct2_noise_edits, include/gct2.h).  The network evaluations reuse the
 planned forward pass of UNetEngine at batch 1 and 6 (captured once into a HIP graph per buffer set), or - for the topology
-variants of train.py:20, 26, 27 - VariantEngine.predict, layer by layer.  Returns the tensors the reference hands to tf.summary."""
+variants of train.py:20, 26, 27 - VariantEngine.predict, layer by layer.  Returns the tensors the reference hands to tf.summary.
+
+`generate` - what the reference does not have: n new images from noise at a batch size and step count of the caller's choice,
+reproducible from a seed, with the two controls of every DDIM / DDPM sampler (eta, clipping of the x0 estimate).  Same network
+evaluations; the two pointwise launches of a step are one (gct2_diffusion_step), the state is `fake` alone."""
 from __future__ import annotations
 
 import contextlib
@@ -15,6 +19,7 @@ import gc
 import warnings
 from typing import Callable, Dict, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -23,6 +28,7 @@ from ._lib import SAMPLE_EPS, SAMPLE_ODE, SAMPLE_SCALED_EPS, SAMPLE_X, call
 from .engine import TORCH_DTYPE, UNetEngine
 from .trainer_math import alpha_dash            # train.py:85-93 on python floats, as in the reference
 from .trainer_math import check_noise_schedule, check_timesteps, noise_schedule_name
+from .trainer_math import GENERATE_STREAM, ddim_sigma2, generate_image_stride, generate_offset, sampling_timesteps
 
 
 def sample_mode(predict_x: bool, predict_scaled_epsilon: bool, ordinary_differential_equation: bool) -> int:
@@ -124,19 +130,34 @@ class _Sampler:
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.eng.device).cuda_stream
 
-    def mix(self, B: int, x: torch.Tensor, e: torch.Tensor, alpha: float, fake: torch.Tensor) -> None:
-        """fake = sqrt(alpha) x + sqrt(1 - alpha) e, also written where the network reads its input."""
+    def input_views(self, B: int) -> Tuple[int, int, Optional[int], int]:
+        """(out, ldout, out2, ldout2) of the pointwise kernels: where the network of batch B reads its input in the compute dtype - the
+        planned engine's packed image and the image slice of R_0, or the one tensor VariantEngine.predict is handed"""
         eng = self.eng
         if self.planned:
             b = eng.buffers(B, self.H, self.W)
-            call("gct2_diffusion_mix", eng.dtype, x.data_ptr(), e.data_ptr(), alpha, fake.data_ptr(), b.img.data_ptr(), 4,
-                 eng._slice_ptr(b.R[0], eng.topo.fu(0)), b.ld[0], B * self.H * self.W, 3, self._stream())
-        else:
-            inp = self._inputs.get(B)
-            if inp is None:
-                inp = self._inputs[B] = torch.empty(B, self.H, self.W, 3, dtype=TORCH_DTYPE[eng.dtype], device=eng.device)
-            call("gct2_diffusion_mix", eng.dtype, x.data_ptr(), e.data_ptr(), alpha, fake.data_ptr(), inp.data_ptr(), 3, None, 0,
-                 B * self.H * self.W, 3, self._stream())
+            return b.img.data_ptr(), 4, eng._slice_ptr(b.R[0], eng.topo.fu(0)), b.ld[0]
+        inp = self._inputs.get(B)
+        if inp is None:
+            inp = self._inputs[B] = torch.empty(B, self.H, self.W, 3, dtype=TORCH_DTYPE[eng.dtype], device=eng.device)
+        return inp.data_ptr(), 3, None, 0
+
+    def mix(self, B: int, x: torch.Tensor, e: torch.Tensor, alpha: float, fake: torch.Tensor) -> None:
+        """fake = sqrt(alpha) x + sqrt(1 - alpha) e, also written where the network reads its input."""
+        call("gct2_diffusion_mix", self.eng.dtype, x.data_ptr(), e.data_ptr(), alpha, fake.data_ptr(), *self.input_views(B),
+             B * self.H * self.W, 3, self._stream())
+
+    def start(self, B: int, seed: int, offset: int, image_stride: int, fake: torch.Tensor) -> None:
+        """fake = the normals of generation's stream from `offset` on, images image_stride apart (gct2_diffusion_start)."""
+        call("gct2_diffusion_start", self.eng.dtype, seed, GENERATE_STREAM, offset, image_stride, fake.data_ptr(), *self.input_views(B),
+             B, self.H * self.W * 3, 3, self._stream())
+
+    def fused_step(self, B: int, pred: torch.Tensor, fake: torch.Tensor, a_t: float, a_prev: float, sigma2: float, clip: float, seed: int,
+                   offset: int, image_stride: int, x0: Optional[torch.Tensor]) -> None:
+        """update + clip + re-noising to a_prev in one launch, in place on fake (gct2_diffusion_step); x0: where the x0 estimate goes"""
+        call("gct2_diffusion_step", self.mode, self.eng.dtype, pred.data_ptr(), fake.data_ptr(), a_t, a_prev, sigma2, clip, seed,
+             GENERATE_STREAM, offset, image_stride, fake.data_ptr(), x0.data_ptr() if x0 is not None else None, *self.input_views(B),
+             B, self.H * self.W * 3, 3, self._stream())
 
     def update(self, pred: torch.Tensor, fake: torch.Tensor, alpha: float, alpha_prev: float, x: torch.Tensor, e: Optional[torch.Tensor]) -> None:
         """train.py:382-413 / 452-479 by mode (gct2_diffusion_update)."""
@@ -262,6 +283,120 @@ def _log_sample(eng, example_image, example, dictionary, steps, test_step, predi
                 out[name] = x_theta.clone()
     out["fake"] = x_theta.clone()
     return out
+
+
+def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, eta: float = 0.0, clip_denoised=None, seed: int = 0,
+             first_index: int = 0, batch_size: Optional[int] = None, timesteps=None, noise: Optional[torch.Tensor] = None,
+             use_ema: bool = False, use_graph: bool = True, return_steps=(), size=None, predict_x: Optional[bool] = None,
+             predict_scaled_epsilon: Optional[bool] = None, ordinary_differential_equation: Optional[bool] = None, noise_schedule=None,
+             alpha_dash_offset: Optional[float] = None):
+    """n new images from noise: strided DDIM sampling (Song et al. 2021) over K = num_steps of the engine's `steps` timesteps
+    (trainer_math.sampling_timesteps; None: all of them; or an explicit strictly increasing `timesteps` list within 1..steps), one
+    network evaluation and ONE pointwise launch (gct2_diffusion_step) per step.  Returns fp32 [n,H,W,3] on the device: the x0 estimate
+    of the last step, which the reference logs as `fake` (its schedule never reaches alpha = 1, so the estimate is the sample).
+    eta: 0 the deterministic DDIM step, 1 the DDPM posterior variance (trainer_math.ddim_sigma2).  clip_denoised: True clips every x0
+    estimate to [-1, 1], a float to that bound (eps is re-derived from the clipped estimate); None / False: no clipping.
+    seed, first_index: image g = first_index + position draws its starting noise and the noise of every step from Philox stream
+    GENERATE_STREAM by g alone (trainer_math.generate_offset): the result does not depend on batch_size (default min(n, 64)), and
+    generate(4) is generate(2) followed by generate(2, first_index=2).  noise [n,H,W,3]: the starting noise instead of the drawn one.
+    size: H = W (or (H, W)) when no noise is given; None is the module's `size`.  return_steps: timesteps whose x0 estimate is
+    returned too - then the result is (images, {t: fp32 [n,H,W,3]}).  use_ema: every evaluation reads the parameter averages.
+    The objective switches and the noise schedule resolve like log_sample's; the ODE objective is refused (its network predicts one
+    step back only: striding and eta mean nothing there).  No training state moves: the RNG positions of training and evaluation,
+    optimizer slots, averages, loss scale and recorded plans stay as they are."""
+    eng = denoiser.ensure_engine()
+    steps = int(eng.steps)
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"generate: n must be a positive int, got {n!r}")
+    mode = _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_differential_equation)
+    if mode == SAMPLE_ODE:
+        raise ValueError("generate: the ordinary_differential_equation objective predicts the image one step back only; strided sampling "
+                         "and eta have no meaning there (log_sample runs its sampler)")
+    schedule, offset = _resolve_schedule(eng, noise_schedule, alpha_dash_offset)
+    if not float(eta) >= 0.0:
+        raise ValueError(f"generate: eta must be >= 0, got {eta!r}")
+    if timesteps is not None:
+        given = list(timesteps)
+        if not given or any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) for t in given) or given[0] < 1 or \
+                given[-1] > steps or any(b <= a for a, b in zip(given, given[1:])):
+            raise ValueError(f"generate: timesteps must be strictly increasing integers within 1..{steps}, got {given!r}")
+        taus = [int(t) for t in given]
+        if num_steps is not None and num_steps != len(taus):
+            raise ValueError(f"generate: num_steps = {num_steps!r} disagrees with the {len(taus)} timesteps given")
+    else:
+        try:
+            taus = sampling_timesteps(steps, steps if num_steps is None else num_steps)
+        except ValueError as e:
+            raise ValueError(f"generate: {e}") from None
+    K = len(taus)
+    if clip_denoised is None or clip_denoised is False:
+        clip = 0.0
+    elif clip_denoised is True:
+        clip = 1.0
+    else:
+        clip = float(clip_denoised)
+        if not (clip > 0.0 and clip < float("inf")):
+            raise ValueError(f"generate: clip_denoised must be True, False, None or a finite bound > 0, got {clip_denoised!r}")
+    if noise is not None:
+        if noise.dim() != 4 or noise.shape[0] != n or noise.shape[3] != 3 or (size is not None and tuple(noise.shape[1:3]) != _hw(size)):
+            raise ValueError(f"generate: noise must be [n,H,W,3] = [{n},H,W,3], got {tuple(noise.shape)}")
+        H, W = int(noise.shape[1]), int(noise.shape[2])
+    else:
+        H, W = _hw(M.size if size is None else size)
+    marks = tuple(return_steps)
+    if any(t not in taus for t in marks):
+        raise ValueError(f"generate: return_steps {list(marks)!r} must be among the timesteps sampled, {taus!r}")
+    bs = min(n, 64) if batch_size is None else batch_size
+    if isinstance(bs, bool) or not isinstance(bs, int) or bs < 1:
+        raise ValueError(f"generate: batch_size must be a positive int, got {batch_size!r}")
+    per_image = H * W * 3
+    seed, first_index = int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_index)
+    if first_index < 0 or generate_offset(first_index + n, 0, K, per_image) >= 1 << 64:
+        raise ValueError(f"generate: first_index = {first_index!r} leaves the 64-bit stream")
+    stride = generate_image_stride(K, per_image)
+    alpha = lambda t: float(alpha_dash(t, steps, schedule, offset))
+    plan = []                                   # per step in sampling order: (t, a_t, a_prev, sigma2)
+    for k in range(K):
+        tau = taus[K - 1 - k]
+        a_t, a_prev = alpha(tau), alpha(taus[K - 2 - k] if k < K - 1 else 0)
+        s2 = ddim_sigma2(a_t, a_prev, eta)
+        # the kernel forms sqrt((1 - a_prev) - sigma2) in fp32: a sigma2 clamped at 1 - a_prev in double must not pass it there
+        lim = float(np.float32(1.0) - np.float32(a_prev))
+        plan.append((tau, a_t, a_prev, lim if float(np.float32(s2)) > lim else s2))
+
+    dev = eng.device
+    with (eng.ema_weights() if use_ema else contextlib.nullcontext()):
+        eng.flush_deferred()
+        S = _Sampler(eng, steps, mode, H, W, use_graph, schedule, offset)
+        out = torch.empty(n, H, W, 3, dtype=torch.float32, device=dev)
+        kept = {t: torch.empty_like(out) for t in marks}
+        fake = None
+        for g0 in range(0, n, bs):
+            B = min(bs, n - g0)
+            if fake is None or fake.shape[0] != B:
+                fake = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev)
+            if noise is None:
+                S.start(B, seed, generate_offset(first_index + g0, 0, K, per_image), stride, fake)
+            else:
+                z = noise[g0:g0 + B].to(dev, torch.float32).contiguous()
+                S.mix(B, z, z, 0.0, fake)       # alpha = 0: fake = 0 z + 1 z
+            for k, (tau, a_t, a_prev, s2) in enumerate(plan, 1):
+                S.set_t(B, tau)
+                pred = S.evaluate(B)
+                x0 = out[g0:g0 + B] if k == K else (kept[tau][g0:g0 + B] if tau in kept else None)
+                S.fused_step(B, pred, fake, a_t, a_prev, s2, clip, seed, generate_offset(first_index + g0, k, K, per_image), stride, x0)
+                if k == K and tau in kept:
+                    kept[tau][g0:g0 + B].copy_(x0)
+    return (out, kept) if marks else out
+
+
+def _hw(size) -> Tuple[int, int]:
+    """an image size as (H, W): one int is a square"""
+    if isinstance(size, (tuple, list)):
+        if len(size) != 2:
+            raise ValueError(f"generate: size must be an int or (H, W), got {size!r}")
+        return int(size[0]), int(size[1])
+    return int(size), int(size)
 
 
 def make_log_sample(denoiser: "M.Denoiser", example_image, example, dictionary, sink: Callable[[int, Dict[str, torch.Tensor]], None],

@@ -331,6 +331,50 @@ def training_loss_code(name: str) -> int:
 EVAL_STREAM_T, EVAL_STREAM_EPS = 3, 4
 
 
+# ---- generation (sampler.generate; gct2_diffusion_start / gct2_diffusion_step) --------------------------------------------------------
+# the Philox stream id of generation's noise: streams 1 and 2 are the train step's, 3 and 4 evaluation's
+GENERATE_STREAM = 5
+
+
+def sampling_timesteps(steps: int, num_steps: int) -> list:
+    """the K = num_steps timesteps a strided sampler visits out of 1..steps, ascending: ceil(i steps / K) for i = 1..K (integer
+    arithmetic).  Strictly increasing (steps / K >= 1), ends at `steps`; K = steps is 1..steps.  ValueError unless 1 <= K <= steps."""
+    for name, v in (("steps", steps), ("num_steps", num_steps)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"sampling_timesteps: {name} must be an int, got {v!r}")
+    steps, K = int(steps), int(num_steps)
+    if not 1 <= K <= steps:
+        raise ValueError(f"sampling_timesteps: num_steps must lie in 1..steps = 1..{steps}, got {K}")
+    return [-((-i * steps) // K) for i in range(1, K + 1)]
+
+
+def ddim_sigma2(a_t: float, a_prev: float, eta: float) -> float:
+    """the variance of the noise a sampling step from alpha a_t to alpha a_prev adds (Song et al., DDIM, eq. 16, squared):
+    eta^2 (1 - a_prev) / (1 - a_t) (1 - a_t / a_prev), clamped to [0, 1 - a_prev].  eta = 0 is the deterministic DDIM step, eta = 1
+    the DDPM posterior variance.  Python floats; ValueError for eta < 0 (or NaN)."""
+    eta, a_t, a_prev = float(eta), float(a_t), float(a_prev)
+    if not eta >= 0.0:
+        raise ValueError(f"ddim_sigma2: eta must be >= 0, got {eta!r}")
+    if eta == 0.0 or a_prev <= 0.0 or a_t >= 1.0:
+        return 0.0
+    s = eta * eta * (1.0 - a_prev) / (1.0 - a_t) * (1.0 - a_t / a_prev)
+    return min(max(s, 0.0), 1.0 - a_prev)
+
+
+def generate_offset(g: int, k: int, num_steps: int, per_image: int) -> int:
+    """the first element of stream GENERATE_STREAM that image g (its running index over the whole generation) reads in slot k: 0 is
+    the starting noise, 1..K the steps in sampling order.  Image g owns [g (K + 1) per_image, (g + 1) (K + 1) per_image): its noise
+    depends on g and the seed alone, not on the batch it is drawn in; consecutive images are generate_image_stride apart."""
+    K = int(num_steps)
+    if not (g >= 0 and 0 <= k <= K and per_image >= 1):
+        raise ValueError(f"generate_offset: image {g!r}, slot {k!r} of 0..{K}, per_image {per_image!r}")
+    return (int(g) * (K + 1) + int(k)) * int(per_image)
+
+
+def generate_image_stride(num_steps: int, per_image: int) -> int:
+    return (int(num_steps) + 1) * int(per_image)
+
+
 # ---- image metrics of evaluation (Keras compile(metrics=[...]); gct2_image_metrics) ---------------------------------------------------
 # "mse_x0": the mean squared error of the x0 estimate against the clean image; "psnr", "ssim": tf.image.psnr / tf.image.ssim [TF] of
 # the same pair.  Images live in [-1, 1): max_val = 2

@@ -446,6 +446,33 @@ enum { GCT2_SAMPLE_X = 0, GCT2_SAMPLE_EPS = 1, GCT2_SAMPLE_SCALED_EPS = 2, GCT2_
  * products at steps = 200) from Python floats and only then multiplies fp32 tensors by it; the library does the same on the host. */
 int gct2_diffusion_update(int mode, const float* pred, const float* fake, double alpha, double alpha_prev, float* x_theta,
                           float* eps_theta, size_t n, void* stream);
+/* ---- Denoiser.generate: one strided DDIM / DDPM sampling step (Song et al., "Denoising Diffusion Implicit Models", eq. 12) in ONE
+ * launch - gct2_diffusion_update, the clip of the x0 estimate and gct2_diffusion_mix to a_prev, without x_theta and eps_theta ever
+ * reaching memory.  B images of per_image = H*W*C fp32 elements each, contiguous: pred, fake_in, fake_out and (may be NULL) x0_out are
+ * [B * per_image]; out [B*H*W, C] (ldout) and (may be NULL) out2 (ldout2) are the network's input views in `dtype` as for
+ * gct2_diffusion_mix.  fake_out may equal fake_in.  mode: GCT2_SAMPLE_X, _EPS or _SCALED_EPS; GCT2_SAMPLE_ODE is GCT2_EINVAL (that
+ * network predicts one step back only).  a_t, a_prev, sigma2, clip are DOUBLES, like gct2_diffusion_update's.
+ * GCT2_EINVAL unless a_t in [0, 1) (> 0 for the epsilon modes), a_prev in [0, 1], 0 <= sigma2 and (1.f - (float)a_prev) - (float)sigma2 >= 0,
+ * per_image a multiple of C, ldout >= C, B * per_image < 2^31.
+ * Element i of image b, p = pred, f = fake_in; fp32, every operation rounded once (no fused multiply-add):
+ *   update   sa = (float)sqrt(a_t), sb = (float)sqrt(1 - a_t) (square roots in double, one cast each), then gct2_diffusion_update:
+ *              X: x = p, e = (f - sa p) / sb;   EPS: e = p, x = (f - p sb) / sa;   SCALED_EPS: e = p / sb, x = (f - p) / sa
+ *   clip     only when clip > 0: c = (float)clip, x = x < -c ? -c : (x > c ? c : x) (a NaN stays NaN), then e = (f - sa x) / sb in
+ *            every mode (eps re-derived from the clipped x0).  clip <= 0: x, e are gct2_diffusion_update's bits.
+ *   re-noise A = (float)a_prev, S = (float)sigma2, cx = sqrtf(A), ce = sqrtf((1.f - A) - S), cz = sqrtf(S);
+ *            S == 0: fake' = cx x + ce e, nothing is drawn - with clip <= 0 the bits of gct2_diffusion_update followed by
+ *            gct2_diffusion_mix(alpha = a_prev);  else fake' = (cx x + ce e) + cz z with z = the normal gct2_rng_normal writes for
+ *            element offset + b * image_stride + i of the stream (seed, stream_id), bit for bit, for any offset, image_stride and
+ *            per_image (an image may start and end inside a Philox counter; the counter index is 64 bits wide)
+ *   stores   fake_out[i] = fake'; out / out2: one rounding of fake' to `dtype` at row (b per_image + i) / C, channel (b per_image + i) % C,
+ *            nothing else in the row is touched; x0_out[i] = x if given. */
+int gct2_diffusion_step(int mode, int dtype, const float* pred, const float* fake_in, double a_t, double a_prev, double sigma2,
+                        double clip, uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t image_stride, float* fake_out,
+                        float* x0_out, void* out, int ldout, void* out2, int ldout2, int B, size_t per_image, int C, void* stream);
+/* the starting noise of the same sampler: fake_out[b * per_image + i] = z of stream element offset + b * image_stride + i (the rule
+ * above), also stored once rounded into out / out2.  Shapes and GCT2_EINVAL as for gct2_diffusion_step. */
+int gct2_diffusion_start(int dtype, uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t image_stride, float* fake_out,
+                         void* out, int ldout, void* out2, int ldout2, int B, size_t per_image, int C, void* stream);
 /* the four inputs of the reverse pass built from one inverted noise image eps [H,W,C] (train.py:416-431): out [4,H,W,C] =
  * eps | nearest-upsample x4 of avg_pool2d(eps, 4, 4) | tf.roll by 1 along H and W | per-pixel nearest of the K entries of
  * dictionary [H,W,K,C] (squared distance, first minimum).  H, W multiples of 4. */
