@@ -5,7 +5,7 @@ The directory name carries a hyphen (project convention); import it as `gan_clas
 """
 from . import _lib, build, data, engine, model, sampler, trainer_math # noqa: F401
 from .data import ImageDataset                    # noqa: F401
-from .sampler import generate, log_sample, make_log_sample  # noqa: F401
+from .sampler import encode, generate, log_sample, make_log_sample  # noqa: F401
 from ._lib import BF16, F16, F32, Gct2Error       # noqa: F401
 from .engine import Topology, UNetEngine          # noqa: F401
 from .model import (Adam, Block, Dense, Denoiser, DownShuffle, InverseTimeDecay, LambdaCallback, LossScaleOptimizer,  # noqa: F401
@@ -13,3 +13,4 @@ from .model import (Adam, Block, Dense, Denoiser, DownShuffle, InverseTimeDecay,
                     regularizers, sign_gradient)
 from .trainer_math import METRICS, NOISE_SCHEDULES, alpha_table, noise_table, ssim_window  # noqa: F401
 from .trainer_math import GENERATE_STREAM, ddim_sigma2, sampling_timesteps                 # noqa: F401
+from .trainer_math import check_mask, img2img_steps                                         # noqa: F401

@@ -687,6 +687,34 @@ int gct2_diffusion_start(int dtype, uint64_t seed, uint64_t stream_id, uint64_t 
   return pw_diffusion_start(dtype, seed, stream_id, offset, image_stride, fake_out, out, ldout, out2, ldout2, B, per_image, C, S(stream));
 }
 
+int gct2_diffusion_start_image(int dtype, const float* known, double a, uint64_t seed, uint64_t stream_id, uint64_t offset,
+                               uint64_t image_stride, float* fake_out, void* out, int ldout, void* out2, int ldout2, int B, size_t per_image,
+                               int C, void* stream) {
+  if (!known) return gct2_fail(GCT2_EINVAL, "diffusion_start_image: null pointer");
+  if (int rc = step_views_ok("diffusion_start_image", dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
+  if (!(a >= 0. && a <= 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_start_image: a must be in [0, 1]");
+  return pw_diffusion_start_image(dtype, known, a, seed, stream_id, offset, image_stride, fake_out, out, ldout, out2, ldout2, B, per_image, C,
+                                  S(stream));
+}
+
+int gct2_diffusion_step_masked(int mode, int dtype, const float* pred, const float* fake_in, const float* known, const float* mask, double a_t,
+                               double a_prev, double sigma2, double clip, uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t offset0,
+                               uint64_t image_stride, float* fake_out, float* x0_out, void* out, int ldout, void* out2, int ldout2, int B,
+                               size_t per_image, int C, void* stream) {
+  if (mode < GCT2_SAMPLE_X || mode > GCT2_SAMPLE_SCALED_EPS)
+    return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: mode %d (the ODE objective predicts one step back only: gct2_diffusion_update)", mode);
+  if (!pred || !fake_in || !known || !mask) return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: null pointer");
+  if (int rc = step_views_ok("diffusion_step_masked", dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
+  if (!(a_t >= 0. && a_t < 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: a_t must be in [0, 1)");
+  if (mode != GCT2_SAMPLE_X && !(a_t > 0.))
+    return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: this mode divides by sqrt(a_t): a_t must be > 0");
+  if (!(a_prev >= 0. && a_prev <= 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: a_prev must be in [0, 1]");
+  if (!(sigma2 >= 0.) || !((1.f - (float)a_prev) - (float)sigma2 >= 0.f))
+    return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: sigma2 must be in [0, 1 - a_prev]");
+  return pw_diffusion_step_masked(mode, dtype, pred, fake_in, known, mask, a_t, a_prev, sigma2, clip, seed, stream_id, offset, offset0,
+                                  image_stride, fake_out, x0_out, out, ldout, out2, ldout2, B, per_image, C, S(stream));
+}
+
 int gct2_noise_edits(const float* eps, const float* dictionary, int K, float* out, int H, int W, int C, void* stream) {
   if (!eps || !dictionary || !out) return gct2_fail(GCT2_EINVAL, "noise_edits: null pointer");
   if (H <= 0 || W <= 0 || C <= 0 || K <= 0 || (H & 3) || (W & 3))

@@ -495,6 +495,13 @@ int pw_diffusion_step(int mode, int dtype, const float* pred, const float* fake_
                       int ldout, void* out2, int ldout2, int B, size_t per_image, int C, hipStream_t s);
 int pw_diffusion_start(int dtype, uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t image_stride, float* fake_out, void* out,
                        int ldout, void* out2, int ldout2, int B, size_t per_image, int C, hipStream_t s);
+int pw_diffusion_step_masked(int mode, int dtype, const float* pred, const float* fake_in, const float* known, const float* mask, double a,
+                             double a_prev, double sigma2, double clip, uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t offset0,
+                             uint64_t image_stride, float* fake_out, float* x0_out, void* out, int ldout, void* out2, int ldout2, int B,
+                             size_t per_image, int C, hipStream_t s);
+int pw_diffusion_start_image(int dtype, const float* known, double a, uint64_t seed, uint64_t stream_id, uint64_t offset,
+                             uint64_t image_stride, float* fake_out, void* out, int ldout, void* out2, int ldout2, int B, size_t per_image,
+                             int C, hipStream_t s);
 int pw_noise_edits(const float* eps, const float* dict, int K, float* out, int H, int W, int C, hipStream_t s);
 int pw_image_prepare(const uint8_t* src, const int64_t* offsets, const int32_t* dims, float* dst, int B, int size, hipStream_t s);
 int pw_mse(const float* pred, const float* target, float* dpred, float* loss, float* partials, size_t n, const float* ls, hipStream_t s);

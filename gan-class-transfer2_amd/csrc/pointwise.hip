@@ -1001,6 +1001,137 @@ __global__ void diffusion_step_rng_kernel(const float* __restrict__ pred, const 
     }
   }
 }
+
+// ---- image-conditioned generation (include/gct2.h: gct2_diffusion_start_image, gct2_diffusion_step_masked) ----
+// STEP_START_IMAGE: no update, the value is h = cx known + ck z0 (diffusion_mix_kernel's arithmetic on the draw).  The masked step:
+// step_update's x and fake' (+ cz z when NOISE) become g, and the mask of the element's pixel selects between g and h (x and known for
+// x0_out).  Selects, not a blend, at m >= 1 and m <= 0: a NaN / infinity of g never reaches a kept pixel, a regenerated pixel has
+// diffusion_step's bits
+constexpr int STEP_START_IMAGE = -2;
+__device__ __forceinline__ float mask_select(float m, float g, float h) {
+#pragma clang fp contract(off)
+  return m >= 1.f ? g : (m <= 0.f ? h : m * g + (1.f - m) * h);
+}
+// one element: p, f, kn, m the loaded inputs, z0 / z the two draws.  Returns fake', x0 the composited estimate
+template <int MODE, bool NOISE>
+__device__ __forceinline__ float masked_element(float p, float f, float kn, float m, float z0, float z, const StepCoef& k, float ck, float& x0) {
+#pragma clang fp contract(off)
+  const float h = k.cx * kn + ck * z0;
+  if constexpr (MODE == STEP_START_IMAGE) {
+    x0 = kn;
+    return h;
+  } else {
+    float x;
+    float g = step_update<MODE>(p, f, k, x);
+    if constexpr (NOISE) g = g + k.cz * z;
+    x0 = mask_select(m, x, kn);
+    return mask_select(m, g, h);
+  }
+}
+// sigma^2 = 0 and the start from an image: only z0 is drawn.  The images as one flat range, one element per thread like
+// diffusion_step_kernel, z0 through philox_normal - a whole Philox call per element, and still the faster form: the masked step takes
+// 25.3 us against 28.8 us for a thread per Philox counter with 16-byte accesses, the start 20.3 against 26.1 us, at 64x128x128x3
+// (profiles/img2img_bench.json: consecutive lanes store their copies next to each other, as in diffusion_step_kernel).  Any offset0
+// and image_stride; fake_in may be fake_out (a thread reads its element, then writes it)
+template <typename T, int MODE>
+__global__ void diffusion_masked_flat_kernel(const float* __restrict__ pred, const float* fake_in, const float* __restrict__ known,
+                                             const float* __restrict__ mask, StepCoef k, float ck, uint64_t seed, uint64_t stream_id,
+                                             uint64_t offset0, uint64_t image_stride, float* fake_out, float* __restrict__ x0_out,
+                                             T* __restrict__ out, int ldout, T* __restrict__ out2, int ldout2, size_t n, uint32_t per_image,
+                                             int C) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const uint32_t b = (uint32_t)i / per_image, within = (uint32_t)i - b * per_image;      // n < 2^31 (checked by the entry point)
+    const float z0 = philox_normal(seed, stream_id, offset0 + (uint64_t)b * image_stride + within);
+    const uint32_t pix = (uint32_t)i / (uint32_t)C;
+    float x0, v;
+    if constexpr (MODE == STEP_START_IMAGE) {
+      v = masked_element<MODE, false>(0.f, 0.f, known[i], 0.f, z0, 0.f, k, ck, x0);
+    } else {
+      v = masked_element<MODE, false>(pred[i], fake_in[i], known[i], mask[pix], z0, 0.f, k, ck, x0);
+      if (x0_out) x0_out[i] = x0;
+    }
+    step_store<T>(v, i, pix, (int)((uint32_t)i - pix * (uint32_t)C), fake_out, out, ldout, out2, ldout2);
+  }
+}
+// with noise, two draws per element: diffusion_step_rng_kernel's scheme.  A thread owns one Philox counter of the STARTING noise (element
+// offset0 + b image_stride + i) and its up to four elements.  VEC (the launcher: offset, offset0, image_stride, per_image multiples of
+// 4, 16-byte aligned fp32 planes - what generate passes): the step's noise z sits at the same lanes of its own counter, one more Philox
+// call per thread, and the fp32 planes move as 16-byte accesses; the mask is read per element (a group of four spans up to three pixels
+// at C = 3); 28.1 us where the general form takes 76.1 us.  General form: z per element through philox_normal (the two draws may sit at
+// different lanes of their counters)
+template <typename T, int MODE, bool VEC>
+__global__ void diffusion_masked_rng_kernel(const float* __restrict__ pred, const float* fake_in, const float* __restrict__ known,
+                                            const float* __restrict__ mask, StepCoef k, float ck, uint64_t seed, uint64_t stream_id,
+                                            uint64_t offset, uint64_t offset0, uint64_t image_stride, float* fake_out,
+                                            float* __restrict__ x0_out, T* __restrict__ out, int ldout, T* __restrict__ out2, int ldout2,
+                                            int B, uint32_t per_image, int C) {
+#pragma clang fp contract(off)
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const uint64_t base0 = offset0 + (uint64_t)b * image_stride, end0 = base0 + per_image;
+    const uint64_t base = offset + (uint64_t)b * image_stride;
+    const uint64_t c0 = base0 >> 2;
+    const size_t ncounters = (size_t)(((end0 + 3) >> 2) - c0);
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < ncounters; t += stride) {
+      const uint64_t ctr = c0 + t;
+      uint32_t r[4];
+      philox4x32_10(seed, stream_id, ctr, r);
+      float n0[4];
+      box_muller(r[0], r[1], n0[0], n0[1]);
+      box_muller(r[2], r[3], n0[2], n0[3]);
+      if constexpr (VEC) {
+        const size_t i = (size_t)b * per_image + 4 * t;           // B * per_image < 2^31 (checked by the entry point)
+        float nz[4];
+        philox4x32_10(seed, stream_id, (base >> 2) + t, r);
+        box_muller(r[0], r[1], nz[0], nz[1]);
+        box_muller(r[2], r[3], nz[2], nz[3]);
+        const f32x4_t kn = *reinterpret_cast<const f32x4_t*>(known + i), p = *reinterpret_cast<const f32x4_t*>(pred + i),
+                      f = *reinterpret_cast<const f32x4_t*>(fake_in + i);
+        f32x4_t v, x4;
+        const uint32_t pix0 = (uint32_t)i / (uint32_t)C;
+        const int ch0 = (int)((uint32_t)i - pix0 * (uint32_t)C);
+        uint32_t pix = pix0;
+        int c = ch0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          float x0;
+          v[j] = masked_element<MODE, true>(p[j], f[j], kn[j], mask[pix], n0[j], nz[j], k, ck, x0);
+          x4[j] = x0;
+          if (++c == C) { c = 0; ++pix; }
+        }
+        if (x0_out) *reinterpret_cast<f32x4_t*>(x0_out + i) = x4;
+        *reinterpret_cast<f32x4_t*>(fake_out + i) = v;
+        pix = pix0;
+        c = ch0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          out[(size_t)pix * ldout + c] = from_f32<T>(v[j]);
+          if (out2) out2[(size_t)pix * ldout2 + c] = from_f32<T>(v[j]);
+          if (++c == C) { c = 0; ++pix; }
+        }
+      } else {
+        const uint64_t e0 = 4 * ctr;
+        const uint64_t first = e0 < base0 ? base0 : e0;             // (< end0: the counter range was cut to the image)
+        const uint32_t i0 = (uint32_t)b * per_image + (uint32_t)(first - base0);   // B * per_image < 2^31 (checked by the entry point)
+        uint32_t pix = i0 / (uint32_t)C, c = i0 - pix * (uint32_t)C;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const uint64_t e = e0 + j;
+          if (e < first || e >= end0) continue;
+          const uint32_t within = (uint32_t)(e - base0);
+          const size_t i = (size_t)b * per_image + within;
+          float x0;
+          const float v = masked_element<MODE, true>(pred[i], fake_in[i], known[i], mask[pix], n0[j], philox_normal(seed, stream_id, base + within),
+                                                     k, ck, x0);
+          if (x0_out) x0_out[i] = x0;
+          step_store<T>(v, i, pix, (int)c, fake_out, out, ldout, out2, ldout2);
+          if (++c == (uint32_t)C) { c = 0; ++pix; }
+        }
+      }
+    }
+  }
+}
 // the four noise variants of train.py:416-431 from one eps image [H,W,C]: out[0] = eps, out[1] = nearest-upsample x4 of the
 // 4x4 average pool, out[2] = rolled by one pixel along H and W, out[3] = per-pixel nearest entry of dictionary [H,W,K,C]
 __global__ void noise_edits_kernel(const float* __restrict__ eps, const float* __restrict__ dict, int K, float* __restrict__ out,
@@ -1789,6 +1920,54 @@ int pw_diffusion_start(int dtype, uint64_t seed, uint64_t sid, uint64_t off, uin
     else launch(std::false_type{});
   });
   return gct2_check_launch("diffusion_start");
+}
+int pw_diffusion_step_masked(int mode, int dtype, const float* pred, const float* fake_in, const float* known, const float* mask, double a,
+                             double a_prev, double sigma2, double clip, uint64_t seed, uint64_t sid, uint64_t off, uint64_t off0,
+                             uint64_t image_stride, float* fake_out, float* x0_out, void* out, int ldout, void* out2, int ldout2, int B,
+                             size_t per_image, int C, hipStream_t s) {
+  // pw_diffusion_step's coefficients, and ck of the kept region's forward process
+  const float A = (float)a_prev, S = (float)sigma2;
+  const StepCoef k = {(float)sqrt(a), (float)sqrt(1. - a), clip > 0. ? (float)clip : 0.f, sqrtf(A), sqrtf((1.f - A) - S), sqrtf(S)};
+  const float ck = sqrtf(1.f - A);
+  const size_t n = (size_t)B * per_image;
+  const bool vec = aligned16(pred) && aligned16(fake_in) && aligned16(known) && aligned16(fake_out) && aligned16(x0_out) && off % 4 == 0 &&
+                   off0 % 4 == 0 && image_stride % 4 == 0 && per_image % 4 == 0;
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    T *o = reinterpret_cast<T*>(out), *o2 = reinterpret_cast<T*>(out2);
+    auto launch = [&](auto m) {
+      constexpr int MODE = decltype(m)::value;
+      auto noisy = [&](auto v) {
+        hipLaunchKernelGGL((diffusion_masked_rng_kernel<T, MODE, decltype(v)::value>), step_rng_grid(B, per_image), dim3(256), 0, s, pred,
+                           fake_in, known, mask, k, ck, seed, sid, off, off0, image_stride, fake_out, x0_out, o, ldout, o2, ldout2, B,
+                           (uint32_t)per_image, C);
+      };
+      if (S == 0.f)
+        hipLaunchKernelGGL((diffusion_masked_flat_kernel<T, MODE>), dim3(blocks_for(n, 256)), dim3(256), 0, s, pred, fake_in, known, mask, k, ck,
+                           seed, sid, off0, image_stride, fake_out, x0_out, o, ldout, o2, ldout2, n, (uint32_t)per_image, C);
+      else if (vec) noisy(std::true_type{});
+      else noisy(std::false_type{});
+    };
+    if (mode == GCT2_SAMPLE_X) launch(std::integral_constant<int, GCT2_SAMPLE_X>{});
+    else if (mode == GCT2_SAMPLE_EPS) launch(std::integral_constant<int, GCT2_SAMPLE_EPS>{});
+    else launch(std::integral_constant<int, GCT2_SAMPLE_SCALED_EPS>{});
+  });
+  return gct2_check_launch("diffusion_step_masked");
+}
+int pw_diffusion_start_image(int dtype, const float* known, double a, uint64_t seed, uint64_t sid, uint64_t off, uint64_t image_stride,
+                             float* fake_out, void* out, int ldout, void* out2, int ldout2, int B, size_t per_image, int C, hipStream_t s) {
+  const float A = (float)a;                      // pw_diffusion_mix's coefficients
+  StepCoef k = {};
+  k.cx = sqrtf(A);
+  const float ck = sqrtf(1.f - A);
+  const size_t n = (size_t)B * per_image;
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((diffusion_masked_flat_kernel<T, STEP_START_IMAGE>), dim3(blocks_for(n, 256)), dim3(256), 0, s, (const float*)nullptr,
+                       (const float*)nullptr, known, (const float*)nullptr, k, ck, seed, sid, off, image_stride, fake_out, (float*)nullptr,
+                       reinterpret_cast<T*>(out), ldout, reinterpret_cast<T*>(out2), ldout2, n, (uint32_t)per_image, C);
+  });
+  return gct2_check_launch("diffusion_start_image");
 }
 int pw_noise_edits(const float* eps, const float* dict, int K, float* out, int H, int W, int C, hipStream_t s) {
   hipLaunchKernelGGL(noise_edits_kernel, dim3((H * W + 255) / 256), dim3(256), 0, s, eps, dict, K, out, H, W, C);

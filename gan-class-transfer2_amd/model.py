@@ -666,9 +666,16 @@ class Denoiser(Layer):
 
     def generate(self, n: int, **kw):
         """n new images from noise, fp32 [n,H,W,3] on the device: sampler.generate(self, n, ...) - strided DDIM sampling with
-        num_steps, eta, clip_denoised, seed, first_index, batch_size, timesteps, noise, use_ema, use_graph, return_steps, size"""
+        num_steps, eta, clip_denoised, seed, first_index, batch_size, timesteps, noise, use_ema, use_graph, return_steps, size; init, strength
+        and mask condition the run on images (image-to-image, inpainting)"""
         from .sampler import generate
         return generate(self, n, **kw)
+
+    def encode(self, images, **kw):
+        """images [n,H,W,3] into latents, fp32 [n,H,W,3] on the device: sampler.encode(self, images, ...) - strided DDIM inversion with
+        num_steps, timesteps, batch_size, use_ema, use_graph, start_eps; generate(noise=latent, timesteps=...) decodes them"""
+        from .sampler import encode
+        return encode(self, images, **kw)
 
     def _bind_variant_parameters(self) -> None:
         """the nested eager layers of self.middle share the variant engine's parameters: both enumerate the layers in forward

@@ -11,7 +11,11 @@ variants of train.py:20, 26, 27 - VariantEngine.predict, layer by layer.  Return
 
 `generate` - what the reference does not have: n new images from noise at a batch size and step count of the caller's choice,
 reproducible from a seed, with the two controls of every DDIM / DDPM sampler (eta, clipping of the x0 estimate).  Same network
-evaluations; the two pointwise launches of a step are one (gct2_diffusion_step), the state is `fake` alone."""
+evaluations; the two pointwise launches of a step are one (gct2_diffusion_step), the state is `fake` alone.  With `init=` it starts
+from an image noised to an intermediate timestep (gct2_diffusion_start_image), with `mask=` it regenerates only where the mask says so
+(gct2_diffusion_step_masked).
+
+`encode` - the inversion loop of log_sample as an API: a batch of images into latents over the same strided timesteps."""
 from __future__ import annotations
 
 import contextlib
@@ -29,6 +33,7 @@ from .engine import TORCH_DTYPE, UNetEngine
 from .trainer_math import alpha_dash            # train.py:85-93 on python floats, as in the reference
 from .trainer_math import check_noise_schedule, check_timesteps, noise_schedule_name
 from .trainer_math import GENERATE_STREAM, ddim_sigma2, generate_image_stride, generate_offset, sampling_timesteps
+from .trainer_math import check_mask, img2img_steps
 
 
 def sample_mode(predict_x: bool, predict_scaled_epsilon: bool, ordinary_differential_equation: bool) -> int:
@@ -158,6 +163,19 @@ class _Sampler:
         call("gct2_diffusion_step", self.mode, self.eng.dtype, pred.data_ptr(), fake.data_ptr(), a_t, a_prev, sigma2, clip, seed,
              GENERATE_STREAM, offset, image_stride, fake.data_ptr(), x0.data_ptr() if x0 is not None else None, *self.input_views(B),
              B, self.H * self.W * 3, 3, self._stream())
+
+    def start_image(self, B: int, known: torch.Tensor, alpha: float, seed: int, offset: int, image_stride: int, fake: torch.Tensor) -> None:
+        """fake = sqrt(alpha) known + sqrt(1 - alpha) (the normals `start` would write): gct2_diffusion_start_image"""
+        call("gct2_diffusion_start_image", self.eng.dtype, known.data_ptr(), alpha, seed, GENERATE_STREAM, offset, image_stride,
+             fake.data_ptr(), *self.input_views(B), B, self.H * self.W * 3, 3, self._stream())
+
+    def masked_step(self, B: int, pred: torch.Tensor, fake: torch.Tensor, known: torch.Tensor, mask: torch.Tensor, a_t: float, a_prev: float,
+                    sigma2: float, clip: float, seed: int, offset: int, offset0: int, image_stride: int, x0: Optional[torch.Tensor]) -> None:
+        """fused_step where mask >= 1, the known image re-noised to a_prev with its own starting noise (offset0) where mask <= 0, the
+        blend between: gct2_diffusion_step_masked, in place on fake; x0: the estimate composited with the known image the same way"""
+        call("gct2_diffusion_step_masked", self.mode, self.eng.dtype, pred.data_ptr(), fake.data_ptr(), known.data_ptr(), mask.data_ptr(),
+             a_t, a_prev, sigma2, clip, seed, GENERATE_STREAM, offset, offset0, image_stride, fake.data_ptr(),
+             x0.data_ptr() if x0 is not None else None, *self.input_views(B), B, self.H * self.W * 3, 3, self._stream())
 
     def update(self, pred: torch.Tensor, fake: torch.Tensor, alpha: float, alpha_prev: float, x: torch.Tensor, e: Optional[torch.Tensor]) -> None:
         """train.py:382-413 / 452-479 by mode (gct2_diffusion_update)."""
@@ -289,7 +307,7 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
              first_index: int = 0, batch_size: Optional[int] = None, timesteps=None, noise: Optional[torch.Tensor] = None,
              use_ema: bool = False, use_graph: bool = True, return_steps=(), size=None, predict_x: Optional[bool] = None,
              predict_scaled_epsilon: Optional[bool] = None, ordinary_differential_equation: Optional[bool] = None, noise_schedule=None,
-             alpha_dash_offset: Optional[float] = None):
+             alpha_dash_offset: Optional[float] = None, init: Optional[torch.Tensor] = None, strength: float = 1.0, mask=None):
     """n new images from noise: strided DDIM sampling (Song et al. 2021) over K = num_steps of the engine's `steps` timesteps
     (trainer_math.sampling_timesteps; None: all of them; or an explicit strictly increasing `timesteps` list within 1..steps), one
     network evaluation and ONE pointwise launch (gct2_diffusion_step) per step.  Returns fp32 [n,H,W,3] on the device: the x0 estimate
@@ -303,7 +321,15 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
     returned too - then the result is (images, {t: fp32 [n,H,W,3]}).  use_ema: every evaluation reads the parameter averages.
     The objective switches and the noise schedule resolve like log_sample's; the ODE objective is refused (its network predicts one
     step back only: striding and eta mean nothing there).  No training state moves: the RNG positions of training and evaluation,
-    optimizer slots, averages, loss scale and recorded plans stay as they are."""
+    optimizer slots, averages, loss scale and recorded plans stay as they are.
+    init [n,H,W,3] fp32: image-to-image.  The K' = trainer_math.img2img_steps(K, strength) last steps of the schedule run, from the image
+    noised to the K'-th timestep with its own starting noise (gct2_diffusion_start_image); the step at a timestep reads the Philox slot the
+    full run reads there, so strength only cuts the front of the schedule (strength = 1: all K steps, from the image noised to the
+    last timestep).  return_steps must then lie among the K' timesteps visited.
+    mask with init ([H,W], [n,H,W] or [n,H,W,1]; trainer_math.check_mask): inpainting.  1 regenerates a pixel, 0 keeps it: every step is
+    gct2_diffusion_step_masked, which pins the kept region to init re-noised with the image's starting noise; the result is the last
+    estimate composited with init (kept pixels are init's bits).  ValueError: mask or strength != 1 without init, init with noise, an
+    init of another shape than [n,H,W,3], strength outside (0, 1]."""
     eng = denoiser.ensure_engine()
     steps = int(eng.steps)
     if isinstance(n, bool) or not isinstance(n, int) or n < 1:
@@ -315,19 +341,7 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
     schedule, offset = _resolve_schedule(eng, noise_schedule, alpha_dash_offset)
     if not float(eta) >= 0.0:
         raise ValueError(f"generate: eta must be >= 0, got {eta!r}")
-    if timesteps is not None:
-        given = list(timesteps)
-        if not given or any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) for t in given) or given[0] < 1 or \
-                given[-1] > steps or any(b <= a for a, b in zip(given, given[1:])):
-            raise ValueError(f"generate: timesteps must be strictly increasing integers within 1..{steps}, got {given!r}")
-        taus = [int(t) for t in given]
-        if num_steps is not None and num_steps != len(taus):
-            raise ValueError(f"generate: num_steps = {num_steps!r} disagrees with the {len(taus)} timesteps given")
-    else:
-        try:
-            taus = sampling_timesteps(steps, steps if num_steps is None else num_steps)
-        except ValueError as e:
-            raise ValueError(f"generate: {e}") from None
+    taus = _taus("generate", steps, num_steps, timesteps)
     K = len(taus)
     if clip_denoised is None or clip_denoised is False:
         clip = 0.0
@@ -337,15 +351,33 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
         clip = float(clip_denoised)
         if not (clip > 0.0 and clip < float("inf")):
             raise ValueError(f"generate: clip_denoised must be True, False, None or a finite bound > 0, got {clip_denoised!r}")
-    if noise is not None:
+    if init is None and (mask is not None or strength != 1.0):
+        raise ValueError("generate: mask and strength condition the run on an image: they need init")
+    if init is not None and noise is not None:
+        raise ValueError("generate: init starts from an image noised with the drawn noise; noise cannot be given too")
+    try:
+        K_run = img2img_steps(K, strength)
+    except (TypeError, ValueError):
+        raise ValueError(f"generate: strength must lie in (0, 1], got {strength!r}") from None
+    if init is not None:
+        if not isinstance(init, torch.Tensor) or init.dim() != 4 or init.shape[0] != n or init.shape[3] != 3 or \
+                (size is not None and tuple(init.shape[1:3]) != _hw(size)):
+            raise ValueError(f"generate: init must be [n,H,W,3] = [{n},H,W,3], got {tuple(getattr(init, 'shape', ()))}")
+        H, W = int(init.shape[1]), int(init.shape[2])
+        if mask is not None:
+            try:
+                mask = check_mask(mask, n, H, W)
+            except ValueError as e:
+                raise ValueError(f"generate: {e}") from None
+    elif noise is not None:
         if noise.dim() != 4 or noise.shape[0] != n or noise.shape[3] != 3 or (size is not None and tuple(noise.shape[1:3]) != _hw(size)):
             raise ValueError(f"generate: noise must be [n,H,W,3] = [{n},H,W,3], got {tuple(noise.shape)}")
         H, W = int(noise.shape[1]), int(noise.shape[2])
     else:
         H, W = _hw(M.size if size is None else size)
     marks = tuple(return_steps)
-    if any(t not in taus for t in marks):
-        raise ValueError(f"generate: return_steps {list(marks)!r} must be among the timesteps sampled, {taus!r}")
+    if any(t not in taus[:K_run] for t in marks):
+        raise ValueError(f"generate: return_steps {list(marks)!r} must be among the timesteps sampled, {taus[:K_run]!r}")
     bs = min(n, 64) if batch_size is None else batch_size
     if isinstance(bs, bool) or not isinstance(bs, int) or bs < 1:
         raise ValueError(f"generate: batch_size must be a positive int, got {batch_size!r}")
@@ -375,19 +407,94 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
             B = min(bs, n - g0)
             if fake is None or fake.shape[0] != B:
                 fake = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev)
-            if noise is None:
-                S.start(B, seed, generate_offset(first_index + g0, 0, K, per_image), stride, fake)
+            off0 = generate_offset(first_index + g0, 0, K, per_image)
+            if init is not None:                # the image noised to the first timestep visited, with the noise `start` would write
+                known = init[g0:g0 + B].to(dev, torch.float32).contiguous()
+                keep = None if mask is None else mask[g0:g0 + B].to(dev).contiguous()
+                S.start_image(B, known, plan[K - K_run][1], seed, off0, stride, fake)
+            elif noise is None:
+                S.start(B, seed, off0, stride, fake)
             else:
                 z = noise[g0:g0 + B].to(dev, torch.float32).contiguous()
                 S.mix(B, z, z, 0.0, fake)       # alpha = 0: fake = 0 z + 1 z
             for k, (tau, a_t, a_prev, s2) in enumerate(plan, 1):
+                if k <= K - K_run:              # (init with strength < 1: the front of the schedule is cut, the slots keep their steps)
+                    continue
                 S.set_t(B, tau)
                 pred = S.evaluate(B)
                 x0 = out[g0:g0 + B] if k == K else (kept[tau][g0:g0 + B] if tau in kept else None)
-                S.fused_step(B, pred, fake, a_t, a_prev, s2, clip, seed, generate_offset(first_index + g0, k, K, per_image), stride, x0)
+                off = generate_offset(first_index + g0, k, K, per_image)
+                if init is not None and mask is not None:
+                    S.masked_step(B, pred, fake, known, keep, a_t, a_prev, s2, clip, seed, off, off0, stride, x0)
+                else:
+                    S.fused_step(B, pred, fake, a_t, a_prev, s2, clip, seed, off, stride, x0)
                 if k == K and tau in kept:
                     kept[tau][g0:g0 + B].copy_(x0)
     return (out, kept) if marks else out
+
+
+def encode(denoiser: "M.Denoiser", images: torch.Tensor, num_steps: Optional[int] = None, timesteps=None, batch_size: Optional[int] = None,
+           use_ema: bool = False, use_graph: bool = True, start_eps: Optional[torch.Tensor] = None, predict_x: Optional[bool] = None,
+           predict_scaled_epsilon: Optional[bool] = None, ordinary_differential_equation: Optional[bool] = None, noise_schedule=None,
+           alpha_dash_offset: Optional[float] = None) -> torch.Tensor:
+    """images [n,H,W,3] into latents, fp32 [n,H,W,3] on the device: the forward loop of log_sample (train.py:364-413), strided over the
+    K = num_steps timesteps of generate (trainer_math.sampling_timesteps, or an explicit `timesteps` list), ascending.  The state starts
+    as x_theta = eps_theta = images like the reference's (train.py:367), or eps_theta = start_eps [n,H,W,3]; every step is one
+    network evaluation at its timestep and one gct2_diffusion_step (sigma2 = 0, no clip) that re-mixes the new estimates at the NEXT
+    timestep's alpha; the last re-mixes at alpha = 0, which leaves eps_theta: the latent.  At num_steps = steps it is log_sample's
+    epsilon_theta.  generate(noise=latent, timesteps=...) decodes it, on this denoiser or on another one (class transfer).  batch_size
+    (default min(n, 64)) only cuts the work; the objective switches, the noise schedule and use_ema resolve like generate's, the ODE
+    objective is refused, and no training state moves."""
+    eng = denoiser.ensure_engine()
+    steps = int(eng.steps)
+    mode = _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_differential_equation)
+    if mode == SAMPLE_ODE:
+        raise ValueError("encode: the ordinary_differential_equation objective predicts the image one step back only; a strided "
+                         "inversion has no meaning there (log_sample runs its loop)")
+    schedule, offset = _resolve_schedule(eng, noise_schedule, alpha_dash_offset)
+    if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.shape[0] < 1 or images.shape[3] != 3:
+        raise ValueError(f"encode: images must be [n,H,W,3], got {tuple(getattr(images, 'shape', ()))}")
+    n, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    if start_eps is not None and (not isinstance(start_eps, torch.Tensor) or tuple(start_eps.shape) != tuple(images.shape)):
+        raise ValueError(f"encode: start_eps must have the images' shape {tuple(images.shape)}, got {tuple(getattr(start_eps, 'shape', ()))}")
+    taus = _taus("encode", steps, num_steps, timesteps)
+    K = len(taus)
+    bs = min(n, 64) if batch_size is None else batch_size
+    if isinstance(bs, bool) or not isinstance(bs, int) or bs < 1:
+        raise ValueError(f"encode: batch_size must be a positive int, got {batch_size!r}")
+    alpha = lambda t: float(alpha_dash(t, steps, schedule, offset))
+    dev = eng.device
+    with (eng.ema_weights() if use_ema else contextlib.nullcontext()):
+        eng.flush_deferred()
+        S = _Sampler(eng, steps, mode, H, W, use_graph, schedule, offset)
+        out = torch.empty(n, H, W, 3, dtype=torch.float32, device=dev)
+        for g0 in range(0, n, bs):
+            B = min(bs, n - g0)
+            x = images[g0:g0 + B].to(dev, torch.float32).contiguous()
+            e = x if start_eps is None else start_eps[g0:g0 + B].to(dev, torch.float32).contiguous()
+            fake = out[g0:g0 + B]               # (the state lives in the result's rows: the last step leaves the latent there)
+            S.mix(B, x, e, alpha(taus[0]), fake)
+            for k, tau in enumerate(taus):
+                S.set_t(B, tau)
+                pred = S.evaluate(B)
+                S.fused_step(B, pred, fake, alpha(tau), alpha(taus[k + 1]) if k + 1 < K else 0.0, 0.0, 0.0, 0, 0, 0, None)
+    return out
+
+
+def _taus(who: str, steps: int, num_steps, timesteps) -> list:
+    """the ascending timesteps of a strided run: an explicit list (checked), else sampling_timesteps(steps, num_steps or steps)"""
+    if timesteps is not None:
+        given = list(timesteps)
+        if not given or any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) for t in given) or given[0] < 1 or \
+                given[-1] > steps or any(b <= a for a, b in zip(given, given[1:])):
+            raise ValueError(f"{who}: timesteps must be strictly increasing integers within 1..{steps}, got {given!r}")
+        if num_steps is not None and num_steps != len(given):
+            raise ValueError(f"{who}: num_steps = {num_steps!r} disagrees with the {len(given)} timesteps given")
+        return [int(t) for t in given]
+    try:
+        return sampling_timesteps(steps, steps if num_steps is None else num_steps)
+    except ValueError as e:
+        raise ValueError(f"{who}: {e}") from None
 
 
 def _hw(size) -> Tuple[int, int]:

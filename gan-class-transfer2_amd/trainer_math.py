@@ -375,6 +375,32 @@ def generate_image_stride(num_steps: int, per_image: int) -> int:
     return (int(num_steps) + 1) * int(per_image)
 
 
+def img2img_steps(num_steps: int, strength: float) -> int:
+    """how many of the K = num_steps sampling steps an image-conditioned generate runs: min(K, max(1, int(K strength + 0.5))), the
+    steps at the low-noise end of the schedule (it starts at the K'-th timestep of sampling_timesteps).  strength = 1 is the whole
+    schedule; ValueError unless 0 < strength <= 1."""
+    K, strength = int(num_steps), float(strength)
+    if K < 1:
+        raise ValueError(f"img2img_steps: num_steps must be >= 1, got {num_steps!r}")
+    if not 0.0 < strength <= 1.0:
+        raise ValueError(f"img2img_steps: strength must lie in (0, 1], got {strength!r}")
+    return min(K, max(1, int(K * strength + 0.5)))
+
+
+def check_mask(mask, n: int, H: int, W: int) -> torch.Tensor:
+    """an inpainting mask as contiguous fp32 [n,H,W] (on the mask's device): [H,W] is shared by the n images, [n,H,W] and [n,H,W,1]
+    carry one per image.  1 regenerates a pixel, 0 keeps it (gct2_diffusion_step_masked).  ValueError for any other shape."""
+    m = torch.as_tensor(mask)
+    shape = tuple(m.shape)
+    if shape == (H, W):
+        m = m[None].expand(n, H, W)
+    elif shape == (n, H, W, 1):
+        m = m[..., 0]
+    elif shape != (n, H, W):
+        raise ValueError(f"mask must be [H,W], [n,H,W] or [n,H,W,1] = [{n},{H},{W}(,1)], got {list(shape)}")
+    return m.to(torch.float32).contiguous()
+
+
 # ---- image metrics of evaluation (Keras compile(metrics=[...]); gct2_image_metrics) ---------------------------------------------------
 # "mse_x0": the mean squared error of the x0 estimate against the clean image; "psnr", "ssim": tf.image.psnr / tf.image.ssim [TF] of
 # the same pair.  Images live in [-1, 1): max_val = 2

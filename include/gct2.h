@@ -473,6 +473,40 @@ int gct2_diffusion_step(int mode, int dtype, const float* pred, const float* fak
  * above), also stored once rounded into out / out2.  Shapes and GCT2_EINVAL as for gct2_diffusion_step. */
 int gct2_diffusion_start(int dtype, uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t image_stride, float* fake_out,
                          void* out, int ldout, void* out2, int ldout2, int B, size_t per_image, int C, void* stream);
+/* ---- image-conditioned generation (generate(init=, strength=, mask=)): the start from an image and the masked step, ONE launch each.
+ * Shapes, views and GCT2_EINVAL rules are gct2_diffusion_step's: B images of per_image = H*W*C fp32 elements, per_image a multiple of C,
+ * ldout >= C, B * per_image < 2^31, out / out2 the network's input views in `dtype`; fp32, every operation rounded once (no fused
+ * multiply-add); the bits do not depend on which kernel form runs (one element per thread where only the starting noise is drawn; with
+ * the step's noise a thread per Philox counter, 16-byte accesses when offset, offset0, image_stride and per_image are multiples of 4
+ * and the fp32 planes are 16-byte aligned).  known must not overlap fake_out.
+ *
+ * gct2_diffusion_start_image: the image `known` [B * per_image] noised to alpha a (a double in [0, 1], else GCT2_EINVAL):
+ *   A = (float)a, cx = sqrtf(A), ck = sqrtf(1.f - A);  fake_out[i] = cx known[i] + ck z0[i],  z0 = the normal gct2_rng_normal writes for
+ *   element offset + b * image_stride + i of the stream (seed, stream_id) - the bits of gct2_rng_normal followed by
+ *   gct2_diffusion_mix(x = known, e = z0, alpha = a), the once-rounded copies in out / out2 included.  known must not be NULL. */
+int gct2_diffusion_start_image(int dtype, const float* known, double a, uint64_t seed, uint64_t stream_id, uint64_t offset,
+                               uint64_t image_stride, float* fake_out, void* out, int ldout, void* out2, int ldout2, int B,
+                               size_t per_image, int C, void* stream);
+/* gct2_diffusion_step_masked: gct2_diffusion_step with the region a mask marks as kept pinned to a known image (inpainting).  The
+ * arguments of gct2_diffusion_step, plus known [B * per_image] fp32 (the clean image), mask [B * per_image / C] fp32 (one value per
+ * pixel, shared by its C channels; row (b per_image + i) / C) and offset0, the stream element of image 0's STARTING noise (images
+ * image_stride apart, like offset).  known and mask must not be NULL (GCT2_EINVAL); every other rule is gct2_diffusion_step's.
+ * Element i of image b, m = the mask value of its pixel:
+ *   x, e     gct2_diffusion_step's update and clip, bit for bit
+ *   g        gct2_diffusion_step's fake': cx x + ce e, plus cz z when (float)sigma2 != 0, z at element offset + b image_stride + i
+ *   h        cx known + ck z0,  ck = sqrtf(1.f - A),  z0 at element offset0 + b image_stride + i: the kept region follows the forward
+ *            process with the image's own fixed starting noise (what gct2_diffusion_start_image wrote at its alpha), so a run at
+ *            eta = 0 is deterministic
+ *   fake'    m >= 1 ? g : (m <= 0 ? h : m g + (1.f - m) h)
+ *   x0_out   m >= 1 ? x : (m <= 0 ? known : m x + (1.f - m) known)      (if given)
+ * The selects are deliberate: a fully masked pixel (m >= 1) has gct2_diffusion_step's bits, and a NaN or an infinity in g or x (the
+ * epsilon objectives divide by sqrt(a_t), 0.0025 at t = steps) never reaches a kept pixel (m <= 0).  Mask values outside [0, 1] act as
+ * 0 or 1 through the comparisons; a NaN mask value fails both and blends to NaN.  Stores as gct2_diffusion_step's; fake_out may equal
+ * fake_in.  Measured on one MI355X at 64x128x128x3, bf16 views: profiles/img2img_bench.json. */
+int gct2_diffusion_step_masked(int mode, int dtype, const float* pred, const float* fake_in, const float* known, const float* mask,
+                               double a_t, double a_prev, double sigma2, double clip, uint64_t seed, uint64_t stream_id, uint64_t offset,
+                               uint64_t offset0, uint64_t image_stride, float* fake_out, float* x0_out, void* out, int ldout, void* out2,
+                               int ldout2, int B, size_t per_image, int C, void* stream);
 /* the four inputs of the reverse pass built from one inverted noise image eps [H,W,C] (train.py:416-431): out [4,H,W,C] =
  * eps | nearest-upsample x4 of avg_pool2d(eps, 4, 4) | tf.roll by 1 along H and W | per-pixel nearest of the K entries of
  * dictionary [H,W,K,C] (squared distance, first minimum).  H, W multiples of 4. */
