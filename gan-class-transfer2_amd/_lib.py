@@ -80,6 +80,8 @@ SIGNATURES = {
     "gct2_diffusion_step_masked": [_i, _i, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _u64, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _i, _vp, _i, _i, _sz,
                                    _i, _vp],
     "gct2_diffusion_start_image": [_i, _vp, _d, _u64, _u64, _u64, _u64, _vp, _vp, _i, _vp, _i, _i, _sz, _i, _vp],
+    "gct2_diffusion_step_multistep": [_i, _i, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _i, _vp, _i, _i,
+                                      _sz, _i, _vp],
     "gct2_noise_edits": [_vp, _vp, _i, _vp, _i, _i, _i, _vp],
     "gct2_image_prepare": [_vp, _vp, _vp, _vp, _i, _i, _vp],
     "gct2_conv4s2_fwd": [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],

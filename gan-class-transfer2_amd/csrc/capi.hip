@@ -715,6 +715,25 @@ int gct2_diffusion_step_masked(int mode, int dtype, const float* pred, const flo
                                   image_stride, fake_out, x0_out, out, ldout, out2, ldout2, B, per_image, C, S(stream));
 }
 
+int gct2_diffusion_step_multistep(int mode, int dtype, const float* pred, const float* fake_in, const float* hist_in, const float* known,
+                                  const float* mask, double a_t, double a_prev, double c1, double clip, uint64_t seed, uint64_t stream_id,
+                                  uint64_t offset0, uint64_t image_stride, float* fake_out, float* hist_out, float* x0_out, void* out, int ldout,
+                                  void* out2, int ldout2, int B, size_t per_image, int C, void* stream) {
+  if (mode < GCT2_SAMPLE_X || mode > GCT2_SAMPLE_SCALED_EPS)
+    return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: mode %d (the ODE objective predicts one step back only: gct2_diffusion_update)", mode);
+  if (!pred || !fake_in) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: null pointer");
+  if (!known != !mask) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: known and mask go together (both NULL: the plain step)");
+  if (int rc = step_views_ok("diffusion_step_multistep", dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
+  if (!(a_t >= 0. && a_t < 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: a_t must be in [0, 1)");
+  if (mode != GCT2_SAMPLE_X && !(a_t > 0.))
+    return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: this mode divides by sqrt(a_t): a_t must be > 0");
+  if (!(a_prev >= 0. && a_prev <= 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: a_prev must be in [0, 1]");
+  if (!std::isfinite(c1) || !std::isfinite((float)c1)) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: c1 must be finite in fp32");
+  if ((float)c1 != 0.f && !hist_in) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: c1 != 0 extrapolates from hist_in, which is NULL");
+  return pw_diffusion_step_multistep(mode, dtype, pred, fake_in, hist_in, known, mask, a_t, a_prev, c1, clip, seed, stream_id, offset0,
+                                     image_stride, fake_out, hist_out, x0_out, out, ldout, out2, ldout2, B, per_image, C, S(stream));
+}
+
 int gct2_noise_edits(const float* eps, const float* dictionary, int K, float* out, int H, int W, int C, void* stream) {
   if (!eps || !dictionary || !out) return gct2_fail(GCT2_EINVAL, "noise_edits: null pointer");
   if (H <= 0 || W <= 0 || C <= 0 || K <= 0 || (H & 3) || (W & 3))

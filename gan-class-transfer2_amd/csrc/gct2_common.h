@@ -499,6 +499,10 @@ int pw_diffusion_step_masked(int mode, int dtype, const float* pred, const float
                              double a_prev, double sigma2, double clip, uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t offset0,
                              uint64_t image_stride, float* fake_out, float* x0_out, void* out, int ldout, void* out2, int ldout2, int B,
                              size_t per_image, int C, hipStream_t s);
+int pw_diffusion_step_multistep(int mode, int dtype, const float* pred, const float* fake_in, const float* hist_in, const float* known,
+                                const float* mask, double a, double a_prev, double c1, double clip, uint64_t seed, uint64_t stream_id,
+                                uint64_t offset0, uint64_t image_stride, float* fake_out, float* hist_out, float* x0_out, void* out, int ldout,
+                                void* out2, int ldout2, int B, size_t per_image, int C, hipStream_t s);
 int pw_diffusion_start_image(int dtype, const float* known, double a, uint64_t seed, uint64_t stream_id, uint64_t offset,
                              uint64_t image_stride, float* fake_out, void* out, int ldout, void* out2, int ldout2, int B, size_t per_image,
                              int C, hipStream_t s);

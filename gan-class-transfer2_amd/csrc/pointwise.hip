@@ -1054,6 +1054,58 @@ __global__ void diffusion_masked_flat_kernel(const float* __restrict__ pred, con
     step_store<T>(v, i, pix, (int)((uint32_t)i - pix * (uint32_t)C), fake_out, out, ldout, out2, ldout2);
   }
 }
+// ---- second-order multistep sampling (include/gct2.h: gct2_diffusion_step_multistep; DPM-Solver++ 2M, Lu et al. 2022) ----
+// step_update's clipped estimate x goes to the history plane as it is; the re-noising reads d = x + c (x - hist) in its place, with e
+// re-derived from d.  c == 0 (wave-uniform; the first step, and generate's last): step_update's own fake', the history is never read
+template <int MODE>
+__device__ __forceinline__ float multistep_element(float p, float f, const float* hist_in, size_t i, const StepCoef& k, float c, float& x) {
+#pragma clang fp contract(off)
+  const float g = step_update<MODE>(p, f, k, x);
+  if (c == 0.f) return g;
+  const float d = x + c * (x - hist_in[i]);
+  const float ed = (f - k.sa * d) / k.sb;
+  return k.cx * d + k.ce * ed;
+}
+// the plain form: diffusion_step_kernel's mapping, one element per thread.  fake_in may be fake_out and hist_in may be hist_out (a thread
+// reads its element of both, then writes it)
+template <typename T, int MODE>
+__global__ void diffusion_multistep_kernel(const float* __restrict__ pred, const float* fake_in, const float* hist_in, StepCoef k, float c,
+                                           float* fake_out, float* hist_out, float* __restrict__ x0_out, T* __restrict__ out, int ldout,
+                                           T* __restrict__ out2, int ldout2, size_t n, int C) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    float x;
+    const float v = multistep_element<MODE>(pred[i], fake_in[i], hist_in, i, k, c, x);
+    if (hist_out) hist_out[i] = x;
+    if (x0_out) x0_out[i] = x;
+    const uint32_t pix = (uint32_t)i / (uint32_t)C;               // B * per_image < 2^31 (checked by the entry point)
+    step_store<T>(v, i, pix, (int)((uint32_t)i - pix * (uint32_t)C), fake_out, out, ldout, out2, ldout2);
+  }
+}
+// the masked form: diffusion_masked_flat_kernel's mapping and per-element Philox draw of z0, masked_element's selects over the
+// extrapolated g
+template <typename T, int MODE>
+__global__ void diffusion_multistep_masked_kernel(const float* __restrict__ pred, const float* fake_in, const float* hist_in,
+                                                  const float* __restrict__ known, const float* __restrict__ mask, StepCoef k, float ck, float c,
+                                                  uint64_t seed, uint64_t stream_id, uint64_t offset0, uint64_t image_stride, float* fake_out,
+                                                  float* hist_out, float* __restrict__ x0_out, T* __restrict__ out, int ldout,
+                                                  T* __restrict__ out2, int ldout2, size_t n, uint32_t per_image, int C) {
+#pragma clang fp contract(off)
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const uint32_t b = (uint32_t)i / per_image, within = (uint32_t)i - b * per_image;      // n < 2^31 (checked by the entry point)
+    const float z0 = philox_normal(seed, stream_id, offset0 + (uint64_t)b * image_stride + within);
+    const uint32_t pix = (uint32_t)i / (uint32_t)C;
+    const float kn = known[i], m = mask[pix];
+    float x;
+    const float g = multistep_element<MODE>(pred[i], fake_in[i], hist_in, i, k, c, x);
+    const float h = k.cx * kn + ck * z0;
+    if (hist_out) hist_out[i] = x;
+    if (x0_out) x0_out[i] = mask_select(m, x, kn);
+    step_store<T>(mask_select(m, g, h), i, pix, (int)((uint32_t)i - pix * (uint32_t)C), fake_out, out, ldout, out2, ldout2);
+  }
+}
+
 // with noise, two draws per element: diffusion_step_rng_kernel's scheme.  A thread owns one Philox counter of the STARTING noise (element
 // offset0 + b image_stride + i) and its up to four elements.  VEC (the launcher: offset, offset0, image_stride, per_image multiples of
 // 4, 16-byte aligned fp32 planes - what generate passes): the step's noise z sits at the same lanes of its own counter, one more Philox
@@ -1953,6 +2005,34 @@ int pw_diffusion_step_masked(int mode, int dtype, const float* pred, const float
     else launch(std::integral_constant<int, GCT2_SAMPLE_SCALED_EPS>{});
   });
   return gct2_check_launch("diffusion_step_masked");
+}
+int pw_diffusion_step_multistep(int mode, int dtype, const float* pred, const float* fake_in, const float* hist_in, const float* known,
+                                const float* mask, double a, double a_prev, double c1, double clip, uint64_t seed, uint64_t sid, uint64_t off0,
+                                uint64_t image_stride, float* fake_out, float* hist_out, float* x0_out, void* out, int ldout, void* out2,
+                                int ldout2, int B, size_t per_image, int C, hipStream_t s) {
+  // pw_diffusion_step's coefficients at sigma2 = 0, pw_diffusion_step_masked's ck
+  const float A = (float)a_prev, c = (float)c1;
+  const StepCoef k = {(float)sqrt(a), (float)sqrt(1. - a), clip > 0. ? (float)clip : 0.f, sqrtf(A), sqrtf(1.f - A), 0.f};
+  const float ck = sqrtf(1.f - A);
+  const size_t n = (size_t)B * per_image;
+  with_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    T *o = reinterpret_cast<T*>(out), *o2 = reinterpret_cast<T*>(out2);
+    auto launch = [&](auto m) {
+      constexpr int MODE = decltype(m)::value;
+      if (known)
+        hipLaunchKernelGGL((diffusion_multistep_masked_kernel<T, MODE>), dim3(blocks_for(n, 256)), dim3(256), 0, s, pred, fake_in, hist_in, known,
+                           mask, k, ck, c, seed, sid, off0, image_stride, fake_out, hist_out, x0_out, o, ldout, o2, ldout2, n,
+                           (uint32_t)per_image, C);
+      else
+        hipLaunchKernelGGL((diffusion_multistep_kernel<T, MODE>), dim3(blocks_for(n, 256)), dim3(256), 0, s, pred, fake_in, hist_in, k, c,
+                           fake_out, hist_out, x0_out, o, ldout, o2, ldout2, n, C);
+    };
+    if (mode == GCT2_SAMPLE_X) launch(std::integral_constant<int, GCT2_SAMPLE_X>{});
+    else if (mode == GCT2_SAMPLE_EPS) launch(std::integral_constant<int, GCT2_SAMPLE_EPS>{});
+    else launch(std::integral_constant<int, GCT2_SAMPLE_SCALED_EPS>{});
+  });
+  return gct2_check_launch("diffusion_step_multistep");
 }
 int pw_diffusion_start_image(int dtype, const float* known, double a, uint64_t seed, uint64_t sid, uint64_t off, uint64_t image_stride,
                              float* fake_out, void* out, int ldout, void* out2, int ldout2, int B, size_t per_image, int C, hipStream_t s) {

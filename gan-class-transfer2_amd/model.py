@@ -667,13 +667,15 @@ class Denoiser(Layer):
     def generate(self, n: int, **kw):
         """n new images from noise, fp32 [n,H,W,3] on the device: sampler.generate(self, n, ...) - strided DDIM sampling with
         num_steps, eta, clip_denoised, seed, first_index, batch_size, timesteps, noise, use_ema, use_graph, return_steps, size; init, strength
-        and mask condition the run on images (image-to-image, inpainting)"""
+        and mask condition the run on images (image-to-image, inpainting); solver="dpm2m" is the second-order multistep solver
+        (DPM-Solver++ 2M: one gct2_diffusion_step_multistep launch per step, eta = 0 only), "ddim" the default"""
         from .sampler import generate
         return generate(self, n, **kw)
 
     def encode(self, images, **kw):
         """images [n,H,W,3] into latents, fp32 [n,H,W,3] on the device: sampler.encode(self, images, ...) - strided DDIM inversion with
-        num_steps, timesteps, batch_size, use_ema, use_graph, start_eps; generate(noise=latent, timesteps=...) decodes them"""
+        num_steps, timesteps, batch_size, use_ema, use_graph, start_eps; generate(noise=latent, timesteps=...) decodes them;
+        solver="dpm2m" runs the second-order multistep update up the schedule, "ddim" is the default"""
         from .sampler import encode
         return encode(self, images, **kw)
 

@@ -13,7 +13,8 @@ variants of train.py:20, 26, 27 - VariantEngine.predict, layer by layer.  Return
 reproducible from a seed, with the two controls of every DDIM / DDPM sampler (eta, clipping of the x0 estimate).  Same network
 evaluations; the two pointwise launches of a step are one (gct2_diffusion_step), the state is `fake` alone.  With `init=` it starts
 from an image noised to an intermediate timestep (gct2_diffusion_start_image), with `mask=` it regenerates only where the mask says so
-(gct2_diffusion_step_masked).
+(gct2_diffusion_step_masked).  With `solver="dpm2m"` every step is the second-order multistep update instead (DPM-Solver++ 2M:
+gct2_diffusion_step_multistep, one more fp32 plane that carries the previous step's estimate); `encode` takes the same switch.
 
 `encode` - the inversion loop of log_sample as an API: a batch of images into latents over the same strided timesteps."""
 from __future__ import annotations
@@ -34,6 +35,7 @@ from .trainer_math import alpha_dash            # train.py:85-93 on python float
 from .trainer_math import check_noise_schedule, check_timesteps, noise_schedule_name
 from .trainer_math import GENERATE_STREAM, ddim_sigma2, generate_image_stride, generate_offset, sampling_timesteps
 from .trainer_math import check_mask, img2img_steps
+from .trainer_math import SOLVERS, multistep_coefficient
 
 
 def sample_mode(predict_x: bool, predict_scaled_epsilon: bool, ordinary_differential_equation: bool) -> int:
@@ -177,6 +179,16 @@ class _Sampler:
              a_t, a_prev, sigma2, clip, seed, GENERATE_STREAM, offset, offset0, image_stride, fake.data_ptr(),
              x0.data_ptr() if x0 is not None else None, *self.input_views(B), B, self.H * self.W * 3, 3, self._stream())
 
+    def multistep_step(self, B: int, pred: torch.Tensor, fake: torch.Tensor, hist: torch.Tensor, known: Optional[torch.Tensor],
+                       mask: Optional[torch.Tensor], a_t: float, a_prev: float, c1: float, clip: float, seed: int, offset0: int,
+                       image_stride: int, x0: Optional[torch.Tensor]) -> None:
+        """fused_step at sigma2 = 0 (masked_step with known and mask) re-noising the estimate extrapolated by c1 from the one in hist, which
+        then takes this step's: gct2_diffusion_step_multistep, in place on fake and hist"""
+        call("gct2_diffusion_step_multistep", self.mode, self.eng.dtype, pred.data_ptr(), fake.data_ptr(), hist.data_ptr(),
+             known.data_ptr() if known is not None else None, mask.data_ptr() if mask is not None else None, a_t, a_prev, c1, clip, seed,
+             GENERATE_STREAM, offset0, image_stride, fake.data_ptr(), hist.data_ptr(), x0.data_ptr() if x0 is not None else None,
+             *self.input_views(B), B, self.H * self.W * 3, 3, self._stream())
+
     def update(self, pred: torch.Tensor, fake: torch.Tensor, alpha: float, alpha_prev: float, x: torch.Tensor, e: Optional[torch.Tensor]) -> None:
         """train.py:382-413 / 452-479 by mode (gct2_diffusion_update)."""
         call("gct2_diffusion_update", self.mode, pred.data_ptr(), fake.data_ptr(), alpha, alpha_prev, x.data_ptr(),
@@ -307,7 +319,8 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
              first_index: int = 0, batch_size: Optional[int] = None, timesteps=None, noise: Optional[torch.Tensor] = None,
              use_ema: bool = False, use_graph: bool = True, return_steps=(), size=None, predict_x: Optional[bool] = None,
              predict_scaled_epsilon: Optional[bool] = None, ordinary_differential_equation: Optional[bool] = None, noise_schedule=None,
-             alpha_dash_offset: Optional[float] = None, init: Optional[torch.Tensor] = None, strength: float = 1.0, mask=None):
+             alpha_dash_offset: Optional[float] = None, init: Optional[torch.Tensor] = None, strength: float = 1.0, mask=None,
+             solver: str = "ddim"):
     """n new images from noise: strided DDIM sampling (Song et al. 2021) over K = num_steps of the engine's `steps` timesteps
     (trainer_math.sampling_timesteps; None: all of them; or an explicit strictly increasing `timesteps` list within 1..steps), one
     network evaluation and ONE pointwise launch (gct2_diffusion_step) per step.  Returns fp32 [n,H,W,3] on the device: the x0 estimate
@@ -329,9 +342,20 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
     mask with init ([H,W], [n,H,W] or [n,H,W,1]; trainer_math.check_mask): inpainting.  1 regenerates a pixel, 0 keeps it: every step is
     gct2_diffusion_step_masked, which pins the kept region to init re-noised with the image's starting noise; the result is the last
     estimate composited with init (kept pixels are init's bits).  ValueError: mask or strength != 1 without init, init with noise, an
-    init of another shape than [n,H,W,3], strength outside (0, 1]."""
+    init of another shape than [n,H,W,3], strength outside (0, 1].
+    solver: "ddim" (the default: the calls and the bits described above) or "dpm2m", the second-order multistep solver of the
+    probability-flow ODE (DPM-Solver++ 2M, Lu et al. 2022): every step is ONE gct2_diffusion_step_multistep launch, which re-noises the
+    estimate extrapolated from the previous step's, D = x0 + c1 (x0 - x0_prev) with c1 = trainer_math.multistep_coefficient(alpha of the
+    timestep evaluated before, a_t, a_prev); the previous estimate lives in one more fp32 plane per batch.  No extra network evaluation.
+    c1 = 0 (the DDIM step's bits) at the first step run - of every batch, also after a strength cut - and at the last, whose result is
+    its own x0 estimate; so num_steps <= 2 is solver="ddim" bit for bit.  Deterministic: eta != 0 is a ValueError.  return_steps holds
+    the network's (clipped, with mask composited) estimates, not the extrapolated ones.  An unknown name is a ValueError.  What the
+    solver does to sample quality on a trained network is not measured in this project; its order of accuracy as an integrator is
+    (tests/test_multistep_kernels_gpu.py)."""
     eng = denoiser.ensure_engine()
     steps = int(eng.steps)
+    if solver not in SOLVERS:
+        raise ValueError(f"generate: solver must be one of {SOLVERS!r}, got {solver!r}")
     if isinstance(n, bool) or not isinstance(n, int) or n < 1:
         raise ValueError(f"generate: n must be a positive int, got {n!r}")
     mode = _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_differential_equation)
@@ -341,6 +365,9 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
     schedule, offset = _resolve_schedule(eng, noise_schedule, alpha_dash_offset)
     if not float(eta) >= 0.0:
         raise ValueError(f"generate: eta must be >= 0, got {eta!r}")
+    multistep = solver == "dpm2m"
+    if multistep and float(eta) != 0.0:
+        raise ValueError(f"generate: solver 'dpm2m' is deterministic (it integrates the probability-flow ODE): eta must be 0, got {eta!r}")
     taus = _taus("generate", steps, num_steps, timesteps)
     K = len(taus)
     if clip_denoised is None or clip_denoised is False:
@@ -395,6 +422,9 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
         # the kernel forms sqrt((1 - a_prev) - sigma2) in fp32: a sigma2 clamped at 1 - a_prev in double must not pass it there
         lim = float(np.float32(1.0) - np.float32(a_prev))
         plan.append((tau, a_t, a_prev, lim if float(np.float32(s2)) > lim else s2))
+    # solver="dpm2m": c1 per step.  0 at the first step run (no history yet) and at the last (its re-noised state is never read, the
+    # result is that step's own estimate); between them the estimate of the step before extrapolates
+    c1s = [0.0 if k <= K - K_run or k == K - 1 else multistep_coefficient(plan[k - 1][1], plan[k][1], plan[k][2]) for k in range(K)]
 
     dev = eng.device
     with (eng.ema_weights() if use_ema else contextlib.nullcontext()):
@@ -407,7 +437,9 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
             B = min(bs, n - g0)
             if fake is None or fake.shape[0] != B:
                 fake = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev)
+                hist = torch.empty_like(fake) if multistep else None       # the estimate of the step before (first read at c1 != 0)
             off0 = generate_offset(first_index + g0, 0, K, per_image)
+            known = keep = None
             if init is not None:                # the image noised to the first timestep visited, with the noise `start` would write
                 known = init[g0:g0 + B].to(dev, torch.float32).contiguous()
                 keep = None if mask is None else mask[g0:g0 + B].to(dev).contiguous()
@@ -424,7 +456,10 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
                 pred = S.evaluate(B)
                 x0 = out[g0:g0 + B] if k == K else (kept[tau][g0:g0 + B] if tau in kept else None)
                 off = generate_offset(first_index + g0, k, K, per_image)
-                if init is not None and mask is not None:
+                if multistep:
+                    S.multistep_step(B, pred, fake, hist, known if keep is not None else None, keep, a_t, a_prev, c1s[k - 1], clip, seed, off0,
+                                     stride, x0)
+                elif init is not None and mask is not None:
                     S.masked_step(B, pred, fake, known, keep, a_t, a_prev, s2, clip, seed, off, off0, stride, x0)
                 else:
                     S.fused_step(B, pred, fake, a_t, a_prev, s2, clip, seed, off, stride, x0)
@@ -436,7 +471,7 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
 def encode(denoiser: "M.Denoiser", images: torch.Tensor, num_steps: Optional[int] = None, timesteps=None, batch_size: Optional[int] = None,
            use_ema: bool = False, use_graph: bool = True, start_eps: Optional[torch.Tensor] = None, predict_x: Optional[bool] = None,
            predict_scaled_epsilon: Optional[bool] = None, ordinary_differential_equation: Optional[bool] = None, noise_schedule=None,
-           alpha_dash_offset: Optional[float] = None) -> torch.Tensor:
+           alpha_dash_offset: Optional[float] = None, solver: str = "ddim") -> torch.Tensor:
     """images [n,H,W,3] into latents, fp32 [n,H,W,3] on the device: the forward loop of log_sample (train.py:364-413), strided over the
     K = num_steps timesteps of generate (trainer_math.sampling_timesteps, or an explicit `timesteps` list), ascending.  The state starts
     as x_theta = eps_theta = images like the reference's (train.py:367), or eps_theta = start_eps [n,H,W,3]; every step is one
@@ -444,9 +479,15 @@ def encode(denoiser: "M.Denoiser", images: torch.Tensor, num_steps: Optional[int
     timestep's alpha; the last re-mixes at alpha = 0, which leaves eps_theta: the latent.  At num_steps = steps it is log_sample's
     epsilon_theta.  generate(noise=latent, timesteps=...) decodes it, on this denoiser or on another one (class transfer).  batch_size
     (default min(n, 64)) only cuts the work; the objective switches, the noise schedule and use_ema resolve like generate's, the ODE
-    objective is refused, and no training state moves."""
+    objective is refused, and no training state moves.
+    solver: "ddim" (the default: the calls and the bits described above) or "dpm2m": every step is one gct2_diffusion_step_multistep
+    launch, the same second-order multistep update as generate's run up the schedule - c1 = trainer_math.multistep_coefficient(alpha of
+    the timestep evaluated before, alpha(tau), alpha of the next timestep), 0 at the first step of every batch and, by the helper itself,
+    at the last (it goes to alpha 0).  An unknown name is a ValueError."""
     eng = denoiser.ensure_engine()
     steps = int(eng.steps)
+    if solver not in SOLVERS:
+        raise ValueError(f"encode: solver must be one of {SOLVERS!r}, got {solver!r}")
     mode = _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_differential_equation)
     if mode == SAMPLE_ODE:
         raise ValueError("encode: the ordinary_differential_equation objective predicts the image one step back only; a strided "
@@ -468,16 +509,24 @@ def encode(denoiser: "M.Denoiser", images: torch.Tensor, num_steps: Optional[int
         eng.flush_deferred()
         S = _Sampler(eng, steps, mode, H, W, use_graph, schedule, offset)
         out = torch.empty(n, H, W, 3, dtype=torch.float32, device=dev)
+        hist = None
         for g0 in range(0, n, bs):
             B = min(bs, n - g0)
             x = images[g0:g0 + B].to(dev, torch.float32).contiguous()
             e = x if start_eps is None else start_eps[g0:g0 + B].to(dev, torch.float32).contiguous()
             fake = out[g0:g0 + B]               # (the state lives in the result's rows: the last step leaves the latent there)
             S.mix(B, x, e, alpha(taus[0]), fake)
+            if solver == "dpm2m" and (hist is None or hist.shape[0] != B):
+                hist = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev)
             for k, tau in enumerate(taus):
                 S.set_t(B, tau)
                 pred = S.evaluate(B)
-                S.fused_step(B, pred, fake, alpha(tau), alpha(taus[k + 1]) if k + 1 < K else 0.0, 0.0, 0.0, 0, 0, 0, None)
+                a_t, a_next = alpha(tau), alpha(taus[k + 1]) if k + 1 < K else 0.0
+                if solver == "dpm2m":
+                    c1 = multistep_coefficient(alpha(taus[k - 1]) if k else None, a_t, a_next)
+                    S.multistep_step(B, pred, fake, hist, None, None, a_t, a_next, c1, 0.0, 0, 0, 0, None)
+                else:
+                    S.fused_step(B, pred, fake, a_t, a_next, 0.0, 0.0, 0, 0, 0, None)
     return out
 
 

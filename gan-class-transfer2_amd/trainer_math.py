@@ -387,6 +387,38 @@ def img2img_steps(num_steps: int, strength: float) -> int:
     return min(K, max(1, int(K * strength + 0.5)))
 
 
+# ---- second-order multistep sampling (generate / encode with solver="dpm2m"; gct2_diffusion_step_multistep) ----------------------------
+SOLVERS = ("ddim", "dpm2m")
+
+
+def half_log_snr(a: float) -> float:
+    """lambda of DPM-Solver (Lu et al. 2022): log(alpha / sigma) = 0.5 log(a / (1 - a)) at the cumulative alpha a, from Python floats.
+    -inf at a <= 0, +inf at a >= 1."""
+    a = float(a)
+    if a <= 0.0:
+        return -math.inf
+    if a >= 1.0:
+        return math.inf
+    return 0.5 * math.log(a / (1.0 - a))
+
+
+def multistep_coefficient(a_before: Optional[float], a_t: float, a_prev: float) -> float:
+    """c1 of gct2_diffusion_step_multistep for the step from alpha a_t to alpha a_prev, when the step before was evaluated at alpha
+    a_before: with h = lambda(a_prev) - lambda(a_t) and h_prev = lambda(a_t) - lambda(a_before) (half_log_snr), h / (2 h_prev) - the
+    1 / (2 r) of DPM-Solver++ 2M, r = h_prev / h.  0.0 without history (a_before None), where one of the three lambdas is not finite
+    (alpha 0 or 1: the ends of the process) and at h_prev == 0.  Either direction: descending alphas (generate) and ascending ones
+    (encode) both give c1 > 0 on a monotone schedule."""
+    if a_before is None:
+        return 0.0
+    l_before, l_t, l_prev = half_log_snr(a_before), half_log_snr(a_t), half_log_snr(a_prev)
+    if not (math.isfinite(l_before) and math.isfinite(l_t) and math.isfinite(l_prev)):
+        return 0.0
+    h, h_prev = l_prev - l_t, l_t - l_before
+    if h_prev == 0.0:
+        return 0.0
+    return h / (2.0 * h_prev)
+
+
 def check_mask(mask, n: int, H: int, W: int) -> torch.Tensor:
     """an inpainting mask as contiguous fp32 [n,H,W] (on the mask's device): [H,W] is shared by the n images, [n,H,W] and [n,H,W,1]
     carry one per image.  1 regenerates a pixel, 0 keeps it (gct2_diffusion_step_masked).  ValueError for any other shape."""

@@ -507,6 +507,35 @@ int gct2_diffusion_step_masked(int mode, int dtype, const float* pred, const flo
                                double a_t, double a_prev, double sigma2, double clip, uint64_t seed, uint64_t stream_id, uint64_t offset,
                                uint64_t offset0, uint64_t image_stride, float* fake_out, float* x0_out, void* out, int ldout, void* out2,
                                int ldout2, int B, size_t per_image, int C, void* stream);
+/* gct2_diffusion_step_multistep: one second-order multistep step of the probability-flow ODE (DPM-Solver++ 2M, Lu et al. 2022, "DPM-Solver++:
+ * Fast Solver for Guided Sampling of Diffusion Probabilistic Models") in ONE launch - gct2_diffusion_step at sigma2 = 0 with the x0 estimate
+ * of the re-noising replaced by D = x + c (x - hist_in), the estimate extrapolated from the one of the step before.  c1 is a host scalar
+ * (trainer_math.multistep_coefficient: h / (2 h_prev) in half-log-SNR), hist_in / hist_out one fp32 plane [B * per_image] carried
+ * between steps.  There is no sigma2: the solver is deterministic.
+ * Shapes, views, alignment freedom and GCT2_EINVAL rules are gct2_diffusion_step's: modes X / EPS / SCALED_EPS (ODE refused), a_t in
+ * [0, 1) (> 0 for the epsilon modes), a_prev in [0, 1], per_image a multiple of C, ldout >= C, B * per_image < 2^31.
+ * known and mask are both NULL (the plain step) or both non-NULL (the masked step: gct2_diffusion_step_masked's known [B * per_image]
+ * and mask [B * per_image / C]); one without the other is GCT2_EINVAL.  seed, stream_id, offset0 and image_stride are read only in the
+ * masked form, for the starting noise z0, with exactly the meaning they have in gct2_diffusion_step_masked.
+ * c1 must be finite (also once cast to fp32), else GCT2_EINVAL; hist_in must not be NULL when (float)c1 != 0, else GCT2_EINVAL.
+ * Aliasing: hist_out may be NULL, hist_out may equal hist_in, fake_out may equal fake_in: a thread reads its element before it writes
+ * it.  x0_out (may be NULL) and known overlap nothing that is written.
+ * Element i of image b, fp32, every operation rounded once (no fused multiply-add):
+ *   x, e        gct2_diffusion_step's update and clip, bit for bit
+ *   hist_out[i] = x: the clipped network estimate, not yet extrapolated and not yet composited
+ *   c = (float)c1 == 0 (wave-uniform):  g = cx x + ce e,  cx = sqrtf(A), ce = sqrtf(1.f - A), A = (float)a_prev: the bits of
+ *               gct2_diffusion_step at sigma2 = 0.  hist_in is never read: NaN / infinity garbage there (or NULL) is harmless
+ *   c != 0:     d = x + c * (x - hist_in[i]);  ed = (fake_in[i] - sa d) / sb;  g = cx d + ce ed.  d is not clipped again
+ *   plain form  fake' = g, x0_out = x
+ *   masked form fake' and x0_out are gct2_diffusion_step_masked's selects over g, h = cx known + ck z0, x and known, bit for bit:
+ *               fake' = m >= 1 ? g : (m <= 0 ? h : m g + (1.f - m) h),  x0_out = m >= 1 ? x : (m <= 0 ? known : m x + (1.f - m) known);
+ *               a NaN or an infinity of g or x never reaches a kept pixel (m <= 0)
+ *   stores      gct2_diffusion_step's: fake_out[i] = fake', one rounding of fake' to `dtype` in out / out2
+ * Measured on one MI355X at 64x128x128x3, bf16 views: profiles/multistep_bench.json. */
+int gct2_diffusion_step_multistep(int mode, int dtype, const float* pred, const float* fake_in, const float* hist_in, const float* known,
+                                  const float* mask, double a_t, double a_prev, double c1, double clip, uint64_t seed, uint64_t stream_id,
+                                  uint64_t offset0, uint64_t image_stride, float* fake_out, float* hist_out, float* x0_out, void* out,
+                                  int ldout, void* out2, int ldout2, int B, size_t per_image, int C, void* stream);
 /* the four inputs of the reverse pass built from one inverted noise image eps [H,W,C] (train.py:416-431): out [4,H,W,C] =
  * eps | nearest-upsample x4 of avg_pool2d(eps, 4, 4) | tf.roll by 1 along H and W | per-pixel nearest of the K entries of
  * dictionary [H,W,K,C] (squared distance, first minimum).  H, W multiples of 4. */
