@@ -19,6 +19,7 @@ DENSE2_FAST_PIXELS = 64
 DENSE2_PLAIN_MAX = 256
 # gct2_diffusion_update modes (include/gct2.h; the sampler's objective switches, train.py:29-32)
 SAMPLE_X, SAMPLE_EPS, SAMPLE_SCALED_EPS, SAMPLE_ODE = 0, 1, 2, 3
+SAMPLE_V = 5          # the v objective (predict_v); code 4 is reserved and refused
 BUILD_STAMP = 1
 # gct2_adam_keras_clipped modes and the reduction's constants (include/gct2.h)
 CLIP_NONE, CLIP_VALUE, CLIP_NORM, CLIP_GLOBAL_NORM = 0, 1, 2, 3
@@ -119,6 +120,8 @@ SIGNATURES = {
     "gct2_loss_fwd_bwd": [_i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp],
     "gct2_eval_loss_scratch": [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)],
     "gct2_eval_loss_rows": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp],
+    "gct2_objective_loss_scratch": [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)],
+    "gct2_objective_loss_fwd_bwd": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp],
     "gct2_image_metrics_scratch": [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t)],
     "gct2_image_metrics": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp],
     "gct2_adam_keras_multi": [_vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _f, _f, _f, _vp, _i, _vp],
@@ -213,7 +216,7 @@ def call(name: str, *args) -> None:
 
 # the entry points a plan can hold (csrc/plan.hip ENTRIES): everything that enqueues work on a stream + the one-shot ReLU plane
 PLANNABLE = frozenset(n for n, sig in SIGNATURES.items() if n == "gct2_ctx_set_relu_bits" or (
-    not n.startswith(("gct2_ctx_", "gct2_plan_", "gct2_loss_scale_init")) and n not in ("gct2_abi_version", "gct2_build_flags", "gct2_device_check", "gct2_stream_occupy", "gct2_sumsq_layout", "gct2_loss_scratch", "gct2_eval_loss_scratch", "gct2_image_metrics_scratch", "gct2_dense_steps_scratch", "gct2_dense2_scratch")))
+    not n.startswith(("gct2_ctx_", "gct2_plan_", "gct2_loss_scale_init")) and n not in ("gct2_abi_version", "gct2_build_flags", "gct2_device_check", "gct2_stream_occupy", "gct2_sumsq_layout", "gct2_loss_scratch", "gct2_eval_loss_scratch", "gct2_objective_loss_scratch", "gct2_image_metrics_scratch", "gct2_dense_steps_scratch", "gct2_dense2_scratch")))
 _recording = None      # the Plan that is recording calls right now (one host thread drives an engine: _lib.call is not re-entrant)
 _FLOAT_STRUCT = struct.Struct("<f")
 _DOUBLE_STRUCT = struct.Struct("<d")

@@ -642,11 +642,11 @@ int gct2_diffusion_mix(int dtype, const float* x_theta, const float* eps_theta, 
 
 int gct2_diffusion_update(int mode, const float* pred, const float* fake, double alpha, double alpha_prev, float* x_theta, float* eps_theta,
                           size_t n, void* stream) {
-  if (mode < GCT2_SAMPLE_X || mode > GCT2_SAMPLE_ODE) return gct2_fail(GCT2_EINVAL, "diffusion_update: unknown mode %d", mode);
+  if ((mode < GCT2_SAMPLE_X || mode > GCT2_SAMPLE_ODE) && mode != GCT2_SAMPLE_V) return gct2_fail(GCT2_EINVAL, "diffusion_update: unknown mode %d", mode);
   if (!pred || !fake || !x_theta || (!eps_theta && mode != GCT2_SAMPLE_ODE) || n == 0)
     return gct2_fail(GCT2_EINVAL, "diffusion_update: null pointer or n == 0");
   if (!(alpha >= 0. && alpha < 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_update: alpha must be in [0, 1)");
-  if (mode != GCT2_SAMPLE_X && !(alpha > 0.)) return gct2_fail(GCT2_EINVAL, "diffusion_update: this mode divides by sqrt(alpha): alpha must be > 0");
+  if (mode != GCT2_SAMPLE_X && mode != GCT2_SAMPLE_V && !(alpha > 0.)) return gct2_fail(GCT2_EINVAL, "diffusion_update: this mode divides by sqrt(alpha): alpha must be > 0");
   if (mode == GCT2_SAMPLE_ODE) {
     if (!(alpha_prev >= 0. && alpha_prev <= 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_update: alpha_prev must be in [0, 1]");
     if (sqrt(alpha_prev) * sqrt(1. - alpha) - sqrt(alpha) * sqrt(1. - alpha_prev) == 0.)
@@ -668,12 +668,12 @@ static int step_views_ok(const char* who, int dtype, const float* fake_out, cons
 int gct2_diffusion_step(int mode, int dtype, const float* pred, const float* fake_in, double a_t, double a_prev, double sigma2, double clip,
                         uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t image_stride, float* fake_out, float* x0_out, void* out,
                         int ldout, void* out2, int ldout2, int B, size_t per_image, int C, void* stream) {
-  if (mode < GCT2_SAMPLE_X || mode > GCT2_SAMPLE_SCALED_EPS)
+  if ((mode < GCT2_SAMPLE_X || mode > GCT2_SAMPLE_SCALED_EPS) && mode != GCT2_SAMPLE_V)
     return gct2_fail(GCT2_EINVAL, "diffusion_step: mode %d (the ODE objective predicts one step back only: gct2_diffusion_update)", mode);
   if (!pred || !fake_in) return gct2_fail(GCT2_EINVAL, "diffusion_step: null pointer");
   if (int rc = step_views_ok("diffusion_step", dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
   if (!(a_t >= 0. && a_t < 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step: a_t must be in [0, 1)");
-  if (mode != GCT2_SAMPLE_X && !(a_t > 0.)) return gct2_fail(GCT2_EINVAL, "diffusion_step: this mode divides by sqrt(a_t): a_t must be > 0");
+  if (mode != GCT2_SAMPLE_X && mode != GCT2_SAMPLE_V && !(a_t > 0.)) return gct2_fail(GCT2_EINVAL, "diffusion_step: this mode divides by sqrt(a_t): a_t must be > 0");
   if (!(a_prev >= 0. && a_prev <= 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step: a_prev must be in [0, 1]");
   if (!(sigma2 >= 0.) || !((1.f - (float)a_prev) - (float)sigma2 >= 0.f))
     return gct2_fail(GCT2_EINVAL, "diffusion_step: sigma2 must be in [0, 1 - a_prev]");
@@ -701,12 +701,12 @@ int gct2_diffusion_step_masked(int mode, int dtype, const float* pred, const flo
                                double a_prev, double sigma2, double clip, uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t offset0,
                                uint64_t image_stride, float* fake_out, float* x0_out, void* out, int ldout, void* out2, int ldout2, int B,
                                size_t per_image, int C, void* stream) {
-  if (mode < GCT2_SAMPLE_X || mode > GCT2_SAMPLE_SCALED_EPS)
+  if ((mode < GCT2_SAMPLE_X || mode > GCT2_SAMPLE_SCALED_EPS) && mode != GCT2_SAMPLE_V)
     return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: mode %d (the ODE objective predicts one step back only: gct2_diffusion_update)", mode);
   if (!pred || !fake_in || !known || !mask) return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: null pointer");
   if (int rc = step_views_ok("diffusion_step_masked", dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
   if (!(a_t >= 0. && a_t < 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: a_t must be in [0, 1)");
-  if (mode != GCT2_SAMPLE_X && !(a_t > 0.))
+  if (mode != GCT2_SAMPLE_X && mode != GCT2_SAMPLE_V && !(a_t > 0.))
     return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: this mode divides by sqrt(a_t): a_t must be > 0");
   if (!(a_prev >= 0. && a_prev <= 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: a_prev must be in [0, 1]");
   if (!(sigma2 >= 0.) || !((1.f - (float)a_prev) - (float)sigma2 >= 0.f))
@@ -719,13 +719,13 @@ int gct2_diffusion_step_multistep(int mode, int dtype, const float* pred, const 
                                   const float* mask, double a_t, double a_prev, double c1, double clip, uint64_t seed, uint64_t stream_id,
                                   uint64_t offset0, uint64_t image_stride, float* fake_out, float* hist_out, float* x0_out, void* out, int ldout,
                                   void* out2, int ldout2, int B, size_t per_image, int C, void* stream) {
-  if (mode < GCT2_SAMPLE_X || mode > GCT2_SAMPLE_SCALED_EPS)
+  if ((mode < GCT2_SAMPLE_X || mode > GCT2_SAMPLE_SCALED_EPS) && mode != GCT2_SAMPLE_V)
     return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: mode %d (the ODE objective predicts one step back only: gct2_diffusion_update)", mode);
   if (!pred || !fake_in) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: null pointer");
   if (!known != !mask) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: known and mask go together (both NULL: the plain step)");
   if (int rc = step_views_ok("diffusion_step_multistep", dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
   if (!(a_t >= 0. && a_t < 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: a_t must be in [0, 1)");
-  if (mode != GCT2_SAMPLE_X && !(a_t > 0.))
+  if (mode != GCT2_SAMPLE_X && mode != GCT2_SAMPLE_V && !(a_t > 0.))
     return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: this mode divides by sqrt(a_t): a_t must be > 0");
   if (!(a_prev >= 0. && a_prev <= 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: a_prev must be in [0, 1]");
   if (!std::isfinite(c1) || !std::isfinite((float)c1)) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: c1 must be finite in fp32");
@@ -821,6 +821,36 @@ int gct2_eval_loss_rows(int kind, const float* pred, const float* x, const float
   if (scratch_floats < need)
     return gct2_fail(GCT2_EINVAL, "eval_loss_rows: %zu floats of scratch, this kind and shape need %zu (gct2_eval_loss_scratch)", scratch_floats, need);
   return eval_loss_rows(kind, pred, x, eps, a, c, w, rows, scratch, B, H, W, C, basis, S(stream));
+}
+
+// shape rules of the weighted objective loss: MSE / L1 under the limits of the per-image losses
+static int check_objective_shape(const char* fn, int kind, int B, int H, int W, int C) {
+  if (kind != GCT2_LOSS_MSE && kind != GCT2_LOSS_L1) return gct2_fail(GCT2_EINVAL, "%s: loss kind %d (GCT2_LOSS_MSE or GCT2_LOSS_L1)", fn, kind);
+  return check_eval_shape(fn, kind, B, H, W, C);
+}
+
+int gct2_objective_loss_scratch(int kind, int B, int H, int W, int C, size_t* floats) {
+  if (!floats) return gct2_fail(GCT2_EINVAL, "objective_loss_scratch: null output pointer");
+  if (int e = check_objective_shape("objective_loss_scratch", kind, B, H, W, C)) return e;
+  *floats = objective_scratch_floats(B, H, W, C);
+  return GCT2_OK;
+}
+
+int gct2_objective_loss_fwd_bwd(int kind, const float* pred, const float* x, const float* eps, const float* a, const float* c, const float* w,
+                                const float* lam, float* dpred, float* loss, float* scratch, size_t scratch_floats, int B, int H, int W, int C,
+                                const float* loss_scale_ptr, void* stream) {
+  if (int e = check_objective_shape("objective_loss_fwd_bwd", kind, B, H, W, C)) return e;
+  if (!pred || !x || !loss || !scratch) return gct2_fail(GCT2_EINVAL, "objective_loss_fwd_bwd: null pointer");
+  if (c && !eps) return gct2_fail(GCT2_EINVAL, "objective_loss_fwd_bwd: c without eps");
+  if (a && eps && !c) return gct2_fail(GCT2_EINVAL, "objective_loss_fwd_bwd: a and eps without c");
+  if (dpred && (dpred == pred || dpred == x || dpred == eps)) return gct2_fail(GCT2_EINVAL, "objective_loss_fwd_bwd: dpred aliases an input");
+  if (((uintptr_t)pred | (uintptr_t)x | (uintptr_t)eps | (uintptr_t)a | (uintptr_t)c | (uintptr_t)w | (uintptr_t)lam | (uintptr_t)dpred |
+       (uintptr_t)loss | (uintptr_t)loss_scale_ptr) % 4 || (uintptr_t)scratch % 16)
+    return gct2_fail(GCT2_EINVAL, "objective_loss_fwd_bwd: scratch must be 16-byte aligned, the other pointers 4-byte aligned");
+  const size_t need = objective_scratch_floats(B, H, W, C);
+  if (scratch_floats < need)
+    return gct2_fail(GCT2_EINVAL, "objective_loss_fwd_bwd: %zu floats of scratch, this shape needs %zu (gct2_objective_loss_scratch)", scratch_floats, need);
+  return objective_loss(kind, pred, x, eps, a, c, w, lam, dpred, loss, scratch, B, H, W, C, loss_scale_ptr, S(stream));
 }
 
 // shape rules of the image metrics: the limits of a (tile, image) grid and of int element indices

@@ -438,6 +438,10 @@ int loss_dct(const float* pred, const float* target, float* dpred, float* loss, 
 size_t eval_scratch_floats(int kind, int B, int H, int W, int C);
 int eval_loss_rows(int kind, const float* pred, const float* x, const float* eps, const float* a, const float* c, const float* w, float* rows,
                    float* scratch, int B, int H, int W, int C, const float* basis, hipStream_t s);
+// the weighted objective loss of gct2_objective_loss_fwd_bwd (MSE / L1): the floats of scratch a shape needs / the launches
+size_t objective_scratch_floats(int B, int H, int W, int C);
+int objective_loss(int kind, const float* pred, const float* x, const float* eps, const float* a, const float* c, const float* w,
+                   const float* lam, float* dpred, float* loss, float* scratch, int B, int H, int W, int C, const float* ls, hipStream_t s);
 
 // metrics.hip: the image metrics of gct2_image_metrics: the floats of scratch a shape needs / the launches
 size_t image_metrics_scratch_floats(int B, int H, int W, int C);

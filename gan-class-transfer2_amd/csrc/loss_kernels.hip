@@ -15,6 +15,9 @@
 //
 // gct2_eval_loss_rows (evaluation: the same four losses PER IMAGE, without gradients) lives here too: it forms the residual from the
 // prediction, the clean image and the noise on load, keeps every partial sum inside one image, and reuses the two forward DCT passes.
+//
+// gct2_objective_loss_fwd_bwd (the MSE / L1 training loss with per-image weights) is that per-image kernel with the gradient store of
+// the kinds above: the target is formed on load, the loss is sum_b lam[b] S_b / n from the same fp64 partial sums.
 #include "gct2_common.h"
 #include <algorithm>
 
@@ -453,6 +456,82 @@ __global__ __launch_bounds__(256) void eval_finish_kernel(const double* __restri
   }
 }
 
+// ---- gct2_objective_loss_fwd_bwd: the weighted training loss of an objective and its gradient in one pass ---------------------------
+// eval_rows_kernel's mapping (grid = (chunks, B), the unaligned head and the last n % 4 elements with the first threads of chunk 0) and
+// its residual d = eval_d(...); besides the fp64 partial sum of the image's loss every element leaves its gradient:
+//   KIND 0 (MSE): dpred = s * ((d * k) * g);   KIND 1 (L1): dpred = s * ((d >= -d ? -k : k) * g);   without g (HAS_G false) the product
+// with g is not formed at all.  g = lam[b] * w[b], lam[b] or w[b].  dpred == nullptr: the loss only
+template <int KIND>
+__global__ __launch_bounds__(256) void objective_loss_kernel(EvalSrc s, const float* __restrict__ lam, float* __restrict__ dpred,
+                                                             double* __restrict__ partials, int n_img, float kf,
+                                                             const float* __restrict__ loss_scale_ptr, int vec) {
+#pragma clang fp contract(off)
+  __shared__ double ws4[4];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const size_t base = (size_t)b * n_img;
+  const EvalCoef k = eval_coef(s, b);
+  const bool has_g = lam != nullptr || k.has_w;                 // (block-uniform)
+  const float g = lam ? (k.has_w ? lam[b] * k.w : lam[b]) : k.w;
+  const float ls = loss_scale_ptr ? *loss_scale_ptr : 1.f;
+  const float* __restrict__ pp = s.pred + base;
+  const float* __restrict__ xp = s.x + base;
+  const float* __restrict__ ep = k.has_eps ? s.eps + base : nullptr;
+  float* __restrict__ op = dpred ? dpred + base : nullptr;
+  const int head = vec ? min(n_img, (int)((4 - (base & 3)) & 3)) : 0;
+  const int n4 = (n_img - head) >> 2, rest = n_img - head - 4 * n4;
+  const int per = (n4 + gridDim.x - 1) / gridDim.x;
+  const int q1 = min(n4, ((int)blockIdx.x + 1) * per);
+  double acc = 0.0;
+  auto element = [&](float d) -> float {                        // adds the loss term, returns the gradient
+#pragma clang fp contract(off)
+    float t;
+    if (KIND == 0) {
+      acc += (double)d * (double)d;
+      t = d * kf;
+    } else {
+      const float nd = -d;
+      const bool first = d >= nd;
+      acc += (double)(first ? d : nd);
+      t = first ? -kf : kf;
+    }
+    if (has_g) t = t * g;
+    return ls * t;
+  };
+  for (int q = blockIdx.x * per + tid; q < q1; q += 256) {
+    const int i = head + 4 * q;
+    const f32x4_t p = ld4(pp + i, vec), x = ld4(xp + i, vec);
+    const f32x4_t e = ep ? ld4(ep + i, vec) : f32x4_t{0.f, 0.f, 0.f, 0.f};
+    f32x4_t gr;
+#pragma unroll
+    for (int j = 0; j < 4; j++) gr[j] = element(eval_d(k, p[j], x[j], e[j]));
+    if (op) st4(op + i, gr, vec);
+  }
+  if (blockIdx.x == 0 && tid < head + rest) {        // at most 6 elements: the unaligned head and the last n % 4
+    const int i = tid < head ? tid : 4 * n4 + tid;
+    const float gr = element(eval_d(k, pp[i], xp[i], ep ? ep[i] : 0.f));
+    if (op) op[i] = gr;
+  }
+  const double sum = block_sum(acc, ws4);
+  if (tid == 0) partials[(size_t)b * gridDim.x + blockIdx.x] = sum;
+}
+
+// loss = (float)(sum_b (double)lam[b] * S_b / dn): S_b = part[b chunks, (b + 1) chunks) added in index order, the images in index order
+// per thread (b = tid, tid + 256, ..) and then over the threads; lam == nullptr: every weight is 1
+__global__ __launch_bounds__(256) void objective_finish_kernel(const double* __restrict__ part, const float* __restrict__ lam, int B, int chunks,
+                                                               double dn, float* __restrict__ loss) {
+#pragma clang fp contract(off)
+  __shared__ double ws4[4];
+  double acc = 0.0;
+  for (int b = threadIdx.x; b < B; b += 256) {
+    const double* __restrict__ p = part + (size_t)b * chunks;
+    double sb = 0.0;
+    for (int i = 0; i < chunks; i++) sb += p[i];
+    acc += lam ? (double)lam[b] * sb : sb;
+  }
+  const double total = block_sum(acc, ws4);
+  if (threadIdx.x == 0) *loss = (float)(total / dn);
+}
+
 }  // namespace
 
 // floats of scratch a kind needs: the partial sums (fp64, two floats each) and, for the DCT, one [B,H,W,C] plane set behind them
@@ -575,4 +654,26 @@ int eval_loss_rows(int kind, const float* pred, const float* x, const float* eps
   hipLaunchKernelGGL(dct_pass_kernel, dim3(B * tiles), dim3(256), 0, s, row);
   hipLaunchKernelGGL(eval_finish_kernel, dim3(B), dim3(256), 0, s, part, tiles, 0, (size_t)0, (double)n_img, 0.0, rows);
   return gct2_check_launch("eval_loss_rows (dct)");
+}
+
+// ---- gct2_objective_loss_fwd_bwd -------------------------------------------------------------------------------------------------
+// scratch: one fp64 partial sum (two floats) per (image, chunk) of eval_rows_kernel's grid
+size_t objective_scratch_floats(int B, int H, int W, int C) {
+  return std::max<size_t>(4, round4(2 * (size_t)B * eval_chunks((size_t)H * W * C)));
+}
+
+int objective_loss(int kind, const float* pred, const float* x, const float* eps, const float* a, const float* c, const float* w,
+                   const float* lam, float* dpred, float* loss, float* scratch, int B, int H, int W, int C, const float* ls, hipStream_t s) {
+  const int n_img = H * W * C;
+  const double dn = (double)B * (double)n_img;
+  const EvalSrc src{pred, x, a ? eps : nullptr, a, c, w};
+  const int vec = !(((uintptr_t)pred | (uintptr_t)x | (uintptr_t)src.eps | (uintptr_t)dpred) % 16);
+  double* part = reinterpret_cast<double*>(scratch);
+  const int chunks = eval_chunks((size_t)n_img);
+  if (kind == GCT2_LOSS_MSE)
+    hipLaunchKernelGGL(objective_loss_kernel<0>, dim3(chunks, B), dim3(256), 0, s, src, lam, dpred, part, n_img, (float)(-2.0 / dn), ls, vec);
+  else
+    hipLaunchKernelGGL(objective_loss_kernel<1>, dim3(chunks, B), dim3(256), 0, s, src, lam, dpred, part, n_img, (float)(1.0 / dn), ls, vec);
+  hipLaunchKernelGGL(objective_finish_kernel, dim3(1), dim3(256), 0, s, part, lam, B, chunks, dn, loss);
+  return gct2_check_launch(kind == GCT2_LOSS_MSE ? "objective_loss_fwd_bwd (mse)" : "objective_loss_fwd_bwd (l1)");
 }

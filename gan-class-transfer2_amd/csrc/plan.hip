@@ -43,6 +43,7 @@ const Entry ENTRIES[] = {
     GCT2_ENTRY(gct2_rng_uniform_int), GCT2_ENTRY(gct2_rng_normal), GCT2_ENTRY(gct2_noise_image), GCT2_ENTRY(gct2_noise_image_rng),
     GCT2_ENTRY(gct2_noise_image_table), GCT2_ENTRY(gct2_noise_image_rng_table),
     GCT2_ENTRY(gct2_mse_fwd_bwd), GCT2_ENTRY(gct2_loss_fwd_bwd), GCT2_ENTRY(gct2_eval_loss_rows), GCT2_ENTRY(gct2_image_metrics), GCT2_ENTRY(gct2_cast_from_f32),
+    GCT2_ENTRY(gct2_objective_loss_fwd_bwd),
     GCT2_ENTRY(gct2_loss_scale_begin), GCT2_ENTRY(gct2_scale_check_finite), GCT2_ENTRY(gct2_loss_scale_update),
     GCT2_ENTRY(gct2_diffusion_mix), GCT2_ENTRY(gct2_diffusion_update), GCT2_ENTRY(gct2_noise_edits), GCT2_ENTRY(gct2_image_prepare),
     GCT2_ENTRY(gct2_diffusion_step), GCT2_ENTRY(gct2_diffusion_start),

@@ -844,6 +844,7 @@ __global__ void diffusion_mix_kernel(const float* __restrict__ x, const float* _
 // one sampler update from the prediction, by objective (train.py:338-355, 382-413, 452-479; modes of include/gct2.h):
 //   X: x = pred, e = (fake - sa x) / sb;  EPS: e = pred, x = (fake - pred sb) / sa;  SCALED_EPS: e = pred / sb, x = (fake - pred) / sa;
 //   ODE: x = (pred sb - fake sb1) / (sa1 sb - sa sb1), e untouched.  sa = sqrt(a_t), sb = sqrt(1 - a_t), sa1 / sb1 the same at t - 1.
+//   V: x = sa fake - sb pred, e = sb fake + sa pred (pred is v = sa eps - sb x, Salimans & Ho 2022): no division, a_t = 0 is valid.
 template <int MODE>
 __global__ void diffusion_update_kernel(const float* __restrict__ pred, const float* __restrict__ fake, float sa, float sb, float sb1, float den,
                                         float* __restrict__ x, float* __restrict__ e, size_t n) {
@@ -860,6 +861,9 @@ __global__ void diffusion_update_kernel(const float* __restrict__ pred, const fl
     } else if (MODE == GCT2_SAMPLE_SCALED_EPS) {
       e[i] = p / sb;
       x[i] = (f - p) / sa;
+    } else if (MODE == GCT2_SAMPLE_V) {
+      x[i] = sa * f - sb * p;
+      e[i] = sb * f + sa * p;
     } else {
       x[i] = (p * sb - f * sb1) / den;
     }
@@ -883,9 +887,12 @@ __device__ __forceinline__ float step_update(float p, float f, const StepCoef& k
   } else if (MODE == GCT2_SAMPLE_EPS) {
     e = p;
     x = (f - p * k.sb) / k.sa;
-  } else {
+  } else if (MODE == GCT2_SAMPLE_SCALED_EPS) {
     e = p / k.sb;
     x = (f - p) / k.sa;
+  } else {                                  // GCT2_SAMPLE_V
+    x = k.sa * f - k.sb * p;
+    e = k.sb * f + k.sa * p;
   }
   if (k.clip > 0.f) {                       // (wave-uniform)  a NaN fails both comparisons and stays
     const float c = k.clip;
@@ -1917,6 +1924,7 @@ int pw_diffusion_update(int mode, const float* pred, const float* fake, double a
   else if (mode == GCT2_SAMPLE_EPS) hipLaunchKernelGGL(diffusion_update_kernel<GCT2_SAMPLE_EPS>, grid, block, 0, s, pred, fake, sa, sb, sb1, den, x, e, n);
   else if (mode == GCT2_SAMPLE_SCALED_EPS)
     hipLaunchKernelGGL(diffusion_update_kernel<GCT2_SAMPLE_SCALED_EPS>, grid, block, 0, s, pred, fake, sa, sb, sb1, den, x, e, n);
+  else if (mode == GCT2_SAMPLE_V) hipLaunchKernelGGL(diffusion_update_kernel<GCT2_SAMPLE_V>, grid, block, 0, s, pred, fake, sa, sb, sb1, den, x, e, n);
   else hipLaunchKernelGGL(diffusion_update_kernel<GCT2_SAMPLE_ODE>, grid, block, 0, s, pred, fake, sa, sb, sb1, den, x, e, n);
   return gct2_check_launch("diffusion_update");
 }
@@ -1954,6 +1962,7 @@ int pw_diffusion_step(int mode, int dtype, const float* pred, const float* fake_
     };
     if (mode == GCT2_SAMPLE_X) launch(std::integral_constant<int, GCT2_SAMPLE_X>{});
     else if (mode == GCT2_SAMPLE_EPS) launch(std::integral_constant<int, GCT2_SAMPLE_EPS>{});
+    else if (mode == GCT2_SAMPLE_V) launch(std::integral_constant<int, GCT2_SAMPLE_V>{});
     else launch(std::integral_constant<int, GCT2_SAMPLE_SCALED_EPS>{});
   });
   return gct2_check_launch("diffusion_step");
@@ -2002,6 +2011,7 @@ int pw_diffusion_step_masked(int mode, int dtype, const float* pred, const float
     };
     if (mode == GCT2_SAMPLE_X) launch(std::integral_constant<int, GCT2_SAMPLE_X>{});
     else if (mode == GCT2_SAMPLE_EPS) launch(std::integral_constant<int, GCT2_SAMPLE_EPS>{});
+    else if (mode == GCT2_SAMPLE_V) launch(std::integral_constant<int, GCT2_SAMPLE_V>{});
     else launch(std::integral_constant<int, GCT2_SAMPLE_SCALED_EPS>{});
   });
   return gct2_check_launch("diffusion_step_masked");
@@ -2030,6 +2040,7 @@ int pw_diffusion_step_multistep(int mode, int dtype, const float* pred, const fl
     };
     if (mode == GCT2_SAMPLE_X) launch(std::integral_constant<int, GCT2_SAMPLE_X>{});
     else if (mode == GCT2_SAMPLE_EPS) launch(std::integral_constant<int, GCT2_SAMPLE_EPS>{});
+    else if (mode == GCT2_SAMPLE_V) launch(std::integral_constant<int, GCT2_SAMPLE_V>{});
     else launch(std::integral_constant<int, GCT2_SAMPLE_SCALED_EPS>{});
   });
   return gct2_check_launch("diffusion_step_multistep");

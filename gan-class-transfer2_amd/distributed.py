@@ -173,6 +173,17 @@ def _refuse_timestep_heads(engine, who: str) -> None:
                          "(the switch is single-GPU only)")
 
 
+def _refuse_loss_weighting(engine, who: str) -> None:
+    """per-timestep loss weights (set_loss_weighting) are single-GPU only: the weighted step is eager on the non-fused head path and
+    its loss is a mean over the local batch.  An engine that has them on is refused, and switching them on later is (the message is
+    stored as engine._weighting_forbidden)"""
+    why = (f"{who} has not been built or tested with per-timestep loss weights: loss_weighting must stay None "
+           f"({who} and loss_weighting do not go together; the setting is single-GPU only)")
+    if getattr(engine, "loss_weighting", None) is not None:
+        raise ValueError(why)
+    engine._weighting_forbidden = why
+
+
 def _refuse_hidden_dense(engine, who: str) -> None:
     """the hidden Dense(pixel_size, relu) layer in front of the head (an engine built with hidden_dense=True) is single-GPU only: the
     two-layer head's kernels and its larger "dense" range have not been built into or tested with a multi-rank exchange"""
@@ -215,6 +226,7 @@ class DataParallelStep:
     def __init__(self, engine, bucket_elems: int = 4 << 20, group=None, force_exchange: bool = False):
         _refuse_timestep_heads(engine, "DataParallelStep")
         _refuse_hidden_dense(engine, "DataParallelStep")
+        _refuse_loss_weighting(engine, "DataParallelStep")
         adam_only = _refuse_optimizer(engine, "DataParallelStep")
         no_reg = _refuse_regularizer(engine, "DataParallelStep")
         _refuse_clipping(engine, "DataParallelStep")
@@ -318,6 +330,7 @@ class ShardedDataParallelStep:
     def __init__(self, engine, bucket_elems: int = 4 << 20, group=None, force_exchange: bool = False, tail_layers: int = 3):
         _refuse_timestep_heads(engine, "ShardedDataParallelStep")
         _refuse_hidden_dense(engine, "ShardedDataParallelStep")
+        _refuse_loss_weighting(engine, "ShardedDataParallelStep")
         adam_only = _refuse_optimizer(engine, "ShardedDataParallelStep")
         no_reg = _refuse_regularizer(engine, "ShardedDataParallelStep")
         _refuse_clipping(engine, "ShardedDataParallelStep")

@@ -331,10 +331,10 @@ class UNetEngine(TrainerState):
                  workspace_mb: int = 64, predict_x: bool = True, predict_scaled_epsilon: bool = False,
                  prediction_weighting: bool = False, ordinary_differential_equation: bool = False, f32_matrix: bool = False,
                  use_ema: bool = False, ema_momentum: float = 0.99, timestep_heads: bool = False,
-                 hidden_dense: bool = False, head_initializer: str = "glorot_uniform"):
+                 hidden_dense: bool = False, head_initializer: str = "glorot_uniform", predict_v: bool = False):
         TM_check_head_options(type(self).__name__, hidden_dense, timestep_heads, head_initializer)
         super().__init__(dtype, device, steps, base_lr, warm_up, beta_1, beta_2, epsilon, loss_scaling, rng_seed, predict_x,
-                         predict_scaled_epsilon, prediction_weighting, ordinary_differential_equation, f32_matrix)
+                         predict_scaled_epsilon, prediction_weighting, ordinary_differential_equation, f32_matrix, predict_v=predict_v)
         self.topo = topo
         # the hidden Dense(pixel_size, relu) layer between the last Block and the head (train.py:195-197, commented out in the reference):
         # dense_hidden.w is (Fu_0 + 3, pixel_size), dense.w becomes (pixel_size, 3), and the pair runs unfused through gct2_dense2_fwd /
@@ -803,12 +803,19 @@ class UNetEngine(TrainerState):
         call("gct2_mix_per_image", b.dpred.data_ptr(), None, w.data_ptr(), None, b.dpred.data_ptr(), b.B, n, self._stream())
         return loss
 
+    def objective_loss_and_dpred(self, b: _Buffers, x: torch.Tensor, grad: bool = True) -> torch.Tensor:
+        """the weighted training loss (set_loss_weighting) and its gradient in one launch (gct2_objective_loss_fwd_bwd): the objective's
+        target is formed inside the kernel from x and b.eps, no target plane is written; grad=False (Trainer.call) is its loss-only form"""
+        b._coef = self._objective_loss_launch(b.loss_store, b.pred, x, b.eps, b.t_int, b.dpred if grad else None, b.loss, self._stream())
+        return b.loss
+
     def fused_head_ok(self) -> bool:
         """the matrix-core head with the split input (R_0's UpShuffle_0 channels + the packed image): the reference topology
         (Fu_0 = 64) in a 16-bit mode with a workspace and the MSE loss the head kernels carry; anything else runs dense_fwd + the loss
-        (gct2_mse_fwd_bwd, or gct2_loss_fwd_bwd for the other training losses) + dense_bwd."""
+        (gct2_mse_fwd_bwd, gct2_loss_fwd_bwd for the other training losses, gct2_objective_loss_fwd_bwd under a loss weighting) +
+        dense_bwd."""
         return (self.use_fused_head and self.dtype != F32 and self.topo.fu(0) == 64 and self.workspace is not None
-                and not self.objective_weighted() and self.training_loss == "mse" and not self.timestep_heads and not self.hidden_dense)
+                and self.loss_weighting is None and not self.objective_weighted() and self.training_loss == "mse" and not self.timestep_heads and not self.hidden_dense)
 
     def head_train(self, b: _Buffers, target: torch.Tensor, target_is_x: bool = False) -> torch.Tensor:
         """Dense(3) + fp32 MSE + both of their gradients in one pass over R_0 (gct2_dense_head_train)."""
@@ -1075,6 +1082,7 @@ class UNetEngine(TrainerState):
         if x.dim() != 4 or x.shape[-1] != 3:
             raise ValueError(f"expected an NHWC batch [B,H,W,3], got {tuple(x.shape)}")
         self._refuse_training_on_averages()
+        self.check_step_settings()
         if x.dtype != torch.float32 or not x.is_contiguous() or x.device != self.device:
             x = x.to(self.device, torch.float32).contiguous()
         B, H, W, _ = x.shape
@@ -1086,7 +1094,8 @@ class UNetEngine(TrainerState):
         if self._flush_event is not None:                      # a flush on another stream (predict / state_dict there): the step waits once
             cur.wait_event(self._flush_event)
             self._flush_event = None
-        if self.use_plan and t_int is None and eps is None and self.default_objective() and _lib._recording is None:
+        if (self.use_plan and t_int is None and eps is None and self.default_objective() and self.loss_weighting is None
+                and _lib._recording is None):
             return self._planned_step(b, x, apply, inline, cur)
         return self._step_body(b, x, t_int, eps, apply, inline)
 
@@ -1109,10 +1118,14 @@ class UNetEngine(TrainerState):
             if eps is not None:
                 b.eps.copy_(eps.to(self.device, torch.float32))
             self.noise_into_r0(b, x)
-        target, w = (x, None) if default_obj else self.make_target(b, x)
+        weights = self.loss_weighting is not None               # the target is then formed inside the loss kernel: no target plane
+        target, w = (x, None) if default_obj or weights else self.make_target(b, x)
         weighted = self.objective_weighted()
         fused = self.fused_head_ok()
-        if fused and self.fused_u0_head_ok(b):
+        if weights:
+            self.forward(b, head=True, planes=True, in_step=True)
+            loss = self.objective_loss_and_dpred(b, x)
+        elif fused and self.fused_u0_head_ok(b):
             self.forward(b, head=False, stop_before_u0=True, planes=True, in_step=True)
             loss = self.u0_head_train(b, target, default_obj)
         else:

@@ -41,6 +41,20 @@ predict_scaled_epsilon = False
 prediction_weighting = False
 ordinary_differential_equation = False
 
+# the v objective (Salimans & Ho 2022, "Progressive Distillation for Fast Sampling of Diffusion Models"; not in the reference): the
+# network predicts v = sqrt(alpha) eps - sqrt(1 - alpha) x, and both estimates the sampler needs - x0 = sqrt(alpha) noised -
+# sqrt(1 - alpha) pred and eps = sqrt(1 - alpha) noised + sqrt(alpha) pred - divide by nothing.  With it, predict_x is ignored; together
+# with predict_scaled_epsilon, prediction_weighting or ordinary_differential_equation it is a ValueError.  A separate global, not one
+# of the four switches of objective_switches(); Trainer reads it before every step, like training_loss
+predict_v = False
+
+# per-timestep loss weights (not in the reference): None (off), "min_snr" (min-SNR-gamma, Hang et al. 2023, with min_snr_gamma), a
+# callable f(snr, t) -> weight or a sequence of `steps` floats (trainer_math.loss_weight_table).  The loss is the mean over the batch
+# of lambda(t_b) times every image's own loss, not renormalised; "mse" and "l1" only.  With weights on the step is eager and runs the
+# non-fused head path through gct2_objective_loss_fwd_bwd; single GPU.  Trainer reads both before every step, like training_loss
+loss_weighting = None
+min_snr_gamma = 5.0
+
 mixed_precision = False
 
 # train.py:254-280: which of Trainer.call's `return` lines is live - "mse" (train.py:272, the reference as committed), "l1"
@@ -106,6 +120,10 @@ def configure(**kw) -> None:
             v = trainer_math.check_noise_schedule(v, 0.0)[0]
         if k == "alpha_dash_offset":
             v = trainer_math.check_noise_schedule(None, v)[1]
+        if k == "loss_weighting":
+            v = trainer_math.check_loss_weighting(v)[0]
+        if k == "min_snr_gamma":
+            v = trainer_math.check_loss_weighting(None, v)[1]
         setattr(mod, k, v)
 
 
@@ -632,6 +650,8 @@ class Denoiser(Layer):
         # no optimizer known yet (train.py:505-509 calls the model before compile): the module-level mixed_precision
         # decides about loss scaling, as it decides about the LossScaleOptimizer wrapper in train.py:82-83
         kw = dict(steps=steps, warm_up=warm_up, seed=self._seed, loss_scaling=bool(mixed_precision), **objective_switches())
+        if predict_v:                                 # (the v objective: a separate global, passed by keyword; ValueError on a clash)
+            kw.update(predict_v=True)
         if self.timestep_heads:                       # (the head's shape was fixed when this Denoiser was constructed)
             kw.update(steps=self._steps, timestep_heads=True)
         if self.hidden_dense:                         # (... and so was the hidden layer in front of it)
@@ -795,13 +815,26 @@ class Trainer(Layer):
             eng.set_gradient_transform(transform)
         # train.py:238-252 reads the objective globals every time Trainer.call runs: an engine built earlier (by denoiser(...),
         # trainable_variables, the log_sample callback) follows the switches as they stand now
-        for k, v in objective_switches().items():
+        switches = objective_switches()
+        trainer_math.check_predict_v(predict_v, switches["predict_scaled_epsilon"], switches["prediction_weighting"],
+                                     switches["ordinary_differential_equation"])      # a clash: ValueError, before anything changes
+        weighting = trainer_math.check_loss_weighting(loss_weighting, min_snr_gamma)
+        if weighting[0] is not None and loss_kind not in trainer_math.WEIGHTED_TRAINING_LOSSES:
+            raise ValueError(f"loss_weighting with training_loss {loss_kind!r}: per-timestep weights are built for "
+                             f"{' and '.join(trainer_math.WEIGHTED_TRAINING_LOSSES)}")
+        for k, v in switches.items():
             setattr(eng, k, v)
+        if bool(predict_v) != bool(getattr(eng, "predict_v", False)):      # (... and the v objective)
+            eng.flush_deferred()
+            eng.predict_v = bool(predict_v)
         eng.training_loss = loss_kind                    # (... and the `return` of train.py:265-280 that is live now)
         if trainer_math.l2_coefficients(l2)[0] != getattr(eng, "l2", 0.0):     # (... and the regularizer of train.py:80)
             eng.set_regularizer(l2)
         if schedule != (getattr(eng, "noise_schedule", "quadratic"), getattr(eng, "alpha_dash_offset", 0.0)):     # (... and alpha_dash's live line)
             eng.set_noise_schedule(*schedule)
+        have = (getattr(eng, "loss_weighting", None), getattr(eng, "min_snr_gamma", 5.0))
+        if weighting[0] != have[0] or (weighting[0] is not None and weighting[1] != have[1]):     # (... and the per-timestep loss weights)
+            eng.set_loss_weighting(*weighting)
         return eng
 
     def call(self, x):
@@ -810,10 +843,13 @@ class Trainer(Layer):
         x = x.to(eng.device, torch.float32).contiguous()
         if self.denoiser.variant():
             return eng.train_step(x, backward=False).clone()[0]
+        eng.check_step_settings()                      # the weighting against the objective as it stands now (ValueError)
         b = eng.buffers(*x.shape[:3])
         eng.sample_noise(b)
         eng.noise_into_r0(b, x, unfused_head=True)     # forward(head=True) reads the image channels from R_0 itself
         eng.forward(b)
+        if eng.loss_weighting is not None:             # the weighted loss: gct2_objective_loss_fwd_bwd's loss-only form
+            return eng.objective_loss_and_dpred(b, x, grad=False).clone()[0]
         if eng.default_objective():
             return eng.loss_and_dpred(b, x, grad=False).clone()[0]
         target, w = eng.make_target(b, x)              # train.py:238-252
@@ -871,6 +907,8 @@ class Trainer(Layer):
         seed: instead of the engine's rng_seed.  use_ema: the averaged weights.  With an L2 regularizer the penalty of the weights
         read is added, as in the train step's loss.  One host synchronisation, at the end.
         return_dict: {"loss": float, "per_image": float32 [N] (the data term of every image), "t": int32 [N]} instead of the float.
+        Under a loss_weighting the rows are multiplied by lambda(t) of their image, the loss is the weighted mean (not renormalised) and
+        return_dict holds the weighted per_image plus "loss_weight", float32 [N]: the caller can divide.
         metrics: names out of trainer_math.METRICS (None: those of compile(); (): none) - the image-space metrics of every image's x0
         estimate against the clean image (gct2_image_metrics), whatever the objective predicts.  With any, the return value is
         [loss, m1, m2, ...] in the order asked, as Keras returns it, each the float64 mean over the images (inf for "psnr" when an
@@ -883,7 +921,7 @@ class Trainer(Layer):
             raise ValueError("evaluate: the dataset never ends (an ImageDataset in training mode): pass steps, or build it with "
                              "ImageDataset.validation")
         eng = self._engine()
-        rows, ts, index = [], [], 0
+        rows, ts, lams, index = [], [], [], 0
         mrows = {n: [] for n in metrics}
 
         def run():
@@ -898,6 +936,8 @@ class Trainer(Layer):
                     r, tt = eng.evaluate_batch(x, index0=index, t=t, seed=seed)
                 rows.append(r)
                 ts.append(tt)
+                if "loss_weight" in eng.last_eval:             # (loss_weighting: r holds the weighted rows, this their weights)
+                    lams.append(eng.last_eval["loss_weight"])
                 index += int(x.shape[0])
                 if steps is not None and k + 1 >= steps:       # (an endless dataset is not asked for a batch nobody reads)
                     break
@@ -922,14 +962,15 @@ class Trainer(Layer):
         loss = float(np.mean(per_image, dtype=np.float64))
         if penalty is not None:
             loss += float(penalty.cpu()[0])
+        weights = {"loss_weight": torch.cat(lams).cpu().numpy()} if lams else {}
         if not metrics:
             if return_dict:
-                return {"loss": loss, "per_image": per_image, "t": t_all}
+                return {"loss": loss, "per_image": per_image, "t": t_all, **weights}
             return loss
         with np.errstate(invalid="ignore"):
             means = {n: float(np.mean(per_metric[n], dtype=np.float64)) for n in metrics}
         if return_dict:
-            out = {"loss": loss, "per_image": per_image, "t": t_all}
+            out = {"loss": loss, "per_image": per_image, "t": t_all, **weights}
             for n in metrics:
                 out[n] = means[n]
                 out["per_image_" + n] = per_metric[n]

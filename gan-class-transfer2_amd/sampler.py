@@ -29,17 +29,21 @@ import torch
 
 from . import _lib
 from . import model as M
-from ._lib import SAMPLE_EPS, SAMPLE_ODE, SAMPLE_SCALED_EPS, SAMPLE_X, call
+from ._lib import SAMPLE_EPS, SAMPLE_ODE, SAMPLE_SCALED_EPS, SAMPLE_V, SAMPLE_X, call
 from .engine import TORCH_DTYPE, UNetEngine
 from .trainer_math import alpha_dash            # train.py:85-93 on python floats, as in the reference
 from .trainer_math import check_noise_schedule, check_timesteps, noise_schedule_name
 from .trainer_math import GENERATE_STREAM, ddim_sigma2, generate_image_stride, generate_offset, sampling_timesteps
 from .trainer_math import check_mask, img2img_steps
 from .trainer_math import SOLVERS, multistep_coefficient
+from .trainer_math import check_predict_v
 
 
-def sample_mode(predict_x: bool, predict_scaled_epsilon: bool, ordinary_differential_equation: bool) -> int:
-    """the branch order of train.py:338-355, 382-413, 452-479: ODE first, then predict_x, then the two epsilon forms."""
+def sample_mode(predict_x: bool, predict_scaled_epsilon: bool, ordinary_differential_equation: bool, predict_v: bool = False) -> int:
+    """the branch order of train.py:338-355, 382-413, 452-479: ODE first, then predict_x, then the two epsilon forms.  predict_v (the v
+    objective, which the reference does not have) comes before all of them: predict_x is ignored, the other two are a ValueError."""
+    if check_predict_v(predict_v, predict_scaled_epsilon, False, ordinary_differential_equation):
+        return SAMPLE_V
     if ordinary_differential_equation:
         return SAMPLE_ODE
     if predict_x:
@@ -204,7 +208,7 @@ class _Sampler:
         self.update(pred, fake, a, alpha_dash(t - 1, self.steps, self.schedule, self.offset), x, None if self.mode == SAMPLE_ODE else e)
 
 
-def _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_differential_equation) -> int:
+def _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_differential_equation, predict_v=None) -> int:
     """the sampler's objective switches: explicit arguments, else the module-level globals (train.py reads its globals when
     log_sample runs).  A network trained for another objective would sample garbage without any error: refuse a mismatch
     with the engine's own switches."""
@@ -212,13 +216,17 @@ def _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_different
                 predict_scaled_epsilon=M.predict_scaled_epsilon if predict_scaled_epsilon is None else predict_scaled_epsilon,
                 ordinary_differential_equation=(M.ordinary_differential_equation if ordinary_differential_equation is None
                                                 else ordinary_differential_equation))
+    if bool(M.predict_v if predict_v is None else predict_v):          # (named only when on: the messages of the reference's switches stay)
+        want["predict_v"] = True
     mode = sample_mode(**want)
     if all(hasattr(eng, k) for k in want):
-        have = sample_mode(eng.predict_x, eng.predict_scaled_epsilon, eng.ordinary_differential_equation)
+        have = sample_mode(eng.predict_x, eng.predict_scaled_epsilon, eng.ordinary_differential_equation,
+                           predict_v=getattr(eng, "predict_v", False))
         if have != mode:
             raise ValueError(f"log_sample: objective switches {want} select sampler mode {mode}, but the engine was set up for "
                              f"mode {have} (predict_x={eng.predict_x}, predict_scaled_epsilon={eng.predict_scaled_epsilon}, "
-                             f"ordinary_differential_equation={eng.ordinary_differential_equation}); train.py:29-32 are read by "
+                             f"ordinary_differential_equation={eng.ordinary_differential_equation}"
+                             f"{', predict_v=True' if getattr(eng, 'predict_v', False) else ''}); train.py:29-32 are read by "
                              "Trainer.call and log_sample alike")
     return mode
 
@@ -242,7 +250,7 @@ def log_sample(denoiser: "M.Denoiser", example_image: torch.Tensor, example: tor
                steps: Optional[int] = None, test_step: Optional[int] = None, predict_x: Optional[bool] = None,
                predict_scaled_epsilon: Optional[bool] = None, ordinary_differential_equation: Optional[bool] = None,
                use_graph: bool = True, use_ema: bool = False, noise_schedule=None, alpha_dash_offset: Optional[float] = None,
-               ) -> Dict[str, torch.Tensor]:
+               predict_v: Optional[bool] = None) -> Dict[str, torch.Tensor]:
     """example_image [1,H,W,3] fp32 in [-1,1) (train.py:305); example [1,2,H,W,3] ~ N(0,1) (train.py:306);
     dictionary [H,W,2**bits_per_pixel,3] ~ N(0,1) (train.py:308-311); all on the HIP device.
     use_ema: every network evaluation reads the engine's parameter averages (Adam(use_ema=True)) instead of the raw iterate.
@@ -251,14 +259,15 @@ def log_sample(denoiser: "M.Denoiser", example_image: torch.Tensor, example: tor
     eng = denoiser.ensure_engine()
     with (eng.ema_weights() if use_ema else contextlib.nullcontext()):
         return _log_sample(eng, example_image, example, dictionary, steps, test_step, predict_x, predict_scaled_epsilon,
-                           ordinary_differential_equation, use_graph, noise_schedule, alpha_dash_offset)
+                           ordinary_differential_equation, use_graph, noise_schedule, alpha_dash_offset, predict_v)
 
 
 def _log_sample(eng, example_image, example, dictionary, steps, test_step, predict_x, predict_scaled_epsilon,
-                ordinary_differential_equation, use_graph, noise_schedule=None, alpha_dash_offset=None) -> Dict[str, torch.Tensor]:
+                ordinary_differential_equation, use_graph, noise_schedule=None, alpha_dash_offset=None,
+                predict_v=None) -> Dict[str, torch.Tensor]:
     steps = M.steps if steps is None else steps
     test_step = M.test_step if test_step is None else test_step
-    mode = _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_differential_equation)
+    mode = _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_differential_equation, predict_v)
     schedule, offset = _resolve_schedule(eng, noise_schedule, alpha_dash_offset)
     alpha = lambda t: alpha_dash(t, steps, schedule, offset)
     dev = eng.device
@@ -320,7 +329,7 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
              use_ema: bool = False, use_graph: bool = True, return_steps=(), size=None, predict_x: Optional[bool] = None,
              predict_scaled_epsilon: Optional[bool] = None, ordinary_differential_equation: Optional[bool] = None, noise_schedule=None,
              alpha_dash_offset: Optional[float] = None, init: Optional[torch.Tensor] = None, strength: float = 1.0, mask=None,
-             solver: str = "ddim"):
+             solver: str = "ddim", predict_v: Optional[bool] = None):
     """n new images from noise: strided DDIM sampling (Song et al. 2021) over K = num_steps of the engine's `steps` timesteps
     (trainer_math.sampling_timesteps; None: all of them; or an explicit strictly increasing `timesteps` list within 1..steps), one
     network evaluation and ONE pointwise launch (gct2_diffusion_step) per step.  Returns fp32 [n,H,W,3] on the device: the x0 estimate
@@ -332,7 +341,8 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
     generate(4) is generate(2) followed by generate(2, first_index=2).  noise [n,H,W,3]: the starting noise instead of the drawn one.
     size: H = W (or (H, W)) when no noise is given; None is the module's `size`.  return_steps: timesteps whose x0 estimate is
     returned too - then the result is (images, {t: fp32 [n,H,W,3]}).  use_ema: every evaluation reads the parameter averages.
-    The objective switches and the noise schedule resolve like log_sample's; the ODE objective is refused (its network predicts one
+    The objective switches (predict_v, the v objective, among them: gct2_diffusion_step's mode V, whose estimates divide by nothing) and
+    the noise schedule resolve like log_sample's; the ODE objective is refused (its network predicts one
     step back only: striding and eta mean nothing there).  No training state moves: the RNG positions of training and evaluation,
     optimizer slots, averages, loss scale and recorded plans stay as they are.
     init [n,H,W,3] fp32: image-to-image.  The K' = trainer_math.img2img_steps(K, strength) last steps of the schedule run, from the image
@@ -358,7 +368,7 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
         raise ValueError(f"generate: solver must be one of {SOLVERS!r}, got {solver!r}")
     if isinstance(n, bool) or not isinstance(n, int) or n < 1:
         raise ValueError(f"generate: n must be a positive int, got {n!r}")
-    mode = _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_differential_equation)
+    mode = _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_differential_equation, predict_v)
     if mode == SAMPLE_ODE:
         raise ValueError("generate: the ordinary_differential_equation objective predicts the image one step back only; strided sampling "
                          "and eta have no meaning there (log_sample runs its sampler)")
@@ -471,7 +481,7 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
 def encode(denoiser: "M.Denoiser", images: torch.Tensor, num_steps: Optional[int] = None, timesteps=None, batch_size: Optional[int] = None,
            use_ema: bool = False, use_graph: bool = True, start_eps: Optional[torch.Tensor] = None, predict_x: Optional[bool] = None,
            predict_scaled_epsilon: Optional[bool] = None, ordinary_differential_equation: Optional[bool] = None, noise_schedule=None,
-           alpha_dash_offset: Optional[float] = None, solver: str = "ddim") -> torch.Tensor:
+           alpha_dash_offset: Optional[float] = None, solver: str = "ddim", predict_v: Optional[bool] = None) -> torch.Tensor:
     """images [n,H,W,3] into latents, fp32 [n,H,W,3] on the device: the forward loop of log_sample (train.py:364-413), strided over the
     K = num_steps timesteps of generate (trainer_math.sampling_timesteps, or an explicit `timesteps` list), ascending.  The state starts
     as x_theta = eps_theta = images like the reference's (train.py:367), or eps_theta = start_eps [n,H,W,3]; every step is one
@@ -488,7 +498,7 @@ def encode(denoiser: "M.Denoiser", images: torch.Tensor, num_steps: Optional[int
     steps = int(eng.steps)
     if solver not in SOLVERS:
         raise ValueError(f"encode: solver must be one of {SOLVERS!r}, got {solver!r}")
-    mode = _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_differential_equation)
+    mode = _resolve_switches(eng, predict_x, predict_scaled_epsilon, ordinary_differential_equation, predict_v)
     if mode == SAMPLE_ODE:
         raise ValueError("encode: the ordinary_differential_equation objective predicts the image one step back only; a strided "
                          "inversion has no meaning there (log_sample runs its loop)")

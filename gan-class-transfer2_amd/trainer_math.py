@@ -177,14 +177,124 @@ def objective_weighted(predict_x: bool, prediction_weighting: bool, ordinary_dif
     return bool(not predict_x and not ordinary_differential_equation and prediction_weighting)
 
 
+def check_predict_v(predict_v: bool, predict_scaled_epsilon: bool = False, prediction_weighting: bool = False,
+                    ordinary_differential_equation: bool = False) -> bool:
+    """predict_v checked against the reference's switches: it replaces predict_x (whose value is then ignored) and does not combine
+    with predict_scaled_epsilon, prediction_weighting or ordinary_differential_equation (ValueError)"""
+    if predict_v:
+        clash = [k for k, on in (("predict_scaled_epsilon", predict_scaled_epsilon), ("prediction_weighting", prediction_weighting),
+                                 ("ordinary_differential_equation", ordinary_differential_equation)) if on]
+        if clash:
+            raise ValueError(f"predict_v does not combine with {', '.join(clash)}: the v objective has one target, "
+                             "sqrt(alpha) eps - sqrt(1 - alpha) x, and one pair of estimates")
+    return bool(predict_v)
+
+
+def weighting_objective(predict_x: bool = True, predict_scaled_epsilon: bool = False, prediction_weighting: bool = False,
+                        ordinary_differential_equation: bool = False, predict_v: bool = False) -> Optional[str]:
+    """what the network predicts, as loss_weight_table names it: "v", "x" or "eps"; None for the scaled-epsilon, ODE and
+    prediction_weighting objectives, which have no named weighting"""
+    if check_predict_v(predict_v, predict_scaled_epsilon, prediction_weighting, ordinary_differential_equation):
+        return "v"
+    if ordinary_differential_equation:
+        return None
+    if predict_x:
+        return "x"
+    return None if (predict_scaled_epsilon or prediction_weighting) else "eps"
+
+
+LOSS_WEIGHTINGS = ("min_snr",)
+WEIGHTED_TRAINING_LOSSES = ("mse", "l1")       # the kinds gct2_objective_loss_fwd_bwd computes
+
+
+def check_loss_weighting(kind, gamma: float = 5.0):
+    """(kind, gamma) checked: None (off), a LOSS_WEIGHTINGS name, a callable f(snr, t) -> weight or a sequence of floats (returned as
+    a tuple: one weight per timestep 1..steps); gamma a finite float > 0 (ValueError)"""
+    try:
+        g = float(gamma)
+    except (TypeError, ValueError):
+        raise ValueError(f"min_snr_gamma must be a finite float > 0, got {gamma!r}") from None
+    if not (math.isfinite(g) and g > 0.0):
+        raise ValueError(f"min_snr_gamma must be a finite float > 0, got {gamma!r}")
+    if kind is None or callable(kind):
+        return kind, g
+    if isinstance(kind, str):
+        if kind not in LOSS_WEIGHTINGS:
+            raise ValueError(f"unknown loss_weighting {kind!r} (one of {', '.join(LOSS_WEIGHTINGS)}, a callable f(snr, t) or a sequence of "
+                             "`steps` floats)")
+        return kind, g
+    try:
+        seq = tuple(float(v) for v in (kind.tolist() if hasattr(kind, "tolist") else kind))
+    except (TypeError, ValueError):
+        raise ValueError(f"loss_weighting must be None, one of {LOSS_WEIGHTINGS}, a callable f(snr, t) or a sequence of floats, "
+                         f"got {kind!r}") from None
+    return seq, g
+
+
+def loss_weight_table(kind, gamma: float = 5.0, steps: int = 200, objective: Optional[str] = "x", schedule=None,
+                      offset: float = 0.0) -> np.ndarray:
+    """float32 [steps + 1]: lambda(t) of configure(loss_weighting=kind) for t = 1..steps, entry 0 zero; formed in Python floats
+    (double) and rounded once.  SNR(t) = alpha / (1 - alpha) with alpha = alpha_table(schedule, offset, steps)[t] as a Python float
+    (inf at alpha = 1).
+      "min_snr" (Hang et al. 2023): the weight that makes the x0-space weight min(SNR, gamma) -
+          objective "x":   min(SNR, gamma)
+          objective "eps": 1 where SNR <= gamma, else gamma / SNR        (no 0 / 0 at alpha = 0)
+          objective "v":   min(SNR, gamma) / (SNR + 1)                   (0 at SNR = inf)
+          any other objective (None: scaled epsilon, ODE, prediction_weighting) is a ValueError
+      a callable f(snr: float, t: int) -> float, or a sequence of `steps` floats (entry t - 1 is lambda(t)): under any objective.
+    Every entry must be finite and >= 0 (ValueError)."""
+    kind, gamma = check_loss_weighting(kind, gamma)
+    steps = int(steps)
+    if kind is None:
+        raise ValueError("loss_weight_table: loss_weighting is None (off): there is no table")
+    if steps < 1:
+        raise ValueError(f"steps must be >= 1, got {steps!r}")
+    alpha = alpha_table(schedule, offset, steps)
+    snr = [0.0] * (steps + 1)
+    for t in range(1, steps + 1):
+        a = float(alpha[t])
+        snr[t] = math.inf if a >= 1.0 else a / (1.0 - a)
+    lam = [0.0] * (steps + 1)
+    if isinstance(kind, str):
+        if objective not in ("x", "eps", "v"):
+            raise ValueError(f"loss_weighting {kind!r} is defined for the x, epsilon and v objectives; predict_scaled_epsilon, "
+                             "prediction_weighting and ordinary_differential_equation take a callable or a table")
+        for t in range(1, steps + 1):
+            r = snr[t]
+            if objective == "x":
+                lam[t] = min(r, gamma)
+            elif objective == "eps":
+                lam[t] = 1.0 if r <= gamma else gamma / r
+            else:
+                lam[t] = 0.0 if math.isinf(r) else min(r, gamma) / (r + 1.0)
+    elif callable(kind):
+        for t in range(1, steps + 1):
+            try:
+                lam[t] = float(kind(snr[t], t))
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"loss_weighting: the callable returned no float at timestep {t}: {e}") from None
+    else:
+        if len(kind) != steps:
+            raise ValueError(f"loss_weighting: a table of {len(kind)} weights for {steps} timesteps")
+        lam[1:] = kind
+    with np.errstate(over="ignore"):
+        out = np.asarray(lam, dtype=np.float64).astype(np.float32)
+    bad = np.flatnonzero(~(np.isfinite(out) & (out >= 0)))
+    if bad.size:
+        raise ValueError(f"loss_weighting: the weight of timestep {int(bad[0])} is {lam[int(bad[0])]!r}: every weight must be finite "
+                         "(in float32) and >= 0")
+    return out
+
+
 def objective_coefficients(t_int: torch.Tensor, steps: int, predict_x: bool = True, predict_scaled_epsilon: bool = False,
                            prediction_weighting: bool = False, ordinary_differential_equation: bool = False,
                            schedule=None, offset: float = 0.0, roots: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-                           ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                           predict_v: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """per-image (a, c, w) of train.py:238-252: target = a x + c eps, prediction weight w (ones unless objective_weighted) -
     contiguous float32 vectors on t_int's device.  The default schedule keeps its torch formula; any other gathers sqrt(alpha) and
     sqrt(1 - alpha), formed on the host in float32 from alpha_table, at t or t - 1 (roots: those two [steps + 1] vectors already on
-    the device - an engine keeps them)."""
+    the device - an engine keeps them).  predict_v (keyword only in practice; predict_x is then ignored): the v objective of Salimans &
+    Ho 2022, target = sqrt(alpha) eps - sqrt(1 - alpha) x, (a, c, w) = (-sb, sa, 1) with the float32 roots at t."""
     t = t_int.to(torch.float32)
     one, zero = torch.ones_like(t), torch.zeros_like(t)
     tabled = not default_noise_schedule(schedule, offset)
@@ -192,6 +302,12 @@ def objective_coefficients(t_int: torch.Tensor, steps: int, predict_x: bool = Tr
         if roots is None:
             roots = tuple(torch.from_numpy(r).to(t_int.device) for r in alpha_roots(schedule, offset, steps))
         at = lambda r, shift: r.index_select(0, (t_int.to(torch.int64) - shift).clamp(0, steps)).contiguous()
+    if predict_v:
+        check_predict_v(predict_v, predict_scaled_epsilon, prediction_weighting, ordinary_differential_equation)
+        if tabled:
+            return (-at(roots[1], 0)).contiguous(), at(roots[0], 0), one
+        av = alpha_dash(t, steps)
+        return (-(1 - av).sqrt()).contiguous(), av.sqrt().contiguous(), one
     if ordinary_differential_equation:                                # train.py:238-242
         if tabled:
             return at(roots[0], 1), at(roots[1], 1), one
@@ -466,8 +582,11 @@ def ssim_window(K: int = 11, sigma: float = 1.5) -> np.ndarray:
     return (g / g.sum()).astype(np.float32)
 
 
-def x0_mode(predict_x: bool, predict_scaled_epsilon: bool, ordinary_differential_equation: bool) -> int:
-    """the gct2_diffusion_update mode of the objective switches (sampler.sample_mode: ODE first, then predict_x, then the epsilon forms)"""
+def x0_mode(predict_x: bool, predict_scaled_epsilon: bool, ordinary_differential_equation: bool, predict_v: bool = False) -> int:
+    """the gct2_diffusion_update mode of the objective switches (sampler.sample_mode: predict_v first - it ignores predict_x and
+    refuses the other two -, then ODE, then predict_x, then the epsilon forms)"""
+    if check_predict_v(predict_v, predict_scaled_epsilon, False, ordinary_differential_equation):
+        return _lib.SAMPLE_V
     if ordinary_differential_equation:
         return _lib.SAMPLE_ODE
     if predict_x:
@@ -480,7 +599,7 @@ def x0_tables(steps: int, mode: int, schedule=None, offset: float = 0.0) -> Opti
     entry 0 is never gathered and holds zeros.  None for SAMPLE_X.  Every coefficient is formed from Python floats and rounded once."""
     if mode == _lib.SAMPLE_X:
         return None
-    if mode not in (_lib.SAMPLE_EPS, _lib.SAMPLE_SCALED_EPS, _lib.SAMPLE_ODE):
+    if mode not in (_lib.SAMPLE_EPS, _lib.SAMPLE_SCALED_EPS, _lib.SAMPLE_ODE, _lib.SAMPLE_V):
         raise ValueError(f"x0_tables: unknown mode {mode!r}")
     steps = int(steps)
     u, v = np.zeros(steps + 1, dtype=np.float32), np.zeros(steps + 1, dtype=np.float32)
@@ -496,6 +615,8 @@ def x0_tables(steps: int, mode: int, schedule=None, offset: float = 0.0) -> Opti
                 uu, vv = -((1 - a1) ** 0.5) / den, (1 - a) ** 0.5 / den
             elif mode == _lib.SAMPLE_EPS:
                 uu, vv = 1.0 / a ** 0.5, -((1 - a) ** 0.5) / a ** 0.5
+            elif mode == _lib.SAMPLE_V:
+                uu, vv = a ** 0.5, -((1 - a) ** 0.5)
             else:
                 uu, vv = 1.0 / a ** 0.5, -1.0 / a ** 0.5
         except ZeroDivisionError:
@@ -513,6 +634,7 @@ def x0_coefficients(t_int, steps: int, mode: int, schedule=None, offset: float =
         SAMPLE_EPS         u = 1 / sqrt(a),  v = -sqrt(1 - a) / sqrt(a)
         SAMPLE_SCALED_EPS  u = 1 / sqrt(a),  v = -1 / sqrt(a)
         SAMPLE_ODE         D = sqrt(a1) sqrt(1 - a) - sqrt(a) sqrt(1 - a1),  u = -sqrt(1 - a1) / D,  v = sqrt(1 - a) / D
+        SAMPLE_V           u = sqrt(a),  v = -sqrt(1 - a)
     each formed per timestep from Python floats (alpha_dash(t, steps, schedule, offset)), the way the sampler forms its coefficients,
     rounded to float32 once and gathered by t.  t_int: a tensor (the result stays on its device) or an array of integers in 1..steps;
     tables: the two [steps + 1] vectors of x0_tables already where t_int lives (an engine keeps them)."""
@@ -666,6 +788,15 @@ class TrainerState:
     # the image metrics of evaluation (evaluate_batch(metrics=...)): the [steps + 1] coefficient tables of the x0 estimate per (mode,
     # schedule, offset) and the SSIM window, on the device; they exist only after the first evaluation that asks for a metric
     _x0_tables = None
+    # the v objective (Salimans & Ho 2022; configure(predict_v=True)): the network predicts v = sqrt(alpha) eps - sqrt(1 - alpha) x, the
+    # target fits the (a, c, w) contract as (-sb, sa, 1) and neither estimate divides by a schedule root.  `Trainer` sets it before
+    # every step; predict_x is ignored while it is on
+    predict_v = False
+    # per-timestep loss weights (configure(loss_weighting=..., min_snr_gamma=...)): None (off), "min_snr", a callable f(snr, t) or a
+    # tuple of `steps` floats; set_loss_weighting() writes the pair.  With weights on the step is eager, takes the non-fused head path
+    # and computes loss and gradient through gct2_objective_loss_fwd_bwd; the [steps + 1] tables exist only after the first use
+    loss_weighting, min_snr_gamma = None, 5.0
+    _weight_tables = None
 
     @property
     def _ema(self) -> Optional[torch.Tensor]:
@@ -684,8 +815,9 @@ class TrainerState:
 
     def __init__(self, dtype: int, device: Optional[torch.device], steps: int, base_lr: float, warm_up: int, beta_1: float,
                  beta_2: float, epsilon: float, loss_scaling: bool, rng_seed: int, predict_x: bool, predict_scaled_epsilon: bool,
-                 prediction_weighting: bool, ordinary_differential_equation: bool, f32_matrix: bool):
+                 prediction_weighting: bool, ordinary_differential_equation: bool, f32_matrix: bool, predict_v: bool = False):
         who = type(self).__name__
+        check_predict_v(predict_v, predict_scaled_epsilon, prediction_weighting, ordinary_differential_equation)
         if f32_matrix and dtype != F32:
             raise ValueError(f"{who}: f32_matrix selects the fp32 matrix-core kernels and needs dtype F32")
         self.lib = _lib.load()
@@ -703,6 +835,8 @@ class TrainerState:
         self.beta_1, self.beta_2, self.epsilon = beta_1, beta_2, epsilon
         self.predict_x, self.predict_scaled_epsilon = predict_x, predict_scaled_epsilon
         self.prediction_weighting, self.ordinary_differential_equation = prediction_weighting, ordinary_differential_equation
+        if predict_v:
+            self.predict_v = True
         self.rng_seed, self.rng_offset_t, self.rng_offset_eps = rng_seed, 0, 0
         self._iterations = 0           # optimizer.iterations [TF] (with loss scaling the counter lives on the device)
         self.loss_scaling = loss_scaling
@@ -727,16 +861,95 @@ class TrainerState:
 
     # ---- the objective (train.py:238-252) ------------------------------------------------------------------------------------
     def default_objective(self) -> bool:
-        return default_objective(self.predict_x, self.ordinary_differential_equation)
+        return not self.predict_v and default_objective(self.predict_x, self.ordinary_differential_equation)
 
     def objective_weighted(self) -> bool:
         return objective_weighted(self.predict_x, self.prediction_weighting, self.ordinary_differential_equation)
 
     def objective_coefficients(self, t_int: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         if self._default_schedule():
-            return objective_coefficients(t_int, self.steps, *(getattr(self, k) for k in OBJECTIVE_SWITCHES))
+            return objective_coefficients(t_int, self.steps, *(getattr(self, k) for k in OBJECTIVE_SWITCHES), predict_v=self.predict_v)
         return objective_coefficients(t_int, self.steps, *(getattr(self, k) for k in OBJECTIVE_SWITCHES), schedule=self.noise_schedule,
-                                      offset=self.alpha_dash_offset, roots=self._schedule_tables()[1:])
+                                      offset=self.alpha_dash_offset, roots=self._schedule_tables()[1:], predict_v=self.predict_v)
+
+    # ---- per-timestep loss weights (min-SNR-gamma, Hang et al. 2023; a callable; a table) --------------------------------------------
+    def set_loss_weighting(self, kind=None, gamma: float = 5.0) -> None:
+        """which lambda(t) multiplies every image's loss: None (off), "min_snr" with its gamma, a callable f(snr, t) or a sequence of
+        `steps` floats (loss_weight_table).  The table is formed here on the host, so an unknown name, a weight that is negative or not
+        finite, a table of the wrong length, the named kind under an objective it is not defined for or a training loss the weighted
+        kernel does not compute is a ValueError before anything changes or is launched.  A setting like set_noise_schedule: it holds
+        from the next step on.  Optimizer launches the engine holds back are flushed first."""
+        kind, gamma = check_loss_weighting(kind, gamma)
+        why = getattr(self, "_weighting_forbidden", None)
+        if why and kind is not None:
+            raise ValueError(why)
+        if kind is not None:
+            self._weight_host(kind, gamma)
+            self._check_weighted_loss(kind)
+        self.flush_deferred()
+        self.loss_weighting, self.min_snr_gamma = kind, gamma
+
+    def _check_weighted_loss(self, kind) -> None:
+        if kind is not None and self.training_loss not in WEIGHTED_TRAINING_LOSSES:
+            raise ValueError(f"loss_weighting with training_loss {self.training_loss!r}: per-timestep weights are built for "
+                             f"{' and '.join(WEIGHTED_TRAINING_LOSSES)} (gct2_objective_loss_fwd_bwd)")
+
+    def _weighting_objective(self) -> Optional[str]:
+        return weighting_objective(*(getattr(self, k) for k in OBJECTIVE_SWITCHES), predict_v=self.predict_v)
+
+    def _weight_host(self, kind, gamma: float) -> dict:
+        """the host table of (kind, gamma, schedule, offset, steps, objective), formed once per engine (a callable is held by the key)"""
+        if self._weight_tables is None:
+            self._weight_tables = {}
+        objective = self._weighting_objective()
+        key = (kind, float(gamma) if isinstance(kind, str) else 0.0, self.noise_schedule, float(self.alpha_dash_offset), int(self.steps),
+               objective if isinstance(kind, str) else None)
+        if key not in self._weight_tables:
+            self._weight_tables[key] = dict(host=loss_weight_table(kind, gamma, self.steps, objective, self.noise_schedule,
+                                                                   self.alpha_dash_offset))
+        return self._weight_tables[key]
+
+    def check_step_settings(self) -> None:
+        """the settings `Trainer` rewrites between steps, checked together before a step, a Trainer.call or an evaluation launches
+        anything: predict_v against the other switches, the weighting against the objective and the training loss (ValueError)"""
+        check_predict_v(self.predict_v, self.predict_scaled_epsilon, self.prediction_weighting, self.ordinary_differential_equation)
+        if self.loss_weighting is not None:
+            self._check_weighted_loss(self.loss_weighting)
+            self._weight_host(self.loss_weighting, self.min_snr_gamma)
+
+    def _loss_weights(self, t_int: torch.Tensor) -> Optional[torch.Tensor]:
+        """per-image float32 lambda(t) of the weighting as it stands, gathered by t from the table on the device (uploaded once per
+        key); None while the weighting is off"""
+        if self.loss_weighting is None:
+            return None
+        entry = self._weight_host(self.loss_weighting, self.min_snr_gamma)
+        if "device" not in entry:
+            entry["device"] = torch.from_numpy(entry["host"]).to(self.device)
+        return entry["device"].index_select(0, t_int.to(torch.int64).clamp(0, self.steps)).contiguous()
+
+    def _objective_loss_launch(self, store: dict, pred: torch.Tensor, x: torch.Tensor, eps: Optional[torch.Tensor], t_int: torch.Tensor,
+                               dpred: Optional[torch.Tensor], loss: torch.Tensor, stream: int) -> tuple:
+        """gct2_objective_loss_fwd_bwd of the current objective, training loss ("mse" / "l1") and weighting on an fp32 [B,H,W,C]
+        prediction: the target is formed inside the kernel from x and eps, no target plane is written; dpred = None: the loss only.
+        Returns the per-image vectors (a, c, w, lam) it read: the caller keeps them alive until the stream has passed the launch."""
+        B, H, W, Cc = pred.shape
+        code = training_loss_code(self.training_loss)
+        key = ("objective", B, H, W, Cc)
+        if key not in store:
+            need = C.c_size_t(0)
+            _lib.check(self.lib.gct2_objective_loss_scratch(code, B, H, W, Cc, C.byref(need)), "gct2_objective_loss_scratch")
+            store[key] = torch.zeros(need.value, dtype=torch.float32, device=self.device)
+        scratch = store[key]
+        a = c = w = None
+        if not self.default_objective():
+            a, c, w = self.objective_coefficients(t_int)
+            if not self.objective_weighted():
+                w = None
+        lam = self._loss_weights(t_int)
+        ptr = lambda v: None if v is None else v.data_ptr()
+        call("gct2_objective_loss_fwd_bwd", code, pred.data_ptr(), x.data_ptr(), None if a is None else eps.data_ptr(), ptr(a), ptr(c), ptr(w),
+             ptr(lam), ptr(dpred), loss.data_ptr(), scratch.data_ptr(), scratch.numel(), B, H, W, Cc, self._ls_ptr(), stream)
+        return a, c, w, lam
 
     # ---- the noise schedule (train.py:85-93) ------------------------------------------------------------------------------------
     def set_noise_schedule(self, schedule="quadratic", offset: float = 0.0) -> None:
@@ -828,7 +1041,7 @@ class TrainerState:
 
     def _x0_coefficients(self, t_int: torch.Tensor) -> Tuple[int, Optional[torch.Tensor], Optional[torch.Tensor]]:
         """(mode, u, v) of x0_coefficients for the objective switches and the noise schedule as they stand"""
-        mode = x0_mode(self.predict_x, self.predict_scaled_epsilon, self.ordinary_differential_equation)
+        mode = x0_mode(self.predict_x, self.predict_scaled_epsilon, self.ordinary_differential_equation, predict_v=self.predict_v)
         if mode == _lib.SAMPLE_X:
             return mode, None, None
         if self._x0_tables is None:
@@ -894,6 +1107,7 @@ class TrainerState:
         if _lib._recording is not None:
             raise _lib.Gct2Error("evaluate_batch inside a plan recording: evaluation is not part of a train step")
         metrics = check_metrics(metrics)
+        self.check_step_settings()
         if x.dim() != 4 or x.shape[-1] != 3:
             raise ValueError(f"expected an NHWC batch [B,H,W,3], got {tuple(x.shape)}")
         index0 = int(index0)
@@ -931,6 +1145,10 @@ class TrainerState:
              scratch.data_ptr(), scratch.numel(), B, H, W, 3, basis.data_ptr() if basis is not None else None, s)
         # what the launches read stays alive with the engine until the next evaluation (and is what the tests restate the rows from)
         self.last_eval = dict(x=x, pred=pred, eps=None if default and eps is None else eps_buf, t_int=t_int, coef=(a, c, w), noised=noised)
+        lam = self._loss_weights(t_int)
+        if lam is not None:                                    # the weighted rows: one op on [B]; the caller can divide by loss_weight
+            rows = rows * lam
+            self.last_eval["loss_weight"] = lam
         if metrics:
             return rows, t_int.clone(), self._eval_metrics(metrics, store, x, pred, eps_buf, t_int)
         return rows, t_int.clone()

@@ -320,10 +320,10 @@ class VariantEngine(TrainerState):
                  predict_x: bool = True, predict_scaled_epsilon: bool = False, prediction_weighting: bool = False,
                  ordinary_differential_equation: bool = False, f32_matrix: bool = False, use_ema: bool = False,
                  ema_momentum: float = 0.99, timestep_heads: bool = False, hidden_dense: bool = False,
-                 head_initializer: str = "glorot_uniform"):
+                 head_initializer: str = "glorot_uniform", predict_v: bool = False):
         check_head_options(type(self).__name__, hidden_dense, timestep_heads, head_initializer)
         super().__init__(dtype, device, steps, base_lr, warm_up, beta_1, beta_2, epsilon, loss_scaling, rng_seed, predict_x,
-                         predict_scaled_epsilon, prediction_weighting, ordinary_differential_equation, f32_matrix)
+                         predict_scaled_epsilon, prediction_weighting, ordinary_differential_equation, f32_matrix, predict_v=predict_v)
         self.octaves = octaves
         self.timestep_heads = bool(timestep_heads)      # train.py:199, 203, 211-214; fixed here: it decides the shape of dense.w / dense.b
         self.hidden_dense = bool(hidden_dense)          # train.py:195-197; fixed here: it adds dense_hidden.w / .b and changes dense.w's shape
@@ -448,6 +448,7 @@ class VariantEngine(TrainerState):
         if x.dim() != 4 or x.shape[-1] != 3:
             raise ValueError(f"expected an NHWC batch [B,H,W,3], got {tuple(x.shape)}")
         self._refuse_training_on_averages()
+        self.check_step_settings()
         x = x.to(self.device, torch.float32).contiguous()
         B, H, W, _ = x.shape
         if H % (2 ** self.octaves) or W % (2 ** self.octaves):
@@ -461,11 +462,14 @@ class VariantEngine(TrainerState):
         noised, t_int, eps = self._noised(x, t_int, eps)
         self.net.t_int = t_int                                 # (the per-timestep heads read it inside their kernels)
         pred = self.top.fwd(noised)
-        target, w = self._objective(x, t_int, eps)
+        weights = self.loss_weighting is not None               # the target is then formed inside the loss kernel: no target plane
+        target, w = (None, None) if weights else self._objective(x, t_int, eps)
         if w is not None:
             call("gct2_mix_per_image", pred.data_ptr(), None, w.data_ptr(), None, pred.data_ptr(), B, H * W * 3, s)
         dpred = torch.empty_like(pred)
-        if self.training_loss != "mse":                        # train.py:265-280 (no gradient when there is no reverse pass)
+        if weights:                                            # set_loss_weighting: loss and gradient in one launch
+            self.last["coef"] = self._objective_loss_launch(self._loss_store, pred, x, eps, t_int, dpred if backward else None, self.loss, s)
+        elif self.training_loss != "mse":                        # train.py:265-280 (no gradient when there is no reverse pass)
             self._loss_launch(self._loss_store, pred, target.data_ptr(), dpred if backward else None, self.loss, s)
         else:
             call("gct2_mse_fwd_bwd", pred.data_ptr(), target.data_ptr(), dpred.data_ptr(), self.loss.data_ptr(), self.partials.data_ptr(), n, self._ls_ptr(), s)

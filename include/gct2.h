@@ -440,8 +440,13 @@ int gct2_diffusion_mix(int dtype, const float* x_theta, const float* eps_theta, 
  *   GCT2_SAMPLE_ODE        (ordinary_differential_equation)
  *                          x_theta = (pred sqrt(1-a) - fake sqrt(1-a1)) / (sqrt(a1) sqrt(1-a) - sqrt(a) sqrt(1-a1));
  *                          eps_theta is NOT touched (the reference never updates it in this branch; may be NULL).
+ *   GCT2_SAMPLE_V          (predict_v: the network predicts v = sqrt(a) eps - sqrt(1-a) x, Salimans & Ho 2022, "Progressive
+ *                          Distillation for Fast Sampling of Diffusion Models")
+ *                          x_theta = fl(fl(sa fake) - fl(sb pred));  eps_theta = fl(fl(sb fake) + fl(sa pred)),
+ *                          sa = (float)sqrt(a), sb = (float)sqrt(1 - a): nothing is divided, alpha = 0 is valid in this mode.
+ * Mode code 4 is reserved and refused (GCT2_EINVAL) by every entry point that takes a mode.
  */
-enum { GCT2_SAMPLE_X = 0, GCT2_SAMPLE_EPS = 1, GCT2_SAMPLE_SCALED_EPS = 2, GCT2_SAMPLE_ODE = 3 };
+enum { GCT2_SAMPLE_X = 0, GCT2_SAMPLE_EPS = 1, GCT2_SAMPLE_SCALED_EPS = 2, GCT2_SAMPLE_ODE = 3, GCT2_SAMPLE_V = 5 };
 /* alpha / alpha_prev are DOUBLES: the reference forms every coefficient (and the ODE denominator, a difference of nearly equal
  * products at steps = 200) from Python floats and only then multiplies fp32 tensors by it; the library does the same on the host. */
 int gct2_diffusion_update(int mode, const float* pred, const float* fake, double alpha, double alpha_prev, float* x_theta,
@@ -450,13 +455,14 @@ int gct2_diffusion_update(int mode, const float* pred, const float* fake, double
  * launch - gct2_diffusion_update, the clip of the x0 estimate and gct2_diffusion_mix to a_prev, without x_theta and eps_theta ever
  * reaching memory.  B images of per_image = H*W*C fp32 elements each, contiguous: pred, fake_in, fake_out and (may be NULL) x0_out are
  * [B * per_image]; out [B*H*W, C] (ldout) and (may be NULL) out2 (ldout2) are the network's input views in `dtype` as for
- * gct2_diffusion_mix.  fake_out may equal fake_in.  mode: GCT2_SAMPLE_X, _EPS or _SCALED_EPS; GCT2_SAMPLE_ODE is GCT2_EINVAL (that
- * network predicts one step back only).  a_t, a_prev, sigma2, clip are DOUBLES, like gct2_diffusion_update's.
- * GCT2_EINVAL unless a_t in [0, 1) (> 0 for the epsilon modes), a_prev in [0, 1], 0 <= sigma2 and (1.f - (float)a_prev) - (float)sigma2 >= 0,
+ * gct2_diffusion_mix.  fake_out may equal fake_in.  mode: GCT2_SAMPLE_X, _EPS, _SCALED_EPS or _V; GCT2_SAMPLE_ODE is GCT2_EINVAL (that
+ * network predicts one step back only), and so is the reserved code 4.  a_t, a_prev, sigma2, clip are DOUBLES, like gct2_diffusion_update's.
+ * GCT2_EINVAL unless a_t in [0, 1) (> 0 for the epsilon modes; 0 is valid for X and V), a_prev in [0, 1], 0 <= sigma2 and (1.f - (float)a_prev) - (float)sigma2 >= 0,
  * per_image a multiple of C, ldout >= C, B * per_image < 2^31.
  * Element i of image b, p = pred, f = fake_in; fp32, every operation rounded once (no fused multiply-add):
  *   update   sa = (float)sqrt(a_t), sb = (float)sqrt(1 - a_t) (square roots in double, one cast each), then gct2_diffusion_update:
- *              X: x = p, e = (f - sa p) / sb;   EPS: e = p, x = (f - p sb) / sa;   SCALED_EPS: e = p / sb, x = (f - p) / sa
+ *              X: x = p, e = (f - sa p) / sb;   EPS: e = p, x = (f - p sb) / sa;   SCALED_EPS: e = p / sb, x = (f - p) / sa;
+ *              V: x = sa f - sb p, e = sb f + sa p (each product and each sum rounded on its own)
  *   clip     only when clip > 0: c = (float)clip, x = x < -c ? -c : (x > c ? c : x) (a NaN stays NaN), then e = (f - sa x) / sb in
  *            every mode (eps re-derived from the clipped x0).  clip <= 0: x, e are gct2_diffusion_update's bits.
  *   re-noise A = (float)a_prev, S = (float)sigma2, cx = sqrtf(A), ce = sqrtf((1.f - A) - S), cz = sqrtf(S);
@@ -512,8 +518,8 @@ int gct2_diffusion_step_masked(int mode, int dtype, const float* pred, const flo
  * of the re-noising replaced by D = x + c (x - hist_in), the estimate extrapolated from the one of the step before.  c1 is a host scalar
  * (trainer_math.multistep_coefficient: h / (2 h_prev) in half-log-SNR), hist_in / hist_out one fp32 plane [B * per_image] carried
  * between steps.  There is no sigma2: the solver is deterministic.
- * Shapes, views, alignment freedom and GCT2_EINVAL rules are gct2_diffusion_step's: modes X / EPS / SCALED_EPS (ODE refused), a_t in
- * [0, 1) (> 0 for the epsilon modes), a_prev in [0, 1], per_image a multiple of C, ldout >= C, B * per_image < 2^31.
+ * Shapes, views, alignment freedom and GCT2_EINVAL rules are gct2_diffusion_step's: modes X / EPS / SCALED_EPS / V (ODE and the reserved
+ * code 4 refused), a_t in [0, 1) (> 0 for the epsilon modes), a_prev in [0, 1], per_image a multiple of C, ldout >= C, B * per_image < 2^31.
  * known and mask are both NULL (the plain step) or both non-NULL (the masked step: gct2_diffusion_step_masked's known [B * per_image]
  * and mask [B * per_image / C]); one without the other is GCT2_EINVAL.  seed, stream_id, offset0 and image_stride are read only in the
  * masked form, for the starting noise z0, with exactly the meaning they have in gct2_diffusion_step_masked.
@@ -621,6 +627,32 @@ int gct2_eval_loss_scratch(int kind, int B, int H, int W, int C, size_t* floats)
 int gct2_eval_loss_rows(int kind, const float* pred, const float* x, const float* eps, const float* a, const float* c,
                         const float* w, float* rows, float* scratch, size_t scratch_floats, int B, int H, int W, int C,
                         const float* basis, void* stream);
+
+/* ---- the training loss of an objective with per-image (per-timestep) weights, forward and backward in ONE pass ----------------------
+ * configure(loss_weighting=...) (min-SNR-gamma, Hang et al. 2023, "Efficient Diffusion Training via Min-SNR Weighting Strategy", a table
+ * or a callable): L = (1/B) sum_b lam[b] l_b with l_b the per-image loss of `kind`; not renormalised by sum(lam).  The objective's target
+ * is formed on load by gct2_eval_loss_rows' rule and never stored, so the step needs no target plane:
+ *   target = x | fl(a[b] * x) | fl(fl(a[b] * x) + fl(c[b] * eps));   p = w ? fl(w[b] * pred) : pred;   d = fl(target - p).
+ * pred, x, eps: fp32 [B,H,W,C] contiguous, C in 1..4, read only; a, c, w, lam: device float[B] or NULL (lam NULL: lambda = 1);
+ * dpred: fp32 [B,H,W,C] or NULL (the loss only: nothing but loss and scratch is written); it must not alias pred, x or eps.
+ * With n_img = H*W*C, n = B n_img, s = *loss_scale_ptr (1 when NULL), S_b the fp64 sum over image b, and g_b = fl(lam[b] * w[b]) when
+ * both are given, lam[b] or w[b] when one is, absent (no multiply) when both are NULL; fp32, every operation rounded once:
+ *   GCT2_LOSS_MSE  loss = (float)(sum_b (double)lam[b] * S_b((double)d * (double)d) / n)
+ *                  dpred = fl(s * fl(fl(d * k) * g_b)),  k = (float)(-2.0 / n)
+ *   GCT2_LOSS_L1   loss = (float)(sum_b (double)lam[b] * S_b(max(d, -d)) / n)
+ *                  dpred = fl(s * fl((d >= -d ? -k1 : k1) * g_b)),  k1 = (float)(1.0 / n)   (the tie and NaN rule of GCT2_LOSS_L1)
+ * loss is never multiplied by s.  No atomics; a work-group never mixes two images; work-groups leave fp64 partial sums in scratch and one
+ * finishing launch adds them in index order (per image, then over the images): the bits depend on the inputs alone.  Images need not
+ * start at 16-byte boundaries (n_img = 105).  scratch: device floats, 16-byte aligned, at least what gct2_objective_loss_scratch reports
+ * (host only, no launch).
+ * GCT2_EINVAL before any launch: kinds other than MSE / L1; NULL pred / x / loss / scratch; c without eps, or a and eps without c;
+ * non-positive dims or C outside 1..4; pointers not 4-byte aligned, scratch not 16-byte aligned; scratch_floats below the query's figure;
+ * B > 65535; n at or beyond 2^31; dpred equal to pred, x or eps.  Measured on one MI355X at 64x128x128x3:
+ * profiles/objective_loss_bench.json. */
+int gct2_objective_loss_scratch(int kind, int B, int H, int W, int C, size_t* floats);
+int gct2_objective_loss_fwd_bwd(int kind, const float* pred, const float* x, const float* eps, const float* a, const float* c,
+                                const float* w, const float* lam, float* dpred, float* loss, float* scratch, size_t scratch_floats,
+                                int B, int H, int W, int C, const float* loss_scale_ptr, void* stream);
 
 /* ---- image metrics of evaluation (Keras compile(metrics=[...]); tf.image.psnr / tf.image.ssim [TF]): PER IMAGE, in image space ----
  * The x0 estimate e of image b against the clean image x: mse[b], psnr[b] and ssim[b] (Wang et al. 2004 with the defaults of
