@@ -4,7 +4,7 @@ The directory name carries a hyphen (project convention); import it as `gan_clas
 (the alias package next to it extends its __path__ here).
 """
 from . import _lib, build, data, engine, model, sampler, trainer_math # noqa: F401
-from .data import ImageDataset                    # noqa: F401
+from .data import CachedImageDataset, ImageDataset, sample_picks  # noqa: F401
 from .sampler import encode, generate, log_sample, make_log_sample  # noqa: F401
 from ._lib import BF16, F16, F32, Gct2Error       # noqa: F401
 from .engine import Topology, UNetEngine          # noqa: F401

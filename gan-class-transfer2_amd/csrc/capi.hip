@@ -746,6 +746,17 @@ int gct2_image_prepare(const uint8_t* src, const int64_t* offsets, const int32_t
   return pw_image_prepare(src, offsets, dims, dst, B, size, S(stream));
 }
 
+int gct2_image_batch_cached(const uint8_t* pool, const int64_t* offsets, const int32_t* hw, int N, uint64_t seed, uint64_t first_sample,
+                            uint64_t sample_stride, int flags, const int32_t* picks_in, int32_t* picks_out, float* dst, int B, int size,
+                            void* stream) {
+  if (!pool || !offsets || !hw || !dst) return gct2_fail(GCT2_EINVAL, "image_batch_cached: null pointer (pool, offsets, hw, dst)");
+  if (B <= 0 || N <= 0 || size <= 0) return gct2_fail(GCT2_EINVAL, "image_batch_cached: B=%d N=%d size=%d must be positive", B, N, size);
+  if (size > 16384) return gct2_fail(GCT2_EINVAL, "image_batch_cached: size=%d is larger than 16384", size);
+  if (flags & ~(GCT2_DATA_SHUFFLE | GCT2_DATA_RANDOM_CROP | GCT2_DATA_FLIP)) return gct2_fail(GCT2_EINVAL, "image_batch_cached: unknown flag bits in %d", flags);
+  if (sample_stride == 0) return gct2_fail(GCT2_EINVAL, "image_batch_cached: sample_stride == 0");
+  return data_image_batch_cached(pool, offsets, hw, N, seed, first_sample, sample_stride, flags, picks_in, picks_out, dst, B, size, S(stream));
+}
+
 int gct2_mse_fwd_bwd(const float* pred, const float* target, float* dpred, float* loss, float* partials, size_t n,
                      const float* loss_scale_ptr, void* stream) {
   if (!pred || !target || !dpred || !loss || !partials || n == 0) return gct2_fail(GCT2_EINVAL, "mse_fwd_bwd: null pointer or n == 0");

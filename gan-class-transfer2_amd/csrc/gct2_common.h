@@ -104,6 +104,25 @@ __device__ __forceinline__ void clock_exit(unsigned long long* stamps, int waves
 #define GCT2_CLOCK_EXIT(stamps, nwaves, wave, lane)
 #endif
 
+// ---- Philox4x32-10 (Salmon et al. 2011), counter = (idx, stream), key = seed: the streams of include/gct2.h (pointwise.hip, data.hip)
+__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+  const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+  const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+  const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+  c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+}
+__device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t stream_id, uint64_t idx, uint32_t (&out)[4]) {
+  uint32_t c[4] = {(uint32_t)idx, (uint32_t)(idx >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32)};
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; r++) {
+    philox_round(c, k0, k1);
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) out[i] = c[i];
+}
+
 template <typename T> struct is16 { static constexpr bool value = sizeof(T) == 2; };
 
 template <typename T> __device__ __forceinline__ float to_f32(T v) { return (float)v; }
@@ -512,6 +531,10 @@ int pw_diffusion_start_image(int dtype, const float* known, double a, uint64_t s
                              int C, hipStream_t s);
 int pw_noise_edits(const float* eps, const float* dict, int K, float* out, int H, int W, int C, hipStream_t s);
 int pw_image_prepare(const uint8_t* src, const int64_t* offsets, const int32_t* dims, float* dst, int B, int size, hipStream_t s);
+// data.hip: gct2_image_batch_cached's one launch (arguments checked by the entry point)
+int data_image_batch_cached(const uint8_t* pool, const int64_t* offsets, const int32_t* hw, int N, uint64_t seed, uint64_t first_sample,
+                            uint64_t sample_stride, int flags, const int32_t* picks_in, int32_t* picks_out, float* dst, int B, int size,
+                            hipStream_t s);
 int pw_mse(const float* pred, const float* target, float* dpred, float* loss, float* partials, size_t n, const float* ls, hipStream_t s);
 int pw_relu_mask(int dtype, const void* act, int ldact, void* d, int ldd, size_t npix, int C, hipStream_t s);
 int pw_add(int dtype, void* dst, int lddst, const void* src, int ldsrc, size_t npix, int C, hipStream_t s);

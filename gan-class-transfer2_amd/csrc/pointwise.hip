@@ -9,24 +9,7 @@ namespace {
 
 constexpr int kMaxBlocks = 2048;   // 256 CUs x 8
 
-// ---- Philox4x32-10 (Salmon et al. 2011), counter = (idx, stream), key = seed -------------------------
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-  const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-  const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-  c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-}
-__device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t stream_id, uint64_t idx, uint32_t (&out)[4]) {
-  uint32_t c[4] = {(uint32_t)idx, (uint32_t)(idx >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32)};
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; i++) out[i] = c[i];
-}
+// (Philox4x32-10 itself: gct2_common.h - data.hip draws from the same streams)
 
 __global__ void rng_uniform_int_kernel(uint64_t seed, uint64_t stream_id, uint64_t offset, int32_t* out, size_t n,
                                        int lo, uint64_t range) {

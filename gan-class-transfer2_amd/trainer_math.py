@@ -450,6 +450,10 @@ EVAL_STREAM_T, EVAL_STREAM_EPS = 3, 4
 # ---- generation (sampler.generate; gct2_diffusion_start / gct2_diffusion_step) --------------------------------------------------------
 # the Philox stream id of generation's noise: streams 1 and 2 are the train step's, 3 and 4 evaluation's
 GENERATE_STREAM = 5
+# the Philox stream ids of the device-resident image cache (data.CachedImageDataset; gct2_image_batch_cached): crop origin and flip of a
+# running sample index, and the round keys of an epoch's permutation
+DATA_STREAM_AUG = 6
+DATA_STREAM_ORDER = 7
 
 
 def sampling_timesteps(steps: int, num_steps: int) -> list:

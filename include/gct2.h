@@ -556,6 +556,40 @@ int gct2_noise_edits(const float* eps, const float* dictionary, int K, float* ou
 int gct2_image_prepare(const uint8_t* src, const int64_t* offsets, const int32_t* dims, float* dst, int B, int size,
                        void* stream);
 
+/* ---- the device-resident image cache (train.py:317 `#.cache("cache")`, kept in HBM): shuffle, crop, flip and the cast of a whole
+ * batch in ONE launch that reads no host data.  pool: the decoded RGB images (u8, HWC) of the whole dataset back to back;
+ * offsets[i] (int64): byte offset of image i in pool; hw[i] = {H0, W0} (int32); N images.  dst: fp32 [B, size, size, 3],
+ *   dst[b,y,x,c] = pool[offsets[item] + ((oy+y) W0 + ox + (flip ? size-1-x : x)) 3 + c] / 128 - 1          (exact in fp32)
+ * with (item, oy, ox, flip) of sample b either read from picks_in[b] (int32 [B,4]; nothing is drawn) or, picks_in == NULL, drawn
+ * for the running sample index k = first_sample + b * sample_stride (uint64, wraps) - a batch is a function of (seed, k) alone,
+ * whatever the batch size.  philox(seed, sid, idx) below is the four words r[0..3] of counter idx on stream sid exactly as
+ * gct2_rng_uniform_int defines them; flags is a set of GCT2_DATA_* bits.
+ *   item   e = k / N, p = k % N.  Without GCT2_DATA_SHUFFLE item = p.  With it item = pi_e(p), a stateless permutation of [0, N)
+ *          per epoch e: N = 1 gives 0; else h = max(1, (bitlen(N-1) + 1) / 2), mask = 2^h - 1, ks = philox(seed, 7, e), round keys
+ *          kj = ks[j & 3] + j * 0x9E3779B9 (mod 2^32) for j = 0..7; v = p; one pass is L = v >> h, R = v & mask, eight rounds
+ *          (L, R) <- (R, L ^ (fmix32(R ^ kj) & mask)), v = (L << h) | R; the pass is repeated until v < N (cycle walking: the domain
+ *          2^(2h) is smaller than 4N); item = v.  fmix32 is murmur3's finaliser: x ^= x >> 16, x *= 0x85EBCA6B, x ^= x >> 13,
+ *          x *= 0xC2B2AE35, x ^= x >> 16.
+ *   crop   r = philox(seed, 6, k), (H0, W0) = hw[item].  With GCT2_DATA_RANDOM_CROP oy = (r[0] (H0-size+1)) >> 32 and
+ *          ox = (r[1] (W0-size+1)) >> 32 (64-bit products); without it the centre crop oy = (H0-size)/2, ox = (W0-size)/2.
+ *   flip   with GCT2_DATA_FLIP r[2] >> 31, else 0.
+ * picks_out (int32 [B,4] or NULL) receives the (item, oy, ox, flip) that were used.  The kernel cannot refuse at run time: a
+ * picks_in row whose item lies outside [0, N) or whose origin lies outside [0, H0-size] x [0, W0-size], and an hw entry smaller than
+ * size, are CLAMPED so that no address leaves the image (item into [0, N), the origin into the image, source pixels onto the last row /
+ * column), and picks_out[b] holds item = -1 with the clamped origin; a flip other than 0 counts as 1.
+ * size % 4 == 0 with a 16-byte aligned dst and a 4-byte aligned pool takes the wide path (four pixels per thread: aligned dword loads
+ * around their 12 source bytes, three 16-byte stores); anything else a per-element path with the same bits.  The wide path reads up
+ * to 3 bytes past the 12 it needs, so THE POOL CARRIES 16 SPARE BYTES BEHIND ITS LAST IMAGE (readable, any value): the caller
+ * guarantees it, as data.py's CachedImageDataset does.
+ * GCT2_EINVAL before any launch: a null pool, offsets, hw or dst; B, N or size <= 0, size > 16384; unknown flag bits;
+ * sample_stride == 0.  Measured on one MI355X: profiles/image_cache_bench.json. */
+#define GCT2_DATA_SHUFFLE 1
+#define GCT2_DATA_RANDOM_CROP 2
+#define GCT2_DATA_FLIP 4
+int gct2_image_batch_cached(const uint8_t* pool, const int64_t* offsets, const int32_t* hw, int N, uint64_t seed,
+                            uint64_t first_sample, uint64_t sample_stride, int flags, const int32_t* picks_in, int32_t* picks_out,
+                            float* dst, int B, int size, void* stream);
+
 /* loss = mean((target - pred)^2) in fp32 (train.py:272); dpred = loss_scale * 2 (pred-target)/n.
  * `loss` (1 float) is overwritten; `partials` is caller scratch of >= 1024 floats.
  * loss_scale_ptr: device pointer to the current loss scale (fp16 mode) or NULL for 1. */
