@@ -6,6 +6,8 @@ The directory name carries a hyphen (project convention); import it as `gan_clas
 from . import _lib, build, data, engine, model, sampler, trainer_math # noqa: F401
 from .data import CachedImageDataset, ImageDataset, sample_picks  # noqa: F401
 from .sampler import encode, generate, log_sample, make_log_sample  # noqa: F401
+from . import image_out                          # noqa: F401
+from .image_out import ImageWriter, SummarySink, generate_to_dir, grid_shape, image_grid, save_images, to_uint8  # noqa: F401
 from ._lib import BF16, F16, F32, Gct2Error       # noqa: F401
 from .engine import Topology, UNetEngine          # noqa: F401
 from .model import (Adam, Block, Dense, Denoiser, DownShuffle, InverseTimeDecay, LambdaCallback, LossScaleOptimizer,  # noqa: F401

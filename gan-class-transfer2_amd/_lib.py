@@ -34,6 +34,8 @@ LOSS_MSE, LOSS_L1, LOSS_MSE_POOLED, LOSS_DCT = 0, 1, 2, 3
 # gct2_image_batch_cached flag bits (include/gct2.h GCT2_DATA_*) and the spare bytes the pool carries behind its last image
 DATA_SHUFFLE, DATA_RANDOM_CROP, DATA_FLIP = 1, 2, 4
 DATA_POOL_PAD = 16
+# gct2_image_grid_u8 quantisation modes (include/gct2.h GCT2_U8_*)
+U8_SUMMARY, U8_DATASET, U8_UNIT = 0, 1, 2
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgct2.so")
@@ -89,6 +91,7 @@ SIGNATURES = {
     "gct2_noise_edits": [_vp, _vp, _i, _vp, _i, _i, _i, _vp],
     "gct2_image_prepare": [_vp, _vp, _vp, _vp, _i, _i, _vp],
     "gct2_image_batch_cached": [_vp, _vp, _vp, _i, _u64, _u64, _u64, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "gct2_image_grid_u8": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_uint32, _vp, _vp],
     "gct2_conv4s2_fwd": [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "gct2_conv4s2_dgrad": [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp],
     "gct2_conv4s2_wgrad": [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],

@@ -757,6 +757,21 @@ int gct2_image_batch_cached(const uint8_t* pool, const int64_t* offsets, const i
   return data_image_batch_cached(pool, offsets, hw, N, seed, first_sample, sample_stride, flags, picks_in, picks_out, dst, B, size, S(stream));
 }
 
+int gct2_image_grid_u8(const void* src, int dtype, int n, int H, int W, int mode, int cols, int rows, int pad, int scale, uint32_t fill_rgb,
+                       uint8_t* out, void* stream) {
+  if (!src || !out) return gct2_fail(GCT2_EINVAL, "image_grid_u8: null pointer (src, out)");
+  if (!dtype_ok(dtype)) return gct2_fail(GCT2_EINVAL, "image_grid_u8: unknown dtype %d", dtype);
+  if (mode != GCT2_U8_SUMMARY && mode != GCT2_U8_DATASET && mode != GCT2_U8_UNIT) return gct2_fail(GCT2_EINVAL, "image_grid_u8: unknown mode %d", mode);
+  if (n <= 0 || H <= 0 || W <= 0 || cols <= 0 || rows <= 0)
+    return gct2_fail(GCT2_EINVAL, "image_grid_u8: n=%d H=%d W=%d cols=%d rows=%d must be positive", n, H, W, cols, rows);
+  if ((long long)cols * rows < n) return gct2_fail(GCT2_EINVAL, "image_grid_u8: cols=%d x rows=%d cells do not hold n=%d images", cols, rows, n);
+  if (scale < 1 || scale > 16) return gct2_fail(GCT2_EINVAL, "image_grid_u8: scale=%d is outside 1..16", scale);
+  if (pad < 0 || pad > 64) return gct2_fail(GCT2_EINVAL, "image_grid_u8: pad=%d is outside 0..64", pad);
+  if (H > 16384 || W > 16384) return gct2_fail(GCT2_EINVAL, "image_grid_u8: H=%d W=%d is larger than 16384", H, W);
+  if (fill_rgb >> 24) return gct2_fail(GCT2_EINVAL, "image_grid_u8: fill_rgb=0x%08x has bits above its 24", fill_rgb);
+  return img_grid_u8(src, dtype, n, H, W, mode, cols, rows, pad, scale, fill_rgb, out, S(stream));
+}
+
 int gct2_mse_fwd_bwd(const float* pred, const float* target, float* dpred, float* loss, float* partials, size_t n,
                      const float* loss_scale_ptr, void* stream) {
   if (!pred || !target || !dpred || !loss || !partials || n == 0) return gct2_fail(GCT2_EINVAL, "mse_fwd_bwd: null pointer or n == 0");

@@ -535,6 +535,9 @@ int pw_image_prepare(const uint8_t* src, const int64_t* offsets, const int32_t* 
 int data_image_batch_cached(const uint8_t* pool, const int64_t* offsets, const int32_t* hw, int N, uint64_t seed, uint64_t first_sample,
                             uint64_t sample_stride, int flags, const int32_t* picks_in, int32_t* picks_out, float* dst, int B, int size,
                             hipStream_t s);
+// image_out.hip: gct2_image_grid_u8's one launch (arguments checked by the entry point; the grid's own size limits here)
+int img_grid_u8(const void* src, int dtype, int n, int H, int W, int mode, int cols, int rows, int pad, int scale, uint32_t fill_rgb,
+                uint8_t* out, hipStream_t s);
 int pw_mse(const float* pred, const float* target, float* dpred, float* loss, float* partials, size_t n, const float* ls, hipStream_t s);
 int pw_relu_mask(int dtype, const void* act, int ldact, void* d, int ldd, size_t npix, int C, hipStream_t s);
 int pw_add(int dtype, void* dst, int lddst, const void* src, int ldsrc, size_t npix, int C, hipStream_t s);

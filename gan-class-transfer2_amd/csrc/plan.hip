@@ -46,7 +46,7 @@ const Entry ENTRIES[] = {
     GCT2_ENTRY(gct2_objective_loss_fwd_bwd),
     GCT2_ENTRY(gct2_loss_scale_begin), GCT2_ENTRY(gct2_scale_check_finite), GCT2_ENTRY(gct2_loss_scale_update),
     GCT2_ENTRY(gct2_diffusion_mix), GCT2_ENTRY(gct2_diffusion_update), GCT2_ENTRY(gct2_noise_edits), GCT2_ENTRY(gct2_image_prepare),
-    GCT2_ENTRY(gct2_image_batch_cached),
+    GCT2_ENTRY(gct2_image_batch_cached), GCT2_ENTRY(gct2_image_grid_u8),
     GCT2_ENTRY(gct2_diffusion_step), GCT2_ENTRY(gct2_diffusion_start),
     GCT2_ENTRY(gct2_diffusion_step_masked), GCT2_ENTRY(gct2_diffusion_start_image), GCT2_ENTRY(gct2_diffusion_step_multistep),
 };

@@ -692,6 +692,13 @@ class Denoiser(Layer):
         from .sampler import generate
         return generate(self, n, **kw)
 
+    def generate_to_dir(self, n: int, directory: str, **kw):
+        """n new images as n PNG files in `directory`: image_out.generate_to_dir(self, n, directory, ...) - generate batch by batch, one
+        gct2_image_grid_u8 launch and one copy per batch, the PNG encoder on a bounded thread pool beside the next batch; pattern, mode,
+        writer, and every keyword of generate but return_steps.  Returns the paths"""
+        from .image_out import generate_to_dir
+        return generate_to_dir(self, n, directory, **kw)
+
     def encode(self, images, **kw):
         """images [n,H,W,3] into latents, fp32 [n,H,W,3] on the device: sampler.encode(self, images, ...) - strided DDIM inversion with
         num_steps, timesteps, batch_size, use_ema, use_graph, start_eps; generate(noise=latent, timesteps=...) decodes them;

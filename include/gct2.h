@@ -590,6 +590,36 @@ int gct2_image_batch_cached(const uint8_t* pool, const int64_t* offsets, const i
                             uint64_t first_sample, uint64_t sample_stride, int flags, const int32_t* picks_in, int32_t* picks_out,
                             float* dst, int B, int size, void* stream);
 
+/* ---- samples as pictures (the other end of the pipeline: what train.py:356, 489-496 hand to tf.summary.image): a batch quantised to
+ * uint8 and laid out as a grid of cells in ONE launch.  src: compact [n, H, W, 3] of `dtype` (GCT2_F32 | GCT2_BF16 | GCT2_F16; 16-bit
+ * values are widened to float32 exactly first).  out: u8 [GH, GW, 3] with
+ *   GH = rows H scale + (rows + 1) pad,   GW = cols W scale + (cols + 1) pad.
+ * Image i sits in cell (i / cols, i % cols), whose origin is (pad + r (H scale + pad), pad + c (W scale + pad)); pixel (y, x) of a
+ * cell is source pixel (y / scale, x / scale): nearest-neighbour integer upscaling.  The padding and the cells i >= n hold fill_rgb
+ * (R = bits 0-7, G = 8-15, B = 16-23).  EVERY BYTE OF out IS WRITTEN BY THE ONE LAUNCH: the caller does no memset.  cols = 1,
+ * pad = 0, scale = 1 is the plain conversion [n, H, W, 3] -> u8 [n, H, W, 3].
+ * Quantisation, fl() one float32 rounding to nearest even:
+ *   GCT2_U8_SUMMARY   z = fl(255.5 fl(fl(0.5 x) + 0.5))     x in [-1, 1]: tf.summary.image(x * 0.5 + 0.5), train.py:356, 489-496
+ *   GCT2_U8_DATASET   z = fl(fl(128 x) + 128.5)              the exact inverse of the loader's value / 128 - 1 (train.py:292)
+ *   GCT2_U8_UNIT      z = fl(255.5 x)                         x already in [0, 1]: masks, weights
+ *   q = 0 for a NaN or z < 1,  255 for z >= 255,  (uint8)trunc(z) otherwise.
+ * 0.5 x and 128 x are exact or overflow to the same infinity, so fma(0.5, x, 0.5) and fl(fl(0.5 x) + 0.5) are the same float, and so
+ * are the two forms of DATASET: the bits do not depend on whether a compiler contracts the multiply-add.  SUMMARY is
+ * tf.image.convert_image_dtype(..., uint8, saturate=True) as tf.summary.image applies it to floats - scale by max + 0.5, saturate,
+ * truncate; parity with TensorFlow is unpinned (there is none here to compare with), and NaN -> 0 is this library's choice.  DATASET
+ * gives q = v for every x = v / 128 - 1, v = 0..255; SUMMARY on the same inputs gives floor(511 v / 512), so 255 -> 254.
+ * All indexing into src and out is size_t: n H W 3 and GH GW 3 may both exceed 2^31.  GW % 4 == 0 with a 4-byte aligned out takes the
+ * wide path (a thread owns four adjacent output pixels: three dword stores, the sources as 16-byte loads where scale == 1 and the four
+ * lie inside one image); anything else a per-pixel path with the same bits.  No strided or ld = 4 sources, no dithering.
+ * GCT2_EINVAL before any launch: a null src or out; an unknown dtype or mode; n, H, W, cols or rows <= 0; cols rows < n; scale outside
+ * 1..16; pad outside 0..64; H or W above 16384; fill_rgb with a non-zero top byte; GH or GW above 2^31 - 1; a work-group count above
+ * 2^31 - 1.  Measured on one MI355X: profiles/image_out_bench.json. */
+#define GCT2_U8_SUMMARY 0   /* tf.summary.image(x * 0.5 + 0.5): train.py:356, 489-496 */
+#define GCT2_U8_DATASET 1   /* exact inverse of the loader's value/128 - 1 (train.py:292) */
+#define GCT2_U8_UNIT    2   /* input already in [0,1]: masks, weights */
+int gct2_image_grid_u8(const void* src, int dtype, int n, int H, int W, int mode, int cols, int rows, int pad, int scale,
+                       uint32_t fill_rgb, uint8_t* out, void* stream);
+
 /* loss = mean((target - pred)^2) in fp32 (train.py:272); dpred = loss_scale * 2 (pred-target)/n.
  * `loss` (1 float) is overwritten; `partials` is caller scratch of >= 1024 floats.
  * loss_scale_ptr: device pointer to the current loss scale (fp16 mode) or NULL for 1. */
