@@ -665,73 +665,105 @@ static int step_views_ok(const char* who, int dtype, const float* fake_out, cons
   return GCT2_OK;
 }
 
+// the scalars every step shares, in the order every step checks them: the objective mode in front of the pointers and views ...
+static int step_mode_ok(const char* who, int mode) {
+  if ((mode < GCT2_SAMPLE_X || mode > GCT2_SAMPLE_SCALED_EPS) && mode != GCT2_SAMPLE_V)
+    return gct2_fail(GCT2_EINVAL, "%s: mode %d (the ODE objective predicts one step back only: gct2_diffusion_update)", who, mode);
+  return GCT2_OK;
+}
+// ... a_t and a_prev behind them
+static int step_scalars_ok(const char* who, int mode, double a_t, double a_prev) {
+  if (!(a_t >= 0. && a_t < 1.)) return gct2_fail(GCT2_EINVAL, "%s: a_t must be in [0, 1)", who);
+  if (mode != GCT2_SAMPLE_X && mode != GCT2_SAMPLE_V && !(a_t > 0.))
+    return gct2_fail(GCT2_EINVAL, "%s: this mode divides by sqrt(a_t): a_t must be > 0", who);
+  if (!(a_prev >= 0. && a_prev <= 1.)) return gct2_fail(GCT2_EINVAL, "%s: a_prev must be in [0, 1]", who);
+  return GCT2_OK;
+}
+static int step_sigma2_ok(const char* who, double a_prev, double sigma2) {
+  if (!(sigma2 >= 0.) || !((1.f - (float)a_prev) - (float)sigma2 >= 0.f)) return gct2_fail(GCT2_EINVAL, "%s: sigma2 must be in [0, 1 - a_prev]", who);
+  return GCT2_OK;
+}
+// the fields every step fills the same way
+static SamplerStep step_views(int mode, int dtype, uint64_t seed, uint64_t stream_id, uint64_t image_stride, float* fake_out, void* out,
+                              int ldout, void* out2, int ldout2, int B, size_t per_image, int C) {
+  SamplerStep st;
+  st.mode = mode; st.dtype = dtype;
+  st.seed = seed; st.stream_id = stream_id; st.image_stride = image_stride;
+  st.fake_out = fake_out; st.out = out; st.ldout = ldout; st.out2 = out2; st.ldout2 = ldout2;
+  st.B = B; st.per_image = per_image; st.C = C;
+  return st;
+}
+
 int gct2_diffusion_step(int mode, int dtype, const float* pred, const float* fake_in, double a_t, double a_prev, double sigma2, double clip,
                         uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t image_stride, float* fake_out, float* x0_out, void* out,
                         int ldout, void* out2, int ldout2, int B, size_t per_image, int C, void* stream) {
-  if ((mode < GCT2_SAMPLE_X || mode > GCT2_SAMPLE_SCALED_EPS) && mode != GCT2_SAMPLE_V)
-    return gct2_fail(GCT2_EINVAL, "diffusion_step: mode %d (the ODE objective predicts one step back only: gct2_diffusion_update)", mode);
-  if (!pred || !fake_in) return gct2_fail(GCT2_EINVAL, "diffusion_step: null pointer");
-  if (int rc = step_views_ok("diffusion_step", dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
-  if (!(a_t >= 0. && a_t < 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step: a_t must be in [0, 1)");
-  if (mode != GCT2_SAMPLE_X && mode != GCT2_SAMPLE_V && !(a_t > 0.)) return gct2_fail(GCT2_EINVAL, "diffusion_step: this mode divides by sqrt(a_t): a_t must be > 0");
-  if (!(a_prev >= 0. && a_prev <= 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step: a_prev must be in [0, 1]");
-  if (!(sigma2 >= 0.) || !((1.f - (float)a_prev) - (float)sigma2 >= 0.f))
-    return gct2_fail(GCT2_EINVAL, "diffusion_step: sigma2 must be in [0, 1 - a_prev]");
-  return pw_diffusion_step(mode, dtype, pred, fake_in, a_t, a_prev, sigma2, clip, seed, stream_id, offset, image_stride, fake_out, x0_out, out,
-                           ldout, out2, ldout2, B, per_image, C, S(stream));
+  const char* who = "diffusion_step";
+  if (int rc = step_mode_ok(who, mode)) return rc;
+  if (!pred || !fake_in) return gct2_fail(GCT2_EINVAL, "%s: null pointer", who);
+  if (int rc = step_views_ok(who, dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
+  if (int rc = step_scalars_ok(who, mode, a_t, a_prev)) return rc;
+  if (int rc = step_sigma2_ok(who, a_prev, sigma2)) return rc;
+  SamplerStep st = step_views(mode, dtype, seed, stream_id, image_stride, fake_out, out, ldout, out2, ldout2, B, per_image, C);
+  st.pred = pred; st.fake_in = fake_in; st.a = a_t; st.a_prev = a_prev; st.sigma2 = sigma2; st.clip = clip;
+  st.offset = offset; st.x0_out = x0_out;
+  return pw_sampler_step(who, st, S(stream));
 }
 
 int gct2_diffusion_start(int dtype, uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t image_stride, float* fake_out, void* out,
                          int ldout, void* out2, int ldout2, int B, size_t per_image, int C, void* stream) {
-  if (int rc = step_views_ok("diffusion_start", dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
-  return pw_diffusion_start(dtype, seed, stream_id, offset, image_stride, fake_out, out, ldout, out2, ldout2, B, per_image, C, S(stream));
+  const char* who = "diffusion_start";
+  if (int rc = step_views_ok(who, dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
+  SamplerStep st = step_views(STEP_START, dtype, seed, stream_id, image_stride, fake_out, out, ldout, out2, ldout2, B, per_image, C);
+  st.offset = offset;
+  return pw_sampler_step(who, st, S(stream));
 }
 
 int gct2_diffusion_start_image(int dtype, const float* known, double a, uint64_t seed, uint64_t stream_id, uint64_t offset,
                                uint64_t image_stride, float* fake_out, void* out, int ldout, void* out2, int ldout2, int B, size_t per_image,
                                int C, void* stream) {
-  if (!known) return gct2_fail(GCT2_EINVAL, "diffusion_start_image: null pointer");
-  if (int rc = step_views_ok("diffusion_start_image", dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
-  if (!(a >= 0. && a <= 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_start_image: a must be in [0, 1]");
-  return pw_diffusion_start_image(dtype, known, a, seed, stream_id, offset, image_stride, fake_out, out, ldout, out2, ldout2, B, per_image, C,
-                                  S(stream));
+  const char* who = "diffusion_start_image";
+  if (!known) return gct2_fail(GCT2_EINVAL, "%s: null pointer", who);
+  if (int rc = step_views_ok(who, dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
+  if (!(a >= 0. && a <= 1.)) return gct2_fail(GCT2_EINVAL, "%s: a must be in [0, 1]", who);
+  SamplerStep st = step_views(STEP_START_IMAGE, dtype, seed, stream_id, image_stride, fake_out, out, ldout, out2, ldout2, B, per_image, C);
+  st.known = known; st.a = a; st.offset0 = offset;
+  return pw_sampler_step(who, st, S(stream));
 }
 
 int gct2_diffusion_step_masked(int mode, int dtype, const float* pred, const float* fake_in, const float* known, const float* mask, double a_t,
                                double a_prev, double sigma2, double clip, uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t offset0,
                                uint64_t image_stride, float* fake_out, float* x0_out, void* out, int ldout, void* out2, int ldout2, int B,
                                size_t per_image, int C, void* stream) {
-  if ((mode < GCT2_SAMPLE_X || mode > GCT2_SAMPLE_SCALED_EPS) && mode != GCT2_SAMPLE_V)
-    return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: mode %d (the ODE objective predicts one step back only: gct2_diffusion_update)", mode);
-  if (!pred || !fake_in || !known || !mask) return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: null pointer");
-  if (int rc = step_views_ok("diffusion_step_masked", dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
-  if (!(a_t >= 0. && a_t < 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: a_t must be in [0, 1)");
-  if (mode != GCT2_SAMPLE_X && mode != GCT2_SAMPLE_V && !(a_t > 0.))
-    return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: this mode divides by sqrt(a_t): a_t must be > 0");
-  if (!(a_prev >= 0. && a_prev <= 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: a_prev must be in [0, 1]");
-  if (!(sigma2 >= 0.) || !((1.f - (float)a_prev) - (float)sigma2 >= 0.f))
-    return gct2_fail(GCT2_EINVAL, "diffusion_step_masked: sigma2 must be in [0, 1 - a_prev]");
-  return pw_diffusion_step_masked(mode, dtype, pred, fake_in, known, mask, a_t, a_prev, sigma2, clip, seed, stream_id, offset, offset0,
-                                  image_stride, fake_out, x0_out, out, ldout, out2, ldout2, B, per_image, C, S(stream));
+  const char* who = "diffusion_step_masked";
+  if (int rc = step_mode_ok(who, mode)) return rc;
+  if (!pred || !fake_in || !known || !mask) return gct2_fail(GCT2_EINVAL, "%s: null pointer", who);
+  if (int rc = step_views_ok(who, dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
+  if (int rc = step_scalars_ok(who, mode, a_t, a_prev)) return rc;
+  if (int rc = step_sigma2_ok(who, a_prev, sigma2)) return rc;
+  SamplerStep st = step_views(mode, dtype, seed, stream_id, image_stride, fake_out, out, ldout, out2, ldout2, B, per_image, C);
+  st.pred = pred; st.fake_in = fake_in; st.known = known; st.mask = mask;
+  st.a = a_t; st.a_prev = a_prev; st.sigma2 = sigma2; st.clip = clip;
+  st.offset = offset; st.offset0 = offset0; st.x0_out = x0_out;
+  return pw_sampler_step(who, st, S(stream));
 }
 
 int gct2_diffusion_step_multistep(int mode, int dtype, const float* pred, const float* fake_in, const float* hist_in, const float* known,
                                   const float* mask, double a_t, double a_prev, double c1, double clip, uint64_t seed, uint64_t stream_id,
                                   uint64_t offset0, uint64_t image_stride, float* fake_out, float* hist_out, float* x0_out, void* out, int ldout,
                                   void* out2, int ldout2, int B, size_t per_image, int C, void* stream) {
-  if ((mode < GCT2_SAMPLE_X || mode > GCT2_SAMPLE_SCALED_EPS) && mode != GCT2_SAMPLE_V)
-    return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: mode %d (the ODE objective predicts one step back only: gct2_diffusion_update)", mode);
-  if (!pred || !fake_in) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: null pointer");
-  if (!known != !mask) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: known and mask go together (both NULL: the plain step)");
-  if (int rc = step_views_ok("diffusion_step_multistep", dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
-  if (!(a_t >= 0. && a_t < 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: a_t must be in [0, 1)");
-  if (mode != GCT2_SAMPLE_X && mode != GCT2_SAMPLE_V && !(a_t > 0.))
-    return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: this mode divides by sqrt(a_t): a_t must be > 0");
-  if (!(a_prev >= 0. && a_prev <= 1.)) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: a_prev must be in [0, 1]");
-  if (!std::isfinite(c1) || !std::isfinite((float)c1)) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: c1 must be finite in fp32");
-  if ((float)c1 != 0.f && !hist_in) return gct2_fail(GCT2_EINVAL, "diffusion_step_multistep: c1 != 0 extrapolates from hist_in, which is NULL");
-  return pw_diffusion_step_multistep(mode, dtype, pred, fake_in, hist_in, known, mask, a_t, a_prev, c1, clip, seed, stream_id, offset0,
-                                     image_stride, fake_out, hist_out, x0_out, out, ldout, out2, ldout2, B, per_image, C, S(stream));
+  const char* who = "diffusion_step_multistep";
+  if (int rc = step_mode_ok(who, mode)) return rc;
+  if (!pred || !fake_in) return gct2_fail(GCT2_EINVAL, "%s: null pointer", who);
+  if (!known != !mask) return gct2_fail(GCT2_EINVAL, "%s: known and mask go together (both NULL: the plain step)", who);
+  if (int rc = step_views_ok(who, dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
+  if (int rc = step_scalars_ok(who, mode, a_t, a_prev)) return rc;
+  if (!std::isfinite(c1) || !std::isfinite((float)c1)) return gct2_fail(GCT2_EINVAL, "%s: c1 must be finite in fp32", who);
+  if ((float)c1 != 0.f && !hist_in) return gct2_fail(GCT2_EINVAL, "%s: c1 != 0 extrapolates from hist_in, which is NULL", who);
+  SamplerStep st = step_views(mode, dtype, seed, stream_id, image_stride, fake_out, out, ldout, out2, ldout2, B, per_image, C);
+  st.pred = pred; st.fake_in = fake_in; st.hist_in = hist_in; st.known = known; st.mask = mask;
+  st.a = a_t; st.a_prev = a_prev; st.c1 = c1; st.clip = clip; st.multistep = true;
+  st.offset0 = offset0; st.hist_out = hist_out; st.x0_out = x0_out;
+  return pw_sampler_step(who, st, S(stream));
 }
 
 int gct2_noise_edits(const float* eps, const float* dictionary, int K, float* out, int H, int W, int C, void* stream) {

@@ -104,7 +104,8 @@ __device__ __forceinline__ void clock_exit(unsigned long long* stamps, int waves
 #define GCT2_CLOCK_EXIT(stamps, nwaves, wave, lane)
 #endif
 
-// ---- Philox4x32-10 (Salmon et al. 2011), counter = (idx, stream), key = seed: the streams of include/gct2.h (pointwise.hip, data.hip)
+// ---- Philox4x32-10 (Salmon et al. 2011), counter = (idx, stream), key = seed: the streams of include/gct2.h (pointwise.hip,
+// sampler.hip, data.hip)
 __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
   const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
   const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
@@ -121,6 +122,26 @@ __device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t stream_id,
   }
 #pragma unroll
   for (int i = 0; i < 4; i++) out[i] = c[i];
+}
+// Box-Muller on the hardware transcendental units: v_log_f32 (log2), v_sin_f32 / v_cos_f32 (argument in revolutions, so
+// u2 goes in as is).  Absolute error 5.3e-7 at most against a float64 Box-Muller of the same uniforms (measured on an MI355X over
+// 5e5 draws, profiles/rng_parity.json; tests/test_pointwise_exact_gpu.py bounds it) - a noise source, not a parity quantity (TF's
+// own stream cannot be reproduced) - and ~5x fewer instructions than libm's logf / sinf / cosf.
+__device__ __forceinline__ void box_muller(uint32_t r0, uint32_t r1, float& zc, float& zs) {
+  const float u1 = ((float)(r0 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float u2 = ((float)(r1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float rad = __builtin_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1));   // -2 ln u1 = -2 ln2 log2 u1
+  zc = rad * __builtin_amdgcn_cosf(u2);
+  zs = rad * __builtin_amdgcn_sinf(u2);
+}
+// element e uses counter e>>2; lanes (0,1) of the counter feed elements 4c,4c+1, lanes (2,3) feed 4c+2,4c+3
+__device__ __forceinline__ float philox_normal(uint64_t seed, uint64_t stream_id, uint64_t e) {
+  uint32_t r[4];
+  philox4x32_10(seed, stream_id, e >> 2, r);
+  const int pair = (int)((e >> 1) & 1);
+  float zc, zs;
+  box_muller(r[2 * pair], r[2 * pair + 1], zc, zs);
+  return (e & 1) ? zs : zc;
 }
 
 template <typename T> struct is16 { static constexpr bool value = sizeof(T) == 2; };
@@ -405,6 +426,37 @@ template <typename F> inline auto with_shadow16(const void* shadow, int dtype, F
   if (!shadow) return f(DTypeTag<float>{}, std::false_type{});
   return with_dtype16(dtype, [&](auto tag) { return f(tag, std::true_type{}); });
 }
+// with_sample_mode(mode, f) calls f(std::integral_constant<int, MODE>{}) for the objective modes of include/gct2.h (callers validate
+// the code; an unknown one takes the GCT2_SAMPLE_ODE arm) - the ONE place where a mode code turns into a template argument
+template <typename F> inline auto with_sample_mode(int mode, F&& f) {
+  if (mode == GCT2_SAMPLE_X) return f(std::integral_constant<int, GCT2_SAMPLE_X>{});
+  if (mode == GCT2_SAMPLE_EPS) return f(std::integral_constant<int, GCT2_SAMPLE_EPS>{});
+  if (mode == GCT2_SAMPLE_SCALED_EPS) return f(std::integral_constant<int, GCT2_SAMPLE_SCALED_EPS>{});
+  if (mode == GCT2_SAMPLE_V) return f(std::integral_constant<int, GCT2_SAMPLE_V>{});
+  return f(std::integral_constant<int, GCT2_SAMPLE_ODE>{});
+}
+
+// ---- host side: the grid of the streaming kernels (pointwise.hip, sampler.hip): a few work-groups per CU, grid-stride loops --------
+constexpr int kMaxBlocks = 2048;   // 256 CUs x 8
+inline int blocks_for(size_t n, int per_block) {
+  size_t b = (n + per_block - 1) / per_block;
+  return (int)(b < 1 ? 1 : (b > (size_t)kMaxBlocks ? kMaxBlocks : b));
+}
+
+// ---- one sampler step (sampler.hip: pw_sampler_step), filled by the five gct2_diffusion_step* / _start* entry points of capi.hip.
+// mode: an objective of include/gct2.h, or a start pseudo-mode: STEP_START (the value is the draw at offset), STEP_START_IMAGE (the
+// value is sqrt(a) known + sqrt(1 - a) z0, z0 drawn at offset0).  Pointers a call does not use stay nullptr
+constexpr int STEP_START = -1, STEP_START_IMAGE = -2;
+struct SamplerStep {
+  int mode = STEP_START, dtype = GCT2_F32;
+  const float *pred = nullptr, *fake_in = nullptr, *hist_in = nullptr, *known = nullptr, *mask = nullptr;
+  double a = 0., a_prev = 0., sigma2 = 0., c1 = 0., clip = 0.;
+  bool multistep = false;                              // gct2_diffusion_step_multistep's call (whatever c1 is)
+  uint64_t seed = 0, stream_id = 0, offset = 0, offset0 = 0, image_stride = 0;
+  float *fake_out = nullptr, *hist_out = nullptr, *x0_out = nullptr;
+  void* out = nullptr; int ldout = 0; void* out2 = nullptr; int ldout2 = 0;
+  int B = 0; size_t per_image = 0; int C = 0;
+};
 
 // ---- host side: every function one translation unit defines and another one calls, declared HERE and nowhere else (each defining
 // file includes this header, so a definition that drifts from its declaration does not compile) ---------------------------------------
@@ -510,25 +562,12 @@ int pw_head_finish(const float* part, int rows, float* dw, float* db, float* los
 int pw_dense_head_train(const gct2_ctx& c, int dtype, const void* x, int ld, const float* w, const float* b, const float* target, float* pred,
                         void* dx, int lddx, float* dw, float* db, float* loss, float* partials, int M, int Cin, int Cout, int Cmask,
                         const float* ls, float* db_dx, const void* x2, int ldx2, int accumulate, hipStream_t s);
+// sampler.hip: the sampler's pointwise steps; pw_sampler_step launches under the entry point's name `what`
 int pw_diffusion_mix(int dtype, const float* x, const float* e, float a, float* fake, void* out, int ldout, void* out2, int ldout2,
                      size_t npix, int C, hipStream_t s);
 int pw_diffusion_update(int mode, const float* pred, const float* fake, double a, double a1, float* x, float* e, size_t n, hipStream_t s);
-int pw_diffusion_step(int mode, int dtype, const float* pred, const float* fake_in, double a, double a_prev, double sigma2, double clip,
-                      uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t image_stride, float* fake_out, float* x0_out, void* out,
-                      int ldout, void* out2, int ldout2, int B, size_t per_image, int C, hipStream_t s);
-int pw_diffusion_start(int dtype, uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t image_stride, float* fake_out, void* out,
-                       int ldout, void* out2, int ldout2, int B, size_t per_image, int C, hipStream_t s);
-int pw_diffusion_step_masked(int mode, int dtype, const float* pred, const float* fake_in, const float* known, const float* mask, double a,
-                             double a_prev, double sigma2, double clip, uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t offset0,
-                             uint64_t image_stride, float* fake_out, float* x0_out, void* out, int ldout, void* out2, int ldout2, int B,
-                             size_t per_image, int C, hipStream_t s);
-int pw_diffusion_step_multistep(int mode, int dtype, const float* pred, const float* fake_in, const float* hist_in, const float* known,
-                                const float* mask, double a, double a_prev, double c1, double clip, uint64_t seed, uint64_t stream_id,
-                                uint64_t offset0, uint64_t image_stride, float* fake_out, float* hist_out, float* x0_out, void* out, int ldout,
-                                void* out2, int ldout2, int B, size_t per_image, int C, hipStream_t s);
-int pw_diffusion_start_image(int dtype, const float* known, double a, uint64_t seed, uint64_t stream_id, uint64_t offset,
-                             uint64_t image_stride, float* fake_out, void* out, int ldout, void* out2, int ldout2, int B, size_t per_image,
-                             int C, hipStream_t s);
+int pw_sampler_step(const char* what, const SamplerStep& st, hipStream_t s);
+// pointwise.hip again
 int pw_noise_edits(const float* eps, const float* dict, int K, float* out, int H, int W, int C, hipStream_t s);
 int pw_image_prepare(const uint8_t* src, const int64_t* offsets, const int32_t* dims, float* dst, int B, int size, hipStream_t s);
 // data.hip: gct2_image_batch_cached's one launch (arguments checked by the entry point)

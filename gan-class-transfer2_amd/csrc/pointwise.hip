@@ -7,9 +7,7 @@
 
 namespace {
 
-constexpr int kMaxBlocks = 2048;   // 256 CUs x 8
-
-// (Philox4x32-10 itself: gct2_common.h - data.hip draws from the same streams)
+// (Philox4x32-10, box_muller and philox_normal: gct2_common.h - sampler.hip and data.hip draw from the same streams)
 
 __global__ void rng_uniform_int_kernel(uint64_t seed, uint64_t stream_id, uint64_t offset, int32_t* out, size_t n,
                                        int lo, uint64_t range) {
@@ -22,26 +20,6 @@ __global__ void rng_uniform_int_kernel(uint64_t seed, uint64_t stream_id, uint64
   out[i] = (int32_t)((uint32_t)lo + (uint32_t)(((uint64_t)r[e & 3] * range) >> 32));
 }
 
-// Box-Muller on the hardware transcendental units: v_log_f32 (log2), v_sin_f32 / v_cos_f32 (argument in revolutions, so
-// u2 goes in as is).  Absolute error 5.3e-7 at most against a float64 Box-Muller of the same uniforms (measured on an MI355X over
-// 5e5 draws, profiles/rng_parity.json; tests/test_pointwise_exact_gpu.py bounds it) - a noise source, not a parity quantity (TF's
-// own stream cannot be reproduced) - and ~5x fewer instructions than libm's logf / sinf / cosf.
-__device__ __forceinline__ void box_muller(uint32_t r0, uint32_t r1, float& zc, float& zs) {
-  const float u1 = ((float)(r0 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  const float u2 = ((float)(r1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  const float rad = __builtin_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1));   // -2 ln u1 = -2 ln2 log2 u1
-  zc = rad * __builtin_amdgcn_cosf(u2);
-  zs = rad * __builtin_amdgcn_sinf(u2);
-}
-// element e uses counter e>>2; lanes (0,1) of the counter feed elements 4c,4c+1, lanes (2,3) feed 4c+2,4c+3
-__device__ __forceinline__ float philox_normal(uint64_t seed, uint64_t stream_id, uint64_t e) {
-  uint32_t r[4];
-  philox4x32_10(seed, stream_id, e >> 2, r);
-  const int pair = (int)((e >> 1) & 1);
-  float zc, zs;
-  box_muller(r[2 * pair], r[2 * pair + 1], zc, zs);
-  return (e & 1) ? zs : zc;
-}
 __global__ void rng_normal_kernel(uint64_t seed, uint64_t stream_id, uint64_t offset, float* out, size_t n) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = philox_normal(seed, stream_id, offset + i);
@@ -804,376 +782,6 @@ __global__ __launch_bounds__(1024) void dense_head_finish_kernel(const float* __
   }
 }
 
-// ---- log_sample (train.py:323-496): the sampler's pointwise steps, fp32 state ------------------------------------------------
-// fake = sqrt(a) x_theta + sqrt(1-a) eps_theta (train.py:372-375, 441-444); also stored in the compute dtype where the network
-// reads its input (packed image and/or the image slice of R_0)
-template <typename T>
-__global__ void diffusion_mix_kernel(const float* __restrict__ x, const float* __restrict__ e, float sa, float sb,
-                                     float* __restrict__ fake, T* __restrict__ out, int ldout, T* __restrict__ out2, int ldout2,
-                                     size_t n, int C) {
-  // plain IEEE multiplies and adds in the order of the formula, no FMA contraction: what an unfused TensorFlow op chain computes
-  // (train.py:372-375), and independent of the code around it (as for adam_keras_update)
-#pragma clang fp contract(off)
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float f = sa * x[i] + sb * e[i];
-    fake[i] = f;
-    const size_t pix = i / C;
-    const int c = (int)(i - pix * C);
-    out[pix * ldout + c] = from_f32<T>(f);
-    if (out2) out2[pix * ldout2 + c] = from_f32<T>(f);
-  }
-}
-// one sampler update from the prediction, by objective (train.py:338-355, 382-413, 452-479; modes of include/gct2.h):
-//   X: x = pred, e = (fake - sa x) / sb;  EPS: e = pred, x = (fake - pred sb) / sa;  SCALED_EPS: e = pred / sb, x = (fake - pred) / sa;
-//   ODE: x = (pred sb - fake sb1) / (sa1 sb - sa sb1), e untouched.  sa = sqrt(a_t), sb = sqrt(1 - a_t), sa1 / sb1 the same at t - 1.
-//   V: x = sa fake - sb pred, e = sb fake + sa pred (pred is v = sa eps - sb x, Salimans & Ho 2022): no division, a_t = 0 is valid.
-template <int MODE>
-__global__ void diffusion_update_kernel(const float* __restrict__ pred, const float* __restrict__ fake, float sa, float sb, float sb1, float den,
-                                        float* __restrict__ x, float* __restrict__ e, size_t n) {
-#pragma clang fp contract(off)          // (f - sa p) / sb etc. as separate roundings, like the reference's op chain (train.py:382-413)
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float p = pred[i], f = fake[i];
-    if (MODE == GCT2_SAMPLE_X) {
-      x[i] = p;
-      e[i] = (f - sa * p) / sb;
-    } else if (MODE == GCT2_SAMPLE_EPS) {
-      e[i] = p;
-      x[i] = (f - p * sb) / sa;
-    } else if (MODE == GCT2_SAMPLE_SCALED_EPS) {
-      e[i] = p / sb;
-      x[i] = (f - p) / sa;
-    } else if (MODE == GCT2_SAMPLE_V) {
-      x[i] = sa * f - sb * p;
-      e[i] = sb * f + sa * p;
-    } else {
-      x[i] = (p * sb - f * sb1) / den;
-    }
-  }
-}
-
-// ---- Denoiser.generate: one strided DDIM / DDPM step in ONE launch (include/gct2.h: gct2_diffusion_step, gct2_diffusion_start) ----
-// diffusion_update_kernel's x / e, the clip of x (and e re-derived from the clipped x), then the re-noising to a_prev with
-// diffusion_mix_kernel's arithmetic and stores - x_theta and eps_theta never reach memory.  Every operation rounds once.
-// STEP_START: no update at all, the value is the draw itself (gct2_diffusion_start).
-constexpr int STEP_START = -1;
-struct StepCoef { float sa, sb, clip, cx, ce, cz; };
-
-template <int MODE>
-__device__ __forceinline__ float step_update(float p, float f, const StepCoef& k, float& x) {
-#pragma clang fp contract(off)
-  float e;
-  if (MODE == GCT2_SAMPLE_X) {
-    x = p;
-    e = (f - k.sa * p) / k.sb;
-  } else if (MODE == GCT2_SAMPLE_EPS) {
-    e = p;
-    x = (f - p * k.sb) / k.sa;
-  } else if (MODE == GCT2_SAMPLE_SCALED_EPS) {
-    e = p / k.sb;
-    x = (f - p) / k.sa;
-  } else {                                  // GCT2_SAMPLE_V
-    x = k.sa * f - k.sb * p;
-    e = k.sb * f + k.sa * p;
-  }
-  if (k.clip > 0.f) {                       // (wave-uniform)  a NaN fails both comparisons and stays
-    const float c = k.clip;
-    x = x < -c ? -c : (x > c ? c : x);
-    e = (f - k.sa * x) / k.sb;
-  }
-  return k.cx * x + k.ce * e;
-}
-template <typename T>
-__device__ __forceinline__ void step_store(float v, size_t i, size_t pix, int c, float* fake_out, T* __restrict__ out, int ldout,
-                                           T* __restrict__ out2, int ldout2) {
-  fake_out[i] = v;
-  out[pix * ldout + c] = from_f32<T>(v);
-  if (out2) out2[pix * ldout2 + c] = from_f32<T>(v);
-}
-
-// one whole Philox counter: four consecutive elements from a flat index that is a multiple of 4, all planes 16-byte aligned - the fp32
-// planes move as 16-byte accesses, the compute-dtype copies element by element (a row holds C of them).  z: the four normals
-template <typename T, int MODE>
-__device__ __forceinline__ void step_quad(const float* __restrict__ pred, const float* fake_in, const StepCoef& k, const float (&z)[4], size_t i,
-                                          float* fake_out, float* __restrict__ x0_out, T* __restrict__ out, int ldout, T* __restrict__ out2,
-                                          int ldout2, int C) {
-#pragma clang fp contract(off)
-  f32x4_t v, x4;
-  if constexpr (MODE == STEP_START) {
-    v = f32x4_t{z[0], z[1], z[2], z[3]};
-  } else {
-    const f32x4_t p = *reinterpret_cast<const f32x4_t*>(pred + i), f = *reinterpret_cast<const f32x4_t*>(fake_in + i);
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      float x;
-      const float m = step_update<MODE>(p[j], f[j], k, x);
-      v[j] = m + k.cz * z[j];
-      x4[j] = x;
-    }
-    if (x0_out) *reinterpret_cast<f32x4_t*>(x0_out + i) = x4;
-  }
-  *reinterpret_cast<f32x4_t*>(fake_out + i) = v;
-  uint32_t pix = (uint32_t)i / (uint32_t)C;                       // B * per_image < 2^31 (checked by the entry point)
-  int c = (int)((uint32_t)i - pix * (uint32_t)C);
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    out[(size_t)pix * ldout + c] = from_f32<T>(v[j]);
-    if (out2) out2[(size_t)pix * ldout2 + c] = from_f32<T>(v[j]);
-    if (++c == C) { c = 0; ++pix; }
-  }
-}
-
-// sigma^2 == 0: nothing is drawn, the images are one flat range, one element per thread (fake_in may be fake_out: a thread reads its
-// element, then writes it).  Four elements per thread with 16-byte accesses measured SLOWER here (25.6 against 20.5 us at 64x128x128x3,
-// profiles/generate_bench.json): consecutive lanes then store their copies 4 elements apart
-template <typename T, int MODE>
-__global__ void diffusion_step_kernel(const float* __restrict__ pred, const float* fake_in, StepCoef k, float* fake_out,
-                                      float* __restrict__ x0_out, T* __restrict__ out, int ldout, T* __restrict__ out2, int ldout2, size_t n,
-                                      int C) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float x;
-    const float v = step_update<MODE>(pred[i], fake_in[i], k, x);
-    if (x0_out) x0_out[i] = x;
-    const uint32_t pix = (uint32_t)i / (uint32_t)C;               // B * per_image < 2^31 (checked by the entry point)
-    step_store<T>(v, i, pix, (int)((uint32_t)i - pix * (uint32_t)C), fake_out, out, ldout, out2, ldout2);
-  }
-}
-
-// with noise: element i of image b adds cz * (the normal of stream element offset + b image_stride + i).  noise_rng_kernel's scheme per
-// image (blockIdx.y walks the images): one thread per Philox counter = up to four consecutive elements, one Philox call and two
-// Box-Muller pairs; an image may start and end inside a counter, whatever offset, image_stride and per_image are.  The counter index
-// is 64 bits wide, so a range across a wrap of its low word needs nothing special.  VEC (the launcher: offset, image_stride and
-// per_image multiples of 4, 16-byte aligned planes - what generate passes): every counter lies inside its image and moves as 16-byte
-// accesses, 25.0 us where the general form takes 57.3 us (profiles/generate_bench.json)
-template <typename T, int MODE, bool VEC>
-__global__ void diffusion_step_rng_kernel(const float* __restrict__ pred, const float* fake_in, StepCoef k, uint64_t seed, uint64_t stream_id,
-                                          uint64_t offset, uint64_t image_stride, float* fake_out, float* __restrict__ x0_out,
-                                          T* __restrict__ out, int ldout, T* __restrict__ out2, int ldout2, int B, uint32_t per_image, int C) {
-#pragma clang fp contract(off)
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
-    const uint64_t base = offset + (uint64_t)b * image_stride, end = base + per_image;
-    const uint64_t c0 = base >> 2;
-    const size_t ncounters = (size_t)(((end + 3) >> 2) - c0);
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < ncounters; t += stride) {
-      const uint64_t ctr = c0 + t;
-      uint32_t r[4];
-      philox4x32_10(seed, stream_id, ctr, r);
-      float nrm[4];
-      box_muller(r[0], r[1], nrm[0], nrm[1]);
-      box_muller(r[2], r[3], nrm[2], nrm[3]);
-      if constexpr (VEC) {
-        step_quad<T, MODE>(pred, fake_in, k, nrm, (size_t)b * per_image + 4 * t, fake_out, x0_out, out, ldout, out2, ldout2, C);
-      } else {
-        const uint64_t e0 = 4 * ctr;
-        const uint64_t first = e0 < base ? base : e0;               // (< end: the counter range was cut to the image)
-        const uint32_t i0 = (uint32_t)b * per_image + (uint32_t)(first - base);   // B * per_image < 2^31 (checked by the entry point)
-        uint32_t pix = i0 / (uint32_t)C, c = i0 - pix * (uint32_t)C;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          const uint64_t e = e0 + j;
-          if (e < first || e >= end) continue;
-          const size_t i = (size_t)b * per_image + (size_t)(e - base);
-          float v;
-          if constexpr (MODE == STEP_START) {
-            v = nrm[j];
-          } else {
-            float x;
-            v = step_update<MODE>(pred[i], fake_in[i], k, x) + k.cz * nrm[j];
-            if (x0_out) x0_out[i] = x;
-          }
-          step_store<T>(v, i, pix, (int)c, fake_out, out, ldout, out2, ldout2);
-          if (++c == (uint32_t)C) { c = 0; ++pix; }
-        }
-      }
-    }
-  }
-}
-
-// ---- image-conditioned generation (include/gct2.h: gct2_diffusion_start_image, gct2_diffusion_step_masked) ----
-// STEP_START_IMAGE: no update, the value is h = cx known + ck z0 (diffusion_mix_kernel's arithmetic on the draw).  The masked step:
-// step_update's x and fake' (+ cz z when NOISE) become g, and the mask of the element's pixel selects between g and h (x and known for
-// x0_out).  Selects, not a blend, at m >= 1 and m <= 0: a NaN / infinity of g never reaches a kept pixel, a regenerated pixel has
-// diffusion_step's bits
-constexpr int STEP_START_IMAGE = -2;
-__device__ __forceinline__ float mask_select(float m, float g, float h) {
-#pragma clang fp contract(off)
-  return m >= 1.f ? g : (m <= 0.f ? h : m * g + (1.f - m) * h);
-}
-// one element: p, f, kn, m the loaded inputs, z0 / z the two draws.  Returns fake', x0 the composited estimate
-template <int MODE, bool NOISE>
-__device__ __forceinline__ float masked_element(float p, float f, float kn, float m, float z0, float z, const StepCoef& k, float ck, float& x0) {
-#pragma clang fp contract(off)
-  const float h = k.cx * kn + ck * z0;
-  if constexpr (MODE == STEP_START_IMAGE) {
-    x0 = kn;
-    return h;
-  } else {
-    float x;
-    float g = step_update<MODE>(p, f, k, x);
-    if constexpr (NOISE) g = g + k.cz * z;
-    x0 = mask_select(m, x, kn);
-    return mask_select(m, g, h);
-  }
-}
-// sigma^2 = 0 and the start from an image: only z0 is drawn.  The images as one flat range, one element per thread like
-// diffusion_step_kernel, z0 through philox_normal - a whole Philox call per element, and still the faster form: the masked step takes
-// 25.3 us against 28.8 us for a thread per Philox counter with 16-byte accesses, the start 20.3 against 26.1 us, at 64x128x128x3
-// (profiles/img2img_bench.json: consecutive lanes store their copies next to each other, as in diffusion_step_kernel).  Any offset0
-// and image_stride; fake_in may be fake_out (a thread reads its element, then writes it)
-template <typename T, int MODE>
-__global__ void diffusion_masked_flat_kernel(const float* __restrict__ pred, const float* fake_in, const float* __restrict__ known,
-                                             const float* __restrict__ mask, StepCoef k, float ck, uint64_t seed, uint64_t stream_id,
-                                             uint64_t offset0, uint64_t image_stride, float* fake_out, float* __restrict__ x0_out,
-                                             T* __restrict__ out, int ldout, T* __restrict__ out2, int ldout2, size_t n, uint32_t per_image,
-                                             int C) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const uint32_t b = (uint32_t)i / per_image, within = (uint32_t)i - b * per_image;      // n < 2^31 (checked by the entry point)
-    const float z0 = philox_normal(seed, stream_id, offset0 + (uint64_t)b * image_stride + within);
-    const uint32_t pix = (uint32_t)i / (uint32_t)C;
-    float x0, v;
-    if constexpr (MODE == STEP_START_IMAGE) {
-      v = masked_element<MODE, false>(0.f, 0.f, known[i], 0.f, z0, 0.f, k, ck, x0);
-    } else {
-      v = masked_element<MODE, false>(pred[i], fake_in[i], known[i], mask[pix], z0, 0.f, k, ck, x0);
-      if (x0_out) x0_out[i] = x0;
-    }
-    step_store<T>(v, i, pix, (int)((uint32_t)i - pix * (uint32_t)C), fake_out, out, ldout, out2, ldout2);
-  }
-}
-// ---- second-order multistep sampling (include/gct2.h: gct2_diffusion_step_multistep; DPM-Solver++ 2M, Lu et al. 2022) ----
-// step_update's clipped estimate x goes to the history plane as it is; the re-noising reads d = x + c (x - hist) in its place, with e
-// re-derived from d.  c == 0 (wave-uniform; the first step, and generate's last): step_update's own fake', the history is never read
-template <int MODE>
-__device__ __forceinline__ float multistep_element(float p, float f, const float* hist_in, size_t i, const StepCoef& k, float c, float& x) {
-#pragma clang fp contract(off)
-  const float g = step_update<MODE>(p, f, k, x);
-  if (c == 0.f) return g;
-  const float d = x + c * (x - hist_in[i]);
-  const float ed = (f - k.sa * d) / k.sb;
-  return k.cx * d + k.ce * ed;
-}
-// the plain form: diffusion_step_kernel's mapping, one element per thread.  fake_in may be fake_out and hist_in may be hist_out (a thread
-// reads its element of both, then writes it)
-template <typename T, int MODE>
-__global__ void diffusion_multistep_kernel(const float* __restrict__ pred, const float* fake_in, const float* hist_in, StepCoef k, float c,
-                                           float* fake_out, float* hist_out, float* __restrict__ x0_out, T* __restrict__ out, int ldout,
-                                           T* __restrict__ out2, int ldout2, size_t n, int C) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float x;
-    const float v = multistep_element<MODE>(pred[i], fake_in[i], hist_in, i, k, c, x);
-    if (hist_out) hist_out[i] = x;
-    if (x0_out) x0_out[i] = x;
-    const uint32_t pix = (uint32_t)i / (uint32_t)C;               // B * per_image < 2^31 (checked by the entry point)
-    step_store<T>(v, i, pix, (int)((uint32_t)i - pix * (uint32_t)C), fake_out, out, ldout, out2, ldout2);
-  }
-}
-// the masked form: diffusion_masked_flat_kernel's mapping and per-element Philox draw of z0, masked_element's selects over the
-// extrapolated g
-template <typename T, int MODE>
-__global__ void diffusion_multistep_masked_kernel(const float* __restrict__ pred, const float* fake_in, const float* hist_in,
-                                                  const float* __restrict__ known, const float* __restrict__ mask, StepCoef k, float ck, float c,
-                                                  uint64_t seed, uint64_t stream_id, uint64_t offset0, uint64_t image_stride, float* fake_out,
-                                                  float* hist_out, float* __restrict__ x0_out, T* __restrict__ out, int ldout,
-                                                  T* __restrict__ out2, int ldout2, size_t n, uint32_t per_image, int C) {
-#pragma clang fp contract(off)
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const uint32_t b = (uint32_t)i / per_image, within = (uint32_t)i - b * per_image;      // n < 2^31 (checked by the entry point)
-    const float z0 = philox_normal(seed, stream_id, offset0 + (uint64_t)b * image_stride + within);
-    const uint32_t pix = (uint32_t)i / (uint32_t)C;
-    const float kn = known[i], m = mask[pix];
-    float x;
-    const float g = multistep_element<MODE>(pred[i], fake_in[i], hist_in, i, k, c, x);
-    const float h = k.cx * kn + ck * z0;
-    if (hist_out) hist_out[i] = x;
-    if (x0_out) x0_out[i] = mask_select(m, x, kn);
-    step_store<T>(mask_select(m, g, h), i, pix, (int)((uint32_t)i - pix * (uint32_t)C), fake_out, out, ldout, out2, ldout2);
-  }
-}
-
-// with noise, two draws per element: diffusion_step_rng_kernel's scheme.  A thread owns one Philox counter of the STARTING noise (element
-// offset0 + b image_stride + i) and its up to four elements.  VEC (the launcher: offset, offset0, image_stride, per_image multiples of
-// 4, 16-byte aligned fp32 planes - what generate passes): the step's noise z sits at the same lanes of its own counter, one more Philox
-// call per thread, and the fp32 planes move as 16-byte accesses; the mask is read per element (a group of four spans up to three pixels
-// at C = 3); 28.1 us where the general form takes 76.1 us.  General form: z per element through philox_normal (the two draws may sit at
-// different lanes of their counters)
-template <typename T, int MODE, bool VEC>
-__global__ void diffusion_masked_rng_kernel(const float* __restrict__ pred, const float* fake_in, const float* __restrict__ known,
-                                            const float* __restrict__ mask, StepCoef k, float ck, uint64_t seed, uint64_t stream_id,
-                                            uint64_t offset, uint64_t offset0, uint64_t image_stride, float* fake_out,
-                                            float* __restrict__ x0_out, T* __restrict__ out, int ldout, T* __restrict__ out2, int ldout2,
-                                            int B, uint32_t per_image, int C) {
-#pragma clang fp contract(off)
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
-    const uint64_t base0 = offset0 + (uint64_t)b * image_stride, end0 = base0 + per_image;
-    const uint64_t base = offset + (uint64_t)b * image_stride;
-    const uint64_t c0 = base0 >> 2;
-    const size_t ncounters = (size_t)(((end0 + 3) >> 2) - c0);
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < ncounters; t += stride) {
-      const uint64_t ctr = c0 + t;
-      uint32_t r[4];
-      philox4x32_10(seed, stream_id, ctr, r);
-      float n0[4];
-      box_muller(r[0], r[1], n0[0], n0[1]);
-      box_muller(r[2], r[3], n0[2], n0[3]);
-      if constexpr (VEC) {
-        const size_t i = (size_t)b * per_image + 4 * t;           // B * per_image < 2^31 (checked by the entry point)
-        float nz[4];
-        philox4x32_10(seed, stream_id, (base >> 2) + t, r);
-        box_muller(r[0], r[1], nz[0], nz[1]);
-        box_muller(r[2], r[3], nz[2], nz[3]);
-        const f32x4_t kn = *reinterpret_cast<const f32x4_t*>(known + i), p = *reinterpret_cast<const f32x4_t*>(pred + i),
-                      f = *reinterpret_cast<const f32x4_t*>(fake_in + i);
-        f32x4_t v, x4;
-        const uint32_t pix0 = (uint32_t)i / (uint32_t)C;
-        const int ch0 = (int)((uint32_t)i - pix0 * (uint32_t)C);
-        uint32_t pix = pix0;
-        int c = ch0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          float x0;
-          v[j] = masked_element<MODE, true>(p[j], f[j], kn[j], mask[pix], n0[j], nz[j], k, ck, x0);
-          x4[j] = x0;
-          if (++c == C) { c = 0; ++pix; }
-        }
-        if (x0_out) *reinterpret_cast<f32x4_t*>(x0_out + i) = x4;
-        *reinterpret_cast<f32x4_t*>(fake_out + i) = v;
-        pix = pix0;
-        c = ch0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          out[(size_t)pix * ldout + c] = from_f32<T>(v[j]);
-          if (out2) out2[(size_t)pix * ldout2 + c] = from_f32<T>(v[j]);
-          if (++c == C) { c = 0; ++pix; }
-        }
-      } else {
-        const uint64_t e0 = 4 * ctr;
-        const uint64_t first = e0 < base0 ? base0 : e0;             // (< end0: the counter range was cut to the image)
-        const uint32_t i0 = (uint32_t)b * per_image + (uint32_t)(first - base0);   // B * per_image < 2^31 (checked by the entry point)
-        uint32_t pix = i0 / (uint32_t)C, c = i0 - pix * (uint32_t)C;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          const uint64_t e = e0 + j;
-          if (e < first || e >= end0) continue;
-          const uint32_t within = (uint32_t)(e - base0);
-          const size_t i = (size_t)b * per_image + within;
-          float x0;
-          const float v = masked_element<MODE, true>(pred[i], fake_in[i], known[i], mask[pix], n0[j], philox_normal(seed, stream_id, base + within),
-                                                     k, ck, x0);
-          if (x0_out) x0_out[i] = x0;
-          step_store<T>(v, i, pix, (int)c, fake_out, out, ldout, out2, ldout2);
-          if (++c == (uint32_t)C) { c = 0; ++pix; }
-        }
-      }
-    }
-  }
-}
 // the four noise variants of train.py:416-431 from one eps image [H,W,C]: out[0] = eps, out[1] = nearest-upsample x4 of the
 // 4x4 average pool, out[2] = rolled by one pixel along H and W, out[3] = per-pixel nearest entry of dictionary [H,W,K,C]
 __global__ void noise_edits_kernel(const float* __restrict__ eps, const float* __restrict__ dict, int K, float* __restrict__ out,
@@ -1703,11 +1311,6 @@ __global__ void ls_begin_schedule_kernel(gct2_loss_scale_state* s, int schedule,
   }
 }
 
-inline int blocks_for(size_t n, int per_block) {
-  size_t b = (n + per_block - 1) / per_block;
-  return (int)(b < 1 ? 1 : (b > (size_t)kMaxBlocks ? kMaxBlocks : b));
-}
-
 }  // namespace
 
 // ---- host launchers (called from capi.hip) ------------------------------------------------------------------
@@ -1887,161 +1490,6 @@ int pw_dense_head_train(const gct2_ctx& c, int dtype, const void* x, int ld, con
     hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0, s, partials, grid, loss, 1.0f / ((float)M * (float)Cout));
     return gct2_check_launch("dense_head_train");
   });
-}
-int pw_diffusion_mix(int dtype, const float* x, const float* e, float a, float* fake, void* out, int ldout, void* out2, int ldout2,
-                     size_t npix, int C, hipStream_t s) {
-  const size_t n = npix * C;
-  with_dtype(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    hipLaunchKernelGGL(diffusion_mix_kernel<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, x, e, sqrtf(a), sqrtf(1.f - a), fake,
-                       reinterpret_cast<T*>(out), ldout, reinterpret_cast<T*>(out2), ldout2, n, C);
-  });
-  return gct2_check_launch("diffusion_mix");
-}
-int pw_diffusion_update(int mode, const float* pred, const float* fake, double a, double a1, float* x, float* e, size_t n, hipStream_t s) {
-  const dim3 grid(blocks_for(n, 256)), block(256);
-  // every scalar in double first, like the Python floats of train.py:382-391, then one cast where it meets an fp32 tensor
-  const double dsa = sqrt(a), dsb = sqrt(1. - a), dsa1 = sqrt(a1), dsb1 = sqrt(1. - a1);
-  const float sa = (float)dsa, sb = (float)dsb, sb1 = (float)dsb1, den = (float)(dsa1 * dsb - dsa * dsb1);
-  if (mode == GCT2_SAMPLE_X) hipLaunchKernelGGL(diffusion_update_kernel<GCT2_SAMPLE_X>, grid, block, 0, s, pred, fake, sa, sb, sb1, den, x, e, n);
-  else if (mode == GCT2_SAMPLE_EPS) hipLaunchKernelGGL(diffusion_update_kernel<GCT2_SAMPLE_EPS>, grid, block, 0, s, pred, fake, sa, sb, sb1, den, x, e, n);
-  else if (mode == GCT2_SAMPLE_SCALED_EPS)
-    hipLaunchKernelGGL(diffusion_update_kernel<GCT2_SAMPLE_SCALED_EPS>, grid, block, 0, s, pred, fake, sa, sb, sb1, den, x, e, n);
-  else if (mode == GCT2_SAMPLE_V) hipLaunchKernelGGL(diffusion_update_kernel<GCT2_SAMPLE_V>, grid, block, 0, s, pred, fake, sa, sb, sb1, den, x, e, n);
-  else hipLaunchKernelGGL(diffusion_update_kernel<GCT2_SAMPLE_ODE>, grid, block, 0, s, pred, fake, sa, sb, sb1, den, x, e, n);
-  return gct2_check_launch("diffusion_update");
-}
-// the grid of the per-image kernels: x over the Philox counters of one image, y over the images, kMaxBlocks work-groups at the most
-static dim3 step_rng_grid(int B, size_t per_image) {
-  const int gx = blocks_for(per_image / 4 + 2, 256);
-  const int gy = std::max(1, std::min(B, kMaxBlocks / gx));
-  return dim3(gx, gy);
-}
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-int pw_diffusion_step(int mode, int dtype, const float* pred, const float* fake_in, double a, double a_prev, double sigma2, double clip,
-                      uint64_t seed, uint64_t sid, uint64_t off, uint64_t image_stride, float* fake_out, float* x0_out, void* out, int ldout,
-                      void* out2, int ldout2, int B, size_t per_image, int C, hipStream_t s) {
-  // sa, sb as pw_diffusion_update forms them; the re-noising coefficients from the fp32 a_prev like pw_diffusion_mix's
-  const float A = (float)a_prev, S = (float)sigma2;
-  const StepCoef k = {(float)sqrt(a), (float)sqrt(1. - a), clip > 0. ? (float)clip : 0.f, sqrtf(A), sqrtf((1.f - A) - S), sqrtf(S)};
-  const size_t n = (size_t)B * per_image;
-  // the four-element form of the with-noise kernel: every image starts on a Philox counter and on a 16-byte boundary
-  const bool vec = aligned16(pred) && aligned16(fake_in) && aligned16(fake_out) && aligned16(x0_out) && off % 4 == 0 && image_stride % 4 == 0 &&
-                   per_image % 4 == 0;
-  with_dtype(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    T *o = reinterpret_cast<T*>(out), *o2 = reinterpret_cast<T*>(out2);
-    auto launch = [&](auto m) {
-      constexpr int MODE = decltype(m)::value;
-      auto noisy = [&](auto v) {
-        hipLaunchKernelGGL((diffusion_step_rng_kernel<T, MODE, decltype(v)::value>), step_rng_grid(B, per_image), dim3(256), 0, s, pred, fake_in,
-                           k, seed, sid, off, image_stride, fake_out, x0_out, o, ldout, o2, ldout2, B, (uint32_t)per_image, C);
-      };
-      if (S == 0.f)
-        hipLaunchKernelGGL((diffusion_step_kernel<T, MODE>), dim3(blocks_for(n, 256)), dim3(256), 0, s, pred, fake_in, k, fake_out, x0_out, o,
-                           ldout, o2, ldout2, n, C);
-      else if (vec) noisy(std::true_type{});
-      else noisy(std::false_type{});
-    };
-    if (mode == GCT2_SAMPLE_X) launch(std::integral_constant<int, GCT2_SAMPLE_X>{});
-    else if (mode == GCT2_SAMPLE_EPS) launch(std::integral_constant<int, GCT2_SAMPLE_EPS>{});
-    else if (mode == GCT2_SAMPLE_V) launch(std::integral_constant<int, GCT2_SAMPLE_V>{});
-    else launch(std::integral_constant<int, GCT2_SAMPLE_SCALED_EPS>{});
-  });
-  return gct2_check_launch("diffusion_step");
-}
-int pw_diffusion_start(int dtype, uint64_t seed, uint64_t sid, uint64_t off, uint64_t image_stride, float* fake_out, void* out, int ldout,
-                       void* out2, int ldout2, int B, size_t per_image, int C, hipStream_t s) {
-  const bool vec = aligned16(fake_out) && off % 4 == 0 && image_stride % 4 == 0 && per_image % 4 == 0;
-  with_dtype(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    auto launch = [&](auto v) {
-      hipLaunchKernelGGL((diffusion_step_rng_kernel<T, STEP_START, decltype(v)::value>), step_rng_grid(B, per_image), dim3(256), 0, s,
-                         (const float*)nullptr, (const float*)nullptr, StepCoef{}, seed, sid, off, image_stride, fake_out, (float*)nullptr,
-                         reinterpret_cast<T*>(out), ldout, reinterpret_cast<T*>(out2), ldout2, B, (uint32_t)per_image, C);
-    };
-    if (vec) launch(std::true_type{});
-    else launch(std::false_type{});
-  });
-  return gct2_check_launch("diffusion_start");
-}
-int pw_diffusion_step_masked(int mode, int dtype, const float* pred, const float* fake_in, const float* known, const float* mask, double a,
-                             double a_prev, double sigma2, double clip, uint64_t seed, uint64_t sid, uint64_t off, uint64_t off0,
-                             uint64_t image_stride, float* fake_out, float* x0_out, void* out, int ldout, void* out2, int ldout2, int B,
-                             size_t per_image, int C, hipStream_t s) {
-  // pw_diffusion_step's coefficients, and ck of the kept region's forward process
-  const float A = (float)a_prev, S = (float)sigma2;
-  const StepCoef k = {(float)sqrt(a), (float)sqrt(1. - a), clip > 0. ? (float)clip : 0.f, sqrtf(A), sqrtf((1.f - A) - S), sqrtf(S)};
-  const float ck = sqrtf(1.f - A);
-  const size_t n = (size_t)B * per_image;
-  const bool vec = aligned16(pred) && aligned16(fake_in) && aligned16(known) && aligned16(fake_out) && aligned16(x0_out) && off % 4 == 0 &&
-                   off0 % 4 == 0 && image_stride % 4 == 0 && per_image % 4 == 0;
-  with_dtype(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    T *o = reinterpret_cast<T*>(out), *o2 = reinterpret_cast<T*>(out2);
-    auto launch = [&](auto m) {
-      constexpr int MODE = decltype(m)::value;
-      auto noisy = [&](auto v) {
-        hipLaunchKernelGGL((diffusion_masked_rng_kernel<T, MODE, decltype(v)::value>), step_rng_grid(B, per_image), dim3(256), 0, s, pred,
-                           fake_in, known, mask, k, ck, seed, sid, off, off0, image_stride, fake_out, x0_out, o, ldout, o2, ldout2, B,
-                           (uint32_t)per_image, C);
-      };
-      if (S == 0.f)
-        hipLaunchKernelGGL((diffusion_masked_flat_kernel<T, MODE>), dim3(blocks_for(n, 256)), dim3(256), 0, s, pred, fake_in, known, mask, k, ck,
-                           seed, sid, off0, image_stride, fake_out, x0_out, o, ldout, o2, ldout2, n, (uint32_t)per_image, C);
-      else if (vec) noisy(std::true_type{});
-      else noisy(std::false_type{});
-    };
-    if (mode == GCT2_SAMPLE_X) launch(std::integral_constant<int, GCT2_SAMPLE_X>{});
-    else if (mode == GCT2_SAMPLE_EPS) launch(std::integral_constant<int, GCT2_SAMPLE_EPS>{});
-    else if (mode == GCT2_SAMPLE_V) launch(std::integral_constant<int, GCT2_SAMPLE_V>{});
-    else launch(std::integral_constant<int, GCT2_SAMPLE_SCALED_EPS>{});
-  });
-  return gct2_check_launch("diffusion_step_masked");
-}
-int pw_diffusion_step_multistep(int mode, int dtype, const float* pred, const float* fake_in, const float* hist_in, const float* known,
-                                const float* mask, double a, double a_prev, double c1, double clip, uint64_t seed, uint64_t sid, uint64_t off0,
-                                uint64_t image_stride, float* fake_out, float* hist_out, float* x0_out, void* out, int ldout, void* out2,
-                                int ldout2, int B, size_t per_image, int C, hipStream_t s) {
-  // pw_diffusion_step's coefficients at sigma2 = 0, pw_diffusion_step_masked's ck
-  const float A = (float)a_prev, c = (float)c1;
-  const StepCoef k = {(float)sqrt(a), (float)sqrt(1. - a), clip > 0. ? (float)clip : 0.f, sqrtf(A), sqrtf(1.f - A), 0.f};
-  const float ck = sqrtf(1.f - A);
-  const size_t n = (size_t)B * per_image;
-  with_dtype(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    T *o = reinterpret_cast<T*>(out), *o2 = reinterpret_cast<T*>(out2);
-    auto launch = [&](auto m) {
-      constexpr int MODE = decltype(m)::value;
-      if (known)
-        hipLaunchKernelGGL((diffusion_multistep_masked_kernel<T, MODE>), dim3(blocks_for(n, 256)), dim3(256), 0, s, pred, fake_in, hist_in, known,
-                           mask, k, ck, c, seed, sid, off0, image_stride, fake_out, hist_out, x0_out, o, ldout, o2, ldout2, n,
-                           (uint32_t)per_image, C);
-      else
-        hipLaunchKernelGGL((diffusion_multistep_kernel<T, MODE>), dim3(blocks_for(n, 256)), dim3(256), 0, s, pred, fake_in, hist_in, k, c,
-                           fake_out, hist_out, x0_out, o, ldout, o2, ldout2, n, C);
-    };
-    if (mode == GCT2_SAMPLE_X) launch(std::integral_constant<int, GCT2_SAMPLE_X>{});
-    else if (mode == GCT2_SAMPLE_EPS) launch(std::integral_constant<int, GCT2_SAMPLE_EPS>{});
-    else if (mode == GCT2_SAMPLE_V) launch(std::integral_constant<int, GCT2_SAMPLE_V>{});
-    else launch(std::integral_constant<int, GCT2_SAMPLE_SCALED_EPS>{});
-  });
-  return gct2_check_launch("diffusion_step_multistep");
-}
-int pw_diffusion_start_image(int dtype, const float* known, double a, uint64_t seed, uint64_t sid, uint64_t off, uint64_t image_stride,
-                             float* fake_out, void* out, int ldout, void* out2, int ldout2, int B, size_t per_image, int C, hipStream_t s) {
-  const float A = (float)a;                      // pw_diffusion_mix's coefficients
-  StepCoef k = {};
-  k.cx = sqrtf(A);
-  const float ck = sqrtf(1.f - A);
-  const size_t n = (size_t)B * per_image;
-  with_dtype(dtype, [&](auto tag) {
-    using T = typename decltype(tag)::type;
-    hipLaunchKernelGGL((diffusion_masked_flat_kernel<T, STEP_START_IMAGE>), dim3(blocks_for(n, 256)), dim3(256), 0, s, (const float*)nullptr,
-                       (const float*)nullptr, known, (const float*)nullptr, k, ck, seed, sid, off, image_stride, fake_out, (float*)nullptr,
-                       reinterpret_cast<T*>(out), ldout, reinterpret_cast<T*>(out2), ldout2, n, (uint32_t)per_image, C);
-  });
-  return gct2_check_launch("diffusion_start_image");
 }
 int pw_noise_edits(const float* eps, const float* dict, int K, float* out, int H, int W, int C, hipStream_t s) {
   hipLaunchKernelGGL(noise_edits_kernel, dim3((H * W + 255) / 256), dim3(256), 0, s, eps, dict, K, out, H, W, C);
