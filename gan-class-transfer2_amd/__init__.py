@@ -17,4 +17,5 @@ from .trainer_math import METRICS, NOISE_SCHEDULES, alpha_table, noise_table, ss
 from .trainer_math import GENERATE_STREAM, ddim_sigma2, sampling_timesteps                 # noqa: F401
 from .trainer_math import check_mask, img2img_steps                                         # noqa: F401
 from .trainer_math import SOLVERS, half_log_snr, multistep_coefficient                      # noqa: F401
+from .trainer_math import quantile_rank                                                     # noqa: F401
 from .trainer_math import LOSS_WEIGHTINGS, loss_weight_table                                # noqa: F401

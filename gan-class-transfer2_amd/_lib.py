@@ -88,6 +88,10 @@ SIGNATURES = {
     "gct2_diffusion_start_image": [_i, _vp, _d, _u64, _u64, _u64, _u64, _vp, _vp, _i, _vp, _i, _i, _sz, _i, _vp],
     "gct2_diffusion_step_multistep": [_i, _i, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _i, _vp, _i, _i,
                                       _sz, _i, _vp],
+    "gct2_x0_quantile_scratch": [_i, _sz, C.POINTER(C.c_size_t)],
+    "gct2_x0_quantile": [_i, _vp, _vp, _d, C.c_uint32, _d, _vp, _vp, _vp, _sz, _i, _sz, _vp],
+    "gct2_diffusion_step_dynamic": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _u64, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _i,
+                                    _vp, _i, _i, _sz, _i, _vp],
     "gct2_noise_edits": [_vp, _vp, _i, _vp, _i, _i, _i, _vp],
     "gct2_image_prepare": [_vp, _vp, _vp, _vp, _i, _i, _vp],
     "gct2_image_batch_cached": [_vp, _vp, _vp, _i, _u64, _u64, _u64, _i, _vp, _vp, _vp, _i, _i, _vp],
@@ -223,7 +227,7 @@ def call(name: str, *args) -> None:
 
 # the entry points a plan can hold (csrc/plan.hip ENTRIES): everything that enqueues work on a stream + the one-shot ReLU plane
 PLANNABLE = frozenset(n for n, sig in SIGNATURES.items() if n == "gct2_ctx_set_relu_bits" or (
-    not n.startswith(("gct2_ctx_", "gct2_plan_", "gct2_loss_scale_init")) and n not in ("gct2_abi_version", "gct2_build_flags", "gct2_device_check", "gct2_stream_occupy", "gct2_sumsq_layout", "gct2_loss_scratch", "gct2_eval_loss_scratch", "gct2_objective_loss_scratch", "gct2_image_metrics_scratch", "gct2_dense_steps_scratch", "gct2_dense2_scratch")))
+    not n.startswith(("gct2_ctx_", "gct2_plan_", "gct2_loss_scale_init")) and n not in ("gct2_abi_version", "gct2_build_flags", "gct2_device_check", "gct2_stream_occupy", "gct2_sumsq_layout", "gct2_loss_scratch", "gct2_eval_loss_scratch", "gct2_objective_loss_scratch", "gct2_image_metrics_scratch", "gct2_dense_steps_scratch", "gct2_dense2_scratch", "gct2_x0_quantile_scratch")))
 _recording = None      # the Plan that is recording calls right now (one host thread drives an engine: _lib.call is not re-entrant)
 _FLOAT_STRUCT = struct.Struct("<f")
 _DOUBLE_STRUCT = struct.Struct("<d")

@@ -766,6 +766,53 @@ int gct2_diffusion_step_multistep(int mode, int dtype, const float* pred, const 
   return pw_sampler_step(who, st, S(stream));
 }
 
+int gct2_x0_quantile_scratch(int B, size_t per_image, size_t* bytes) {
+  if (!bytes || B <= 0 || per_image == 0 || (size_t)B * per_image >= ((size_t)1 << 31))
+    return gct2_fail(GCT2_EINVAL, "x0_quantile_scratch: null pointer or bad shape (B * per_image < 2^31)");
+  *bytes = pw_x0_quantile_scratch(B);
+  return GCT2_OK;
+}
+
+int gct2_x0_quantile(int mode, const float* pred, const float* fake, double a_t, uint32_t rank, double floor, float* rows, float* q_out,
+                     void* scratch, size_t scratch_bytes, int B, size_t per_image, void* stream) {
+  const char* who = "x0_quantile";
+  if (int rc = step_mode_ok(who, mode)) return rc;
+  if (!pred || (!fake && mode != GCT2_SAMPLE_X) || !rows || !scratch) return gct2_fail(GCT2_EINVAL, "%s: null pointer", who);
+  if (B <= 0 || per_image == 0 || (size_t)B * per_image >= ((size_t)1 << 31))
+    return gct2_fail(GCT2_EINVAL, "%s: bad shape (B * per_image < 2^31)", who);
+  if (!(a_t >= 0. && a_t < 1.)) return gct2_fail(GCT2_EINVAL, "%s: a_t must be in [0, 1)", who);
+  if (mode != GCT2_SAMPLE_X && mode != GCT2_SAMPLE_V && !(a_t > 0.))
+    return gct2_fail(GCT2_EINVAL, "%s: this mode divides by sqrt(a_t): a_t must be > 0", who);
+  if (rank < 1 || rank > per_image) return gct2_fail(GCT2_EINVAL, "%s: rank must be in 1..per_image", who);
+  if (!std::isfinite(floor) || !std::isfinite((float)floor) || !((float)floor > 0.f))
+    return gct2_fail(GCT2_EINVAL, "%s: floor must be finite and > 0 in fp32", who);
+  if (scratch_bytes < pw_x0_quantile_scratch(B)) return gct2_fail(GCT2_EINVAL, "%s: scratch too small (gct2_x0_quantile_scratch)", who);
+  return pw_x0_quantile(mode, pred, fake, a_t, rank, (float)floor, rows, q_out, scratch, B, per_image, S(stream));
+}
+
+int gct2_diffusion_step_dynamic(int mode, int dtype, const float* pred, const float* fake_in, const float* hist_in, const float* known,
+                                const float* mask, const float* rows, double a_t, double a_prev, double sigma2, double c1, uint64_t seed,
+                                uint64_t stream_id, uint64_t offset, uint64_t offset0, uint64_t image_stride, float* fake_out, float* hist_out,
+                                float* x0_out, void* out, int ldout, void* out2, int ldout2, int B, size_t per_image, int C, void* stream) {
+  const char* who = "diffusion_step_dynamic";
+  if (int rc = step_mode_ok(who, mode)) return rc;
+  if (!pred || !fake_in || !rows) return gct2_fail(GCT2_EINVAL, "%s: null pointer", who);
+  if (!known != !mask) return gct2_fail(GCT2_EINVAL, "%s: known and mask go together (both NULL: the plain step)", who);
+  if (int rc = step_views_ok(who, dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
+  if (int rc = step_scalars_ok(who, mode, a_t, a_prev)) return rc;
+  if (int rc = step_sigma2_ok(who, a_prev, sigma2)) return rc;
+  if (!std::isfinite(c1) || !std::isfinite((float)c1)) return gct2_fail(GCT2_EINVAL, "%s: c1 must be finite in fp32", who);
+  if ((float)c1 != 0.f && !hist_in) return gct2_fail(GCT2_EINVAL, "%s: c1 != 0 extrapolates from hist_in, which is NULL", who);
+  // the multistep form: a history plane on either side, or an extrapolation
+  const bool multistep = hist_in || hist_out || (float)c1 != 0.f;
+  if (multistep && (float)sigma2 != 0.f) return gct2_fail(GCT2_EINVAL, "%s: the multistep form is deterministic: sigma2 must be 0", who);
+  SamplerStep st = step_views(mode, dtype, seed, stream_id, image_stride, fake_out, out, ldout, out2, ldout2, B, per_image, C);
+  st.pred = pred; st.fake_in = fake_in; st.hist_in = hist_in; st.known = known; st.mask = mask; st.rows = rows;
+  st.a = a_t; st.a_prev = a_prev; st.sigma2 = sigma2; st.c1 = c1; st.multistep = multistep;
+  st.offset = offset; st.offset0 = offset0; st.hist_out = hist_out; st.x0_out = x0_out;
+  return pw_sampler_step(who, st, S(stream));
+}
+
 int gct2_noise_edits(const float* eps, const float* dictionary, int K, float* out, int H, int W, int C, void* stream) {
   if (!eps || !dictionary || !out) return gct2_fail(GCT2_EINVAL, "noise_edits: null pointer");
   if (H <= 0 || W <= 0 || C <= 0 || K <= 0 || (H & 3) || (W & 3))

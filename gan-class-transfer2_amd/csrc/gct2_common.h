@@ -443,13 +443,14 @@ inline int blocks_for(size_t n, int per_block) {
   return (int)(b < 1 ? 1 : (b > (size_t)kMaxBlocks ? kMaxBlocks : b));
 }
 
-// ---- one sampler step (sampler.hip: pw_sampler_step), filled by the five gct2_diffusion_step* / _start* entry points of capi.hip.
+// ---- one sampler step (sampler.hip: pw_sampler_step), filled by the six gct2_diffusion_step* / _start* entry points of capi.hip.
 // mode: an objective of include/gct2.h, or a start pseudo-mode: STEP_START (the value is the draw at offset), STEP_START_IMAGE (the
 // value is sqrt(a) known + sqrt(1 - a) z0, z0 drawn at offset0).  Pointers a call does not use stay nullptr
 constexpr int STEP_START = -1, STEP_START_IMAGE = -2;
 struct SamplerStep {
   int mode = STEP_START, dtype = GCT2_F32;
   const float *pred = nullptr, *fake_in = nullptr, *hist_in = nullptr, *known = nullptr, *mask = nullptr;
+  const float* rows = nullptr;                         // gct2_diffusion_step_dynamic's per-image {s_b, r_b}: takes the place of clip
   double a = 0., a_prev = 0., sigma2 = 0., c1 = 0., clip = 0.;
   bool multistep = false;                              // gct2_diffusion_step_multistep's call (whatever c1 is)
   uint64_t seed = 0, stream_id = 0, offset = 0, offset0 = 0, image_stride = 0;
@@ -567,6 +568,9 @@ int pw_diffusion_mix(int dtype, const float* x, const float* e, float a, float* 
                      size_t npix, int C, hipStream_t s);
 int pw_diffusion_update(int mode, const float* pred, const float* fake, double a, double a1, float* x, float* e, size_t n, hipStream_t s);
 int pw_sampler_step(const char* what, const SamplerStep& st, hipStream_t s);
+size_t pw_x0_quantile_scratch(int B);
+int pw_x0_quantile(int mode, const float* pred, const float* fake, double a_t, uint32_t rank, float floor, float* rows, float* q_out,
+                   void* scratch, int B, size_t per_image, hipStream_t s);
 // pointwise.hip again
 int pw_noise_edits(const float* eps, const float* dict, int K, float* out, int H, int W, int C, hipStream_t s);
 int pw_image_prepare(const uint8_t* src, const int64_t* offsets, const int32_t* dims, float* dst, int B, int size, hipStream_t s);

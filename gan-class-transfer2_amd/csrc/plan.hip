@@ -49,6 +49,7 @@ const Entry ENTRIES[] = {
     GCT2_ENTRY(gct2_image_batch_cached), GCT2_ENTRY(gct2_image_grid_u8),
     GCT2_ENTRY(gct2_diffusion_step), GCT2_ENTRY(gct2_diffusion_start),
     GCT2_ENTRY(gct2_diffusion_step_masked), GCT2_ENTRY(gct2_diffusion_start_image), GCT2_ENTRY(gct2_diffusion_step_multistep),
+    GCT2_ENTRY(gct2_x0_quantile), GCT2_ENTRY(gct2_diffusion_step_dynamic),
 };
 #undef GCT2_ENTRY
 

@@ -1,6 +1,7 @@
 // The sampler's pointwise steps (train.py:323-496 log_sample; Denoiser.generate / encode): gct2_diffusion_mix, gct2_diffusion_update and
-// the five one-launch steps gct2_diffusion_step / _start / _start_image / _step_masked / _step_multistep, which are ONE per-element
-// computation (step_element) behind two traversals (sampler_flat_kernel, sampler_counter_kernel).  fp32 state, HBM-bound.
+// the six one-launch steps gct2_diffusion_step / _start / _start_image / _step_masked / _step_multistep / _step_dynamic, which are ONE
+// per-element computation (step_element) behind two traversals (sampler_flat_kernel, sampler_counter_kernel); gct2_x0_quantile, the
+// per-image order statistic of |x0| that feeds _step_dynamic (a radix select over sample_estimate's x).  fp32 state, HBM-bound.
 #include "gct2_common.h"
 #include <algorithm>
 
@@ -78,14 +79,32 @@ struct SamplerArgs {
   float* fake_out; float* hist_out; float* __restrict__ x0_out;
   void* __restrict__ out; int ldout; void* __restrict__ out2; int ldout2;
   int B; uint32_t per_image; int C;         // B * per_image < 2^31 (checked by the entry point)
+  // gct2_diffusion_step_dynamic: {s_b, r_b} per image in the place of clip, else nullptr.  The LAST field: every field in front of it
+  // keeps its kernarg offset.  Without DYN, 78 of the 105 step kernels are then instruction for instruction what they were without the
+  // field (only the offsets of the hidden arguments behind the struct move); the 27 four-element counter kernels load B / per_image / C
+  // and the hidden grid size in another order, since the two no longer sit side by side (one to six more instructions of 370 to 870)
+  const float* __restrict__ rows;
 };
 
-template <int MODE>
-__device__ __forceinline__ float step_update(float p, float f, const SamplerArgs& k, float& x) {
+// the bound of image b's estimate, DYN (gct2_diffusion_step_dynamic) only: gct2_x0_quantile's {s_b, r_b}.  DYN is a template flag, not
+// a test of k.rows at run time: the run-time test slowed the existing step with noise (profiles/dynamic_threshold_bench.json,
+// dropped_forms: figures recorded once from that build); without DYN the kernels are the ones the other entry points always had
+struct ImageBound { float s, r; };
+template <bool DYN>
+__device__ __forceinline__ ImageBound image_bound(const SamplerArgs& k, uint32_t b) {
+  if constexpr (DYN) return ImageBound{k.rows[2 * b], k.rows[2 * b + 1]};
+  else return ImageBound{0.f, 1.f};
+}
+template <int MODE, bool DYN>
+__device__ __forceinline__ float step_update(float p, float f, const SamplerArgs& k, ImageBound q, float& x) {
 #pragma clang fp contract(off)
   float e;
   sample_estimate<MODE>(p, f, k.sa, k.sb, x, e);
-  if (k.clip > 0.f) {                       // (wave-uniform)  a NaN fails both comparisons and stays
+  if constexpr (DYN) {                      // dynamic thresholding: clip to the image's own bound, rescale to the floor
+    x = x < -q.s ? -q.s : (x > q.s ? q.s : x);
+    x = x * q.r;                            // one rounded multiply; r == 1.0f leaves the bits alone
+    e = (f - k.sa * x) / k.sb;
+  } else if (k.clip > 0.f) {                       // (wave-uniform)  a NaN fails both comparisons and stays
     const float c = k.clip;
     x = x < -c ? -c : (x > c ? c : x);
     e = (f - k.sa * x) / k.sb;
@@ -105,9 +124,9 @@ __device__ __forceinline__ float mask_select(float m, float g, float h) {
 //   MULTI (DPM-Solver++ 2M, Lu et al. 2022): the re-noising reads d = x + c1 (x - hist) in x's place, with e re-derived from d.
 //   c1 == 0 (wave-uniform; the first step, and generate's last): step_update's own fake', the history is never read.
 //   NOISE: + cz z.  MASKED: the mask of the element's pixel selects between that g and h (x and kn for x0)
-template <int MODE, bool MASKED, bool MULTI, bool NOISE>
-__device__ __forceinline__ float step_element(float p, float f, float kn, float m, float z0, float z, size_t i, const SamplerArgs& k, float& x,
-                                              float& x0) {
+template <int MODE, bool MASKED, bool MULTI, bool NOISE, bool DYN>
+__device__ __forceinline__ float step_element(float p, float f, float kn, float m, float z0, float z, size_t i, const SamplerArgs& k,
+                                              ImageBound q, float& x, float& x0) {
 #pragma clang fp contract(off)
   if constexpr (MODE == STEP_START) {
     return z;
@@ -115,7 +134,7 @@ __device__ __forceinline__ float step_element(float p, float f, float kn, float 
     x0 = kn;
     return k.cx * kn + k.ck * z0;
   } else {
-    float g = step_update<MODE>(p, f, k, x);
+    float g = step_update<MODE, DYN>(p, f, k, q, x);
     if constexpr (MULTI) {
       if (k.c1 != 0.f) {
         const float d = x + k.c1 * (x - k.hist_in[i]);
@@ -167,7 +186,7 @@ __device__ __forceinline__ void counter_normals(const SamplerArgs& a, uint64_t c
 // element, and still the faster form: the masked step takes 25.3 us against 28.8 us for a thread per Philox counter with 16-byte
 // accesses, the start 20.3 against 26.1 us, at 64x128x128x3 (profiles/img2img_bench.json: consecutive lanes store their copies next to
 // each other).  Any offset0 and image_stride
-template <typename T, int MODE, bool MASKED, bool MULTI>
+template <typename T, int MODE, bool MASKED, bool MULTI, bool DYN>
 __global__ void sampler_flat_kernel(const SamplerArgs a) {
   const size_t n = (size_t)a.B * a.per_image, stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -180,8 +199,9 @@ __global__ void sampler_flat_kernel(const SamplerArgs a) {
     const uint32_t pix = (uint32_t)i / (uint32_t)a.C;
     if constexpr (MASKED) m = a.mask[pix];
     if constexpr (MODE != STEP_START_IMAGE) { p = a.pred[i]; f = a.fake_in[i]; }
+    const ImageBound q = image_bound<DYN>(a, (uint32_t)i / a.per_image);
     float x, x0;
-    const float v = step_element<MODE, MASKED, MULTI, false>(p, f, kn, m, z0, 0.f, i, a, x, x0);
+    const float v = step_element<MODE, MASKED, MULTI, false, DYN>(p, f, kn, m, z0, 0.f, i, a, q, x, x0);
     if constexpr (MULTI) if (a.hist_out) a.hist_out[i] = x;
     if constexpr (MODE != STEP_START_IMAGE) if (a.x0_out) a.x0_out[i] = x0;
     step_store<T>(v, i, pix, (int)((uint32_t)i - pix * (uint32_t)a.C), a);
@@ -199,7 +219,7 @@ __global__ void sampler_flat_kernel(const SamplerArgs a) {
 // thread, the mask is read per element (a group of four spans up to three pixels at C = 3), 28.1 us where the general form takes
 // 76.1 us (profiles/img2img_bench.json).  General form, MASKED: z per element through philox_normal (the two draws may sit at
 // different lanes of their counters)
-template <typename T, int MODE, bool MASKED, bool VEC>
+template <typename T, int MODE, bool MASKED, bool VEC, bool DYN>
 __global__ void sampler_counter_kernel(const SamplerArgs a) {
   constexpr bool STEP = MODE != STEP_START;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -207,6 +227,7 @@ __global__ void sampler_counter_kernel(const SamplerArgs a) {
     const uint64_t base = a.offset + (uint64_t)b * a.image_stride;                       // the step noise of the image
     const uint64_t own = MASKED ? a.offset0 + (uint64_t)b * a.image_stride : base, end = own + a.per_image;
     const uint64_t c0 = own >> 2;
+    const ImageBound q = image_bound<DYN>(a, (uint32_t)b);
     const size_t ncounters = (size_t)(((end + 3) >> 2) - c0);
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < ncounters; t += stride) {
       const uint64_t ctr = c0 + t;
@@ -227,10 +248,10 @@ __global__ void sampler_counter_kernel(const SamplerArgs a) {
         for (int j = 0; j < 4; j++) {
           float x, x0;
           if constexpr (MASKED) {
-            v[j] = step_element<MODE, true, false, true>(p[j], f[j], kn[j], a.mask[pix], n0[j], nz[j], i, a, x, x0);
+            v[j] = step_element<MODE, true, false, true, DYN>(p[j], f[j], kn[j], a.mask[pix], n0[j], nz[j], i, a, q, x, x0);
             if (++c == a.C) { c = 0; ++pix; }
           } else {
-            v[j] = step_element<MODE, false, false, true>(p[j], f[j], 0.f, 0.f, 0.f, n0[j], i, a, x, x0);
+            v[j] = step_element<MODE, false, false, true, DYN>(p[j], f[j], 0.f, 0.f, 0.f, n0[j], i, a, q, x, x0);
           }
           if constexpr (STEP) x4[j] = x0;
         }
@@ -250,15 +271,152 @@ __global__ void sampler_counter_kernel(const SamplerArgs a) {
           float p = 0.f, f = 0.f, v, x, x0;
           if constexpr (STEP) { p = a.pred[i]; f = a.fake_in[i]; }
           if constexpr (MASKED)
-            v = step_element<MODE, true, false, true>(p, f, a.known[i], a.mask[pix], n0[j], philox_normal(a.seed, a.stream_id, base + within), i,
-                                                      a, x, x0);
+            v = step_element<MODE, true, false, true, DYN>(p, f, a.known[i], a.mask[pix], n0[j], philox_normal(a.seed, a.stream_id, base + within), i,
+                                                      a, q, x, x0);
           else
-            v = step_element<MODE, false, false, true>(p, f, 0.f, 0.f, 0.f, n0[j], i, a, x, x0);
+            v = step_element<MODE, false, false, true, DYN>(p, f, 0.f, 0.f, 0.f, n0[j], i, a, q, x, x0);
           if constexpr (STEP) if (a.x0_out) a.x0_out[i] = x0;
           step_store<T>(v, i, pix, (int)c, a);
           if (++c == (uint32_t)a.C) { c = 0; ++pix; }
         }
       }
+    }
+  }
+}
+
+// ---- dynamic thresholding (Saharia et al. 2022, "Imagen", section 2.3): the per-image order statistic of |x0| (include/gct2.h:
+// gct2_x0_quantile) ----
+// A radix select over the 31 bits of key = bits(x) & 0x7fffffff, x sample_estimate's - the step's own x0, re-formed from pred / fake on
+// every pass, never stored.  Three digit passes, top first: 11 + 10 + 10 bits.  A pass histograms, per image, the digit of the keys
+// whose higher digits equal the prefix found so far; the next pass (the finish after the last) scans that table for the bin that holds
+// the rank left and carries {prefix, rank left} on in `state`.  Integer atomics only: the counts, hence every bit of the result, do not
+// depend on the order of the adds or on the grid.
+// scratch, uint32: tables [B][QSEL_ROW] (the three passes' bins side by side, zeroed by the launcher), then state [B][4] =
+// {prefix, rank left} after digit 0 (written by pass 1) and after digit 1 (written by pass 2)
+constexpr int QSEL_ROW = 4096, QSEL_THREADS = 256, QSEL_WAVES = QSEL_THREADS / 64, QSEL_PER_GROUP = 4096;
+// the histogram in LDS.  Shipped: one per wave (privatised).  -DGCT2_QSEL_WAVE_AGGREGATE (`make qsel_agg`: libgct2_qsel_agg.so, a
+// measurement build for scripts/bench_dynamic_threshold.py --variant, never loaded by the package) builds the other form instead: ONE
+// histogram per work-group, equal digits of a wave collapsed into one add by ballot / readlane.  Same bits either way
+#ifdef GCT2_QSEL_WAVE_AGGREGATE
+constexpr int QSEL_HISTS = 1;
+#else
+constexpr int QSEL_HISTS = QSEL_WAVES;
+#endif
+__host__ __device__ constexpr int qsel_bits(int pass) { return pass == 0 ? 11 : 10; }
+__host__ __device__ constexpr int qsel_shift(int pass) { return pass == 0 ? 20 : (pass == 1 ? 10 : 0); }
+__host__ __device__ constexpr int qsel_offset(int pass) { return pass == 0 ? 0 : (pass == 1 ? 2048 : 3072); }
+
+// the bin of table[0, bins) that holds the rank-th smallest (1-based, 1 <= rank <= the table's total) and the rank left inside that
+// bin.  The whole work-group calls it (bins a multiple of QSEL_THREADS); scan: QSEL_THREADS words, sel: 2 words of LDS
+__device__ __forceinline__ void qsel_find(const uint32_t* __restrict__ table, int bins, uint32_t rank, uint32_t* scan, uint32_t* sel,
+                                          uint32_t& digit, uint32_t& left) {
+  const int t = threadIdx.x, per = bins / QSEL_THREADS;
+  uint32_t sum = 0;
+  for (int j = 0; j < per; j++) sum += table[t * per + j];
+  scan[t] = sum;
+  if (t == 0) { sel[0] = 0; sel[1] = 1; }
+  __syncthreads();
+  for (int d = 1; d < QSEL_THREADS; d <<= 1) {          // inclusive scan of the threads' sums
+    const uint32_t add = t >= d ? scan[t - d] : 0u;
+    __syncthreads();
+    scan[t] += add;
+    __syncthreads();
+  }
+  const uint32_t incl = scan[t];
+  uint32_t below = incl - sum;
+  if (below < rank && rank <= incl) {                   // exactly one thread: its bins hold the rank
+    for (int j = 0; j < per; j++) {
+      const uint32_t c = table[t * per + j];
+      if (rank <= below + c) { sel[0] = (uint32_t)(t * per + j); sel[1] = rank - below; break; }
+      below += c;
+    }
+  }
+  __syncthreads();
+  digit = sel[0];
+  left = sel[1];
+  __syncthreads();                                      // (sel and scan are free again)
+}
+
+// one digit pass: blockIdx.x walks an image's elements, blockIdx.y the images.  Shipped: a histogram per wave in LDS (4 x 2048 x 4 B = 32 KB at
+// the top digit, which is essentially the exponent: most of an image falls into a handful of bins, and the waves of a work-group
+// would serialise on them), summed and flushed bin by bin - non-zero bins only - into the image's table
+template <int MODE, int PASS>
+__global__ void __launch_bounds__(QSEL_THREADS) x0_select_pass_kernel(const float* __restrict__ pred, const float* __restrict__ fake, float sa,
+                                                                      float sb, uint32_t rank, uint32_t* __restrict__ tables,
+                                                                      uint32_t* __restrict__ state, int B, uint32_t per_image) {
+  constexpr int BINS = 1 << qsel_bits(PASS), SHIFT = qsel_shift(PASS);
+  __shared__ uint32_t hist[QSEL_HISTS * BINS];
+  __shared__ uint32_t scan[QSEL_THREADS];
+  __shared__ uint32_t sel[2];
+  const int t = threadIdx.x;
+  uint32_t* mine = hist + (QSEL_HISTS > 1 ? t >> 6 : 0) * BINS;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    uint32_t* table = tables + (size_t)b * QSEL_ROW;
+    uint32_t prefix = 0;
+    if constexpr (PASS > 0) {                           // the digit the pass before found, from its table
+      uint32_t high = 0, left = rank, digit;
+      if constexpr (PASS == 2) { high = state[4 * b]; left = state[4 * b + 1]; }
+      qsel_find(table + qsel_offset(PASS - 1), 1 << qsel_bits(PASS - 1), left, scan, sel, digit, left);
+      prefix = (high << qsel_bits(PASS - 1)) | digit;
+      if (blockIdx.x == 0 && t == 0) { state[4 * b + 2 * (PASS - 1)] = prefix; state[4 * b + 2 * (PASS - 1) + 1] = left; }
+    }
+    for (int j = t; j < QSEL_HISTS * BINS; j += QSEL_THREADS) hist[j] = 0;
+    __syncthreads();
+    const float* p_b = pred + (size_t)b * per_image;
+    const float* f_b = MODE == GCT2_SAMPLE_X ? nullptr : fake + (size_t)b * per_image;
+    // (every lane of a wave takes the same trips: the loop runs on the wave's first element, a lane past the image counts nothing)
+#ifndef GCT2_QSEL_WAVE_AGGREGATE
+#pragma unroll 4
+#endif
+    for (uint32_t i0 = blockIdx.x * QSEL_THREADS + (t & ~63); i0 < per_image; i0 += gridDim.x * QSEL_THREADS) {
+      const uint32_t i = i0 + (t & 63);
+      const bool in = i < per_image;
+      const float p = in ? p_b[i] : 0.f;
+      float f = 0.f, x, e;
+      if constexpr (MODE != GCT2_SAMPLE_X) f = in ? f_b[i] : 0.f;
+      sample_estimate<MODE>(p, f, sa, sb, x, e);
+      const uint32_t key = __float_as_uint(x) & 0x7fffffffu;
+      bool counts = in;
+      if constexpr (PASS > 0) counts = in && (key >> (SHIFT + qsel_bits(PASS))) == prefix;
+      const uint32_t digit = (key >> SHIFT) & (BINS - 1);
+#ifdef GCT2_QSEL_WAVE_AGGREGATE
+      unsigned long long todo = __ballot(counts);
+      while (todo) {                                    // (wave-uniform) one add per distinct digit among the counting lanes
+        const int leader = __ffsll((long long)todo) - 1;
+        const uint32_t d = (uint32_t)__shfl((int)digit, leader);
+        const unsigned long long same = __ballot(counts && digit == d);
+        if ((t & 63) == leader) atomicAdd(&mine[d], (uint32_t)__popcll(same));
+        todo &= ~same;
+      }
+#else
+      if (counts) atomicAdd(&mine[digit], 1u);
+#endif
+    }
+    __syncthreads();
+    for (int j = t; j < BINS; j += QSEL_THREADS) {
+      uint32_t c = 0;
+#pragma unroll
+      for (int w = 0; w < QSEL_HISTS; w++) c += hist[w * BINS + j];
+      if (c) atomicAdd(&table[qsel_offset(PASS) + j], c);
+    }
+    __syncthreads();                                    // (the next image zeroes the histograms)
+  }
+}
+
+// the last digit from the last pass's table, then the finishing rule of include/gct2.h, once per image
+__global__ void __launch_bounds__(QSEL_THREADS) x0_select_finish_kernel(const uint32_t* __restrict__ tables, const uint32_t* __restrict__ state,
+                                                                        float F, float* __restrict__ rows, float* __restrict__ q_out, int B) {
+  __shared__ uint32_t scan[QSEL_THREADS];
+  __shared__ uint32_t sel[2];
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    uint32_t digit, left;
+    qsel_find(tables + (size_t)b * QSEL_ROW + qsel_offset(2), 1 << qsel_bits(2), state[4 * b + 3], scan, sel, digit, left);
+    if (threadIdx.x == 0) {
+      const float q = __uint_as_float((state[4 * b + 2] << qsel_bits(2)) | digit);
+      const float s = (q > F && q < INFINITY) ? q : F;  // a NaN or infinite q falls back to the fixed bound
+      rows[2 * b] = s;
+      rows[2 * b + 1] = s == F ? 1.f : F / s;
+      if (q_out) q_out[b] = q;
     }
   }
 }
@@ -286,6 +444,27 @@ int pw_diffusion_update(int mode, const float* pred, const float* fake, double a
   });
   return gct2_check_launch("diffusion_update");
 }
+size_t pw_x0_quantile_scratch(int B) { return (size_t)B * (QSEL_ROW + 4) * sizeof(uint32_t); }
+// a memset of the tables, three digit passes and the finish, all on s: no host synchronisation, nothing read back
+int pw_x0_quantile(int mode, const float* pred, const float* fake, double a_t, uint32_t rank, float floor, float* rows, float* q_out,
+                   void* scratch, int B, size_t per_image, hipStream_t s) {
+  const float sa = (float)sqrt(a_t), sb = (float)sqrt(1. - a_t);           // as pw_sampler_step forms them
+  uint32_t* tables = static_cast<uint32_t*>(scratch);
+  uint32_t* state = tables + (size_t)B * QSEL_ROW;
+  if (hipMemsetAsync(tables, 0, (size_t)B * QSEL_ROW * sizeof(uint32_t), s) != hipSuccess) return gct2_check_launch("x0_quantile");
+  const int gx = blocks_for(per_image, QSEL_PER_GROUP);
+  const dim3 grid(gx, std::max(1, std::min(B, kMaxBlocks / gx))), block(QSEL_THREADS);
+  with_sample_mode(mode, [&](auto m) {
+    constexpr int MODE = decltype(m)::value;
+    if constexpr (MODE != GCT2_SAMPLE_ODE) {            // (refused by the entry point)
+      hipLaunchKernelGGL((x0_select_pass_kernel<MODE, 0>), grid, block, 0, s, pred, fake, sa, sb, rank, tables, state, B, (uint32_t)per_image);
+      hipLaunchKernelGGL((x0_select_pass_kernel<MODE, 1>), grid, block, 0, s, pred, fake, sa, sb, rank, tables, state, B, (uint32_t)per_image);
+      hipLaunchKernelGGL((x0_select_pass_kernel<MODE, 2>), grid, block, 0, s, pred, fake, sa, sb, rank, tables, state, B, (uint32_t)per_image);
+    }
+  });
+  hipLaunchKernelGGL(x0_select_finish_kernel, dim3(std::min(B, kMaxBlocks)), block, 0, s, tables, state, floor, rows, q_out, B);
+  return gct2_check_launch("x0_quantile");
+}
 // the grid of the per-image kernels: x over the Philox counters of one image, y over the images, kMaxBlocks work-groups at the most
 static dim3 step_rng_grid(int B, size_t per_image) {
   const int gx = blocks_for(per_image / 4 + 2, 256);
@@ -305,6 +484,7 @@ int pw_sampler_step(const char* what, const SamplerStep& st, hipStream_t s) {
   k.fake_out = st.fake_out; k.hist_out = st.hist_out; k.x0_out = st.x0_out;
   k.out = st.out; k.ldout = st.ldout; k.out2 = st.out2; k.ldout2 = st.ldout2;
   k.B = st.B; k.per_image = (uint32_t)st.per_image; k.C = st.C;
+  k.rows = st.rows;
   float S = 0.f;
   if (st.mode == STEP_START_IMAGE) {               // pw_diffusion_mix's coefficients
     const float A = (float)st.a;
@@ -330,21 +510,24 @@ int pw_sampler_step(const char* what, const SamplerStep& st, hipStream_t s) {
       constexpr int MODE = decltype(m)::value;
       if constexpr (MODE == STEP_START) {
         with_flag(vec, [&](auto v) {
-          hipLaunchKernelGGL((sampler_counter_kernel<T, MODE, false, decltype(v)::value>), counter_grid, block, 0, s, k);
+          hipLaunchKernelGGL((sampler_counter_kernel<T, MODE, false, decltype(v)::value, false>), counter_grid, block, 0, s, k);
         });
       } else if constexpr (MODE == STEP_START_IMAGE) {
-        hipLaunchKernelGGL((sampler_flat_kernel<T, MODE, false, false>), flat_grid, block, 0, s, k);
+        hipLaunchKernelGGL((sampler_flat_kernel<T, MODE, false, false, false>), flat_grid, block, 0, s, k);
       } else if constexpr (MODE != GCT2_SAMPLE_ODE) {    // (refused by the entry points: the ODE objective has no such step)
         with_flag(masked, [&](auto mk) {
           constexpr bool MASKED = decltype(mk)::value;
-          if (flat)
-            with_flag(st.multistep, [&](auto mu) {
-              hipLaunchKernelGGL((sampler_flat_kernel<T, MODE, MASKED, decltype(mu)::value>), flat_grid, block, 0, s, k);
-            });
-          else
-            with_flag(vec, [&](auto v) {
-              hipLaunchKernelGGL((sampler_counter_kernel<T, MODE, MASKED, decltype(v)::value>), counter_grid, block, 0, s, k);
-            });
+          with_flag(k.rows != nullptr, [&](auto dy) {
+            constexpr bool DYN = decltype(dy)::value;
+            if (flat)
+              with_flag(st.multistep, [&](auto mu) {
+                hipLaunchKernelGGL((sampler_flat_kernel<T, MODE, MASKED, decltype(mu)::value, DYN>), flat_grid, block, 0, s, k);
+              });
+            else
+              with_flag(vec, [&](auto v) {
+                hipLaunchKernelGGL((sampler_counter_kernel<T, MODE, MASKED, decltype(v)::value, DYN>), counter_grid, block, 0, s, k);
+              });
+          });
         });
       }
     };

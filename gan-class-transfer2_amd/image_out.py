@@ -303,7 +303,10 @@ def generate_to_dir(denoiser, n: int, directory: str, pattern: str = "{:06d}.png
         raise ValueError(f"generate_to_dir: mode must be one of {sorted(MODES)!r}, got {mode!r}")
     if generate_kw.get("return_steps"):
         raise ValueError("generate_to_dir: return_steps has no file to go to; call generate")
+    if generate_kw.get("return_thresholds"):
+        raise ValueError("generate_to_dir: return_thresholds has no file to go to; call generate")
     generate_kw.pop("return_steps", None)
+    generate_kw.pop("return_thresholds", None)
     bs = generate_kw.pop("batch_size", None)
     bs = min(n, 64) if bs is None else bs
     if isinstance(bs, bool) or not isinstance(bs, int) or bs < 1:

@@ -688,7 +688,9 @@ class Denoiser(Layer):
         """n new images from noise, fp32 [n,H,W,3] on the device: sampler.generate(self, n, ...) - strided DDIM sampling with
         num_steps, eta, clip_denoised, seed, first_index, batch_size, timesteps, noise, use_ema, use_graph, return_steps, size; init, strength
         and mask condition the run on images (image-to-image, inpainting); solver="dpm2m" is the second-order multistep solver
-        (DPM-Solver++ 2M: one gct2_diffusion_step_multistep launch per step, eta = 0 only), "ddim" the default"""
+        (DPM-Solver++ 2M: one gct2_diffusion_step_multistep launch per step, eta = 0 only), "ddim" the default; clip_denoised="dynamic"
+        with dynamic_percentile, dynamic_floor and return_thresholds is dynamic thresholding (a per-image order statistic of |x0| in the
+        fixed bound's place: gct2_x0_quantile and one gct2_diffusion_step_dynamic launch per step)"""
         from .sampler import generate
         return generate(self, n, **kw)
 

@@ -16,11 +16,17 @@ from an image noised to an intermediate timestep (gct2_diffusion_start_image), w
 (gct2_diffusion_step_masked).  With `solver="dpm2m"` every step is the second-order multistep update instead (DPM-Solver++ 2M:
 gct2_diffusion_step_multistep, one more fp32 plane that carries the previous step's estimate); `encode` takes the same switch.
 
+With `clip_denoised="dynamic"` the fixed clip bound gives way to dynamic thresholding (Saharia et al. 2022): per image and per step a
+high order statistic of |x0| (gct2_x0_quantile, a radix select) bounds the estimate, and one gct2_diffusion_step_dynamic launch takes
+the place of whichever of the three steps the run would have used.
+
 `encode` - the inversion loop of log_sample as an API: a batch of images into latents over the same strided timesteps."""
 from __future__ import annotations
 
 import contextlib
+import ctypes as C
 import gc
+import math
 import warnings
 from typing import Callable, Dict, Optional, Tuple
 
@@ -37,6 +43,7 @@ from .trainer_math import GENERATE_STREAM, ddim_sigma2, generate_image_stride, g
 from .trainer_math import check_mask, img2img_steps
 from .trainer_math import SOLVERS, multistep_coefficient
 from .trainer_math import check_predict_v
+from .trainer_math import quantile_rank
 
 
 def sample_mode(predict_x: bool, predict_scaled_epsilon: bool, ordinary_differential_equation: bool, predict_v: bool = False) -> int:
@@ -76,6 +83,7 @@ class _Sampler:
         # of the evaluation, outside the graph.  Without the switch nothing is launched for t (train.py:207: "t is ignored")
         self.heads = bool(getattr(eng, "timestep_heads", False))
         self._t: Dict[int, int] = {}
+        self._dynamic: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}     # per batch size: gct2_x0_quantile's (scratch, rows [B,2])
 
     # ---- network evaluation ---------------------------------------------------------------------------------------------
     def _graph_for(self, b):
@@ -192,6 +200,31 @@ class _Sampler:
              known.data_ptr() if known is not None else None, mask.data_ptr() if mask is not None else None, a_t, a_prev, c1, clip, seed,
              GENERATE_STREAM, offset0, image_stride, fake.data_ptr(), hist.data_ptr(), x0.data_ptr() if x0 is not None else None,
              *self.input_views(B), B, self.H * self.W * 3, 3, self._stream())
+
+    def dynamic_rows(self, B: int, pred: torch.Tensor, fake: torch.Tensor, a_t: float, rank: int, floor: float) -> torch.Tensor:
+        """per image, the rank-th smallest |x0| of the step's own estimate against the floor: gct2_x0_quantile into this batch size's
+        fp32 [B,2] = {s_b, r_b} (valid until the next call at B); the scratch lives beside it"""
+        per_image = self.H * self.W * 3
+        held = self._dynamic.get(B)
+        if held is None:
+            need = C.c_size_t(0)
+            call("gct2_x0_quantile_scratch", B, per_image, C.byref(need))
+            held = self._dynamic[B] = (torch.empty(need.value, dtype=torch.uint8, device=self.eng.device),
+                                       torch.empty(B, 2, dtype=torch.float32, device=self.eng.device))
+        scratch, rows = held
+        call("gct2_x0_quantile", self.mode, pred.data_ptr(), fake.data_ptr(), a_t, rank, floor, rows.data_ptr(), None, scratch.data_ptr(),
+             scratch.numel(), B, per_image, self._stream())
+        return rows
+
+    def dynamic_step(self, B: int, pred: torch.Tensor, fake: torch.Tensor, hist: Optional[torch.Tensor], known: Optional[torch.Tensor],
+                     mask: Optional[torch.Tensor], rows: torch.Tensor, a_t: float, a_prev: float, sigma2: float, c1: float, seed: int,
+                     offset: int, offset0: int, image_stride: int, x0: Optional[torch.Tensor]) -> None:
+        """fused_step / masked_step (known and mask) / multistep_step (hist) with rows [B,2] = {s_b, r_b} in the place of the scalar
+        clip: gct2_diffusion_step_dynamic, in place on fake (and hist)"""
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        call("gct2_diffusion_step_dynamic", self.mode, self.eng.dtype, pred.data_ptr(), fake.data_ptr(), ptr(hist), ptr(known), ptr(mask),
+             rows.data_ptr(), a_t, a_prev, sigma2, c1, seed, GENERATE_STREAM, offset, offset0, image_stride, fake.data_ptr(), ptr(hist),
+             ptr(x0), *self.input_views(B), B, self.H * self.W * 3, 3, self._stream())
 
     def update(self, pred: torch.Tensor, fake: torch.Tensor, alpha: float, alpha_prev: float, x: torch.Tensor, e: Optional[torch.Tensor]) -> None:
         """train.py:382-413 / 452-479 by mode (gct2_diffusion_update)."""
@@ -329,7 +362,8 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
              use_ema: bool = False, use_graph: bool = True, return_steps=(), size=None, predict_x: Optional[bool] = None,
              predict_scaled_epsilon: Optional[bool] = None, ordinary_differential_equation: Optional[bool] = None, noise_schedule=None,
              alpha_dash_offset: Optional[float] = None, init: Optional[torch.Tensor] = None, strength: float = 1.0, mask=None,
-             solver: str = "ddim", predict_v: Optional[bool] = None):
+             solver: str = "ddim", predict_v: Optional[bool] = None, dynamic_percentile: Optional[float] = None,
+             dynamic_floor: Optional[float] = None, return_thresholds: bool = False):
     """n new images from noise: strided DDIM sampling (Song et al. 2021) over K = num_steps of the engine's `steps` timesteps
     (trainer_math.sampling_timesteps; None: all of them; or an explicit strictly increasing `timesteps` list within 1..steps), one
     network evaluation and ONE pointwise launch (gct2_diffusion_step) per step.  Returns fp32 [n,H,W,3] on the device: the x0 estimate
@@ -361,7 +395,18 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
     its own x0 estimate; so num_steps <= 2 is solver="ddim" bit for bit.  Deterministic: eta != 0 is a ValueError.  return_steps holds
     the network's (clipped, with mask composited) estimates, not the extrapolated ones.  An unknown name is a ValueError.  What the
     solver does to sample quality on a trained network is not measured in this project; its order of accuracy as an integrator is
-    (tests/test_multistep_kernels_gpu.py)."""
+    (tests/test_multistep_kernels_gpu.py).
+    clip_denoised="dynamic": dynamic thresholding (Saharia et al. 2022, "Imagen", section 2.3) in the fixed clip's place.  At every step
+    and for every image, s = the trainer_math.quantile_rank(dynamic_percentile, H W 3)-th smallest |x0| of the network's estimate (the
+    exact order statistic, one gct2_x0_quantile call); where s > dynamic_floor the estimate is clipped to [-s, s] and multiplied by
+    dynamic_floor / s, elsewhere it is clipped to dynamic_floor like clip_denoised=dynamic_floor (a NaN or infinite s too); eps is
+    re-derived either way, in ONE gct2_diffusion_step_dynamic launch that stands for the plain, the masked and the multistep step.  It
+    composes with every other argument (with mask= the statistic runs over the whole estimate, kept pixels included); a huge floor is
+    clip_denoised=floor bit for bit.  return_thresholds=True appends {t: fp32 [n]} to the result: s of every image at every timestep
+    run, which shows whether the percentile ever engages.  ValueError: dynamic_percentile outside (0, 1], a dynamic_floor that is not
+    finite and > 0, either of them (anything but None, the defaults 0.995 and 1.0 included) or return_thresholds without
+    clip_denoised="dynamic", any other string.  dynamic_percentile=None is 0.995, dynamic_floor=None is 1.0.  Not covered: interpolated percentiles, per-channel or mask-aware statistics, encode, log_sample, the data-parallel
+    wrappers.  What it does to the sample quality of a trained network is not measured in this project."""
     eng = denoiser.ensure_engine()
     steps = int(eng.steps)
     if solver not in SOLVERS:
@@ -380,14 +425,39 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
         raise ValueError(f"generate: solver 'dpm2m' is deterministic (it integrates the probability-flow ODE): eta must be 0, got {eta!r}")
     taus = _taus("generate", steps, num_steps, timesteps)
     K = len(taus)
-    if clip_denoised is None or clip_denoised is False:
+    dynamic = isinstance(clip_denoised, str) and clip_denoised == "dynamic"
+    if dynamic:
         clip = 0.0
-    elif clip_denoised is True:
-        clip = 1.0
+        try:
+            percentile = 0.995 if dynamic_percentile is None else float(dynamic_percentile)
+            floor = 1.0 if dynamic_floor is None else float(dynamic_floor)
+        except (TypeError, ValueError):
+            raise ValueError(f"generate: dynamic_percentile and dynamic_floor must be numbers, got {dynamic_percentile!r}, "
+                             f"{dynamic_floor!r}") from None
+        if isinstance(dynamic_percentile, bool) or not 0.0 < percentile <= 1.0:
+            raise ValueError(f"generate: dynamic_percentile must lie in (0, 1], got {dynamic_percentile!r}")
+        with np.errstate(over="ignore"):
+            floor32 = float(np.float32(floor))          # the kernel's F
+        if isinstance(dynamic_floor, bool) or not (floor > 0.0 and math.isfinite(floor) and math.isfinite(floor32) and floor32 > 0.0):
+            raise ValueError(f"generate: dynamic_floor must be a finite bound > 0 (also in fp32), got {dynamic_floor!r}")
     else:
-        clip = float(clip_denoised)
-        if not (clip > 0.0 and clip < float("inf")):
-            raise ValueError(f"generate: clip_denoised must be True, False, None or a finite bound > 0, got {clip_denoised!r}")
+        if dynamic_percentile is not None or dynamic_floor is not None or return_thresholds:
+            raise ValueError('generate: dynamic_percentile, dynamic_floor and return_thresholds belong to clip_denoised="dynamic", got '
+                             f"clip_denoised={clip_denoised!r}")
+        if clip_denoised is None or clip_denoised is False:
+            clip = 0.0
+        elif clip_denoised is True:
+            clip = 1.0
+        else:
+            try:
+                if isinstance(clip_denoised, str):
+                    raise ValueError
+                clip = float(clip_denoised)
+            except (TypeError, ValueError):
+                clip = float("nan")
+            if not (clip > 0.0 and clip < float("inf")):
+                raise ValueError('generate: clip_denoised must be True, False, None, "dynamic" or a finite bound > 0, got '
+                                 f"{clip_denoised!r}")
     if init is None and (mask is not None or strength != 1.0):
         raise ValueError("generate: mask and strength condition the run on an image: they need init")
     if init is not None and noise is not None:
@@ -419,6 +489,7 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
     if isinstance(bs, bool) or not isinstance(bs, int) or bs < 1:
         raise ValueError(f"generate: batch_size must be a positive int, got {batch_size!r}")
     per_image = H * W * 3
+    rank = quantile_rank(percentile, per_image) if dynamic else 0
     seed, first_index = int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_index)
     if first_index < 0 or generate_offset(first_index + n, 0, K, per_image) >= 1 << 64:
         raise ValueError(f"generate: first_index = {first_index!r} leaves the 64-bit stream")
@@ -442,6 +513,7 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
         S = _Sampler(eng, steps, mode, H, W, use_graph, schedule, offset)
         out = torch.empty(n, H, W, 3, dtype=torch.float32, device=dev)
         kept = {t: torch.empty_like(out) for t in marks}
+        bounds = {tau: torch.empty(n, dtype=torch.float32, device=dev) for tau in taus[:K_run]} if dynamic and return_thresholds else None
         fake = None
         for g0 in range(0, n, bs):
             B = min(bs, n - g0)
@@ -466,7 +538,14 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
                 pred = S.evaluate(B)
                 x0 = out[g0:g0 + B] if k == K else (kept[tau][g0:g0 + B] if tau in kept else None)
                 off = generate_offset(first_index + g0, k, K, per_image)
-                if multistep:
+                if dynamic:
+                    rows = S.dynamic_rows(B, pred, fake, a_t, rank, floor)
+                    if bounds is not None:
+                        bounds[tau][g0:g0 + B].copy_(rows[:, 0])
+                    masked = init is not None and mask is not None
+                    S.dynamic_step(B, pred, fake, hist, known if masked else None, keep if masked else None, rows, a_t, a_prev,
+                                   0.0 if multistep else s2, c1s[k - 1] if multistep else 0.0, seed, off, off0, stride, x0)
+                elif multistep:
                     S.multistep_step(B, pred, fake, hist, known if keep is not None else None, keep, a_t, a_prev, c1s[k - 1], clip, seed, off0,
                                      stride, x0)
                 elif init is not None and mask is not None:
@@ -475,7 +554,10 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
                     S.fused_step(B, pred, fake, a_t, a_prev, s2, clip, seed, off, stride, x0)
                 if k == K and tau in kept:
                     kept[tau][g0:g0 + B].copy_(x0)
-    return (out, kept) if marks else out
+    result = (out, kept) if marks else out
+    if bounds is not None:
+        result = (*result, bounds) if marks else (out, bounds)
+    return result
 
 
 def encode(denoiser: "M.Denoiser", images: torch.Tensor, num_steps: Optional[int] = None, timesteps=None, batch_size: Optional[int] = None,

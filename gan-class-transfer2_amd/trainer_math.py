@@ -539,6 +539,19 @@ def multistep_coefficient(a_before: Optional[float], a_t: float, a_prev: float) 
     return h / (2.0 * h_prev)
 
 
+# ---- dynamic thresholding (generate with clip_denoised="dynamic"; gct2_x0_quantile) -----------------------------------------------------
+def quantile_rank(p: float, n: int) -> int:
+    """the 1-based rank of the order statistic that stands for the p-quantile of n values, p in (0, 1]: min(n, max(1, ceil(p n))) - no
+    interpolation (it differs from numpy.percentile's "linear" by less than one element's gap).  A Python int computed once on the
+    host: the kernel never sees p.  ValueError for p outside (0, 1] or n < 1."""
+    p, n = float(p), int(n)
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"quantile_rank: p must lie in (0, 1], got {p!r}")
+    if n < 1:
+        raise ValueError(f"quantile_rank: n must be a positive int, got {n!r}")
+    return min(n, max(1, math.ceil(p * n)))
+
+
 def check_mask(mask, n: int, H: int, W: int) -> torch.Tensor:
     """an inpainting mask as contiguous fp32 [n,H,W] (on the mask's device): [H,W] is shared by the n images, [n,H,W] and [n,H,W,1]
     carry one per image.  1 regenerates a pixel, 0 keeps it (gct2_diffusion_step_masked).  ValueError for any other shape."""

@@ -542,6 +542,56 @@ int gct2_diffusion_step_multistep(int mode, int dtype, const float* pred, const 
                                   const float* mask, double a_t, double a_prev, double c1, double clip, uint64_t seed, uint64_t stream_id,
                                   uint64_t offset0, uint64_t image_stride, float* fake_out, float* hist_out, float* x0_out, void* out,
                                   int ldout, void* out2, int ldout2, int B, size_t per_image, int C, void* stream);
+/* ---- dynamic thresholding (generate(clip_denoised="dynamic"); Saharia et al. 2022, "Photorealistic Text-to-Image Diffusion Models with
+ * Deep Language Understanding" (Imagen), section 2.3): per image and per step, a high order statistic of |x0| takes the place of the
+ * fixed clip bound, and an estimate clipped to it is scaled back to the fixed bound.  Two calls per step: the select, then the step.
+ *
+ * gct2_x0_quantile: per image, the rank-th smallest |x0| of the step's own estimate, exactly - no interpolation, no sampling, no
+ * approximation by histogram bin.  pred, fake: fp32 [B * per_image]; rows: fp32 [B][2]; q_out: fp32 [B] or NULL.
+ *   key order   x_i is gct2_diffusion_step's UNCLIPPED update for the mode (X: x = p; EPS: x = (f - p sb) / sa; SCALED_EPS: x = (f - p) / sa;
+ *               V: x = sa f - sb p), sa = (float)sqrt(a_t), sb = (float)sqrt(1 - a_t) formed exactly as the step forms them, every
+ *               operation rounded once: the select's x_i is the step's x_i bit for bit.  key_i = bits(x_i) & 0x7fffffff, compared as
+ *               uint32: the order of |x| with -0 = +0, +inf above every finite value and every NaN above +inf.
+ *   statistic   q_b = the value whose key is the rank-th smallest (1-based) among the per_image keys of image b.
+ *   finishing   once per image, F = (float)floor:  s_b = (q_b > F && q_b < INFINITY) ? q_b : F  (a NaN or infinite q_b falls back to
+ *               the fixed bound);  r_b = (s_b == F) ? 1.0f : F / s_b  (one fp32 division);  rows[2b] = s_b, rows[2b+1] = r_b,
+ *               q_out[b] = q_b (the raw bits).
+ *   modes       GCT2_SAMPLE_X, _EPS, _SCALED_EPS, _V; GCT2_SAMPLE_ODE and the reserved code 4 are GCT2_EINVAL.  In mode X fake is not
+ *               read and may be NULL: the call is then "the k-th smallest |v| per row" of any fp32 plane.  a_t follows
+ *               gct2_diffusion_step's rules: in [0, 1), > 0 for the epsilon modes.
+ *   GCT2_EINVAL unless 1 <= rank <= per_image, floor is finite and > 0 (also once cast to fp32), B * per_image < 2^31, and
+ *               scratch_bytes >= what gct2_x0_quantile_scratch(B, per_image, &bytes) reports (scratch: device memory, 4-byte aligned).
+ *   stream      the call assumes nothing about the scratch contents: it zeroes what it needs on `stream`.  No host synchronisation and
+ *               no device-to-host copy: the call can sit between graph replays of the network.  The result is a pure function of
+ *               the inputs - the same bits on every run and for every grid size: only integer atomics add (their result does not
+ *               depend on the order), no floating-point atomics.
+ *   how         a radix select over the 31 key bits in three digit passes (11 + 10 + 10 bits, the top digit first) and a finishing
+ *               launch; every pass re-forms x from pred / fake, nothing is materialised.  Measured on one MI355X at 64x128x128x3:
+ *               profiles/dynamic_threshold_bench.json. */
+int gct2_x0_quantile_scratch(int B, size_t per_image, size_t* bytes);
+int gct2_x0_quantile(int mode, const float* pred, const float* fake, double a_t, uint32_t rank, double floor, float* rows, float* q_out,
+                     void* scratch, size_t scratch_bytes, int B, size_t per_image, void* stream);
+/* gct2_diffusion_step_dynamic: the step with a per-image bound - gct2_diffusion_step, gct2_diffusion_step_masked and
+ * gct2_diffusion_step_multistep in one entry point, with rows [B][2] = {s_b, r_b} (what gct2_x0_quantile wrote) in the place of the
+ * scalar clip.  The arguments are the union of the masked and the multistep step's; every rule not named here is theirs.
+ *   forms       known and mask both NULL: the plain step; both non-NULL: the masked step (one alone is GCT2_EINVAL).  The multistep
+ *               form is taken when hist_in or hist_out is non-NULL or (float)c1 != 0; it is deterministic: with (float)sigma2 != 0
+ *               it is GCT2_EINVAL.  c1 must be finite in fp32, hist_in non-NULL when (float)c1 != 0.  rows == NULL is GCT2_EINVAL.
+ *   element i of image b, s = rows[2b], r = rows[2b+1], after gct2_diffusion_step's unclipped update x:
+ *               x = x < -s ? -s : (x > s ? s : x)      (a NaN stays NaN)
+ *               x = x * r                               (one rounded multiply; r == 1.0f leaves the bits alone)
+ *               e = (f - sa * x) / sb                   (eps re-derived, as the fixed clip does)
+ *               everything after that is the existing step's bits: rows {F, 1} for every image give gct2_diffusion_step /
+ *               _step_masked / _step_multistep at clip = F.  hist_out and x0_out carry this thresholded x; the multistep
+ *               extrapolation d = x + c (x - hist_in) is not thresholded again.  |x| <= F exactly when F is a power of two (the
+ *               default 1): s fl(F / s) rounds back to F; for another F it can land one unit in the last place above it.
+ *   masked form the select ran over the WHOLE network estimate, kept pixels included: the bound of an image does not know its mask.
+ * Measured on one MI355X at 64x128x128x3, bf16 views: profiles/dynamic_threshold_bench.json. */
+int gct2_diffusion_step_dynamic(int mode, int dtype, const float* pred, const float* fake_in, const float* hist_in, const float* known,
+                                const float* mask, const float* rows, double a_t, double a_prev, double sigma2, double c1, uint64_t seed,
+                                uint64_t stream_id, uint64_t offset, uint64_t offset0, uint64_t image_stride, float* fake_out,
+                                float* hist_out, float* x0_out, void* out, int ldout, void* out2, int ldout2, int B, size_t per_image,
+                                int C, void* stream);
 /* the four inputs of the reverse pass built from one inverted noise image eps [H,W,C] (train.py:416-431): out [4,H,W,C] =
  * eps | nearest-upsample x4 of avg_pool2d(eps, 4, 4) | tf.roll by 1 along H and W | per-pixel nearest of the K entries of
  * dictionary [H,W,K,C] (squared distance, first minimum).  H, W multiples of 4. */
