@@ -761,8 +761,10 @@ int launch(gct2_ctx& c, TapGemmParams p, hipStream_t s) {
     if (int e = tapgemm_dbq_flush_for(c, p.db, p.db_split, p.db2, p.N - p.db_split, s)) return e;
     zero_overwritten_db(p, s);
   }
-  gct2_log(c, "tap:%s:%dx%d:%s:ksplit=%d%s%s", FORM == FORM_CONV ? "conv" : FORM == FORM_CONVT ? "convT" : "s1", BM, BN,
-           EPI == EPI_BIAS_ACT ? "bias_act" : "mask", p.ksplit, p.wstat ? ":wstat" : "", (p.bits && p.wide && p.ksplit == 1) ? ":bits" : "");
+  // (":e8": the GEMM kernel's 8-byte epilogue applies the epilogue itself - a view that is not 16-byte aligned, no split-K)
+  gct2_log(c, "tap:%s:%dx%d:%s:ksplit=%d%s%s%s", FORM == FORM_CONV ? "conv" : FORM == FORM_CONVT ? "convT" : "s1", BM, BN,
+           EPI == EPI_BIAS_ACT ? "bias_act" : "mask", p.ksplit, p.wstat ? ":wstat" : "", (p.bits && p.wide && p.ksplit == 1) ? ":bits" : "",
+           (!p.wide && p.ksplit == 1) ? ":e8" : "");
   hipLaunchKernelGGL(kern, grid, dim3((BM / 64) * (BN / 64) * 64), 0, s, p);
   if (p.ksplit > 1) {
     hipLaunchKernelGGL((tapgemm_finalize_kernel<T, EPI>), dim3((unsigned)fin_rows, (p.N + 127) / 128), dim3(256), 0, s, p, npix);

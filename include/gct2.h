@@ -29,6 +29,17 @@
  *    direct form, returns GCT2_EINVAL past its own bound (stated there).  Output, mask (act), bit-plane and fp32 views have no limit
  *    beyond the pixel count.  The pointwise entry points take size_t pixel counts, or int M / B*HW that they check against 2^31 where
  *    they index with int; gct2_dense_head_train bounds ldx by its LDS tile (its message names it).
+ *  - alignment ("Alignment classes"; tests/test_alignment_exact_gpu.py): the layer entry points (gct2_conv4s2_*,
+ *    gct2_convT4s2_fwd / _dgrad / _wgrad, gct2_conv2d_s1_*) take ANY element-aligned view and array: x, dz, act, y, dx at multiples of
+ *    the element size with any ld >= the channel count, w likewise, bias / dw / db at multiples of 4 bytes.  Alignment selects the
+ *    kernel and never the result: 16-byte aligned views whose ld is a multiple of 8 elements run the 16-byte paths (what the engine
+ *    passes); an output or mask view that is only 8-byte aligned (or whose ld is 8 k + 4) runs the tap GEMM's 8-byte epilogue
+ *    (launch-log token ":e8") and keeps the halo kernel out; anything less aligned on x, dz, w, bias, y, dx, act, dw runs the direct
+ *    kernels; the image layer (Cin <= 4) reads a source that is not a whole number of 8-byte pixels channel by channel; the fp32
+ *    matrix-core kernels stage a misaligned operand element by element; a dw that is not 16-byte aligned gets atomics or one owner
+ *    instead of ordered slabs.  On exact-sum inputs (tests/exact_cases.py) every one of these paths stores the same bits; on
+ *    other inputs they differ by the order of the fp32 additions only.  GCT2_EINVAL for alignment only where an entry point says so
+ *    (scratch, bias-queue and optimizer arenas, gct2_convT4s2_fwd_head_train, the adam range of the weight-gradient calls).
  */
 #ifndef GCT2_H
 #define GCT2_H

@@ -163,12 +163,15 @@ def view_of(buf, off, C):
     return buf[1:-1, ..., off:off + C]
 
 
-def guarded(t, fill=float("nan")):
-    """a weight or bias array with GUARD elements of `fill` in front and behind; returns the flat buffer and the pointer to the data"""
+def guarded(t, fill=float("nan"), offset=0):
+    """a weight or bias array with GUARD elements of `fill` in front and behind; returns the flat buffer and the pointer to the data.
+    offset: the data starts that many elements later (a pointer off the buffer's alignment, tests/alignment_cases.py); the front guard
+    grows by them, the one behind keeps its GUARD elements"""
     flat = t.reshape(-1)
-    buf = torch.full((flat.numel() + 2 * GUARD,), fill, dtype=t.dtype, device=t.device)
-    buf[GUARD:GUARD + flat.numel()] = flat
-    return buf, buf.data_ptr() + GUARD * buf.element_size()
+    assert offset >= 0
+    buf = torch.full((flat.numel() + 2 * GUARD + offset,), fill, dtype=t.dtype, device=t.device)
+    buf[GUARD + offset:GUARD + offset + flat.numel()] = flat
+    return buf, buf.data_ptr() + (GUARD + offset) * buf.element_size()
 
 
 def guarded_data(buf, shape):
@@ -241,6 +244,7 @@ WGRAD_TUNING_SHAPE = (4, 32, 32, 64, 128)     # 16 steps of 64 rows: room for fo
 S1_SHAPES = [(1, 5, 7, 3, 8, 3), (1, 9, 11, 24, 40, 5), (2, 6, 4, 40, 16, 1), (2, 4, 4, 264, 128, 3)]     # (..., KS)
 DENSE_SHAPE = (1000, 67, 3)                   # M, Cin, Cout
 BIAS_GRAD_CASES = [("conv_dgrad", (1, 12, 20, 72, 32)), ("convT_dgrad", (1, 12, 20, 72, 16))]
+IMAGE_EXTRA_SHAPES = [(2, 16, 16, 1, 8), (2, 16, 16, 2, 8)]          # the image layer at Cin = 1 and 2 (tests/alignment_cases.py)
 TAP_ENTRIES = ("conv_fwd", "convT_fwd", "conv_dgrad", "convT_dgrad")
 WGRAD_ENTRIES = ("conv_wgrad", "convT_wgrad")
 S1_ENTRIES = ("s1_fwd", "s1_dgrad", "s1_wgrad")
@@ -419,8 +423,9 @@ def _dense_terms(c, index):
 # ---- the GPU case list (tests/test_kernels_exact_gpu.py runs it; tests/test_exact_cases_cpu.py checks the inputs of every entry) ---------
 
 def reference_cases():
-    """every (entry, shape, dtype, special) whose inputs a test of tests/test_kernels_exact_gpu.py uses"""
-    out = []
+    """every (entry, shape, dtype, special) whose inputs a test of tests/test_kernels_exact_gpu.py or tests/test_alignment_exact_gpu.py
+    uses"""
+    out = [(entry, s, dt, None) for dt in (BF16, F16) for entry in ("conv_fwd", "conv_wgrad") for s in IMAGE_EXTRA_SHAPES]
     for dt in (F32, BF16, F16):
         for entry in TAP_ENTRIES:
             out += [(entry, s, dt, None) for s in TAP_SHAPES]

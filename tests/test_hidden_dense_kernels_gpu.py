@@ -85,9 +85,10 @@ def expected_path(dt, cin, ldx, chid):
 
 
 class Case:
-    """inputs on the CPU in float64 (already representable in the dtype) and on the device"""
+    """inputs on the CPU in float64 (already representable in the dtype) and on the device.  xoff: x starts that many elements behind
+    the start of its allocation (NaN in front of it)"""
 
-    def __init__(self, gpu, dt, M, cin, ldx, chid, cout, seed, exact):
+    def __init__(self, gpu, dt, M, cin, ldx, chid, cout, seed, exact, xoff=0):
         rng = np.random.default_rng(seed)
         self.dt, self.M, self.cin, self.ldx, self.chid, self.cout, self.gpu = dt, M, cin, ldx, chid, cout, gpu
         if exact:
@@ -109,6 +110,10 @@ class Case:
         xp[:, :cin] = x
         dev = lambda a, t=torch.float32: torch.from_numpy(np.ascontiguousarray(a)).to(t).to(gpu).contiguous()
         self.d_x, self.d_w1 = dev(xp, TD[dt]), dev(w1, TD[dt])
+        if xoff:
+            self.x_alloc = torch.full((M * ldx + xoff,), float("nan"), dtype=TD[dt], device=gpu)
+            self.x_alloc[xoff:] = self.d_x.reshape(-1)
+            self.d_x = self.x_alloc[xoff:].view(M, ldx)
         self.d_b1, self.d_w2, self.d_b2, self.d_dy = dev(b1), dev(w2), dev(b2), dev(dy)
         # float64 reference with the dtype's rounding points
         self.pre = x @ w1 + b1
@@ -192,6 +197,19 @@ def test_exact_sums_forward_and_all_gradients(gpu, dt, M_i, cin, ldx, chid):
     check_exact(c, ctx, cin - 3)
     want = expected_path(dt, cin, ldx, chid)
     assert ctx.read_launch_log() == [f"dense2:fwd:{want}", f"dense2:bwd:{want}"]
+
+
+@pytest.mark.parametrize("dt", (BF16, F16))
+def test_x_off_its_16_byte_alignment_takes_the_plain_kernels_exact(gpu, dt):
+    """the other side of fast_ok's alignment line (dense2.hip): a shape the matrix-core kernels take, with x 8 bytes behind a 16-byte
+    boundary, runs the plain kernels - the same exact results"""
+    cin, ldx, chid = SHAPES[0]
+    assert expected_path(dt, cin, ldx, chid) == "mfma"
+    c = Case(gpu, dt, m_values()[0], cin, ldx, chid, 3, seed=100 * chid + cin, exact=True, xoff=4)
+    assert c.x_alloc.data_ptr() % 256 == 0 and c.d_x.data_ptr() % 16 == 8
+    ctx = new_ctx()
+    check_exact(c, ctx, cin - 3)
+    assert ctx.read_launch_log() == ["dense2:fwd:plain", "dense2:bwd:plain"]
 
 
 @pytest.mark.parametrize("dt", (F32, BF16, F16))

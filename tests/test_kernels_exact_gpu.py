@@ -68,11 +68,11 @@ def lay(mode, C, role):
 class Out:
     """an output view inside a sentinel-filled buffer; check() compares it bit by bit and proves that nothing around it changed"""
 
-    def __init__(self, init, ld, off, guard=False):
+    def __init__(self, init, ld, off, guard=False, goff=0):
         self.shape = tuple(init.shape)
-        if guard:
-            self.buf, self.ptr = E.guarded(init, SENTINEL)
-            self.inside = (slice(E.GUARD, E.GUARD + init.numel()),)
+        if guard:                                           # goff: E.guarded's element offset (a misaligned fp32 array)
+            self.buf, self.ptr = E.guarded(init, SENTINEL, goff)
+            self.inside = (slice(E.GUARD + goff, E.GUARD + goff + init.numel()),)
         else:
             self.buf, self.ptr = E.poisoned_view(init, ld, off, SENTINEL)
             self.inside = (slice(1, -1), Ellipsis, slice(off, off + init.shape[-1]))
@@ -94,8 +94,9 @@ def nan_like(shape, dt, gpu):
 
 class Place:
     """where the runners below put the views of a case.  This one: every view in a poisoned buffer of its own at lay()'s stride and
-    channel offset.  tests/test_large_views_gpu.py overrides it per role ("x", "dz", "act", "y", "dx") to give one view a stride of
-    millions of elements."""
+    channel offset, every weight, bias and fp32 gradient array between guards.  tests/test_large_views_gpu.py overrides it per role
+    ("x", "dz", "act", "y", "dx") to give one view a stride of millions of elements, tests/alignment_cases.py to choose the alignment
+    of every role ("w", "bias", "dw", "db" included)."""
 
     def inp(self, role, t, mode, kind):
         """an input view (kind: "in" or "act", lay()'s roles) -> (buffer, device pointer, ld)"""
@@ -106,6 +107,14 @@ class Place:
         """an output view holding `init` -> (an object with .ptr and .check(want, what, names), ld)"""
         ld, off = lay(mode, init.shape[-1], "out")
         return Out(init, ld, off), ld
+
+    def param(self, role, t):
+        """a weight or bias array ("w", "bias") -> (buffer, device pointer)"""
+        return E.guarded(t)
+
+    def grad(self, role, init):
+        """an fp32 gradient array ("dw", "db", "db2") holding `init` -> an object with .ptr and .check(want, what, names)"""
+        return Out(init, 0, 0, guard=True)
 
 
 PLACE = Place()
@@ -146,8 +155,8 @@ def run_fwd(gpu, entry, shape, mode, ws=False, tuning=0, halo=False, contains=()
     B, H, W, Cin, Cout = shape
     c = make_ctx(gpu, mode, ws, tuning)
     xb, xp, ldx = place.inp("x", dev(cs.x, dt, gpu), mode, "in")
-    wb, wp = E.guarded(dev(cs.w, dt, gpu))
-    bb, bp = E.guarded(dev(cs.bias, F32, gpu))
+    wb, wp = place.param("w", dev(cs.w, dt, gpu))
+    bb, bp = place.param("bias", dev(cs.bias, F32, gpu))
     for relu in variants:
         y, ldy = place.out("y", nan_like(cs.ref.shape, dt, gpu), mode)
         lib().call(FN[entry], c.handle, dt, xp, ldx, wp, bp, y.ptr, ldy, B, H, W, Cin, Cout, relu, stream())
@@ -164,7 +173,7 @@ def run_dgrad(gpu, entry, shape, mode, ws=False, tuning=0, halo=False, contains=
     B, H, W, Cin, Cout = shape
     c = make_ctx(gpu, mode, ws, tuning)
     dzb, dzp, lddz = place.inp("dz", dev(cs.dz, dt, gpu), mode, "in")
-    wb, wp = E.guarded(dev(cs.w, dt, gpu))
+    wb, wp = place.param("w", dev(cs.w, dt, gpu))
     ab, ap, ldact = place.inp("act", dev(cs.act, dt, gpu), mode, "act")
     for masked, accumulate in variants:
         dx, lddx = place.out("dx", dev(cs.prev, dt, gpu) if accumulate else nan_like(cs.prev.shape, dt, gpu), mode)
@@ -246,8 +255,8 @@ def run_wgrad(gpu, entry, shape, mode, ws, tuning=0, contains=(), place=PLACE):
     c = make_ctx(gpu, mode, ws, tuning)
     xb, xp, ldx = place.inp("x", dev(cs.x, dt, gpu), mode, "in")
     dzb, dzp, lddz = place.inp("dz", dev(cs.dz, dt, gpu), mode, "in")
-    dw = Out(nan_like(cs.dw.shape, F32, gpu), 0, 0, guard=True)
-    db = Out(nan_like(cs.db.shape, F32, gpu), 0, 0, guard=True)
+    dw = place.grad("dw", nan_like(cs.dw.shape, F32, gpu))
+    db = place.grad("db", nan_like(cs.db.shape, F32, gpu))
     tail = (shape[5],) if entry == "s1_wgrad" else ()
     extra = () if entry == "s1_wgrad" else (None,)          # gct2_adam_args of the 4x4 entries
     for accumulate in (0, 1):
@@ -320,10 +329,10 @@ def run_s1(gpu, entry, shape, mode, ws, place=PLACE, variants=None, prefix="defa
     else:
         cs = E.make_case(entry, shape, dt)
         c = make_ctx(gpu, mode, ws)
-        wb, wp = E.guarded(dev(cs.w, dt, gpu))
+        wb, wp = place.param("w", dev(cs.w, dt, gpu))
         if entry == "s1_fwd":
             xb, xp, ldx = place.inp("x", dev(cs.x, dt, gpu), mode, "in")
-            bb, bp = E.guarded(dev(cs.bias, F32, gpu))
+            bb, bp = place.param("bias", dev(cs.bias, F32, gpu))
             for relu in variants or (0, 1):
                 y, ldy = place.out("y", nan_like(cs.ref.shape, dt, gpu), mode)
                 lib().call(FN[entry], c.handle, dt, xp, ldx, wp, bp, y.ptr, ldy, B, H, W, Cin, Cout, KS, relu, stream())
@@ -382,10 +391,7 @@ def test_dense_fwd_bwd_exact(gpu, mode):
 
 # ---- fused bias gradients of the input-gradient calls -----------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("scratch", ["none", "ws", "ws+queue"])
-@pytest.mark.parametrize("mode", ["bf16", "f16", "f32", "f32m"])
-@pytest.mark.parametrize("entry,shape", E.BIAS_GRAD_CASES)
-def test_fused_bias_gradients_exact(gpu, entry, shape, mode, scratch):
+def run_bias_grads(gpu, entry, shape, mode, scratch, place=PLACE, contains=(), tuning=0):
     """db / db2 = column sums of the masked gradient of THIS call, split at a multiple of 8 inside a ragged Cin = 72; first call
     overwrites (over NaN), second adds.  include/gct2.h does not say whether the fp32 rows or the stored rows are summed, so the
     operands come from {-1, 0, 1}: |dx| <= 256 is exact in bf16 and both definitions are the same number.  Equality in every
@@ -397,18 +403,17 @@ def test_fused_bias_gradients_exact(gpu, entry, shape, mode, scratch):
     g = E.dgrad_ref(cs, 1, 0)
     assert np.abs(g).max() <= 256 and np.abs(2 * g).max() <= 512          # the precondition: every stored value is exact in bf16
     cs_sum = g.reshape(-1, Cin).sum(0)
-    c = make_ctx(gpu, mode, ws=scratch != "none")
+    c = make_ctx(gpu, mode, ws=scratch != "none", tuning=tuning)
     if scratch == "ws+queue":
         c.set_bias_queue(torch.full((1 << 20,), NAN, dtype=torch.float32, device=gpu))
-    dzb, dzp = E.poisoned_view(dev(cs.dz, dt, gpu), *lay(mode, Cout, "in"))
-    wb, wp = E.guarded(dev(cs.w, dt, gpu))
-    ab, ap = E.poisoned_view(dev(cs.act, dt, gpu), *lay(mode, Cin, "act"))
-    lddx, offdx = lay(mode, Cin, "out")
-    dx = Out(nan_like(g.shape, dt, gpu), lddx, offdx)
-    db = Out(nan_like((split,), F32, gpu), 0, 0, guard=True)
-    db2 = Out(nan_like((Cin - split,), F32, gpu), 0, 0, guard=True)
+    dzb, dzp, lddz = place.inp("dz", dev(cs.dz, dt, gpu), mode, "in")
+    wb, wp = place.param("w", dev(cs.w, dt, gpu))
+    ab, ap, ldact = place.inp("act", dev(cs.act, dt, gpu), mode, "act")
+    dx, lddx = place.out("dx", nan_like(g.shape, dt, gpu), mode)
+    db = place.grad("db", nan_like((split,), F32, gpu))
+    db2 = place.grad("db2", nan_like((Cin - split,), F32, gpu))
     for k, (accumulate, db_acc) in enumerate([(0, 0), (1, 3)], 1):
-        lib().call(FN[entry], c.handle, dt, dzp, dzb.shape[-1], wp, ap, ab.shape[-1], dx.ptr, lddx, B, H, W, Cin, Cout, accumulate,
+        lib().call(FN[entry], c.handle, dt, dzp, lddz, wp, ap, ldact, dx.ptr, lddx, B, H, W, Cin, Cout, accumulate,
                    db.ptr, split, db2.ptr, db_acc, stream())
         if scratch != "ws+queue":
             what = f"{entry} {shape} {mode} {scratch} call {k}"
@@ -422,7 +427,15 @@ def test_fused_bias_gradients_exact(gpu, entry, shape, mode, scratch):
         db.check(E.expected(2 * cs_sum[:split], F32), what + " db", ("c",))
         db2.check(E.expected(2 * cs_sum[split:], F32), what + " db2", ("c",))
         c.set_bias_queue(None)
-    check_log(c, tap_family(entry, shape, mode))
+    return check_log(c, tap_family(entry, shape, mode), contains)
+
+
+@pytest.mark.parametrize("scratch", ["none", "ws", "ws+queue"])
+@pytest.mark.parametrize("mode", ["bf16", "f16", "f32", "f32m"])
+@pytest.mark.parametrize("entry,shape", E.BIAS_GRAD_CASES)
+def test_fused_bias_gradients_exact(gpu, entry, shape, mode, scratch):
+    """every reduction mode of the fused bias gradients on 16-byte views (run_bias_grads)"""
+    run_bias_grads(gpu, entry, shape, mode, scratch)
 
 
 # ---- c. overflow and non-finite gradients -----------------------------------------------------------------------------------------------

@@ -45,12 +45,13 @@ def stream():
 
 
 class Guarded:
-    """a flat float32 device buffer [GUARD | n | GUARD]: `inner` is what the kernel gets, the guards must keep their fill"""
+    """a flat float32 device buffer [GUARD + shift | n | GUARD]: `inner` is what the kernel gets (shift: floats by which it misses a
+    16-byte boundary), the guards must keep their fill"""
 
-    def __init__(self, gpu, n, fill, values=None):
-        self.n, self.fill = n, fill
-        self.full = torch.full((n + 2 * GUARD,), fill, dtype=torch.float32, device=gpu)
-        self.inner = self.full[GUARD:GUARD + n]
+    def __init__(self, gpu, n, fill, values=None, shift=0):
+        self.n, self.fill, self.lo = n, fill, GUARD + shift
+        self.full = torch.full((n + 2 * GUARD + shift,), fill, dtype=torch.float32, device=gpu)
+        self.inner = self.full[self.lo:self.lo + n]
         if values is not None:
             self.inner.copy_(torch.from_numpy(np.ascontiguousarray(values, np.float32).ravel()))
         self.before = self.full.clone()
@@ -59,7 +60,7 @@ class Guarded:
         return self.inner.data_ptr()
 
     def guards_intact(self):
-        g = torch.cat([self.full[:GUARD], self.full[GUARD + self.n:]])
+        g = torch.cat([self.full[:self.lo], self.full[self.lo + self.n:]])
         return bool(torch.isnan(g).all()) if np.isnan(self.fill) else bool((g == self.fill).all())
 
     def unchanged(self):
@@ -68,17 +69,18 @@ class Guarded:
 
 class Case:
     """one kind and shape on the device: guarded inputs, outputs and scratch; run() launches, checks every guard and returns
-    (loss float32, dpred float32 array or None)"""
+    (loss float32, dpred float32 array or None).  shift: pred, target and dpred start that many floats behind a 16-byte boundary (basis
+    and scratch have to keep theirs: include/gct2.h)"""
 
-    def __init__(self, gpu, kind, pred, target, G=None):
+    def __init__(self, gpu, kind, pred, target, G=None, shift=0):
         self.gpu, self.kind, self.shape = gpu, K.KINDS[kind], pred.shape
         n = pred.size
-        self.pred, self.target = Guarded(gpu, n, np.nan, pred), Guarded(gpu, n, np.nan, target)
+        self.pred, self.target = Guarded(gpu, n, np.nan, pred, shift), Guarded(gpu, n, np.nan, target, shift)
         self.basis = Guarded(gpu, G.size, np.nan, G) if G is not None else None
         need = ctypes.c_size_t(0)
         lib().check(lib().load().gct2_loss_scratch(self.kind, *self.shape, ctypes.byref(need)), "gct2_loss_scratch")
         self.need = need.value
-        self.dpred, self.loss, self.scratch = Guarded(gpu, n, SENTINEL), Guarded(gpu, 1, SENTINEL), Guarded(gpu, self.need, SENTINEL)
+        self.dpred, self.loss, self.scratch = Guarded(gpu, n, SENTINEL, shift=shift), Guarded(gpu, 1, SENTINEL), Guarded(gpu, self.need, SENTINEL)
 
     def run(self, scale=None, grad=True, s=None, entry="gct2_loss_fwd_bwd"):
         self.dpred.full.fill_(SENTINEL); self.loss.full.fill_(SENTINEL)
@@ -153,6 +155,26 @@ def test_exact_inputs_bit_for_bit(gpu, case):
         assert bits(loss) == bits(want["loss_bits"]), (loss, want["loss_bits"])
     else:
         assert abs(float(loss) - want["loss"]) <= 1e-6 * want["loss"], (loss, want["loss"])
+
+
+@pytest.mark.parametrize("case", [("l1", (3, 5, 7, 3)), ("mse_pooled", (2, 16, 32, 3)), ("dct", (2, 20, 20, 3))], ids=ident)
+def test_operands_off_the_16_byte_grid_give_the_same_bits(gpu, case):
+    """pred, target and dpred 4, 8 and 12 bytes behind a 16-byte boundary (the header asks 4 bytes of them): the kernels read and
+    write them element by element instead of in 16-byte groups (loss_kernels.hip: `vec`, the DCT's `xvec`) - the restatement's bits
+    like the aligned call, with a loss scale as well"""
+    kind, shape = case
+    pred, target, G = exact_inputs(kind, shape)
+    want = K.restate(K.KINDS[kind], pred, target, G)
+    aligned = Case(gpu, kind, pred, target, G)
+    assert aligned.pred.ptr() % 16 == 0 and aligned.target.ptr() % 16 == 0 and aligned.dpred.ptr() % 16 == 0
+    base_loss, base = aligned.run(1024.0)
+    for shift in (1, 2, 3):
+        c = Case(gpu, kind, pred, target, G, shift=shift)
+        assert c.pred.ptr() % 16 == 4 * shift and c.dpred.ptr() % 16 == 4 * shift and c.scratch.ptr() % 16 == 0
+        loss, dpred = c.run()
+        assert np.array_equal(dpred, want["dpred_bits"]) and bits(loss) == bits(want["loss_bits"]), shift
+        loss, dpred = c.run(1024.0)
+        assert np.array_equal(bits(dpred), bits(base)) and bits(loss) == bits(base_loss), shift
 
 
 # ---- 2. real values --------------------------------------------------------------------------------------------------------------------

@@ -235,6 +235,36 @@ def test_noise_rng_four_pixel_kernel_at_the_carry(gpu, dt):
     fast.untouched_outside("four-pixel kernel")
 
 
+@pytest.mark.parametrize("which", ["x", "out"])
+@pytest.mark.parametrize("dt", [BF16, F16], ids=["bf16", "f16"])
+def test_noise_rng_packed_call_off_its_alignment_takes_the_general_kernel(gpu, dt, which):
+    """the other side of the four-pixel kernel's alignment condition (pointwise.hip: launch_noise_rng): the train step's call with x
+    4 bytes, or out 8 bytes, off a 16-byte boundary runs the general kernel - the aligned call's bits in channels 0 .. 2, slot 3 left
+    alone (the four-pixel kernel writes a zero there), nothing beside the view touched"""
+    B, HW, C, steps, off = 2, 8, 3, 200, 24
+    seed, sid = P.SEEDS[-1]
+    x, t = noise_rng_inputs(gpu, B, HW)
+    fast = Out((B, HW, 4), E.TDT[dt], gpu, ld=4, off=0)
+    assert x.data_ptr() % 16 == 0 and fast.ptr % 16 == 0
+    lib().call("gct2_noise_image_rng", dt, x.data_ptr(), t.data_ptr(), seed, sid, off, None, fast.ptr, 4, None, 0, B, HW, C, steps, stream())
+    f = fast.got()
+    assert float(f[..., 3].float().abs().max()) == 0 and float(f[..., :3].float().abs().max()) > 0      # the four-pixel kernel ran
+    xb, xp = E.guarded(x, offset=1 if which == "x" else 0)
+    flat = Out(((B * HW + 2) * 4,), E.TDT[dt], gpu)              # the packed image between two guard pixels: it starts 8 bytes in
+    op = flat.at(4) if which == "out" else flat.at(8)
+    assert flat.ptr % 16 == 0 and (xp % 16, op % 16) == ((4, 0) if which == "x" else (0, 8))
+    lib().call("gct2_noise_image_rng", dt, xp, t.data_ptr(), seed, sid, off, None, op, 4, None, 0, B, HW, C, steps, stream())
+    got = flat.got()
+    first = 1 if which == "out" else 2
+    g = got.reshape(B * HW + 2, 4)[first:first + B * HW].reshape(B, HW, 4)
+    stored_sentinel = float(torch.tensor(SENTINEL).to(E.TDT[dt]))
+    assert float((g[..., 3].float() - stored_sentinel).abs().max()) == 0
+    E.assert_elementwise_equal(g[..., :3].contiguous(), f[..., :3].contiguous(), ("b", "p", "c"), f"general kernel, {which} off its alignment")
+    rest = torch.cat([got[:4 * first], got[4 * (first + B * HW):]]).float()
+    assert float((rest - stored_sentinel).abs().max()) == 0
+    flat.untouched_outside("general kernel")
+
+
 # ---- gct2_noise_image, fp32 and bf16 -------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("steps", P.NOISE_STEPS)
