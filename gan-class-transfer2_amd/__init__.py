@@ -19,3 +19,6 @@ from .trainer_math import check_mask, img2img_steps                             
 from .trainer_math import SOLVERS, half_log_snr, multistep_coefficient                      # noqa: F401
 from .trainer_math import quantile_rank                                                     # noqa: F401
 from .trainer_math import LOSS_WEIGHTINGS, loss_weight_table                                # noqa: F401
+from . import distill                                                                       # noqa: F401
+from .distill import Distiller, clone_denoiser, progressive_distill                         # noqa: F401
+from .trainer_math import DISTILL_STREAM_EPS, DISTILL_STREAM_PAIR, distill_grid, distill_table  # noqa: F401

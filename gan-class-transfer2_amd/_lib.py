@@ -20,6 +20,7 @@ DENSE2_PLAIN_MAX = 256
 # gct2_diffusion_update modes (include/gct2.h; the sampler's objective switches, train.py:29-32)
 SAMPLE_X, SAMPLE_EPS, SAMPLE_SCALED_EPS, SAMPLE_ODE = 0, 1, 2, 3
 SAMPLE_V = 5          # the v objective (predict_v); code 4 is reserved and refused
+DISTILL_ROW = 12      # include/gct2.h GCT2_DISTILL_ROW: the floats of a row of gct2_distill_*'s table
 BUILD_STAMP = 1
 # gct2_adam_keras_clipped modes and the reduction's constants (include/gct2.h)
 CLIP_NONE, CLIP_VALUE, CLIP_NORM, CLIP_GLOBAL_NORM = 0, 1, 2, 3
@@ -92,6 +93,9 @@ SIGNATURES = {
     "gct2_x0_quantile": [_i, _vp, _vp, _d, C.c_uint32, _d, _vp, _vp, _vp, _sz, _i, _sz, _vp],
     "gct2_diffusion_step_dynamic": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _u64, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _i,
                                     _vp, _i, _i, _sz, _i, _vp],
+    "gct2_distill_start": [_i, _vp, _vp, _vp, _vp, _vp, _i, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _sz, _i, _vp],
+    "gct2_distill_step": [_i, _i, _vp, _vp, _vp, _vp, _i, _d, _vp, _vp, _i, _vp, _i, _i, _sz, _i, _vp],
+    "gct2_distill_target": [_i, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _vp, _i, _sz, _vp],
     "gct2_noise_edits": [_vp, _vp, _i, _vp, _i, _i, _i, _vp],
     "gct2_image_prepare": [_vp, _vp, _vp, _vp, _i, _i, _vp],
     "gct2_image_batch_cached": [_vp, _vp, _vp, _i, _u64, _u64, _u64, _i, _vp, _vp, _vp, _i, _i, _vp],

@@ -813,6 +813,40 @@ int gct2_diffusion_step_dynamic(int mode, int dtype, const float* pred, const fl
   return pw_sampler_step(who, st, S(stream));
 }
 
+// ---- progressive distillation (distill.hip): the per-image forms of the start from an image and of the sigma^2 = 0 step, and the
+// teacher's second step fused with the target solve
+int gct2_distill_start(int dtype, const float* x, const float* eps, const int32_t* pair, const float* table, const int32_t* ttable, int N, uint64_t seed,
+                       uint64_t stream_id, uint64_t offset, uint64_t image_stride, float* z0_out, int32_t* t_out, int32_t* t1_out, void* out,
+                       int ldout, void* out2, int ldout2, int B, size_t per_image, int C, void* stream) {
+  const char* who = "distill_start";
+  if (!x || !pair || !table || !ttable) return gct2_fail(GCT2_EINVAL, "%s: null pointer", who);
+  if (N < 1) return gct2_fail(GCT2_EINVAL, "%s: N must be >= 1", who);
+  if (int rc = step_views_ok(who, dtype, z0_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
+  return pw_distill_start(dtype, x, eps, pair, table, ttable, N, seed, stream_id, offset, image_stride, z0_out, t_out, t1_out, out, ldout, out2,
+                          ldout2, B, per_image, C, S(stream));
+}
+
+int gct2_distill_step(int mode, int dtype, const float* pred, const float* z0, const int32_t* pair, const float* table, int N, double clip,
+                      float* z1_out, void* out, int ldout, void* out2, int ldout2, int B, size_t per_image, int C, void* stream) {
+  const char* who = "distill_step";
+  if (int rc = step_mode_ok(who, mode)) return rc;
+  if (!pred || !z0 || !pair || !table) return gct2_fail(GCT2_EINVAL, "%s: null pointer", who);
+  if (N < 1) return gct2_fail(GCT2_EINVAL, "%s: N must be >= 1", who);
+  if (int rc = step_views_ok(who, dtype, z1_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
+  return pw_distill_step(mode, dtype, pred, z0, pair, table, N, clip, z1_out, out, ldout, out2, ldout2, B, per_image, C, S(stream));
+}
+
+int gct2_distill_target(int mode, const float* pred2, const float* z1, const float* z0, const int32_t* pair, const float* table, int N,
+                        double clip, float* x_out, float* eps_out, int B, size_t per_image, void* stream) {
+  const char* who = "distill_target";
+  if (int rc = step_mode_ok(who, mode)) return rc;
+  if (!pred2 || !z1 || !z0 || !pair || !table || !x_out || !eps_out) return gct2_fail(GCT2_EINVAL, "%s: null pointer", who);
+  if (N < 1) return gct2_fail(GCT2_EINVAL, "%s: N must be >= 1", who);
+  if (B <= 0 || per_image == 0 || per_image >= ((size_t)1 << 31) || (size_t)B * per_image >= ((size_t)1 << 31))
+    return gct2_fail(GCT2_EINVAL, "%s: bad shape (B * per_image < 2^31)", who);
+  return pw_distill_target(mode, pred2, z1, z0, pair, table, N, clip, x_out, eps_out, B, per_image, S(stream));
+}
+
 int gct2_noise_edits(const float* eps, const float* dictionary, int K, float* out, int H, int W, int C, void* stream) {
   if (!eps || !dictionary || !out) return gct2_fail(GCT2_EINVAL, "noise_edits: null pointer");
   if (H <= 0 || W <= 0 || C <= 0 || K <= 0 || (H & 3) || (W & 3))

@@ -149,6 +149,29 @@ template <typename T> struct is16 { static constexpr bool value = sizeof(T) == 2
 template <typename T> __device__ __forceinline__ float to_f32(T v) { return (float)v; }
 template <typename T> __device__ __forceinline__ T from_f32(float v) { return (T)v; }
 
+// the estimates from the prediction, by objective (train.py:338-355, 382-413, 452-479; modes of include/gct2.h) - the ONE place
+// (sampler.hip, distill.hip):
+//   X: x = pred, e = (fake - sa x) / sb;  EPS: e = pred, x = (fake - pred sb) / sa;  SCALED_EPS: e = pred / sb, x = (fake - pred) / sa;
+//   V: x = sa fake - sb pred, e = sb fake + sa pred (pred is v = sa eps - sb x, Salimans & Ho 2022): no division, a_t = 0 is valid.
+// sa = sqrt(a_t), sb = sqrt(1 - a_t)
+template <int MODE>
+__device__ __forceinline__ void sample_estimate(float p, float f, float sa, float sb, float& x, float& e) {
+#pragma clang fp contract(off)          // (f - sa p) / sb etc. as separate roundings, like the reference's op chain (train.py:382-413)
+  if (MODE == GCT2_SAMPLE_X) {
+    x = p;
+    e = (f - sa * p) / sb;
+  } else if (MODE == GCT2_SAMPLE_EPS) {
+    e = p;
+    x = (f - p * sb) / sa;
+  } else if (MODE == GCT2_SAMPLE_SCALED_EPS) {
+    e = p / sb;
+    x = (f - p) / sa;
+  } else {                                  // GCT2_SAMPLE_V
+    x = sa * f - sb * p;
+    e = sb * f + sa * p;
+  }
+}
+
 // D(16x16,f32) += A(16x32) * B(32x16); operands as raw 128-bit fragments (8 x 16-bit).
 // lane l holds A[row l&15][k = 8*(l>>4)+j], B[k = 8*(l>>4)+j][col l&15], D[row 4*(l>>4)+r][col l&15]
 // (verified on hardware by tests/hw_probe/probe_mfma_tr.hip).
@@ -571,6 +594,14 @@ int pw_sampler_step(const char* what, const SamplerStep& st, hipStream_t s);
 size_t pw_x0_quantile_scratch(int B);
 int pw_x0_quantile(int mode, const float* pred, const float* fake, double a_t, uint32_t rank, float floor, float* rows, float* q_out,
                    void* scratch, int B, size_t per_image, hipStream_t s);
+// distill.hip: gct2_distill_start / _step / _target's one launch each (arguments checked by the entry points)
+int pw_distill_start(int dtype, const float* x, const float* eps, const int32_t* pair, const float* table, const int32_t* ttable, int N, uint64_t seed,
+                     uint64_t stream_id, uint64_t offset, uint64_t image_stride, float* z0_out, int32_t* t_out, int32_t* t1_out, void* out,
+                     int ldout, void* out2, int ldout2, int B, size_t per_image, int C, hipStream_t s);
+int pw_distill_step(int mode, int dtype, const float* pred, const float* z0, const int32_t* pair, const float* table, int N, double clip,
+                    float* z1_out, void* out, int ldout, void* out2, int ldout2, int B, size_t per_image, int C, hipStream_t s);
+int pw_distill_target(int mode, const float* pred2, const float* z1, const float* z0, const int32_t* pair, const float* table, int N,
+                      double clip, float* x_out, float* eps_out, int B, size_t per_image, hipStream_t s);
 // pointwise.hip again
 int pw_noise_edits(const float* eps, const float* dict, int K, float* out, int H, int W, int C, hipStream_t s);
 int pw_image_prepare(const uint8_t* src, const int64_t* offsets, const int32_t* dims, float* dst, int B, int size, hipStream_t s);

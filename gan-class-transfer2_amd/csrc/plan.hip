@@ -50,6 +50,7 @@ const Entry ENTRIES[] = {
     GCT2_ENTRY(gct2_diffusion_step), GCT2_ENTRY(gct2_diffusion_start),
     GCT2_ENTRY(gct2_diffusion_step_masked), GCT2_ENTRY(gct2_diffusion_start_image), GCT2_ENTRY(gct2_diffusion_step_multistep),
     GCT2_ENTRY(gct2_x0_quantile), GCT2_ENTRY(gct2_diffusion_step_dynamic),
+    GCT2_ENTRY(gct2_distill_start), GCT2_ENTRY(gct2_distill_step), GCT2_ENTRY(gct2_distill_target),
 };
 #undef GCT2_ENTRY
 

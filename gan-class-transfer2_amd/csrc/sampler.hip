@@ -27,28 +27,7 @@ __global__ void diffusion_mix_kernel(const float* __restrict__ x, const float* _
     if (out2) out2[pix * ldout2 + c] = from_f32<T>(f);
   }
 }
-// the estimates from the prediction, by objective (train.py:338-355, 382-413, 452-479; modes of include/gct2.h) - the ONE place:
-//   X: x = pred, e = (fake - sa x) / sb;  EPS: e = pred, x = (fake - pred sb) / sa;  SCALED_EPS: e = pred / sb, x = (fake - pred) / sa;
-//   V: x = sa fake - sb pred, e = sb fake + sa pred (pred is v = sa eps - sb x, Salimans & Ho 2022): no division, a_t = 0 is valid.
-// sa = sqrt(a_t), sb = sqrt(1 - a_t)
-template <int MODE>
-__device__ __forceinline__ void sample_estimate(float p, float f, float sa, float sb, float& x, float& e) {
-#pragma clang fp contract(off)          // (f - sa p) / sb etc. as separate roundings, like the reference's op chain (train.py:382-413)
-  if (MODE == GCT2_SAMPLE_X) {
-    x = p;
-    e = (f - sa * p) / sb;
-  } else if (MODE == GCT2_SAMPLE_EPS) {
-    e = p;
-    x = (f - p * sb) / sa;
-  } else if (MODE == GCT2_SAMPLE_SCALED_EPS) {
-    e = p / sb;
-    x = (f - p) / sa;
-  } else {                                  // GCT2_SAMPLE_V
-    x = sa * f - sb * p;
-    e = sb * f + sa * p;
-  }
-}
-// one sampler update: sample_estimate's x / e, or
+// one sampler update: sample_estimate's x / e (gct2_common.h), or
 //   ODE: x = (pred sb - fake sb1) / (sa1 sb - sa sb1), e untouched; sa1 / sb1 are sa / sb at t - 1
 template <int MODE>
 __global__ void diffusion_update_kernel(const float* __restrict__ pred, const float* __restrict__ fake, float sa, float sb, float sb1, float den,

@@ -127,11 +127,25 @@ class _Sampler:
         if self.planned:
             self.eng.buffers(B, self.H, self.W).t_int.fill_(t)
 
+    def set_t_rows(self, B: int, t: torch.Tensor) -> None:
+        """set_t's per-image form: t int32 [B] on the device, one timestep per image (a distillation batch), copied where the head
+        kernels read it - no host round trip, so nothing is checked here: the caller's values come from a table of valid timesteps"""
+        if not self.heads:
+            return
+        if self.planned:
+            self.eng.buffers(B, self.H, self.W).t_int.copy_(t)
+        else:
+            self._t[B] = t
+
     def evaluate(self, B: int) -> torch.Tensor:
         """denoiser((fake, t)) on the image gct2_diffusion_mix has just stored: t is ignored (train.py:208-210) unless the engine
         carries the per-timestep heads (set_t).  Returns the fp32 prediction [B,H,W,3] (valid until the next evaluation)."""
         eng = self.eng
         if not self.planned:
+            if self.heads and torch.is_tensor(self._t[B]):       # set_t_rows: predict's body with the device-resident timesteps
+                eng.flush_deferred()
+                eng.net.t_int = self._t[B]
+                return eng.top.fwd(self._inputs[B])
             return eng.predict(self._inputs[B], self._t[B]) if self.heads else eng.predict(self._inputs[B])
         b = eng.buffers(B, self.H, self.W)
         eng.flush_deferred()                     # optimizer launches the last train step held back: never inside a captured graph

@@ -552,6 +552,82 @@ def quantile_rank(p: float, n: int) -> int:
     return min(n, max(1, math.ceil(p * n)))
 
 
+# ---- progressive distillation (distill.Distiller; gct2_distill_start / _step / _target) -------------------------------------------------
+# the Philox stream ids that belong to distillation alone: the pair of sample k at position k of stream 8, its noise at positions
+# [k per_image, (k + 1) per_image) of stream 9
+DISTILL_STREAM_PAIR = 8
+DISTILL_STREAM_EPS = 9
+# the columns of a row of distill_table (include/gct2.h GCT2_DISTILL_ROW)
+DISTILL_COLUMNS = ("sa0", "sb0", "sa1", "sb1", "sa2", "sb2", "r", "den", "cx0", "ck0", "cx1", "ce1")
+
+
+def distill_grid(steps: int, student_steps: int, timesteps=None) -> list:
+    """the teacher's ascending grid of K = 2N timesteps for a student of N = student_steps steps: sampling_timesteps(steps, 2N), or an
+    explicit strictly increasing list of 2N integers within 1..steps.  Pair j = 1..N is (t, t', t'') = (taus[2j-1], taus[2j-2],
+    taus[2j-3]); pair 1 has no t''.  The student's grid taus[1::2] of the default is sampling_timesteps(steps, N)
+    (ceil(2i steps / 2N) = ceil(i steps / N)): a distilled student is sampled with plain generate(num_steps=N).
+    ValueError unless 1 <= N and 2N <= steps."""
+    for name, v in (("steps", steps), ("student_steps", student_steps)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"distill_grid: {name} must be an int, got {v!r}")
+    steps, N = int(steps), int(student_steps)
+    if not (1 <= N and 2 * N <= steps):
+        raise ValueError(f"distill_grid: the teacher takes 2 N = {2 * N} of steps = {steps} timesteps: 1 <= N and 2 N <= steps")
+    if timesteps is None:
+        return sampling_timesteps(steps, 2 * N)
+    given = list(timesteps)
+    if len(given) != 2 * N or any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) for t in given) or given[0] < 1 or \
+            given[-1] > steps or any(b <= a for a, b in zip(given, given[1:])):
+        raise ValueError(f"distill_grid: timesteps must be {2 * N} strictly increasing integers within 1..{steps}, got {given!r}")
+    return [int(t) for t in given]
+
+
+def distill_table(taus, steps: int, schedule=None, offset: float = 0.0, mode: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """(float32 [N][12], int32 [N][2]) of an ascending grid taus of 2N timesteps: what gct2_distill_start / _step / _target read.
+    Row j - 1 belongs to pair j, (t, t', t'') = (taus[2j-1], taus[2j-2], taus[2j-3]), alphas a0, a1, a2 = alpha_dash of them as
+    Python floats: DISTILL_COLUMNS = {sa0, sb0, sa1, sb1, sa2, sb2, r, den, cx0, ck0, cx1, ce1}; the int part holds {t, t'}.
+      sa, sb    (float)sqrt(a), (float)sqrt(1 - a): square roots in double, one cast each (gct2_diffusion_step's sa / sb at a_t = a)
+      r, den    (float)(sb2 / sb0) and (float)(sa2 - (sb2 / sb0) sa0), in double from the double roots, rounded once
+      cx0, ck0  sqrtf((float)a0), sqrtf(1.f - (float)a0): the pair gct2_diffusion_start_image forms at a = a0 - the teacher's z_t is the
+                bits generate(init=) would start from
+      cx1, ce1  sqrtf((float)a1), sqrtf(1.f - (float)a1): the pair gct2_diffusion_step re-noises with at a_prev = a1 - the teacher's
+                first step is generate's step bit for bit (a float32 root of a float32 alpha can differ from sa1 / sb1 in the last place)
+    The end point of pair 1 is a2 = 1, (sa2, sb2, r, den) = (1, 0, 0, 1): generate returns the last step's x0 estimate, not an image
+    re-noised to alpha_dash(0) (0.25 on the default schedule), so the student's last estimate is trained onto what the teacher's
+    generate returns.  ValueError if a den <= 0 (alpha is not strictly decreasing along the grid; on a monotone schedule
+    den > sa2 - sa0 > 0), if an alpha leaves gct2_diffusion_step's range (a_t in [0, 1)), or - mode given, an objective code of
+    include/gct2.h - if a_t = 0 under an objective that divides by sqrt(a_t) (the epsilon modes)."""
+    taus = [int(t) for t in taus]
+    if not taus or len(taus) % 2 or any(b <= a for a, b in zip(taus, taus[1:])):
+        raise ValueError(f"distill_table: taus must be an even number of strictly increasing timesteps, got {taus!r}")
+    N = len(taus) // 2
+    tab, tt = np.zeros((N, len(DISTILL_COLUMNS)), dtype=np.float32), np.zeros((N, 2), dtype=np.int32)
+    f32 = np.float32
+    divides = mode in (_lib.SAMPLE_EPS, _lib.SAMPLE_SCALED_EPS)
+    for j in range(1, N + 1):
+        t, t1 = taus[2 * j - 1], taus[2 * j - 2]
+        a0, a1 = float(alpha_dash(t, steps, schedule, offset)), float(alpha_dash(t1, steps, schedule, offset))
+        a2 = float(alpha_dash(taus[2 * j - 3], steps, schedule, offset)) if j > 1 else 1.0
+        for name, a in (("t", a0), ("t'", a1)):
+            if not 0.0 <= a < 1.0:
+                raise ValueError(f"distill_table: alpha({name}) = {a!r} of pair {j} is outside [0, 1)")
+            if divides and not a > 0.0:
+                raise ValueError(f"distill_table: alpha({name}) = 0 at pair {j}: the teacher's objective divides by sqrt(alpha)")
+        if not 0.0 <= a2 <= 1.0:
+            raise ValueError(f"distill_table: alpha(t'') = {a2!r} of pair {j} is outside [0, 1]")
+        (sa0, sb0), (sa1, sb1), (sa2, sb2) = ((math.sqrt(a), math.sqrt(1.0 - a)) for a in (a0, a1, a2))
+        r = sb2 / sb0
+        den = sa2 - r * sa0
+        if not f32(den) > 0:
+            raise ValueError(f"distill_table: den = {den!r} at pair {j} (t, t', t'' = {t}, {t1}, {taus[2 * j - 3] if j > 1 else None}): "
+                             "alpha must decrease strictly along the grid")
+        A0, A1 = f32(a0), f32(a1)
+        tab[j - 1] = [f32(sa0), f32(sb0), f32(sa1), f32(sb1), f32(sa2), f32(sb2), f32(r), f32(den),
+                      np.sqrt(A0), np.sqrt(f32(1.0) - A0), np.sqrt(A1), np.sqrt(f32(1.0) - A1)]
+        tt[j - 1] = [t, t1]
+    return tab, tt
+
+
 def check_mask(mask, n: int, H: int, W: int) -> torch.Tensor:
     """an inpainting mask as contiguous fp32 [n,H,W] (on the mask's device): [H,W] is shared by the n images, [n,H,W] and [n,H,W,1]
     carry one per image.  1 regenerates a pixel, 0 keeps it (gct2_diffusion_step_masked).  ValueError for any other shape."""

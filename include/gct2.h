@@ -603,6 +603,48 @@ int gct2_diffusion_step_dynamic(int mode, int dtype, const float* pred, const fl
                                 uint64_t stream_id, uint64_t offset, uint64_t offset0, uint64_t image_stride, float* fake_out,
                                 float* hist_out, float* x0_out, void* out, int ldout, void* out2, int ldout2, int B, size_t per_image,
                                 int C, void* stream);
+/* ---- progressive distillation (Salimans & Ho 2022, "Progressive Distillation for Fast Sampling of Diffusion Models"; Distiller):
+ * a student learns to do in ONE DDIM step what its teacher does in two.  A batch holds a different timestep per image, so the
+ * scalars (a_t, a_prev) of the sampler's entry points become a row of a host-built table per image:
+ *   pair   [B] int32, 1-based (what gct2_rng_uniform_int(..., 1, N) draws): image b reads row clamp(pair[b], 1, N) - 1 of both tables,
+ *          so no value reads outside them
+ *   table  [N][GCT2_DISTILL_ROW] fp32 (trainer_math.distill_table) for the timesteps t > t' > t'' of a pair of teacher steps:
+ *            {sa0, sb0, sa1, sb1, sa2, sb2, r, den, cx0, ck0, cx1, ce1}
+ *          sa = (float)sqrt(a), sb = (float)sqrt(1 - a) at a = alpha(t), alpha(t'), alpha(t'') (square roots in double, one cast each:
+ *          gct2_diffusion_step's sa / sb);  r = (float)(sb2 / sb0), den = (float)(sa2 - (sb2 / sb0) sa0) from the double roots, rounded
+ *          once;  cx0 = sqrtf((float)alpha(t)), ck0 = sqrtf(1.f - (float)alpha(t)): gct2_diffusion_start_image's pair at a = alpha(t);
+ *          cx1 = sqrtf((float)alpha(t')), ce1 = sqrtf(1.f - (float)alpha(t')): gct2_diffusion_step's re-noising pair at a_prev = alpha(t').
+ *          The first pair of a grid has no t'': its end point is alpha = 1, {sa2, sb2, r, den} = {1, 0, 0, 1} (generate returns the last
+ *          step's x0 estimate, not a re-noised image).  The caller guarantees sb0 > 0, den > 0 and gct2_diffusion_step's a_t rule.
+ *   ttable [N][2] int32 {t, t'}
+ * Shapes, views and their GCT2_EINVAL rules are gct2_diffusion_step's: B images of per_image fp32 elements, per_image a multiple of C,
+ * ldout >= C, B * per_image < 2^31; also GCT2_EINVAL: a NULL pointer (t_out, t1_out and out2 may be NULL), N < 1, GCT2_SAMPLE_ODE and the
+ * reserved code 4.  fp32, every operation rounded once (no fused multiply-add).  No output overlaps an input or another output.
+ *
+ * gct2_distill_start: gct2_diffusion_start_image with a per-image alpha.  z0_out[i] = cx0 x[i] + ck0 e, e the normal gct2_rng_normal
+ *   writes for element offset + b image_stride + i of the stream (seed, stream_id) - or, eps != NULL, e = eps[i] and nothing is drawn
+ *   (a pinned batch); z0 once rounded into out / out2;
+ *   t_out[b] = t, t1_out[b] = t' of the image's row.  Image by image the bits of gct2_diffusion_start_image(a = alpha(t)).
+ * gct2_distill_step: the teacher's first step t -> t'.  Per image gct2_diffusion_step at sigma2 = 0 with (sa0, sb0) as a_t's and
+ *   (cx1, ce1) as a_prev's coefficients, the same clip (> 0: x clipped, e re-derived), bit for bit; z1_out and out / out2 are its
+ *   fake_out and views.  Nothing else is stored.
+ * gct2_distill_target: the teacher's second step t' -> t'' fused with the solve for the student's pseudo pair; z'' never reaches memory.
+ *   Element i of image b, p = pred2, f1 = z1, f0 = z0:
+ *     (x2, e2)  gct2_diffusion_step's update at (sa1, sb1) and clip, bit for bit
+ *     xt = (sb2 == 0) ? x2 : fl( fl( fl(fl(sa2 x2) + fl(sb2 e2)) - fl(r f0) ) / den )
+ *     et = fl( fl( f0 - fl(sa0 xt) ) / sb0 )
+ *   x_out[i] = xt, eps_out[i] = et: one DDIM step from z0 with the estimate xt lands on the teacher's z'', and a student handed
+ *   (xt, et) at timestep t is noised back to z0 up to rounding.  It takes no views and no C.  Four elements per thread with 16-byte
+ *   accesses when per_image is a multiple of 4 and the five planes are 16-byte aligned, one element per thread otherwise: same bits.
+ * Measured on one MI355X at 64x128x128x3, bf16 views: profiles/distill_bench.json. */
+#define GCT2_DISTILL_ROW 12
+int gct2_distill_start(int dtype, const float* x, const float* eps, const int32_t* pair, const float* table, const int32_t* ttable, int N, uint64_t seed,
+                       uint64_t stream_id, uint64_t offset, uint64_t image_stride, float* z0_out, int32_t* t_out, int32_t* t1_out,
+                       void* out, int ldout, void* out2, int ldout2, int B, size_t per_image, int C, void* stream);
+int gct2_distill_step(int mode, int dtype, const float* pred, const float* z0, const int32_t* pair, const float* table, int N, double clip,
+                      float* z1_out, void* out, int ldout, void* out2, int ldout2, int B, size_t per_image, int C, void* stream);
+int gct2_distill_target(int mode, const float* pred2, const float* z1, const float* z0, const int32_t* pair, const float* table, int N,
+                        double clip, float* x_out, float* eps_out, int B, size_t per_image, void* stream);
 /* the four inputs of the reverse pass built from one inverted noise image eps [H,W,C] (train.py:416-431): out [4,H,W,C] =
  * eps | nearest-upsample x4 of avg_pool2d(eps, 4, 4) | tf.roll by 1 along H and W | per-pixel nearest of the K entries of
  * dictionary [H,W,K,C] (squared distance, first minimum).  H, W multiples of 4. */
