@@ -18,6 +18,7 @@ from .trainer_math import GENERATE_STREAM, ddim_sigma2, sampling_timesteps      
 from .trainer_math import check_mask, img2img_steps                                         # noqa: F401
 from .trainer_math import SOLVERS, half_log_snr, multistep_coefficient                      # noqa: F401
 from .trainer_math import quantile_rank                                                     # noqa: F401
+from .trainer_math import guidance_launches, guidance_table                                 # noqa: F401
 from .trainer_math import LOSS_WEIGHTINGS, loss_weight_table                                # noqa: F401
 from . import distill                                                                       # noqa: F401
 from .distill import Distiller, clone_denoiser, progressive_distill                         # noqa: F401

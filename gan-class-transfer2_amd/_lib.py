@@ -93,6 +93,9 @@ SIGNATURES = {
     "gct2_x0_quantile": [_i, _vp, _vp, _d, C.c_uint32, _d, _vp, _vp, _vp, _sz, _i, _sz, _vp],
     "gct2_diffusion_step_dynamic": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _u64, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _i,
                                     _vp, _i, _i, _sz, _i, _vp],
+    "gct2_x0_quantile_guided": [_i, _vp, _vp, _d, _vp, _d, C.c_uint32, _d, _vp, _vp, _vp, _sz, _i, _sz, _vp],
+    "gct2_diffusion_step_guided": [_i, _i, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _d, _u64, _u64, _u64, _u64, _u64, _vp, _vp, _vp,
+                                   _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _sz, _i, _vp],
     "gct2_distill_start": [_i, _vp, _vp, _vp, _vp, _vp, _i, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _sz, _i, _vp],
     "gct2_distill_step": [_i, _i, _vp, _vp, _vp, _vp, _i, _d, _vp, _vp, _i, _vp, _i, _i, _sz, _i, _vp],
     "gct2_distill_target": [_i, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _vp, _i, _sz, _vp],

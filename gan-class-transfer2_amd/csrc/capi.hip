@@ -787,7 +787,7 @@ int gct2_x0_quantile(int mode, const float* pred, const float* fake, double a_t,
   if (!std::isfinite(floor) || !std::isfinite((float)floor) || !((float)floor > 0.f))
     return gct2_fail(GCT2_EINVAL, "%s: floor must be finite and > 0 in fp32", who);
   if (scratch_bytes < pw_x0_quantile_scratch(B)) return gct2_fail(GCT2_EINVAL, "%s: scratch too small (gct2_x0_quantile_scratch)", who);
-  return pw_x0_quantile(mode, pred, fake, a_t, rank, (float)floor, rows, q_out, scratch, B, per_image, S(stream));
+  return pw_x0_quantile(mode, pred, fake, a_t, rank, (float)floor, rows, q_out, scratch, B, per_image, false, nullptr, 1.f, S(stream));
 }
 
 int gct2_diffusion_step_dynamic(int mode, int dtype, const float* pred, const float* fake_in, const float* hist_in, const float* known,
@@ -810,6 +810,62 @@ int gct2_diffusion_step_dynamic(int mode, int dtype, const float* pred, const fl
   st.pred = pred; st.fake_in = fake_in; st.hist_in = hist_in; st.known = known; st.mask = mask; st.rows = rows;
   st.a = a_t; st.a_prev = a_prev; st.sigma2 = sigma2; st.c1 = c1; st.multistep = multistep;
   st.offset = offset; st.offset0 = offset0; st.hist_out = hist_out; st.x0_out = x0_out;
+  return pw_sampler_step(who, st, S(stream));
+}
+
+// ---- two-network guidance: the select and the step on p = pred_guide + w (pred - pred_guide), never materialised
+static int guide_weight_ok(const char* who, double w) {
+  if (!std::isfinite(w) || !std::isfinite((float)w)) return gct2_fail(GCT2_EINVAL, "%s: w must be finite in fp32", who);
+  return GCT2_OK;
+}
+
+int gct2_x0_quantile_guided(int mode, const float* pred, const float* pred_guide, double w, const float* fake, double a_t, uint32_t rank,
+                            double floor, float* rows, float* q_out, void* scratch, size_t scratch_bytes, int B, size_t per_image,
+                            void* stream) {
+  const char* who = "x0_quantile_guided";
+  if (int rc = step_mode_ok(who, mode)) return rc;
+  if (!pred || !pred_guide || (!fake && mode != GCT2_SAMPLE_X) || !rows || !scratch) return gct2_fail(GCT2_EINVAL, "%s: null pointer", who);
+  if (int rc = guide_weight_ok(who, w)) return rc;
+  if (B <= 0 || per_image == 0 || (size_t)B * per_image >= ((size_t)1 << 31))
+    return gct2_fail(GCT2_EINVAL, "%s: bad shape (B * per_image < 2^31)", who);
+  if (!(a_t >= 0. && a_t < 1.)) return gct2_fail(GCT2_EINVAL, "%s: a_t must be in [0, 1)", who);
+  if (mode != GCT2_SAMPLE_X && mode != GCT2_SAMPLE_V && !(a_t > 0.))
+    return gct2_fail(GCT2_EINVAL, "%s: this mode divides by sqrt(a_t): a_t must be > 0", who);
+  if (rank < 1 || rank > per_image) return gct2_fail(GCT2_EINVAL, "%s: rank must be in 1..per_image", who);
+  if (!std::isfinite(floor) || !std::isfinite((float)floor) || !((float)floor > 0.f))
+    return gct2_fail(GCT2_EINVAL, "%s: floor must be finite and > 0 in fp32", who);
+  if (scratch_bytes < pw_x0_quantile_scratch(B)) return gct2_fail(GCT2_EINVAL, "%s: scratch too small (gct2_x0_quantile_scratch)", who);
+  return pw_x0_quantile(mode, pred, fake, a_t, rank, (float)floor, rows, q_out, scratch, B, per_image, true, pred_guide, (float)w, S(stream));
+}
+
+int gct2_diffusion_step_guided(int mode, int dtype, const float* pred, const float* pred_guide, double w, const float* fake_in,
+                               const float* hist_in, const float* known, const float* mask, const float* rows, double a_t, double a_prev,
+                               double sigma2, double c1, double clip, uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t offset0,
+                               uint64_t image_stride, float* fake_out, float* hist_out, float* x0_out, void* out, int ldout, void* out2,
+                               int ldout2, void* out3, int ldout3, void* out4, int ldout4, int B, size_t per_image, int C, void* stream) {
+  const char* who = "diffusion_step_guided";
+  if (int rc = step_mode_ok(who, mode)) return rc;
+  if (!pred || !fake_in) return gct2_fail(GCT2_EINVAL, "%s: null pointer", who);
+  if (int rc = guide_weight_ok(who, w)) return rc;
+  if (!pred_guide && (float)w != 1.f) return gct2_fail(GCT2_EINVAL, "%s: pred_guide is NULL (p = pred): w must be 1", who);
+  if (rows && clip != 0.) return gct2_fail(GCT2_EINVAL, "%s: rows is the per-image bound: clip must be 0", who);
+  if (!known != !mask) return gct2_fail(GCT2_EINVAL, "%s: known and mask go together (both NULL: the plain step)", who);
+  if (int rc = step_views_ok(who, dtype, fake_out, out, ldout, out2, ldout2, B, per_image, C)) return rc;
+  if (out4 && !out3) return gct2_fail(GCT2_EINVAL, "%s: out4 without out3", who);
+  if ((out3 && ldout3 < C) || (out4 && ldout4 < C)) return gct2_fail(GCT2_EINVAL, "%s: ldout3 / ldout4 must be >= C", who);
+  if (int rc = step_scalars_ok(who, mode, a_t, a_prev)) return rc;
+  if (int rc = step_sigma2_ok(who, a_prev, sigma2)) return rc;
+  if (!std::isfinite(c1) || !std::isfinite((float)c1)) return gct2_fail(GCT2_EINVAL, "%s: c1 must be finite in fp32", who);
+  if ((float)c1 != 0.f && !hist_in) return gct2_fail(GCT2_EINVAL, "%s: c1 != 0 extrapolates from hist_in, which is NULL", who);
+  // the multistep form: a history plane on either side, or an extrapolation
+  const bool multistep = hist_in || hist_out || (float)c1 != 0.f;
+  if (multistep && (float)sigma2 != 0.f) return gct2_fail(GCT2_EINVAL, "%s: the multistep form is deterministic: sigma2 must be 0", who);
+  SamplerStep st = step_views(mode, dtype, seed, stream_id, image_stride, fake_out, out, ldout, out2, ldout2, B, per_image, C);
+  st.pred = pred; st.fake_in = fake_in; st.hist_in = hist_in; st.known = known; st.mask = mask; st.rows = rows;
+  st.a = a_t; st.a_prev = a_prev; st.sigma2 = sigma2; st.c1 = c1; st.clip = clip; st.multistep = multistep;
+  st.offset = offset; st.offset0 = offset0; st.hist_out = hist_out; st.x0_out = x0_out;
+  st.guided = true; st.pred_guide = pred_guide; st.w = w;
+  st.out3 = out3; st.ldout3 = ldout3; st.out4 = out4; st.ldout4 = ldout4;
   return pw_sampler_step(who, st, S(stream));
 }
 

@@ -480,6 +480,11 @@ struct SamplerStep {
   float *fake_out = nullptr, *hist_out = nullptr, *x0_out = nullptr;
   void* out = nullptr; int ldout = 0; void* out2 = nullptr; int ldout2 = 0;
   int B = 0; size_t per_image = 0; int C = 0;
+  // gct2_diffusion_step_guided (guided: its kernels, also with pred_guide nullptr): p = pred_guide + w (pred - pred_guide), and the
+  // guide engine's input views, which take what out / out2 take
+  bool guided = false;
+  const float* pred_guide = nullptr; double w = 1.;
+  void* out3 = nullptr; int ldout3 = 0; void* out4 = nullptr; int ldout4 = 0;
 };
 
 // ---- host side: every function one translation unit defines and another one calls, declared HERE and nowhere else (each defining
@@ -593,7 +598,7 @@ int pw_diffusion_update(int mode, const float* pred, const float* fake, double a
 int pw_sampler_step(const char* what, const SamplerStep& st, hipStream_t s);
 size_t pw_x0_quantile_scratch(int B);
 int pw_x0_quantile(int mode, const float* pred, const float* fake, double a_t, uint32_t rank, float floor, float* rows, float* q_out,
-                   void* scratch, int B, size_t per_image, hipStream_t s);
+                   void* scratch, int B, size_t per_image, bool guided, const float* pred_guide, float w, hipStream_t s);
 // distill.hip: gct2_distill_start / _step / _target's one launch each (arguments checked by the entry points)
 int pw_distill_start(int dtype, const float* x, const float* eps, const int32_t* pair, const float* table, const int32_t* ttable, int N, uint64_t seed,
                      uint64_t stream_id, uint64_t offset, uint64_t image_stride, float* z0_out, int32_t* t_out, int32_t* t1_out, void* out,

@@ -12,7 +12,7 @@
 
 namespace {
 
-constexpr int MAX_ARGS = 28;
+constexpr int MAX_ARGS = 35;
 
 // one 64-bit slot per argument: pointers and 64-bit integers as they are, ints sign-extended, floats as their bit pattern in the
 // low half, doubles as their bit pattern
@@ -50,6 +50,7 @@ const Entry ENTRIES[] = {
     GCT2_ENTRY(gct2_diffusion_step), GCT2_ENTRY(gct2_diffusion_start),
     GCT2_ENTRY(gct2_diffusion_step_masked), GCT2_ENTRY(gct2_diffusion_start_image), GCT2_ENTRY(gct2_diffusion_step_multistep),
     GCT2_ENTRY(gct2_x0_quantile), GCT2_ENTRY(gct2_diffusion_step_dynamic),
+    GCT2_ENTRY(gct2_x0_quantile_guided), GCT2_ENTRY(gct2_diffusion_step_guided),
     GCT2_ENTRY(gct2_distill_start), GCT2_ENTRY(gct2_distill_step), GCT2_ENTRY(gct2_distill_target),
 };
 #undef GCT2_ENTRY
@@ -89,7 +90,7 @@ int gct2_plan_add_call(gct2_plan* plan, const char* name, const uint64_t* args, 
   for (int e = 0; e < (int)(sizeof(ENTRIES) / sizeof(ENTRIES[0])); e++) {
     if (strcmp(ENTRIES[e].name, name)) continue;
     if (nargs != ENTRIES[e].nargs) return gct2_fail(GCT2_EINVAL, "plan_add_call: %s takes %d arguments, got %d", name, ENTRIES[e].nargs, nargs);
-    static_assert(MAX_ARGS >= 28, "gct2_convT4s2_fwd_head_train has 28 arguments");
+    static_assert(MAX_ARGS >= 35, "gct2_diffusion_step_guided has 35 arguments");
     if (nargs > MAX_ARGS) return gct2_fail(GCT2_EINVAL, "plan_add_call: too many arguments");
     Op op{};
     op.kind = OP_CALL; op.entry = e; op.nargs = nargs; op.event = -1; op.stream = nullptr;

@@ -2,8 +2,11 @@
 // the six one-launch steps gct2_diffusion_step / _start / _start_image / _step_masked / _step_multistep / _step_dynamic, which are ONE
 // per-element computation (step_element) behind two traversals (sampler_flat_kernel, sampler_counter_kernel); gct2_x0_quantile, the
 // per-image order statistic of |x0| that feeds _step_dynamic (a radix select over sample_estimate's x).  fp32 state, HBM-bound.
+// Two-network guidance: gct2_diffusion_step_guided and gct2_x0_quantile_guided are the same kernels with GUIDED set - the prediction is
+// combined from two planes on the way in, the compute-dtype copy goes to a second engine's views on the way out.
 #include "gct2_common.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -64,25 +67,45 @@ struct SamplerArgs {
   // and the hidden grid size in another order, since the two no longer sit side by side (one to six more instructions of 370 to 870)
   const float* __restrict__ rows;
 };
+// gct2_diffusion_step_guided: a struct of its own behind SamplerArgs, so no field of the existing kernels' argument moves.  pred_guide
+// nullptr: p = pred (w is then 1).  out3 / out4: the guide engine's input views, nullptr where the call has none
+struct GuidedArgs : SamplerArgs {
+  const float* __restrict__ pred_guide; float w;
+  void* __restrict__ out3; int ldout3; void* __restrict__ out4; int ldout4;
+};
+template <bool GUIDED> using StepArgs = std::conditional_t<GUIDED, GuidedArgs, SamplerArgs>;
+// the prediction a guided step uses, p = p_guide + w (p_main - p_guide): three operations, each rounded once (the ONE place: the
+// guided step and the guided select form the same bits)
+__device__ __forceinline__ float guided_pred(float pm, float pg, float w) {
+#pragma clang fp contract(off)
+  const float d = pm - pg;
+  const float t = w * d;
+  return pg + t;
+}
 
 // the bound of image b's estimate, DYN (gct2_diffusion_step_dynamic) only: gct2_x0_quantile's {s_b, r_b}.  DYN is a template flag, not
 // a test of k.rows at run time: the run-time test slowed the existing step with noise (profiles/dynamic_threshold_bench.json,
 // dropped_forms: figures recorded once from that build); without DYN the kernels are the ones the other entry points always had
 struct ImageBound { float s, r; };
-template <bool DYN>
+// GUIDED kernels choose between rows and the scalar clip at run time (wave-uniform; no earlier timing depends on them, and the
+// instantiation count stays what one flag costs): the scalar clip is the bound {clip, 1}, whose multiply leaves the bits alone
+template <bool DYN, bool GUIDED>
 __device__ __forceinline__ ImageBound image_bound(const SamplerArgs& k, uint32_t b) {
   if constexpr (DYN) return ImageBound{k.rows[2 * b], k.rows[2 * b + 1]};
+  else if constexpr (GUIDED) return k.rows ? ImageBound{k.rows[2 * b], k.rows[2 * b + 1]} : ImageBound{k.clip, 1.f};
   else return ImageBound{0.f, 1.f};
 }
-template <int MODE, bool DYN>
+template <int MODE, bool DYN, bool GUIDED>
 __device__ __forceinline__ float step_update(float p, float f, const SamplerArgs& k, ImageBound q, float& x) {
 #pragma clang fp contract(off)
   float e;
   sample_estimate<MODE>(p, f, k.sa, k.sb, x, e);
-  if constexpr (DYN) {                      // dynamic thresholding: clip to the image's own bound, rescale to the floor
-    x = x < -q.s ? -q.s : (x > q.s ? q.s : x);
-    x = x * q.r;                            // one rounded multiply; r == 1.0f leaves the bits alone
-    e = (f - k.sa * x) / k.sb;
+  if constexpr (DYN || GUIDED) {            // dynamic thresholding: clip to the image's own bound, rescale to the floor
+    if (DYN || k.rows || q.s > 0.f) {       // (GUIDED, wave-uniform: rows, else the scalar clip where there is one)
+      x = x < -q.s ? -q.s : (x > q.s ? q.s : x);
+      x = x * q.r;                          // one rounded multiply; r == 1.0f leaves the bits alone
+      e = (f - k.sa * x) / k.sb;
+    }
   } else if (k.clip > 0.f) {                       // (wave-uniform)  a NaN fails both comparisons and stays
     const float c = k.clip;
     x = x < -c ? -c : (x > c ? c : x);
@@ -103,7 +126,7 @@ __device__ __forceinline__ float mask_select(float m, float g, float h) {
 //   MULTI (DPM-Solver++ 2M, Lu et al. 2022): the re-noising reads d = x + c1 (x - hist) in x's place, with e re-derived from d.
 //   c1 == 0 (wave-uniform; the first step, and generate's last): step_update's own fake', the history is never read.
 //   NOISE: + cz z.  MASKED: the mask of the element's pixel selects between that g and h (x and kn for x0)
-template <int MODE, bool MASKED, bool MULTI, bool NOISE, bool DYN>
+template <int MODE, bool MASKED, bool MULTI, bool NOISE, bool DYN, bool GUIDED = false>
 __device__ __forceinline__ float step_element(float p, float f, float kn, float m, float z0, float z, size_t i, const SamplerArgs& k,
                                               ImageBound q, float& x, float& x0) {
 #pragma clang fp contract(off)
@@ -113,7 +136,7 @@ __device__ __forceinline__ float step_element(float p, float f, float kn, float 
     x0 = kn;
     return k.cx * kn + k.ck * z0;
   } else {
-    float g = step_update<MODE, DYN>(p, f, k, q, x);
+    float g = step_update<MODE, DYN, GUIDED>(p, f, k, q, x);
     if constexpr (MULTI) {
       if (k.c1 != 0.f) {
         const float d = x + k.c1 * (x - k.hist_in[i]);
@@ -132,21 +155,30 @@ __device__ __forceinline__ float step_element(float p, float f, float kn, float 
     }
   }
 }
-template <typename T>
-__device__ __forceinline__ void step_store(float v, size_t i, size_t pix, int c, const SamplerArgs& a) {
+// (A: SamplerArgs, or GuidedArgs with the guide engine's views out3 / out4, which take the same compute-dtype value)
+template <typename T, typename A>
+__device__ __forceinline__ void step_store(float v, size_t i, size_t pix, int c, const A& a) {
   a.fake_out[i] = v;
   static_cast<T*>(a.out)[pix * a.ldout + c] = from_f32<T>(v);
   if (a.out2) static_cast<T*>(a.out2)[pix * a.ldout2 + c] = from_f32<T>(v);
+  if constexpr (std::is_same_v<A, GuidedArgs>) {
+    if (a.out3) static_cast<T*>(a.out3)[pix * a.ldout3 + c] = from_f32<T>(v);
+    if (a.out4) static_cast<T*>(a.out4)[pix * a.ldout4 + c] = from_f32<T>(v);
+  }
 }
 // one whole Philox counter: four consecutive elements from a flat index that is a multiple of 4, all planes 16-byte aligned - the fp32
 // plane moves as a 16-byte access, the compute-dtype copies element by element (a row holds C of them)
-template <typename T>
-__device__ __forceinline__ void store_quad(f32x4_t v, size_t i, uint32_t pix, int c, const SamplerArgs& a) {
+template <typename T, typename A>
+__device__ __forceinline__ void store_quad(f32x4_t v, size_t i, uint32_t pix, int c, const A& a) {
   *reinterpret_cast<f32x4_t*>(a.fake_out + i) = v;
 #pragma unroll
   for (int j = 0; j < 4; j++) {
     static_cast<T*>(a.out)[(size_t)pix * a.ldout + c] = from_f32<T>(v[j]);
     if (a.out2) static_cast<T*>(a.out2)[(size_t)pix * a.ldout2 + c] = from_f32<T>(v[j]);
+    if constexpr (std::is_same_v<A, GuidedArgs>) {
+      if (a.out3) static_cast<T*>(a.out3)[(size_t)pix * a.ldout3 + c] = from_f32<T>(v[j]);
+      if (a.out4) static_cast<T*>(a.out4)[(size_t)pix * a.ldout4 + c] = from_f32<T>(v[j]);
+    }
     if (++c == a.C) { c = 0; ++pix; }
   }
 }
@@ -165,8 +197,8 @@ __device__ __forceinline__ void counter_normals(const SamplerArgs& a, uint64_t c
 // element, and still the faster form: the masked step takes 25.3 us against 28.8 us for a thread per Philox counter with 16-byte
 // accesses, the start 20.3 against 26.1 us, at 64x128x128x3 (profiles/img2img_bench.json: consecutive lanes store their copies next to
 // each other).  Any offset0 and image_stride
-template <typename T, int MODE, bool MASKED, bool MULTI, bool DYN>
-__global__ void sampler_flat_kernel(const SamplerArgs a) {
+template <typename T, int MODE, bool MASKED, bool MULTI, bool DYN, bool GUIDED = false>
+__global__ void sampler_flat_kernel(const StepArgs<GUIDED> a) {
   const size_t n = (size_t)a.B * a.per_image, stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     float p = 0.f, f = 0.f, kn = 0.f, m = 0.f, z0 = 0.f;
@@ -178,9 +210,10 @@ __global__ void sampler_flat_kernel(const SamplerArgs a) {
     const uint32_t pix = (uint32_t)i / (uint32_t)a.C;
     if constexpr (MASKED) m = a.mask[pix];
     if constexpr (MODE != STEP_START_IMAGE) { p = a.pred[i]; f = a.fake_in[i]; }
-    const ImageBound q = image_bound<DYN>(a, (uint32_t)i / a.per_image);
+    if constexpr (GUIDED) if (a.pred_guide) p = guided_pred(p, a.pred_guide[i], a.w);
+    const ImageBound q = image_bound<DYN, GUIDED>(a, (uint32_t)i / a.per_image);
     float x, x0;
-    const float v = step_element<MODE, MASKED, MULTI, false, DYN>(p, f, kn, m, z0, 0.f, i, a, q, x, x0);
+    const float v = step_element<MODE, MASKED, MULTI, false, DYN, GUIDED>(p, f, kn, m, z0, 0.f, i, a, q, x, x0);
     if constexpr (MULTI) if (a.hist_out) a.hist_out[i] = x;
     if constexpr (MODE != STEP_START_IMAGE) if (a.x0_out) a.x0_out[i] = x0;
     step_store<T>(v, i, pix, (int)((uint32_t)i - pix * (uint32_t)a.C), a);
@@ -198,15 +231,15 @@ __global__ void sampler_flat_kernel(const SamplerArgs a) {
 // thread, the mask is read per element (a group of four spans up to three pixels at C = 3), 28.1 us where the general form takes
 // 76.1 us (profiles/img2img_bench.json).  General form, MASKED: z per element through philox_normal (the two draws may sit at
 // different lanes of their counters)
-template <typename T, int MODE, bool MASKED, bool VEC, bool DYN>
-__global__ void sampler_counter_kernel(const SamplerArgs a) {
+template <typename T, int MODE, bool MASKED, bool VEC, bool DYN, bool GUIDED = false>
+__global__ void sampler_counter_kernel(const StepArgs<GUIDED> a) {
   constexpr bool STEP = MODE != STEP_START;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
     const uint64_t base = a.offset + (uint64_t)b * a.image_stride;                       // the step noise of the image
     const uint64_t own = MASKED ? a.offset0 + (uint64_t)b * a.image_stride : base, end = own + a.per_image;
     const uint64_t c0 = own >> 2;
-    const ImageBound q = image_bound<DYN>(a, (uint32_t)b);
+    const ImageBound q = image_bound<DYN, GUIDED>(a, (uint32_t)b);
     const size_t ncounters = (size_t)(((end + 3) >> 2) - c0);
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < ncounters; t += stride) {
       const uint64_t ctr = c0 + t;
@@ -219,6 +252,11 @@ __global__ void sampler_counter_kernel(const SamplerArgs a) {
         f32x4_t p = {}, f = {}, kn = {}, v, x4;
         if constexpr (MASKED) kn = *reinterpret_cast<const f32x4_t*>(a.known + i);
         if constexpr (STEP) { p = *reinterpret_cast<const f32x4_t*>(a.pred + i); f = *reinterpret_cast<const f32x4_t*>(a.fake_in + i); }
+        if constexpr (GUIDED) if (a.pred_guide) {
+          const f32x4_t pg = *reinterpret_cast<const f32x4_t*>(a.pred_guide + i);
+#pragma unroll
+          for (int j = 0; j < 4; j++) p[j] = guided_pred(p[j], pg[j], a.w);
+        }
         const uint32_t pix0 = (uint32_t)i / (uint32_t)a.C;
         const int ch0 = (int)((uint32_t)i - pix0 * (uint32_t)a.C);
         uint32_t pix = pix0;
@@ -227,10 +265,10 @@ __global__ void sampler_counter_kernel(const SamplerArgs a) {
         for (int j = 0; j < 4; j++) {
           float x, x0;
           if constexpr (MASKED) {
-            v[j] = step_element<MODE, true, false, true, DYN>(p[j], f[j], kn[j], a.mask[pix], n0[j], nz[j], i, a, q, x, x0);
+            v[j] = step_element<MODE, true, false, true, DYN, GUIDED>(p[j], f[j], kn[j], a.mask[pix], n0[j], nz[j], i, a, q, x, x0);
             if (++c == a.C) { c = 0; ++pix; }
           } else {
-            v[j] = step_element<MODE, false, false, true, DYN>(p[j], f[j], 0.f, 0.f, 0.f, n0[j], i, a, q, x, x0);
+            v[j] = step_element<MODE, false, false, true, DYN, GUIDED>(p[j], f[j], 0.f, 0.f, 0.f, n0[j], i, a, q, x, x0);
           }
           if constexpr (STEP) x4[j] = x0;
         }
@@ -249,11 +287,12 @@ __global__ void sampler_counter_kernel(const SamplerArgs a) {
           const size_t i = (size_t)b * a.per_image + within;
           float p = 0.f, f = 0.f, v, x, x0;
           if constexpr (STEP) { p = a.pred[i]; f = a.fake_in[i]; }
+          if constexpr (GUIDED) if (a.pred_guide) p = guided_pred(p, a.pred_guide[i], a.w);
           if constexpr (MASKED)
-            v = step_element<MODE, true, false, true, DYN>(p, f, a.known[i], a.mask[pix], n0[j], philox_normal(a.seed, a.stream_id, base + within), i,
-                                                      a, q, x, x0);
+            v = step_element<MODE, true, false, true, DYN, GUIDED>(p, f, a.known[i], a.mask[pix], n0[j],
+                                                                   philox_normal(a.seed, a.stream_id, base + within), i, a, q, x, x0);
           else
-            v = step_element<MODE, false, false, true, DYN>(p, f, 0.f, 0.f, 0.f, n0[j], i, a, q, x, x0);
+            v = step_element<MODE, false, false, true, DYN, GUIDED>(p, f, 0.f, 0.f, 0.f, n0[j], i, a, q, x, x0);
           if constexpr (STEP) if (a.x0_out) a.x0_out[i] = x0;
           step_store<T>(v, i, pix, (int)c, a);
           if (++c == (uint32_t)a.C) { c = 0; ++pix; }
@@ -319,10 +358,14 @@ __device__ __forceinline__ void qsel_find(const uint32_t* __restrict__ table, in
 // one digit pass: blockIdx.x walks an image's elements, blockIdx.y the images.  Shipped: a histogram per wave in LDS (4 x 2048 x 4 B = 32 KB at
 // the top digit, which is essentially the exponent: most of an image falls into a handful of bins, and the waves of a work-group
 // would serialise on them), summed and flushed bin by bin - non-zero bins only - into the image's table
-template <int MODE, int PASS>
+// G (gct2_x0_quantile_guided only): the guide's plane and the weight behind the existing arguments, every pass forms guided_pred before
+// the estimate - the guided step's x0 bit for bit, nothing materialised
+struct QselGuide { const float* __restrict__ pred_guide; float w; };
+template <int MODE, int PASS, typename... G>
 __global__ void __launch_bounds__(QSEL_THREADS) x0_select_pass_kernel(const float* __restrict__ pred, const float* __restrict__ fake, float sa,
                                                                       float sb, uint32_t rank, uint32_t* __restrict__ tables,
-                                                                      uint32_t* __restrict__ state, int B, uint32_t per_image) {
+                                                                      uint32_t* __restrict__ state, int B, uint32_t per_image, G... g) {
+  static_assert(sizeof...(G) == 0 || (sizeof...(G) == 1 && (std::is_same_v<G, QselGuide> && ...)), "G is nothing or one QselGuide");
   constexpr int BINS = 1 << qsel_bits(PASS), SHIFT = qsel_shift(PASS);
   __shared__ uint32_t hist[QSEL_HISTS * BINS];
   __shared__ uint32_t scan[QSEL_THREADS];
@@ -350,7 +393,11 @@ __global__ void __launch_bounds__(QSEL_THREADS) x0_select_pass_kernel(const floa
     for (uint32_t i0 = blockIdx.x * QSEL_THREADS + (t & ~63); i0 < per_image; i0 += gridDim.x * QSEL_THREADS) {
       const uint32_t i = i0 + (t & 63);
       const bool in = i < per_image;
-      const float p = in ? p_b[i] : 0.f;
+      float p = in ? p_b[i] : 0.f;
+      if constexpr (sizeof...(G) > 0) {
+        const QselGuide guide = (g, ...);
+        p = guided_pred(p, in ? guide.pred_guide[(size_t)b * per_image + i] : 0.f, guide.w);
+      }
       float f = 0.f, x, e;
       if constexpr (MODE != GCT2_SAMPLE_X) f = in ? f_b[i] : 0.f;
       sample_estimate<MODE>(p, f, sa, sb, x, e);
@@ -425,24 +472,33 @@ int pw_diffusion_update(int mode, const float* pred, const float* fake, double a
 }
 size_t pw_x0_quantile_scratch(int B) { return (size_t)B * (QSEL_ROW + 4) * sizeof(uint32_t); }
 // a memset of the tables, three digit passes and the finish, all on s: no host synchronisation, nothing read back
+// guided (gct2_x0_quantile_guided): the passes that combine pred with pred_guide, whatever w is
 int pw_x0_quantile(int mode, const float* pred, const float* fake, double a_t, uint32_t rank, float floor, float* rows, float* q_out,
-                   void* scratch, int B, size_t per_image, hipStream_t s) {
+                   void* scratch, int B, size_t per_image, bool guided, const float* pred_guide, float w, hipStream_t s) {
+  const char* what = guided ? "x0_quantile_guided" : "x0_quantile";
   const float sa = (float)sqrt(a_t), sb = (float)sqrt(1. - a_t);           // as pw_sampler_step forms them
   uint32_t* tables = static_cast<uint32_t*>(scratch);
   uint32_t* state = tables + (size_t)B * QSEL_ROW;
-  if (hipMemsetAsync(tables, 0, (size_t)B * QSEL_ROW * sizeof(uint32_t), s) != hipSuccess) return gct2_check_launch("x0_quantile");
+  if (hipMemsetAsync(tables, 0, (size_t)B * QSEL_ROW * sizeof(uint32_t), s) != hipSuccess) return gct2_check_launch(what);
   const int gx = blocks_for(per_image, QSEL_PER_GROUP);
   const dim3 grid(gx, std::max(1, std::min(B, kMaxBlocks / gx))), block(QSEL_THREADS);
   with_sample_mode(mode, [&](auto m) {
     constexpr int MODE = decltype(m)::value;
     if constexpr (MODE != GCT2_SAMPLE_ODE) {            // (refused by the entry point)
-      hipLaunchKernelGGL((x0_select_pass_kernel<MODE, 0>), grid, block, 0, s, pred, fake, sa, sb, rank, tables, state, B, (uint32_t)per_image);
-      hipLaunchKernelGGL((x0_select_pass_kernel<MODE, 1>), grid, block, 0, s, pred, fake, sa, sb, rank, tables, state, B, (uint32_t)per_image);
-      hipLaunchKernelGGL((x0_select_pass_kernel<MODE, 2>), grid, block, 0, s, pred, fake, sa, sb, rank, tables, state, B, (uint32_t)per_image);
+      if (guided) {
+        const QselGuide g{pred_guide, w};
+        hipLaunchKernelGGL((x0_select_pass_kernel<MODE, 0, QselGuide>), grid, block, 0, s, pred, fake, sa, sb, rank, tables, state, B, (uint32_t)per_image, g);
+        hipLaunchKernelGGL((x0_select_pass_kernel<MODE, 1, QselGuide>), grid, block, 0, s, pred, fake, sa, sb, rank, tables, state, B, (uint32_t)per_image, g);
+        hipLaunchKernelGGL((x0_select_pass_kernel<MODE, 2, QselGuide>), grid, block, 0, s, pred, fake, sa, sb, rank, tables, state, B, (uint32_t)per_image, g);
+      } else {
+        hipLaunchKernelGGL((x0_select_pass_kernel<MODE, 0>), grid, block, 0, s, pred, fake, sa, sb, rank, tables, state, B, (uint32_t)per_image);
+        hipLaunchKernelGGL((x0_select_pass_kernel<MODE, 1>), grid, block, 0, s, pred, fake, sa, sb, rank, tables, state, B, (uint32_t)per_image);
+        hipLaunchKernelGGL((x0_select_pass_kernel<MODE, 2>), grid, block, 0, s, pred, fake, sa, sb, rank, tables, state, B, (uint32_t)per_image);
+      }
     }
   });
   hipLaunchKernelGGL(x0_select_finish_kernel, dim3(std::min(B, kMaxBlocks)), block, 0, s, tables, state, floor, rows, q_out, B);
-  return gct2_check_launch("x0_quantile");
+  return gct2_check_launch(what);
 }
 // the grid of the per-image kernels: x over the Philox counters of one image, y over the images, kMaxBlocks work-groups at the most
 static dim3 step_rng_grid(int B, size_t per_image) {
@@ -483,6 +539,34 @@ int pw_sampler_step(const char* what, const SamplerStep& st, hipStream_t s) {
                    (start || (aligned16(st.pred) && aligned16(st.fake_in) && aligned16(st.x0_out))) &&
                    (!masked || (aligned16(st.known) && st.offset0 % 4 == 0));
   const dim3 flat_grid(blocks_for((size_t)st.B * st.per_image, 256)), counter_grid = step_rng_grid(st.B, st.per_image), block(256);
+  if (st.guided) {
+    // gct2_diffusion_step_guided: its own instantiations (GUIDED; rows or the scalar clip at run time), never the kernels above
+    GuidedArgs g = {};
+    static_cast<SamplerArgs&>(g) = k;
+    g.pred_guide = st.pred_guide; g.w = (float)st.w;
+    g.out3 = st.out3; g.ldout3 = st.ldout3; g.out4 = st.out4; g.ldout4 = st.ldout4;
+    const bool gvec = vec && (!st.pred_guide || aligned16(st.pred_guide));
+    with_dtype(st.dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      with_sample_mode(st.mode, [&](auto m) {
+        constexpr int MODE = decltype(m)::value;
+        if constexpr (MODE != GCT2_SAMPLE_ODE) {         // (refused by the entry point)
+          with_flag(masked, [&](auto mk) {
+            constexpr bool MASKED = decltype(mk)::value;
+            if (flat)
+              with_flag(st.multistep, [&](auto mu) {
+                hipLaunchKernelGGL((sampler_flat_kernel<T, MODE, MASKED, decltype(mu)::value, false, true>), flat_grid, block, 0, s, g);
+              });
+            else
+              with_flag(gvec, [&](auto v) {
+                hipLaunchKernelGGL((sampler_counter_kernel<T, MODE, MASKED, decltype(v)::value, false, true>), counter_grid, block, 0, s, g);
+              });
+          });
+        }
+      });
+    });
+    return gct2_check_launch(what);
+  }
   with_dtype(st.dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     auto launch = [&](auto m) {

@@ -690,7 +690,9 @@ class Denoiser(Layer):
         and mask condition the run on images (image-to-image, inpainting); solver="dpm2m" is the second-order multistep solver
         (DPM-Solver++ 2M: one gct2_diffusion_step_multistep launch per step, eta = 0 only), "ddim" the default; clip_denoised="dynamic"
         with dynamic_percentile, dynamic_floor and return_thresholds is dynamic thresholding (a per-image order statistic of |x0| in the
-        fixed bound's place: gct2_x0_quantile and one gct2_diffusion_step_dynamic launch per step)"""
+        fixed bound's place: gct2_x0_quantile and one gct2_diffusion_step_dynamic launch per step); guide= with guidance_scale,
+        guidance_interval and guide_use_ema is two-network guidance (a second Denoiser's prediction pushed away from, combined inside one
+        gct2_diffusion_step_guided launch per step)"""
         from .sampler import generate
         return generate(self, n, **kw)
 

@@ -20,6 +20,11 @@ With `clip_denoised="dynamic"` the fixed clip bound gives way to dynamic thresho
 high order statistic of |x0| (gct2_x0_quantile, a radix select) bounds the estimate, and one gct2_diffusion_step_dynamic launch takes
 the place of whichever of the three steps the run would have used.
 
+With `guide=` a second denoiser's prediction is taken at every step whose weight is not 1 and the step samples from
+p_guide + w (p_main - p_guide) (two-network guidance: autoguidance, class guidance between two denoisers): ONE
+gct2_diffusion_step_guided launch combines the two planes on the way in, runs whichever step the run would have used, and also writes
+the next input into the guide engine's buffers; gct2_x0_quantile_guided is the select on the combined estimate.
+
 `encode` - the inversion loop of log_sample as an API: a batch of images into latents over the same strided timesteps."""
 from __future__ import annotations
 
@@ -44,6 +49,7 @@ from .trainer_math import check_mask, img2img_steps
 from .trainer_math import SOLVERS, multistep_coefficient
 from .trainer_math import check_predict_v
 from .trainer_math import quantile_rank
+from .trainer_math import guidance_launches, guidance_table
 
 
 def sample_mode(predict_x: bool, predict_scaled_epsilon: bool, ordinary_differential_equation: bool, predict_v: bool = False) -> int:
@@ -218,16 +224,9 @@ class _Sampler:
     def dynamic_rows(self, B: int, pred: torch.Tensor, fake: torch.Tensor, a_t: float, rank: int, floor: float) -> torch.Tensor:
         """per image, the rank-th smallest |x0| of the step's own estimate against the floor: gct2_x0_quantile into this batch size's
         fp32 [B,2] = {s_b, r_b} (valid until the next call at B); the scratch lives beside it"""
-        per_image = self.H * self.W * 3
-        held = self._dynamic.get(B)
-        if held is None:
-            need = C.c_size_t(0)
-            call("gct2_x0_quantile_scratch", B, per_image, C.byref(need))
-            held = self._dynamic[B] = (torch.empty(need.value, dtype=torch.uint8, device=self.eng.device),
-                                       torch.empty(B, 2, dtype=torch.float32, device=self.eng.device))
-        scratch, rows = held
+        scratch, rows = self._rows(B)
         call("gct2_x0_quantile", self.mode, pred.data_ptr(), fake.data_ptr(), a_t, rank, floor, rows.data_ptr(), None, scratch.data_ptr(),
-             scratch.numel(), B, per_image, self._stream())
+             scratch.numel(), B, self.H * self.W * 3, self._stream())
         return rows
 
     def dynamic_step(self, B: int, pred: torch.Tensor, fake: torch.Tensor, hist: Optional[torch.Tensor], known: Optional[torch.Tensor],
@@ -239,6 +238,36 @@ class _Sampler:
         call("gct2_diffusion_step_dynamic", self.mode, self.eng.dtype, pred.data_ptr(), fake.data_ptr(), ptr(hist), ptr(known), ptr(mask),
              rows.data_ptr(), a_t, a_prev, sigma2, c1, seed, GENERATE_STREAM, offset, offset0, image_stride, fake.data_ptr(), ptr(hist),
              ptr(x0), *self.input_views(B), B, self.H * self.W * 3, 3, self._stream())
+
+    def _rows(self, B: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        held = self._dynamic.get(B)
+        if held is None:
+            need = C.c_size_t(0)
+            call("gct2_x0_quantile_scratch", B, self.H * self.W * 3, C.byref(need))
+            held = self._dynamic[B] = (torch.empty(need.value, dtype=torch.uint8, device=self.eng.device),
+                                       torch.empty(B, 2, dtype=torch.float32, device=self.eng.device))
+        return held
+
+    def guided_rows(self, B: int, pred: torch.Tensor, pred_guide: torch.Tensor, w: float, fake: torch.Tensor, a_t: float, rank: int,
+                    floor: float) -> torch.Tensor:
+        """dynamic_rows on the combined prediction p = pred_guide + w (pred - pred_guide), formed pass by pass and never stored:
+        gct2_x0_quantile_guided, into the same [B,2] and scratch"""
+        scratch, rows = self._rows(B)
+        call("gct2_x0_quantile_guided", self.mode, pred.data_ptr(), pred_guide.data_ptr(), w, fake.data_ptr(), a_t, rank, floor,
+             rows.data_ptr(), None, scratch.data_ptr(), scratch.numel(), B, self.H * self.W * 3, self._stream())
+        return rows
+
+    def guided_step(self, B: int, pred: torch.Tensor, pred_guide: Optional[torch.Tensor], w: float, fake: torch.Tensor,
+                    hist: Optional[torch.Tensor], known: Optional[torch.Tensor], mask: Optional[torch.Tensor], rows: Optional[torch.Tensor],
+                    a_t: float, a_prev: float, sigma2: float, c1: float, clip: float, seed: int, offset: int, offset0: int, image_stride: int,
+                    x0: Optional[torch.Tensor], guide_views=(None, 0, None, 0)) -> None:
+        """whichever of fused_step / masked_step / multistep_step / dynamic_step the arguments select, on pred_guide + w (pred - pred_guide)
+        (pred_guide None: on pred), the result also stored to guide_views - the guide engine's input_views: gct2_diffusion_step_guided, in
+        place on fake (and hist)"""
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        call("gct2_diffusion_step_guided", self.mode, self.eng.dtype, pred.data_ptr(), ptr(pred_guide), w, fake.data_ptr(), ptr(hist),
+             ptr(known), ptr(mask), ptr(rows), a_t, a_prev, sigma2, c1, clip, seed, GENERATE_STREAM, offset, offset0, image_stride,
+             fake.data_ptr(), ptr(hist), ptr(x0), *self.input_views(B), *guide_views, B, self.H * self.W * 3, 3, self._stream())
 
     def update(self, pred: torch.Tensor, fake: torch.Tensor, alpha: float, alpha_prev: float, x: torch.Tensor, e: Optional[torch.Tensor]) -> None:
         """train.py:382-413 / 452-479 by mode (gct2_diffusion_update)."""
@@ -377,7 +406,8 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
              predict_scaled_epsilon: Optional[bool] = None, ordinary_differential_equation: Optional[bool] = None, noise_schedule=None,
              alpha_dash_offset: Optional[float] = None, init: Optional[torch.Tensor] = None, strength: float = 1.0, mask=None,
              solver: str = "ddim", predict_v: Optional[bool] = None, dynamic_percentile: Optional[float] = None,
-             dynamic_floor: Optional[float] = None, return_thresholds: bool = False):
+             dynamic_floor: Optional[float] = None, return_thresholds: bool = False, guide: Optional["M.Denoiser"] = None,
+             guidance_scale=None, guidance_interval=None, guide_use_ema: bool = False):
     """n new images from noise: strided DDIM sampling (Song et al. 2021) over K = num_steps of the engine's `steps` timesteps
     (trainer_math.sampling_timesteps; None: all of them; or an explicit strictly increasing `timesteps` list within 1..steps), one
     network evaluation and ONE pointwise launch (gct2_diffusion_step) per step.  Returns fp32 [n,H,W,3] on the device: the x0 estimate
@@ -420,7 +450,26 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
     run, which shows whether the percentile ever engages.  ValueError: dynamic_percentile outside (0, 1], a dynamic_floor that is not
     finite and > 0, either of them (anything but None, the defaults 0.995 and 1.0 included) or return_thresholds without
     clip_denoised="dynamic", any other string.  dynamic_percentile=None is 0.995, dynamic_floor=None is 1.0.  Not covered: interpolated percentiles, per-channel or mask-aware statistics, encode, log_sample, the data-parallel
-    wrappers.  What it does to the sample quality of a trained network is not measured in this project."""
+    wrappers.  What it does to the sample quality of a trained network is not measured in this project.
+    guide: a second Denoiser - two-network guidance.  At every step the prediction the step uses is p = p_guide + w (p_main - p_guide), both
+    networks evaluated at the same fake and timestep under the same objective (where x0 is affine in the prediction, so this is the same
+    combination of the two x0 estimates): w = 1 the main network alone, w = 0 the guide alone, w > 1 extrapolates away from the guide.  With
+    a less-trained or smaller checkpoint of the same model as the guide (clone_denoiser, a checkpoint, the raw weights against the
+    averages) this is autoguidance (Karras et al. 2024); with a guide trained on everything and a main model trained on one class it is
+    class guidance between two denoisers (Liu et al. 2022).  guidance_scale: a float, a callable f(t) -> float or a sequence of `steps`
+    floats indexed by t - 1; guidance_interval=(t_lo, t_hi) keeps the weight for t_lo <= t <= t_hi and sets it to 1 elsewhere
+    (Kynkaanniemi et al. 2024); both resolve on the host (trainer_math.guidance_table).  A step whose weight is exactly 1.0 does not
+    evaluate the guide, and a run whose weights are all 1 is guide=None launch for launch (trainer_math.guidance_launches).  The combine
+    is fp32, d = p_main - p_guide, t = (float)w d, p = p_guide + t, each rounded once, inside ONE gct2_diffusion_step_guided launch per
+    step that is otherwise the step the run would have used and also stores the next input into the guide engine's buffers; under
+    clip_denoised="dynamic" the select is gct2_x0_quantile_guided on the same p - guidance above 1 is what pushes x0 outside [-1, 1]
+    and gives dynamic thresholding its purpose.  guide_use_ema: the guide reads its averages, independently of use_ema.  It composes
+    with every other argument; each network replays its own captured forward graph; no training state of either denoiser moves.
+    ValueError before any launch: guidance_scale or guidance_interval without guide, guide without guidance_scale, a guide that is the
+    main denoiser's own engine (use clone_denoiser), a guide with other steps, noise schedule, offset, objective, compute dtype or
+    device, a weight that is not finite, an interval outside 1..steps or with t_lo > t_hi.  What guidance does to the sample quality
+    of a trained network is not measured in this project (no data, no Inception network).  Not covered: encode, log_sample, Distiller,
+    the data-parallel wrappers."""
     eng = denoiser.ensure_engine()
     steps = int(eng.steps)
     if solver not in SOLVERS:
@@ -432,6 +481,32 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
         raise ValueError("generate: the ordinary_differential_equation objective predicts the image one step back only; strided sampling "
                          "and eta have no meaning there (log_sample runs its sampler)")
     schedule, offset = _resolve_schedule(eng, noise_schedule, alpha_dash_offset)
+    geng, weights = None, None
+    if guide is None:
+        if guidance_scale is not None or guidance_interval is not None or guide_use_ema:
+            raise ValueError("generate: guidance_scale, guidance_interval and guide_use_ema belong to guide=, which is None")
+    else:
+        if guidance_scale is None:
+            raise ValueError("generate: guide= needs guidance_scale (1.0 is the main network alone)")
+        geng = guide.ensure_engine()
+        if geng is eng:
+            raise ValueError("generate: the guide is the main denoiser's own engine; guide with a copy (clone_denoiser) or another checkpoint")
+        if int(geng.steps) != steps or _resolve_schedule(geng, None, None) != (schedule, offset):
+            raise ValueError(f"generate: the guide (steps {geng.steps}, schedule {_resolve_schedule(geng, None, None)!r}) and the main denoiser "
+                             f"(steps {steps}, schedule {(schedule, offset)!r}) must share steps, noise schedule and offset")
+        try:
+            gmode = _resolve_switches(geng, predict_x, predict_scaled_epsilon, ordinary_differential_equation, predict_v)
+        except ValueError as e:
+            raise ValueError(f"generate: the guide predicts under another objective than the main denoiser ({e})") from None
+        if gmode != mode:
+            raise ValueError(f"generate: the guide's sampler mode {gmode} differs from the main denoiser's {mode}")
+        try:
+            weights = guidance_table(guidance_scale, steps, guidance_interval)
+        except ValueError as e:
+            raise ValueError(f"generate: {e}") from None
+        if geng.dtype != eng.dtype or geng.device != eng.device:
+            raise ValueError(f"generate: the guide computes in dtype {geng.dtype} on {geng.device}, the main denoiser in {eng.dtype} on "
+                             f"{eng.device}: the fused step writes one value into both networks' inputs")
     if not float(eta) >= 0.0:
         raise ValueError(f"generate: eta must be >= 0, got {eta!r}")
     multistep = solver == "dpm2m"
@@ -521,14 +596,25 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
     # result is that step's own estimate); between them the estimate of the step before extrapolates
     c1s = [0.0 if k <= K - K_run or k == K - 1 else multistep_coefficient(plan[k - 1][1], plan[k][1], plan[k][2]) for k in range(K)]
 
+    # guidance: what every step run launches (the same for every batch), from the weights of the timesteps in sampling order
+    start_copy, launches = guidance_launches([weights[plan[k][0] - 1] for k in range(K - K_run, K)]) if geng is not None else (False, None)
+
     dev = eng.device
-    with (eng.ema_weights() if use_ema else contextlib.nullcontext()):
+    with contextlib.ExitStack() as weights_read:
+        if use_ema:
+            weights_read.enter_context(eng.ema_weights())
+        if geng is not None and guide_use_ema:
+            weights_read.enter_context(geng.ema_weights())
         eng.flush_deferred()
         S = _Sampler(eng, steps, mode, H, W, use_graph, schedule, offset)
+        SG = None
+        if geng is not None:
+            geng.flush_deferred()
+            SG = _Sampler(geng, steps, mode, H, W, use_graph, schedule, offset)
         out = torch.empty(n, H, W, 3, dtype=torch.float32, device=dev)
         kept = {t: torch.empty_like(out) for t in marks}
         bounds = {tau: torch.empty(n, dtype=torch.float32, device=dev) for tau in taus[:K_run]} if dynamic and return_thresholds else None
-        fake = None
+        fake = gstart = None
         for g0 in range(0, n, bs):
             B = min(bs, n - g0)
             if fake is None or fake.shape[0] != B:
@@ -545,6 +631,10 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
             else:
                 z = noise[g0:g0 + B].to(dev, torch.float32).contiguous()
                 S.mix(B, z, z, 0.0, fake)       # alpha = 0: fake = 0 z + 1 z
+            if start_copy:                      # the first step run reads the guide: its views take the start, once per batch
+                if gstart is None or gstart.shape[0] != B:
+                    gstart = torch.empty_like(fake)     # (the fp32 output of the copy: the state itself is read only)
+                SG.mix(B, fake, fake, 0.0, gstart)
             for k, (tau, a_t, a_prev, s2) in enumerate(plan, 1):
                 if k <= K - K_run:              # (init with strength < 1: the front of the schedule is cut, the slots keep their steps)
                     continue
@@ -552,7 +642,22 @@ def generate(denoiser: "M.Denoiser", n: int, num_steps: Optional[int] = None, et
                 pred = S.evaluate(B)
                 x0 = out[g0:g0 + B] if k == K else (kept[tau][g0:g0 + B] if tau in kept else None)
                 off = generate_offset(first_index + g0, k, K, per_image)
-                if dynamic:
+                guided_entry, with_guide, write_views = launches[k - 1 - (K - K_run)] if launches is not None else (False, False, False)
+                if guided_entry:
+                    w, pg = weights[tau - 1], None
+                    if with_guide:
+                        SG.set_t(B, tau)
+                        pg = SG.evaluate(B)
+                    masked = init is not None and mask is not None
+                    rows = None
+                    if dynamic:
+                        rows = S.guided_rows(B, pred, pg, w, fake, a_t, rank, floor) if with_guide else S.dynamic_rows(B, pred, fake, a_t, rank, floor)
+                        if bounds is not None:
+                            bounds[tau][g0:g0 + B].copy_(rows[:, 0])
+                    S.guided_step(B, pred, pg, w if with_guide else 1.0, fake, hist, known if masked else None, keep if masked else None, rows,
+                                  a_t, a_prev, 0.0 if multistep else s2, c1s[k - 1] if multistep else 0.0, 0.0 if dynamic else clip, seed, off, off0,
+                                  stride, x0, SG.input_views(B) if write_views else (None, 0, None, 0))
+                elif dynamic:
                     rows = S.dynamic_rows(B, pred, fake, a_t, rank, floor)
                     if bounds is not None:
                         bounds[tau][g0:g0 + B].copy_(rows[:, 0])

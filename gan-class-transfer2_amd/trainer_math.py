@@ -552,6 +552,69 @@ def quantile_rank(p: float, n: int) -> int:
     return min(n, max(1, math.ceil(p * n)))
 
 
+# ---- two-network guidance (generate with guide=; gct2_diffusion_step_guided / gct2_x0_quantile_guided) -----------------------------------
+def guidance_table(scale, steps: int, interval=None) -> list:
+    """the guidance weight of every timestep as Python floats: entry t - 1 is w(t), t = 1..steps, of p = p_guide + w (p_main - p_guide).
+    scale: a float (every timestep), a callable f(t: int) -> float, or a sequence of `steps` floats - the forms loss_weighting takes.
+    interval = (t_lo, t_hi), ints with 1 <= t_lo <= t_hi <= steps: the weight holds for t_lo <= t <= t_hi and is 1.0 - the main network
+    alone - elsewhere (Kynkaanniemi et al. 2024, "Applying Guidance in a Limited Interval Improves Sample and Distribution Quality in
+    Diffusion Models").  Every weight must be finite, also as the float32 the kernel receives; a bool is no weight (ValueError)."""
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError(f"guidance_table: steps must be >= 1, got {steps!r}")
+    if scale is None or isinstance(scale, (bool, np.bool_, str)):
+        raise ValueError(f"guidance_scale must be a float, a callable f(t) or a sequence of {steps} floats, got {scale!r}")
+    if callable(scale):
+        raw = [scale(t) for t in range(1, steps + 1)]
+    elif isinstance(scale, (int, float, np.integer, np.floating)):
+        raw = [scale] * steps
+    else:
+        try:
+            raw = list(scale.tolist() if hasattr(scale, "tolist") else scale)
+        except TypeError:
+            raise ValueError(f"guidance_scale must be a float, a callable f(t) or a sequence of {steps} floats, got {scale!r}") from None
+        if len(raw) != steps:
+            raise ValueError(f"guidance_scale: a table of {len(raw)} weights for {steps} timesteps")
+    table = []
+    for t, v in enumerate(raw, 1):
+        try:
+            if isinstance(v, (bool, np.bool_, str)):
+                raise TypeError
+            w = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"guidance_scale: the weight of timestep {t} is {v!r}, not a float") from None
+        with np.errstate(over="ignore"):
+            if not (math.isfinite(w) and math.isfinite(float(np.float32(w)))):
+                raise ValueError(f"guidance_scale: the weight of timestep {t} is {w!r}: every weight must be finite (in float32)")
+        table.append(w)
+    if interval is not None:
+        try:
+            lo, hi = interval
+        except (TypeError, ValueError):
+            raise ValueError(f"guidance_interval must be (t_lo, t_hi), got {interval!r}") from None
+        if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in (lo, hi)) or not 1 <= lo <= hi <= steps:
+            raise ValueError(f"guidance_interval must be ints with 1 <= t_lo <= t_hi <= {steps}, got {interval!r}")
+        table = [w if lo <= t <= hi else 1.0 for t, w in enumerate(table, 1)]
+    return table
+
+
+def guidance_launches(weights) -> Tuple[bool, list]:
+    """what a guided run launches, from the weights of the steps it runs in sampling order (one batch): (start_copy, per step
+    (guided_entry, pred_guide, write_views)).
+      pred_guide    the step combines the two predictions: its weight is not exactly 1.0 (only then is the guide evaluated)
+      write_views   the step stores its result into the guide engine's input views too: exactly when the NEXT step reads the guide
+      guided_entry  the step is gct2_diffusion_step_guided (with the guided select under dynamic thresholding) - when it needs
+                    pred_guide or the views; else the existing entry point, so an all-ones run is guide=None launch for launch
+      start_copy    the first step run reads the guide: one gct2_diffusion_mix(fake, fake, alpha = 0) writes the guide's views, once
+                    per batch"""
+    guided = [float(w) != 1.0 for w in weights]
+    steps = []
+    for k, g in enumerate(guided):
+        views = k + 1 < len(guided) and guided[k + 1]
+        steps.append((g or views, g, views))
+    return bool(guided and guided[0]), steps
+
+
 # ---- progressive distillation (distill.Distiller; gct2_distill_start / _step / _target) -------------------------------------------------
 # the Philox stream ids that belong to distillation alone: the pair of sample k at position k of stream 8, its noise at positions
 # [k per_image, (k + 1) per_image) of stream 9

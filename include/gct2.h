@@ -603,6 +603,40 @@ int gct2_diffusion_step_dynamic(int mode, int dtype, const float* pred, const fl
                                 uint64_t stream_id, uint64_t offset, uint64_t offset0, uint64_t image_stride, float* fake_out,
                                 float* hist_out, float* x0_out, void* out, int ldout, void* out2, int ldout2, int B, size_t per_image,
                                 int C, void* stream);
+/* ---- two-network guidance (generate(guide=...): autoguidance, Karras et al. 2024, "Guiding a Diffusion Model with a Bad Version of
+ * Itself"; class guidance between two denoisers, Liu et al. 2022, "Compositional Visual Generation with Composable Diffusion Models"):
+ * the step samples from p = p_guide + w (p_main - p_guide), two networks' predictions under the same objective at the same fake.
+ *   the combine fp32, no contraction, every operation rounded once:  d = pred - pred_guide;  t = (float)w * d;  p = pred_guide + t.
+ *               w = 1 is pred up to that rounding, w = 0 is pred_guide's bits on finite planes (t is a zero; a -0 of pred_guide may become +0).  p never reaches memory:
+ *               the step and the select each form it from the two planes, by the same three operations, hence the same bits.
+ *
+ * gct2_diffusion_step_guided: ONE launch for the plain, with-noise, masked, multistep and dynamic forms of the step.  The arguments are
+ * gct2_diffusion_step_dynamic's with pred_guide and w behind pred, the scalar clip behind c1 and a second pair of views out3 / out4
+ * behind out / out2; every rule not named here (the forms, c1, sigma2, the alignment-selected paths, B * per_image < 2^31, the Philox
+ * positions) is the existing entry points'.
+ *   bound       rows == NULL: the scalar clip, 0 = none (gct2_diffusion_step's rule); rows != NULL: the per-image bound
+ *               (gct2_diffusion_step_dynamic's rule), clip must then be 0, else GCT2_EINVAL.
+ *   pred_guide  fp32 [B * per_image], or NULL: p = pred, and (float)w must be 1, else GCT2_EINVAL.  w must be finite in fp32.
+ *   out3, out4  the guide engine's input views (compute dtype, leading dimensions ldout3 / ldout4 >= C): the kernel stores there the
+ *               value it stores to out / out2.  Both may be NULL; out4 without out3 is GCT2_EINVAL.
+ *   plain form  pred_guide, out3 and out4 all NULL: every output is bit for bit the existing entry point's for that form.
+ *   guided form every output is bit for bit that existing entry point run on the plane p formed by the three operations above.
+ *               A NaN of pred_guide under mask <= 0 never reaches a kept pixel (the masked step's selects).
+ * The guided kernels are instantiations of their own (the existing entry points launch the kernels they always had) and choose between
+ * rows and the scalar clip at run time.
+ *
+ * gct2_x0_quantile_guided: gct2_x0_quantile with pred_guide (non-NULL) and w: every digit pass forms p by the combine before the
+ * estimate, so the select's x is the guided step's x bit for bit.  Same scratch (gct2_x0_quantile_scratch), same finishing rule, integer
+ * atomics only, no host synchronisation.
+ * Measured on one MI355X at 64x128x128x3, bf16 views: profiles/guidance_bench.json. */
+int gct2_x0_quantile_guided(int mode, const float* pred, const float* pred_guide, double w, const float* fake, double a_t, uint32_t rank,
+                            double floor, float* rows, float* q_out, void* scratch, size_t scratch_bytes, int B, size_t per_image,
+                            void* stream);
+int gct2_diffusion_step_guided(int mode, int dtype, const float* pred, const float* pred_guide, double w, const float* fake_in,
+                               const float* hist_in, const float* known, const float* mask, const float* rows, double a_t, double a_prev,
+                               double sigma2, double c1, double clip, uint64_t seed, uint64_t stream_id, uint64_t offset, uint64_t offset0,
+                               uint64_t image_stride, float* fake_out, float* hist_out, float* x0_out, void* out, int ldout, void* out2,
+                               int ldout2, void* out3, int ldout3, void* out4, int ldout4, int B, size_t per_image, int C, void* stream);
 /* ---- progressive distillation (Salimans & Ho 2022, "Progressive Distillation for Fast Sampling of Diffusion Models"; Distiller):
  * a student learns to do in ONE DDIM step what its teacher does in two.  A batch holds a different timestep per image, so the
  * scalars (a_t, a_prev) of the sampler's entry points become a row of a host-built table per image:
